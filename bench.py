@@ -37,7 +37,9 @@ Rank 0 prints ONE JSON line (contract in the task statement) carrying
   steps each, timed the same way (N=1 only);
 * `gsm` (with `--driver gsm`): cycles of the real driver, `gsm.GrowingStringDriver`, on the fully grown string, and what the
   driver adds on top of the bare evaluation;
-* `cpu_baseline`: the repo's own CPU restatement (the reference's fairchem path cannot run here) on a bounded sample.
+* `cpu_baseline`: the repo's own CPU restatement (the reference's fairchem path cannot run here) on a bounded sample;
+* `dump_outputs` (with `--dump-outputs DIR`): what the last timed step returned, written to DIR as float64 .npy files (`dump_outputs()`),
+  so that two builds can be compared output for output on the same seeded inputs.
 """
 from __future__ import annotations
 
@@ -154,6 +156,35 @@ CONFIGS = {     # BASELINE.json configs: (atoms, images, what it is)
     "c5": (20000, 8, "c5: ~20 000-atom protein-ligand complex, 8 images (one image per chunk on one GPU; one image per GPU on the node)"),
 }
 
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir: str, energy: np.ndarray, forces: np.ndarray, string: np.ndarray, limit: int = DUMP_LIMIT_BYTES) -> dict:
+    """Write what the timed string iteration returned in its last step as float64 ``out_dir/<name>.npy``: ``energy`` [K] (Hartree) and
+    ``forces`` [K, N, 3] (Hartree/Bohr) from the evaluator, ``string`` [K, N, 3] (Bohr) from the string update.  When they would exceed
+    `limit` bytes, the per-atom arrays keep a fixed seeded sample of atoms (the same for every run of the same sizes) and
+    ``atom_index`` [M] holds the sampled atom indices.  Returns the description that goes into the result line."""
+    k = energy.shape[0]
+    arrays = {"energy": np.asarray(energy, np.float64),
+              "forces": np.asarray(forces, np.float64).reshape(k, -1, 3),
+              "string": np.asarray(string, np.float64).reshape(k, -1, 3)}
+    n = arrays["forces"].shape[1]
+    per_atom = 2 * k * 3 * 8
+    sampled = None
+    if arrays["energy"].nbytes + n * per_atom > limit:
+        m = (limit - arrays["energy"].nbytes) // (per_atom + 8)         # + 8: the float64 index of each sampled atom
+        if m < 1:
+            raise SystemExit(f"bench.py: --dump-outputs cannot fit one atom of {k} images into {limit} bytes")
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=m, replace=False))
+        arrays["forces"], arrays["string"] = arrays["forces"][:, idx], arrays["string"][:, idx]
+        arrays["atom_index"] = idx.astype(np.float64)
+        sampled = {"atoms": int(m), "of": int(n), "seed": DUMP_SAMPLE_SEED}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "arrays": {name: list(a.shape) for name, a in arrays.items()}, "atom_sample": sampled}
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -176,7 +207,11 @@ def main():
     ap.add_argument("--gsm-cycles", type=int, default=8)
     ap.add_argument("--fp32-steps", type=int, default=5)
     ap.add_argument("--fp32-warmup", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (energy, forces, updated string; float64 .npy, <= 64 MB) to DIR")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.atoms is None:
         args.atoms = CONFIGS[args.config][0]
     if args.images is None:
@@ -225,9 +260,10 @@ def main():
         eng.set_system(z, charge=0, spin=1, task="omol")
         return eng
 
-    def run(precision: str, steps: int, warmup: int, lanes: str = "", images=None, force_collective: bool = False):
+    def run(precision: str, steps: int, warmup: int, lanes: str = "", images=None, force_collective: bool = False, outputs=None):
         """W untimed + K timed string iterations on a fresh engine in `precision` mode; returns (dt, profile, edges, maxdeg, resolved mode).
-        `images`: another batch of the same system (the 2-image shard); `force_collective`: issue the all-gather in a one-rank group too."""
+        `images`: another batch of the same system (the 2-image shard); `force_collective`: issue the all-gather in a one-rank group too;
+        `outputs`: a dict that receives what the last timed step returned (host copies of energy, forces and the updated string)."""
         eng = make_engine(precision, lanes)
         imgs_run = imgs if images is None else images
         k = len(imgs_run)
@@ -246,21 +282,23 @@ def main():
                 # every rank of the 8-GPU job -- with the other ranks' forces stood in for by copies of the local ones
                 e, fl = ev(xc[:k])
                 f = fl.repeat(-(-k_full // k), 1)[:k_full]
-            return string_step(xc, f, max_step=0.1, alpha=0.5, fix_ends=False), e
+            return string_step(xc, f, max_step=0.1, alpha=0.5, fix_ends=False), e, f
 
         for _ in range(warmup):
-            x, e = step(x)
+            x, e, f = step(x)
         fence()
         eng.profile_enable(True)
         eng.profile_read(True)
         t0 = time.perf_counter()
         for _ in range(steps):
-            x, e = step(x)
+            x, e, f = step(x)
         fence()
         dt = time.perf_counter() - t0
         prof = eng.profile_read(True)
         eng.profile_enable(False)
         ev.flush()                                      # the deferred check of the last step
+        if outputs is not None:
+            outputs.update(energy=e.cpu().numpy(), forces=f.cpu().numpy(), string=x.cpu().numpy())
         ne_local, maxdeg = eng.graph_stats()            # edges of this rank's images in the last step
         if not bool(torch.isfinite(e).all()) or eng.widened:
             raise SystemExit("bench.py: non-finite energies / a precision change inside the timed region")
@@ -435,7 +473,8 @@ def main():
         return out_h
 
     mode_req = os.environ.get("UMX_PRECISION", "auto")           # "auto" = bf16x3: >= 24-bit products in both passes (include/umx.h)
-    dt, prof, ne_local, maxdeg, resolved, lanes_used = run(mode_req, args.steps, args.warmup)
+    last = {} if args.dump_outputs and rank == 0 else None
+    dt, prof, ne_local, maxdeg, resolved, lanes_used = run(mode_req, args.steps, args.warmup, outputs=last)
     mode = {"split-f16": "split", "split-bf16": "split-bf16", "bf16x3": "bf16x3", "fp32": "fp32"}[resolved]
     tt = torch.tensor([dt, float(ne_local)], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
     if world > 1:
@@ -502,6 +541,8 @@ def main():
                                                "achieved": f32["alg_flops"] / max(f32["ms"], 1e-9) / 1e9 if split else 0.0,
                                                "peak": PEAK_FP64_MFMA_TFLOPS if os.environ.get("UMX_NODE_F64", "1") != "0" else PEAK_FP32_MFMA_TFLOPS}},
         }
+        if last is not None:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, last["energy"], last["forces"], last["string"])
         # second regime: the HBM-bound gather / rotate / gate / segmented-reduce kernels.  Everything outside the two GEMM
         # families is timed as the remainder of the step; the fused radial-MLP kernels (VALU / fp32-MFMA bound, not HBM bound) are timed
         # live as their own family (ABI v7) and taken OUT of the HBM figure, so that `achieved` is not a blend of two bounds.

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -73,3 +74,26 @@ def test_bench_other_configs_and_the_hessian_leg():
     assert "error" not in h, h
     assert h["columns"] == 12 and h["displaced_geometries"] == 24 and h["engine_calls"] == 1 and h["finite"] and h["columns_per_s"] > 0
     assert h["full_hessian_columns"] == 3 * (120 - 12) and h["extrapolated_full_hessian_s"] == pytest.approx(h["full_hessian_columns"] / h["columns_per_s"], rel=1e-9)
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`--dump-outputs DIR`: what the last timed step returned (energy, forces, updated string) as float64 .npy files.  The same
+    arguments give the same seeded inputs, and the engine is bitwise reproducible, so two runs write the same arrays bit for bit."""
+    cmd = [sys.executable, "bench.py", "--config", "c1", "--steps", "3", "--warmup", "1", "--driver", "string", "--no-fp32-mode", "--no-fast-mode"]
+    names = ("energy", "forces", "string")
+    runs = []
+    for i in range(2):
+        out_dir = str(tmp_path / f"run{i}")
+        out = subprocess.run(cmd + ["--dump-outputs", out_dir], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        assert d["dump_outputs"]["arrays"] == {"energy": [8], "forces": [8, 50, 3], "string": [8, 50, 3]} and d["dump_outputs"]["atom_sample"] is None
+        assert sorted(os.listdir(out_dir)) == [n + ".npy" for n in names]
+        arrs = {n: np.load(os.path.join(out_dir, n + ".npy")) for n in names}
+        for n, a in arrs.items():
+            assert a.dtype == np.float64 and np.isfinite(a).all(), n
+        assert np.abs(arrs["forces"]).max() > 0 and np.abs(arrs["energy"]).min() > 0
+        runs.append(arrs)
+    for n in names:
+        assert np.array_equal(runs[0][n], runs[1][n]), n

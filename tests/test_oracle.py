@@ -162,10 +162,15 @@ def test_oracle_c1_golden_first_image(oracle):
     assert np.abs(f - g["forces"][0]).max() < 1e-10
 
 
-def test_float32_torch_arithmetic_deviates_per_atom(weights, oracle):
+def test_float32_torch_arithmetic_deviation_per_atom(weights, oracle):
     """Context for the energy tolerance (NOTES.md section 3): the same restatement run in torch float32 -- the reference's dtype and
-    op style -- deviates from float64 arithmetic by ~1e-7 eV PER ATOM (one-signed: shared quantities are rounded the same way for every
-    atom), i.e. 1e-4 eV is already exceeded near 1000 atoms by float32 arithmetic itself.  The engine is held to <= 2.5e-8 eV per atom."""
+    op style -- deviates from float64 arithmetic by up to ~1e-7 eV PER ATOM, i.e. 1e-4 eV can already be exceeded near 1000 atoms by
+    float32 arithmetic itself.  The engine is held to <= 2.5e-8 eV per atom.
+
+    Size and sign of the deviation are set by the order of the float32 sums, i.e. by the host's BLAS kernel path and thread count
+    (MKL picks its kernels by CPU vendor and ISA): measured at 90 / 140 atoms from -2.3e-7 to -7.6e-9 / from -2.3e-7 to +3.9e-8 eV per
+    atom, either sign at 140 atoms.  What held on every path measured: above the engine's bound at one of the two sizes at least, far below
+    1e-6 at both."""
     from oracle.escn_md_oracle import Oracle
 
     o32 = Oracle(weights, dtype=torch.float32)
@@ -177,5 +182,5 @@ def test_float32_torch_arithmetic_deviates_per_atom(weights, oracle):
         e32, f32 = o32.energy_forces(z, p32)
         per_atom.append((e32 - e64) / n)
         assert np.abs(f32 - f64).max() < 2e-5                      # forces: float32 round-off only
-    assert all(2e-8 < abs(d) < 1e-6 for d in per_atom), per_atom     # ~1e-7 eV per atom ...
-    assert np.sign(per_atom[0]) == np.sign(per_atom[1])              # ... with the same sign
+    assert all(abs(d) < 1e-6 for d in per_atom), per_atom            # <= ~1e-7 eV per atom ...
+    assert max(abs(d) for d in per_atom) > 2e-8, per_atom            # ... and not below the engine's bound
