@@ -118,7 +118,7 @@ static inline float bf16_rne(float x) {
  * cols[nc]: the output columns to compute (sub-sampling).  Y is [M x nc]. */
 /* "aligned planes" (round 6).  Stage 1 of a pass cuts, toward zero, every bit of a product below 2^-24 of the pass's largest product
  * exponent -- a product more than 2^-10 below the largest one loses low bits, and its error follows the product's SIGN (coherent over all
- * edges where an activation column is one-signed and consistently small: a dead SiLU unit).  Cure without losing a bit: the LEADING plane of an
+ * edges where an activation column is one-signed and consistently small: a dead SiLU unit).  Cure (small in-group elements keep 16-23 bits, unbiased): the LEADING plane of an
  * element is rounded to a multiple of Q = 2^(e_max - dem) of its PASS GROUP (the 8 consecutive k of one row that one pass sees; e_max = exponent
  * of the group's largest magnitude) before it is rounded to bf16; the following planes take the exact remainder as before.  With dem_a + dem_w
  * <= 24 every leading product's lowest bit lies at or above 2^(e_a,max + e_b,max - 24) >= 2^(epmax - 24): stage 1 has nothing to cut.
