@@ -7,8 +7,14 @@ The 16 images of the ONE path are sharded contiguously over the ranks (strong sc
 is fixed by BASELINE.json's workload, N=1 evaluates all 16 images on one GPU).
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 3 --warmup 1
+
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes `--dump-outputs` and prints the line
+(`value`, `dtype`, `ms_per_step`, `config`, and the `roofline` read off the timed steps themselves).  Every leg that takes runs of its
+own -- `serial_schedule`, `shard`, `split_bf16_mode`, `fast_mode`, `fp32_mode`, `hessian`, `gsm`, `cpu_baseline` -- runs only with
+`--full` (N=1), where the `--no-*` options and `--driver` choose among them.
 
 Rank 0 prints ONE JSON line (contract in the task statement) carrying
 
@@ -28,14 +34,14 @@ Rank 0 prints ONE JSON line (contract in the task statement) carrying
 * `shard`: what ONE rank of the 8-GPU headline run does per iteration -- the 2-image batch through the same evaluator plus the RCCL
   all-gather of [E | status | F] (a one-rank nccl group here: the collective runs, on this GPU alone) -- driver-timed; the it/s derived
   from it is a PROJECTION, not a measurement;
-* `--config c1|c2|c4|c5`: the other BASELINE configs through the same evaluator (`config.workload` names them; c4 adds the
+* `--config c1|c2|c4|c5`: the other BASELINE configs through the same evaluator (`config.workload` names them; with `--full`, c4 adds the
   finite-difference Hessian loop of `uma_pysis.py:595-686` on a bounded sample of its 2 x 3N_active displaced geometries);
 * `split_bf16_mode`: the same workload with the headline mode's forward pass and the fast mode's 16-bit reverse pass (`UMX_PRECISION=split-bf16`:
   the headline mode's energy bit for bit).
 * `fast_mode`: the same workload in the opt-in fast mode (`UMX_PRECISION=split`: 22-23-bit forward activations, 16-bit reverse
   products -- narrower than float32, hence not the headline) and `fp32_mode`: on the fp32 MFMA (`UMX_PRECISION=fp32`), a few
   steps each, timed the same way (N=1 only);
-* `gsm` (with `--driver gsm`): cycles of the real driver, `gsm.GrowingStringDriver`, on the fully grown string, and what the
+* `gsm` (with `--full`, `--driver gsm`): cycles of the real driver, `gsm.GrowingStringDriver`, on the fully grown string, and what the
   driver adds on top of the bare evaluation;
 * `cpu_baseline`: the repo's own CPU restatement (the reference's fairchem path cannot run here) on a bounded sample;
 * `dump_outputs` (with `--dump-outputs DIR`): what the last timed step returned, written to DIR as float64 .npy files (`dump_outputs()`),
@@ -194,15 +200,18 @@ def main():
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c3", help="BASELINE config (default c3, the headline); --atoms / --images override its sizes")
     ap.add_argument("--atoms", type=int, default=None)
     ap.add_argument("--images", type=int, default=None)
-    ap.add_argument("--no-shard", action="store_true", help="skip the `shard` leg (2-image batch + one-rank RCCL all-gather)")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: after the headline, run every other leg (serial_schedule, shard, split_bf16_mode, fast_mode, fp32_mode, hessian, gsm, "
+                         "cpu_baseline; the --no-* options and --driver choose among them).  Off: the run times the headline steps and nothing else")
+    ap.add_argument("--no-shard", action="store_true", help="--full: skip the `shard` leg (2-image batch + one-rank RCCL all-gather)")
     ap.add_argument("--shard-steps", type=int, default=20)
-    ap.add_argument("--no-serial", action="store_true", help="skip the `serial_schedule` side run (UMX_STREAMS=1)")
-    ap.add_argument("--hessian-sample-atoms", type=int, default=200, help="c4: atoms whose 3 DOF columns the FD-Hessian sample builds (2 x 3 x this many displaced geometries); 0 = the WHOLE Hessian of the config (every active column, device entry only: ~6.5 minutes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fp32-mode", action="store_true")
-    ap.add_argument("--no-fast-mode", action="store_true")
+    ap.add_argument("--no-serial", action="store_true", help="--full: skip the `serial_schedule` side run (UMX_STREAMS=1)")
+    ap.add_argument("--hessian-sample-atoms", type=int, default=200, help="--full, c4: atoms whose 3 DOF columns the FD-Hessian sample builds (2 x 3 x this many displaced geometries); 0 = the WHOLE Hessian of the config (every active column, device entry only: ~6.5 minutes)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the `cpu_baseline` leg")
+    ap.add_argument("--no-fp32-mode", action="store_true", help="--full: skip the `fp32_mode` leg")
+    ap.add_argument("--no-fast-mode", action="store_true", help="--full: skip the `fast_mode` and `split_bf16_mode` legs")
     ap.add_argument("--driver", choices=["string", "gsm"], default="gsm",
-                    help="gsm (default, N=1 only): additionally time cycles of the real driver, gsm.GrowingStringDriver, on the fully grown string "
+                    help="gsm (default; with --full, N=1 only): additionally time cycles of the real driver, gsm.GrowingStringDriver, on the fully grown string "
                          "(device resident) -> `gsm` object; string: skip that leg")
     ap.add_argument("--gsm-cycles", type=int, default=8)
     ap.add_argument("--fp32-steps", type=int, default=5)
@@ -547,11 +556,12 @@ def main():
         # families is timed as the remainder of the step; the fused radial-MLP kernels (VALU / fp32-MFMA bound, not HBM bound) are timed
         # live as their own family (ABI v7) and taken OUT of the HBM figure, so that `achieved` is not a blend of two bounds.
         # Two lanes (UMX_STREAMS=2 / UMX_LANES_AUTO_EDGES; not the default) overlap kernels of different families, so the remainder of the
-        # step is no longer "the other kernels": the family breakdown comes from a serial-schedule side run (UMX_STREAMS=1) of the same
-        # workload, the headline stays what the product does by default.
+        # step is no longer "the other kernels": with --full the family breakdown comes from a serial-schedule side run (UMX_STREAMS=1) of
+        # the same workload, the headline stays what the product does by default.
         two_lanes = lanes_used == 2
+        legs = args.full and world == 1                 # the legs beyond the headline: each takes runs of its own
         ser = None
-        if world == 1 and two_lanes and not args.no_serial:
+        if legs and two_lanes and not args.no_serial:
             try:
                 sdt, sprof, _, _, _, _ = run(mode_req, max(2, min(args.steps, 5)), 1, lanes="1")
                 ssteps = max(2, min(args.steps, 5))
@@ -581,7 +591,8 @@ def main():
             out["roofline"]["serial_schedule_frac"] = out["roofline"]["serial_schedule_achieved"] / peak
         hb = {"bound": "hbm", "kernels": "HBM-bound edge / node kernels: k_gather_rotate_mod_q3, k_modrot_bwd_pl, k_gate_edge_*, k_rotate_back_*, norms, graph build "
                                          "(everything outside the GEMM families and the fused radial-MLP kernels)",
-              "ms_per_step": edge_ms, "schedule": "serial side run (UMX_STREAMS=1)" if ser else "the timed region (one lane)",
+              "ms_per_step": edge_ms, "schedule": ("serial side run (UMX_STREAMS=1)" if ser else "the timed region (one lane)" if not two_lanes
+                                                   else "the timed region (two lanes: the families overlap, so this remainder is not theirs alone)"),
               "peak": PEAK_HBM_GBPS, "unit": "GB/s", "traffic_per_step": None, "achieved": None, "frac": None,
               "traffic_source": pmc_note,
               "radial": {"kernels": "k_radial_head / k_radial_tail (fused radial-MLP layers: libm-accurate VALU transcendentals + fp32 MFMA)", "bound": "valu/mfma-f32",
@@ -620,22 +631,22 @@ def main():
             except Exception as exc:
                 return {"value": None, "error": f"{type(exc).__name__}: {exc}"}
 
-        if world == 1 and not args.no_fast_mode and mode != "split":
+        if legs and not args.no_fast_mode and mode != "split":
             # the FAST mode (opt-in, UMX_PRECISION=split): 22-23 bit forward activations, 16-bit reverse products -- narrower than the
             # reference's float32, so it is NOT the headline; tolerances are met with margin (tests/test_gpu_baseline_sizes.py)
             out["fast_mode"] = side_mode("split", args.fp32_steps, args.fp32_warmup, "split_bf16", PEAK_BF16_MFMA_TFLOPS,
                                          "f16-split (fwd 2 x 3 fp16 planes / 4 products, reverse 2 x 2 bf16 planes / 3 products): narrower than float32")
-        if world == 1 and not args.no_fast_mode and mode == "bf16x3":
+        if legs and not args.no_fast_mode and mode == "bf16x3":
             # split-bf16: the headline mode's forward pass (its ENERGY bit for bit) with the fast mode's 16-bit reverse pass (forces <= 7e-6 eV/A off)
             out["split_bf16_mode"] = side_mode("split-bf16", args.fp32_steps, args.fp32_warmup, "split_bf16", PEAK_BF16_MFMA_TFLOPS,
                                                "bf16-split (fwd as the headline: 3 x 3 bf16 planes / 6 products; reverse 2 x 2 bf16 planes / 3 products): "
                                                "the headline mode's energy, a 16-bit reverse pass")
-        if world == 1 and split and not args.no_fp32_mode:
+        if legs and split and not args.no_fp32_mode:
             # every GEMM on v_mfma_f32_32x32x2_f32: the same float32 products as the headline mode's, on the fp32 matrix pipe
             out["fp32_mode"] = side_mode("fp32", args.fp32_steps, args.fp32_warmup, "fp32", PEAK_FP32_MFMA_TFLOPS, "f32 (all GEMMs on v_mfma_f32_32x32x2_f32)")
         os.environ["UMX_PRECISION"] = mode_req
         shard_images = {"c3": 2, "c4": 3, "c5": 1}.get(args.config) if (n, k) == CONFIGS[args.config][:2] else None
-        if world == 1 and shard_images and not args.no_shard:
+        if legs and shard_images and not args.no_shard:
             # what ONE rank of the 8-GPU run does per iteration (BASELINE c3: "16 images sharded 2-images/GPU across 8 x MI355X"): the 2-image batch
             # through the same evaluator + the all-gather, issued for real on a one-rank RCCL group (nccl backend; the identity, but the call, its
             # stream ordering and its latency are there).  Driver-timed; any it/s derived from it is a projection of the 8-GPU run, not a measurement.
@@ -659,17 +670,17 @@ def main():
                                         "are not in it), not a measurement -- RCCL has never run on more than one rank here"}
             except Exception as exc:
                 out["shard"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if world == 1 and args.config == "c4":
+        if legs and args.config == "c4":
             try:
                 out["hessian"] = run_hessian(mode_req, args.hessian_sample_atoms)
             except Exception as exc:
                 out["hessian"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if world == 1 and args.driver == "gsm":
+        if legs and args.driver == "gsm":
             try:
                 out["gsm"] = run_gsm(mode_req, args.gsm_cycles, 3)
             except Exception as exc:
                 out["gsm"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if world == 1 and not args.no_cpu_baseline and args.config == "c3":
+        if legs and not args.no_cpu_baseline and args.config == "c3":
             try:
                 out["cpu_baseline"] = cpu_baseline(edges_iter, n, k)
             except Exception as exc:  # the baseline is informative; never lose the GPU numbers to it

@@ -12,7 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_json_line_contract():
-    out = subprocess.run([sys.executable, "bench.py", "--atoms", "60", "--images", "4", "--steps", "2", "--warmup", "1", "--driver", "gsm", "--gsm-cycles", "4"],
+    """`--full`: the headline and every leg beside it."""
+    out = subprocess.run([sys.executable, "bench.py", "--atoms", "60", "--images", "4", "--steps", "2", "--warmup", "1", "--driver", "gsm", "--gsm-cycles", "4", "--full"],
                          cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -56,18 +57,44 @@ def test_bench_json_line_contract():
     assert "c1 in full" in c["sample"] and "3 of 12 images" in c["sample"] and c["c3_images_timed"] in (1, 2)
 
 
+LEGS = ("serial_schedule", "shard", "split_bf16_mode", "fast_mode", "fp32_mode", "hessian", "gsm", "cpu_baseline")
+
+
+def test_bench_plain_run_is_the_headline_alone():
+    """Without `--full` the run times the headline steps and prints the line: the contract's keys and the roofline read off the
+    timed steps, and none of the legs that take runs of their own -- `--driver gsm` and c4's Hessian included."""
+    for cfg in (["--atoms", "60", "--images", "4"], ["--config", "c4", "--atoms", "120", "--images", "6"]):
+        out = subprocess.run([sys.executable, "bench.py", *cfg, "--steps", "2", "--warmup", "1", "--driver", "gsm"],
+                             cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                    "dtype", "data", "config", "roofline"):
+            assert key in d, key
+        assert d["metric"] == "path_opt_string_iterations_per_s" and d["unit"] == "iterations/s" and d["higher_is_better"] is True
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-6
+        assert d["precision_mode"] == "bf16x3" and d["dtype"] == "bf16x3-split"
+        r = d["roofline"]
+        assert 0.0 < r["frac"] < 1.0 and r["lanes"] == 1
+        hb = r["hbm_regime"]
+        assert hb["ms_per_step"] + hb["radial"]["ms_per_step"] + r["ms_per_step"] + r["other_gemm_family"]["ms_per_step"] == pytest.approx(d["ms_per_step"], rel=1e-9)
+        assert [leg for leg in LEGS if leg in d] == []
+
+
 def test_bench_other_configs_and_the_hessian_leg():
-    """`--config`: the BASELINE configs the headline line does not carry -- c1 in full, and c4's FD-Hessian leg on a
+    """`--config ... --full`: the BASELINE configs the headline line does not carry -- c1 in full, and c4's FD-Hessian leg on a
     reduced size so the test stays short (the loop, its accounting and the extrapolation are what is checked; profiles/r05_bench_c4.json
     has the real size)."""
-    out = subprocess.run([sys.executable, "bench.py", "--config", "c1", "--steps", "3", "--warmup", "1", "--driver", "string", "--no-fp32-mode", "--no-fast-mode"],
-                         cwd=ROOT, capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, "bench.py", "--config", "c1", "--steps", "3", "--warmup", "1", "--driver", "string", "--no-fp32-mode", "--no-fast-mode",
+                          "--full"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["config"]["name"] == "c1" and d["config"]["atoms"] == 50 and d["config"]["images"] == 8 and d["config"]["workload"].startswith("c1: 50-atom")
     assert "cpu_baseline" not in d and d["roofline"]["frac"] > 0
     out = subprocess.run([sys.executable, "bench.py", "--config", "c4", "--atoms", "120", "--images", "6", "--steps", "2", "--warmup", "1", "--driver", "string",
-                          "--no-fp32-mode", "--no-fast-mode", "--hessian-sample-atoms", "4"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                          "--no-fp32-mode", "--no-fast-mode", "--hessian-sample-atoms", "4", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     h = d["hessian"]

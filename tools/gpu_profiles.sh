@@ -35,13 +35,13 @@ fi
 if [ $STEP = all ] || [ $STEP = bench ]; then
 echo "== 4. bench line (AFTER the PMC summaries, so that the traffic figure is the one of this very build)" &&
 { [ ! -f $P/${RND}_pmc_hbm_traffic_bf16x3.json ] || cp $P/${RND}_pmc_hbm_traffic_bf16x3.json $P/${RND}_pmc_hbm_traffic_split.json profiles/; } &&   # (a separate gpurun call: the caller has copied them into profiles/ already)
-( TIMEFORMAT="%R s wall"; { time timeout -k 10 900 python3 bench.py --steps 5 --warmup 2 --driver gsm --gsm-cycles 10 > $O/bench.log 2> $O/bench.err; } 2> $P/${RND}_bench_c3_n1.walltime ) &&
+( TIMEFORMAT="%R s wall"; { time timeout -k 10 900 python3 bench.py --steps 5 --warmup 2 --driver gsm --gsm-cycles 10 --full > $O/bench.log 2> $O/bench.err; } 2> $P/${RND}_bench_c3_n1.walltime ) &&
 grep '^{' $O/bench.log | tail -n 1 > $P/${RND}_bench_c3_n1.json || exit 1
 fi
 if [ $STEP = all ] || [ $STEP = cfg ]; then
 echo "== 5. the other BASELINE configs: bench lines (bench.py --config), kernel stats of c1 / c2 / c5" &&
-for c in c1 c2 c4; do timeout -k 10 700 python3 bench.py --config $c --steps 5 --warmup 2 --no-fp32-mode --no-fast-mode --driver string > $O/bench_$c.log 2>&1 && grep '^{' $O/bench_$c.log | tail -n 1 > $P/${RND}_bench_$c.json || exit 1; done
-timeout -k 10 500 python3 bench.py --config c5 --steps 2 --warmup 1 --no-fp32-mode --no-fast-mode --driver string > $O/bench_c5.log 2>&1 && grep '^{' $O/bench_c5.log | tail -n 1 > $P/${RND}_bench_c5.json || exit 1
+for c in c1 c2 c4; do timeout -k 10 700 python3 bench.py --config $c --steps 5 --warmup 2 --no-fp32-mode --no-fast-mode --driver string --full > $O/bench_$c.log 2>&1 && grep '^{' $O/bench_$c.log | tail -n 1 > $P/${RND}_bench_$c.json || exit 1; done
+timeout -k 10 500 python3 bench.py --config c5 --steps 2 --warmup 1 --no-fp32-mode --no-fast-mode --driver string --full > $O/bench_c5.log 2>&1 && grep '^{' $O/bench_c5.log | tail -n 1 > $P/${RND}_bench_c5.json || exit 1
 rocprofv3 --kernel-trace --stats -d $O/c2 -o kt -f csv -- python3 tools/gpu_eval_config.py c2 5 > $O/c2.log 2>&1 &&
 ( echo "# rocprofv3 --kernel-trace --stats -- python3 tools/gpu_eval_config.py c2 5  (MI355X, round 6: c2 = 500 atoms x 12 images, 7 batched E+F evaluations incl. 2 warm-up, default mode bf16x3)"; cat $O/c2/kt_kernel_stats.csv ) > $P/${RND}_c2_kernel_stats_bf16x3.csv &&
 rocprofv3 --kernel-trace --stats -d $O/c1 -o kt -f csv -- python3 tools/gpu_eval_config.py c1 20 > $O/c1.log 2>&1 &&
