@@ -53,7 +53,7 @@ const char* umx_build_digest(void);
 int umx_create(umx_engine** out, int device_ordinal);
 int umx_destroy(umx_engine* eng);
 
-/* Text of the last error on this engine (or of the last failed umx_create when eng == NULL).   */
+/* Text of the last error on this engine (or of the last failed umx_create / umx_peer_sum when eng == NULL). */
 const char* umx_last_error(const umx_engine* eng);
 
 /* Load a merged UMA-S parameter set from a host-memory UMXW0001 blob
@@ -184,6 +184,21 @@ int umx_energy_forces_dev(umx_engine* eng, int n_images, const float* d_pos_ang,
 int umx_gp_begin(umx_engine* eng, const float* d_pos_ang, int node_lo, int node_hi, double* d_energy_ev,
                  float* d_forces_ev_ang, void* hip_stream);
 int umx_gp_step(umx_engine* eng, float** d_buf, size_t* count, int* done);
+
+/* In-process exchange for graph-parallel participants that live in ONE process (parallel.LocalEnginePool: G engines, one host thread;
+ * no reference counterpart -- the reference's workers exchange through Ray / torch.distributed, uma_pysis.py:228-242).  Sums the
+ * `n_peers` float32 device buffers `d_bufs[r][0..count)` element-wise IN PLACE, so that afterwards EVERY buffer holds
+ * ((b0[i] + b1[i]) + b2[i]) + ... in float32, added in list order without FMA contraction -- the same bits in every buffer, and
+ * what numpy's float32 addition in that order gives.  Buffer r belongs to the participant on device `device_ordinals[r]` whose work
+ * is ordered on `hip_streams[r]` (the stream handed to umx_gp_begin; NULL = that device's legacy default stream): all work of the
+ * exchange is enqueued on those streams and ordered among them with HIP events (hipStreamWaitEvent), nothing blocks the host.  The
+ * buffer is cut into n_peers slices on 16-byte boundaries (any count: empty slices and a ragged tail included); participant r reads
+ * slice r of every buffer, adds, and pushes the result into slice r of every buffer.  Buffers must be 16-byte aligned and distinct;
+ * they may all live on one device (the one-GPU rehearsal), otherwise peer access is enabled once per device pair and the call refuses
+ * (UMX_ERR_HIP) when it cannot be.  Takes no engine: the error text is umx_last_error(NULL).  One caller at a time (the event set is
+ * shared).  n_peers <= 16.  Additive to ABI v10.  More than one physical device has never run: peer access, cross-device events and
+ * xGMI traffic are unmeasured.                                                                                                    */
+int umx_peer_sum(int n_peers, float* const* d_bufs, size_t count, const int* device_ordinals, void* const* hip_streams);
 
 /* Block until all work enqueued by this engine has finished (including work it put on a
  * caller's stream through umx_energy_forces_dev).  Returns UMX_ERR_RANGE (and clears the flag) when a

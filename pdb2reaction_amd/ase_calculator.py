@@ -49,8 +49,13 @@ class UMXCalculator(_AseBase):
     implemented_properties = ["energy", "forces"]
 
     def __init__(self, model: str = "uma-s-1p1", task_name: str = "omol", device: str = "auto", charge: int = 0, spin: int = 1,
-                 radius: Optional[float] = None, max_neigh: Optional[int] = None, **kwargs):
+                 radius: Optional[float] = None, max_neigh: Optional[int] = None, workers: int = 1, **kwargs):
+        """workers > 1 (outside a torch.distributed process group): that many engines in this process when there are that many
+        devices (``UMX_LOCAL_DEVICES`` names them), as in ``uma_pysis.UMAcore`` -- ``calculate_images`` deals its images over them,
+        a single image is evaluated graph-parallel (``parallel.LocalEnginePool``); ``local_devices`` lists the ordinals in use."""
         super().__init__(**kwargs)
+        self.workers = max(int(workers or 1), 1)
+        self.local_devices = None
         self.model, self.task_name, self.device = model, task_name, device
         self.default_charge, self.default_spin = int(charge), int(spin)
         self.radius, self.max_neigh = radius, max_neigh
@@ -71,8 +76,18 @@ class UMXCalculator(_AseBase):
         charge, spin = int(info.get("charge", self.default_charge)), int(info.get("spin", self.default_spin))
         if self._engine is None:
             self._weights = resolve_weights(self.model)
-            self._engine = Engine(_device_index(self.device))
-            self._engine.load_weights(self._weights)
+            pool_devices = None
+            if self.workers > 1:
+                from . import parallel as P
+
+                if not P.process_group_active():
+                    pool_devices = P.local_devices_for(self.workers)
+            if pool_devices is not None:
+                self._engine = P.LocalEnginePool.create(pool_devices, self._weights, engine_factory=Engine)     # same methods as one engine
+            else:
+                self._engine = Engine(_device_index(self.device))
+                self._engine.load_weights(self._weights)
+            self.local_devices = list(pool_devices) if pool_devices is not None else [_device_index(self.device)]
             from ._host import cap_pools_to_usable_cores
 
             cap_pools_to_usable_cores()          # the DMF driver's dense linear algebra between two calls must not starve the GPU feeder

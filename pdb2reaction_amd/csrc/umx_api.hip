@@ -15,6 +15,7 @@
 #include <cstring>
 #include <functional>
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -26,6 +27,7 @@
 #include "umx_kernels_pl.h"
 #include "umx_kernels.h"
 #include "umx_radial.h"
+#include "umx_peer.h"
 
 using namespace umx;
 
@@ -2008,6 +2010,89 @@ int umx_gp_step(umx_engine* eng, float** d_buf, size_t* count, int* done) {
   }
   gp_clear(eng);
   return st;
+}
+
+// ---- in-process peer sum (umx_peer.h) -----------------------------------------------------------------------------------------------
+namespace {
+struct PeerState {
+  hipEvent_t ev_in[PEER_MAX] = {}, ev_out[PEER_MAX] = {};   // per participant: "my buffer is ready" / "my slice has landed everywhere"
+  int ev_dev[PEER_MAX];
+  std::set<std::pair<int, int>> enabled;                    // device pairs whose peer access is on
+  PeerState() { for (int& d : ev_dev) d = -1; }
+} g_peer;
+
+int peer_fail(int code, const std::string& msg) { g_create_err = msg; return code; }
+
+#define PEERCHK(expr)                                                                                          \
+  do {                                                                                                         \
+    hipError_t _e = (expr);                                                                                    \
+    if (_e != hipSuccess) { (void)hipSetDevice(dev0); return peer_fail(UMX_ERR_HIP, std::string("umx_peer_sum: " #expr ": ") + hipGetErrorName(_e)); } \
+  } while (0)
+}  // namespace
+
+int umx_peer_sum(int n_peers, float* const* d_bufs, size_t count, const int* device_ordinals, void* const* hip_streams) {
+  if (n_peers < 1 || n_peers > PEER_MAX || !d_bufs || !device_ordinals || !hip_streams)
+    return peer_fail(UMX_ERR_ARG, "umx_peer_sum: 1.." + std::to_string(PEER_MAX) + " participants with buffers, device ordinals and streams");
+  int ndev = 0, dev0 = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev0) != hipSuccess) return peer_fail(UMX_ERR_NO_DEVICE, "umx_peer_sum: no HIP device visible");
+  PeerBufs b{};
+  for (int r = 0; r < n_peers; ++r) {
+    if (!d_bufs[r] || (reinterpret_cast<uintptr_t>(d_bufs[r]) & 15) != 0) return peer_fail(UMX_ERR_ARG, "umx_peer_sum: buffer " + std::to_string(r) + " is null or not 16-byte aligned");
+    if (device_ordinals[r] < 0 || device_ordinals[r] >= ndev) return peer_fail(UMX_ERR_ARG, "umx_peer_sum: device ordinal of participant " + std::to_string(r) + " out of range");
+    for (int q = 0; q < r; ++q)
+      if (d_bufs[q] == d_bufs[r]) return peer_fail(UMX_ERR_ARG, "umx_peer_sum: participants " + std::to_string(q) + " and " + std::to_string(r) + " list the same buffer");
+    b.p[r] = d_bufs[r];
+  }
+  if (n_peers == 1 || count == 0) return UMX_OK;
+  // peer access, once per ordered device pair (nothing to do when all buffers share a device)
+  for (int r = 0; r < n_peers; ++r)
+    for (int q = 0; q < n_peers; ++q) {
+      const int a = device_ordinals[r], c = device_ordinals[q];
+      if (a == c || g_peer.enabled.count({a, c})) continue;
+      int can = 0;
+      PEERCHK(hipDeviceCanAccessPeer(&can, a, c));
+      if (!can) return peer_fail(UMX_ERR_HIP, "umx_peer_sum: device " + std::to_string(a) + " cannot access the memory of device " + std::to_string(c) +
+                                 " (hipDeviceCanAccessPeer = 0): the in-process pool needs peer access between all of its devices");
+      PEERCHK(hipSetDevice(a));
+      const hipError_t e = hipDeviceEnablePeerAccess(c, 0);
+      if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) {
+        (void)hipSetDevice(dev0);
+        return peer_fail(UMX_ERR_HIP, "umx_peer_sum: peer access from device " + std::to_string(a) + " to device " + std::to_string(c) + " cannot be enabled: " + hipGetErrorName(e));
+      }
+      (void)hipGetLastError();
+      g_peer.enabled.insert({a, c});
+    }
+  for (int r = 0; r < n_peers; ++r) {
+    if (g_peer.ev_dev[r] == device_ordinals[r]) continue;
+    if (g_peer.ev_dev[r] >= 0) { PEERCHK(hipSetDevice(g_peer.ev_dev[r])); (void)hipEventDestroy(g_peer.ev_in[r]); (void)hipEventDestroy(g_peer.ev_out[r]); g_peer.ev_dev[r] = -1; }
+    PEERCHK(hipSetDevice(device_ordinals[r]));
+    PEERCHK(hipEventCreateWithFlags(&g_peer.ev_in[r], hipEventDisableTiming));
+    PEERCHK(hipEventCreateWithFlags(&g_peer.ev_out[r], hipEventDisableTiming));
+    g_peer.ev_dev[r] = device_ordinals[r];
+  }
+  // opening barrier: every buffer is complete (and no longer read by its owner's earlier work) before a peer reads or writes it
+  for (int r = 0; r < n_peers; ++r) {
+    PEERCHK(hipSetDevice(device_ordinals[r]));
+    PEERCHK(hipEventRecord(g_peer.ev_in[r], static_cast<hipStream_t>(hip_streams[r])));
+  }
+  for (int r = 0; r < n_peers; ++r) {
+    hipStream_t s = static_cast<hipStream_t>(hip_streams[r]);
+    PEERCHK(hipSetDevice(device_ordinals[r]));
+    for (int q = 0; q < n_peers; ++q)
+      if (q != r) PEERCHK(hipStreamWaitEvent(s, g_peer.ev_in[q], 0));
+    size_t lo, hi;
+    peer_slice(count, n_peers, r, &lo, &hi);
+    PEERCHK(launch_peer_sum(b, n_peers, lo, hi, s));
+    PEERCHK(hipEventRecord(g_peer.ev_out[r], s));
+  }
+  // closing barrier: a participant goes on only when every peer's slice has landed in its buffer
+  for (int r = 0; r < n_peers; ++r) {
+    PEERCHK(hipSetDevice(device_ordinals[r]));
+    for (int q = 0; q < n_peers; ++q)
+      if (q != r) PEERCHK(hipStreamWaitEvent(static_cast<hipStream_t>(hip_streams[r]), g_peer.ev_out[q], 0));
+  }
+  (void)hipSetDevice(dev0);
+  return UMX_OK;
 }
 
 int umx_energy_forces(umx_engine* eng, int n_images, const float* pos, double* energy, float* forces) {

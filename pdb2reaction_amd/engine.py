@@ -78,6 +78,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "umx_energy_forces_dev": ([vp, i32, vp, vp, vp, vp], i32),
         "umx_gp_begin": ([vp, vp, i32, i32, vp, vp, vp], i32),
         "umx_gp_step": ([vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(i32)], i32),
+        "umx_peer_sum": ([i32, C.POINTER(vp), C.c_size_t, C.POINTER(i32), C.POINTER(vp)], i32),
         "umx_synchronize": ([vp], i32),
         "umx_last_graph_stats": ([vp, i64p, C.POINTER(C.c_int32)], i32),
         "umx_last_partitions": ([vp], i32),
@@ -120,13 +121,31 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 
 EXPORTED_SYMBOLS = (
     "umx_abi_version", "umx_build_digest", "umx_create", "umx_destroy", "umx_last_error", "umx_load_weights", "umx_set_precision", "umx_precision_mode", "umx_model_variant", "umx_set_system",
-    "umx_set_workspace_limit", "umx_energy_forces", "umx_energy_forces_dev", "umx_gp_begin", "umx_gp_step", "umx_synchronize",
+    "umx_set_workspace_limit", "umx_energy_forces", "umx_energy_forces_dev", "umx_gp_begin", "umx_gp_step", "umx_peer_sum", "umx_synchronize",
     "umx_last_graph_stats", "umx_last_partitions", "umx_last_lanes", "umx_reserve_images", "umx_workspace_stats", "umx_profile_enable", "umx_profile_read", "umx_bond_changes", "umx_debug_fetch", "umx_debug_keep",
 )
 
 
+def peer_sum(ptrs: Sequence[int], count: int, devices: Sequence[int], streams: Sequence[int]) -> None:
+    """``umx_peer_sum``: sum the float32 device buffers ``ptrs[r][0:count]`` in place, in list order, so that every buffer holds the
+    same bits afterwards; buffer r belongs to device ``devices[r]`` and is ordered on the ``hipStream_t`` handle ``streams[r]``
+    (0 = that device's legacy default stream).  Enqueues only; the host does not wait."""
+    lib = load_library()
+    n = len(ptrs)
+    if len(devices) != n or len(streams) != n:
+        raise ValueError(f"peer_sum: {n} buffers, {len(devices)} devices, {len(streams)} streams")
+    bufs = (C.c_void_p * n)(*[int(p) for p in ptrs])
+    devs = (C.c_int * n)(*[int(d) for d in devices])
+    strs = (C.c_void_p * n)(*[int(s) or None for s in streams])
+    st = lib.umx_peer_sum(n, bufs, int(count), devs, strs)
+    if st != 0:
+        err = UmxError(f"umx_peer_sum failed ({st}): {lib.umx_last_error(None).decode()}")
+        err.status = st
+        raise err
+
+
 class Engine:
-    """One UMA-S engine on one GPU (one per process/rank)."""
+    """One UMA-S engine on one GPU (one per process/rank, or several per process in a ``parallel.LocalEnginePool``)."""
 
     def __init__(self, device: int = 0, precision: Optional[str] = None):
         """precision: None = the UMX_PRECISION environment variable (default "auto" = "bf16x3": 3 x 3 bf16 planes / 6 products in both

@@ -1,10 +1,15 @@
-"""Multi-GPU evaluation of a reaction string: one process per GPU.
+"""Multi-GPU evaluation of a reaction string: one process per GPU (1, 2), or several GPUs from ONE process (3).
 
 1. IMAGE SHARDING (the default): images of one string split into contiguous blocks, ONE all-gather of
    per-image [E | F(3N)] (float64) per string iteration -- :class:`ShardedImageEvaluator`.
 2. GRAPH-PARALLEL SINGLE IMAGE (rows a12 / f4; for fewer images than GPUs, e.g. one 20 000-atom structure): the
    reference's ``workers > 1`` semantics (``uma_pysis.py:220-242``) -- the graph of ONE image partitioned by target node over
    the ranks, node-level buffers all-reduced at the engine's exchange points -- :class:`GraphParallelEvaluator`.
+3. LOCAL ENGINE POOL: G engines in one process, no ``torch.distributed`` and no launcher -- what the reference's single-process
+   ``workers=G`` calculator does (``uma_pysis.py:220-242``, ``path_opt.py:545-559,823``).  Batches are dealt over the engines in
+   the blocks of (1), one host thread per engine; one image is evaluated graph-parallel as in (2) with the exchange done by
+   ``umx_peer_sum`` (the engines' partial-sum buffers are addressable from every device of the process) --
+   :class:`LocalEnginePool`.
 
 The reference evaluates the images serially through one shared calculator (``path_opt.py:949-954``,
 ``GS_KW["scheduler"] = None`` at ``path_opt.py:184``); its ``workers>1`` knob is graph-parallelism
@@ -15,8 +20,11 @@ string update.  Payload at 2000 atoms x 16 images: 768 KB -> latency bound, a si
 """
 from __future__ import annotations
 
-from typing import Callable, Optional, Sequence, Tuple
+import os
+from concurrent.futures import ThreadPoolExecutor
+from typing import Callable, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -325,3 +333,281 @@ class EngineStringEvaluator(ShardedStringEvaluator):
         if self._frozen.numel():
             f[:, self._frozen, :] = 0.0                                              # uma_pysis.py:561-567
         return self._e[:kl] * self._e2h, f
+
+
+# ================================================================================================================================
+#                                   several engines in ONE process (no process group)
+# ================================================================================================================================
+def process_group_active() -> bool:
+    return bool(dist.is_available() and dist.is_initialized())
+
+
+def local_devices_for(workers: int, device_count: Optional[Callable[[], int]] = None) -> Optional[List[int]]:
+    """Device ordinals of an in-process pool for ``workers`` (> 1) engines, or None when there is nothing to build one from.
+
+    ``UMX_LOCAL_DEVICES="0,1,2,3"`` names them explicitly; an ordinal may repeat (``"0,0"``: several engines share that device -- the
+    rehearsal of the path on a one-GPU box).  Its length must equal ``workers`` (``ValueError`` otherwise).  Without the variable: the
+    first ``workers`` visible devices when there are that many, else None (the caller keeps its single engine)."""
+    workers = int(workers)
+    env = os.environ.get("UMX_LOCAL_DEVICES", "").strip()
+    if env:
+        try:
+            devs = [int(t) for t in env.split(",")]
+        except ValueError:
+            raise ValueError(f"UMX_LOCAL_DEVICES={env!r}: expected comma-separated device ordinals such as '0,1,2,3'") from None
+        if any(d < 0 for d in devs):
+            raise ValueError(f"UMX_LOCAL_DEVICES={env!r}: device ordinals are non-negative")
+        if len(devs) != workers:
+            raise ValueError(f"UMX_LOCAL_DEVICES={env!r} names {len(devs)} device(s) but workers={workers}: the two must agree")
+        return devs
+    n = int(device_count() if device_count is not None else torch.cuda.device_count())
+    return list(range(workers)) if workers > 1 and n >= workers else None
+
+
+def shared_workspace_limits(devices: Sequence[int], free_bytes: Callable[[int], int]) -> List[int]:
+    """Workspace cap in bytes per engine of a pool (0 = leave the engine's own rule): engines that share a device ordinal share its
+    HBM, so the cap one engine would have -- ``UMX_WS_GB`` GiB (default 160), but no more than the automatic 85 % of what is free on
+    the device now, which is all there is with ``UMX_WS_GB=0`` -- is divided among them."""
+    devices = [int(d) for d in devices]
+    env_gb = int(os.environ.get("UMX_WS_GB", "160") or 0)
+    out = []
+    for d in devices:
+        share = devices.count(d)
+        if share == 1:
+            out.append(0)
+            continue
+        cap = int(free_bytes(d) * 0.85)
+        if env_gb > 0:
+            cap = min(cap, env_gb << 30)
+        out.append(max(cap // share, 1))
+    return out
+
+
+class LocalEnginePool:
+    """G engines owned by ONE process, one per listed device ordinal, all with the same weights, precision mode and system.
+
+    * ``energy_forces(coords[K,N,3])`` with K >= 2: engine r evaluates the contiguous block ``shard_bounds(K, G, r)`` on a host
+      thread of its own (the ctypes call releases the GIL); results are concatenated in image order.  Engines whose block is empty
+      do nothing.  Results do not depend on how a batch is chunked (include/umx.h), so this IS the single-engine result, bit for bit.
+      When engines raise, all threads are joined first and the error of the lowest engine index is raised.  An fp16 range violation
+      (fast split-f16 mode) that widened one engine widens ALL of them and the whole batch is evaluated again, so that one result
+      never mixes two arithmetics.
+    * K == 1: graph-parallel over the pool (unless ``gp=False`` / ``UMX_WORKERS_GP=0``: engine 0 alone).  Engine r builds the incoming
+      edges of the target nodes ``shard_bounds(N, G, r)``; all engines step to the next exchange point, ``umx_peer_sum`` adds their
+      partial-sum buffers in place in engine order, and so on until done (10 exchanges).  Energies and forces are then complete --
+      and identical in every bit -- on every engine; engine 0's are returned.
+
+    More than one PHYSICAL device has never run: two engines on device 0 show the host path and the sum only.
+    """
+
+    def __init__(self, engines: Sequence, *, gp: Optional[bool] = None, peer_sum: Optional[Callable] = None,
+                 tensor_device: Optional[Callable] = None, free_bytes: Optional[Callable[[int], int]] = None):
+        """engines: G engines (``engine.Engine`` or anything with its methods), weights loaded; ``create`` builds them.
+        gp: None = the ``UMX_WORKERS_GP`` switch (default on).  peer_sum / tensor_device / free_bytes: the device exchange
+        (``engine.peer_sum``), where engine r's staging tensors live (``cuda:<engine.device>``) and the free HBM of an ordinal
+        (``torch.cuda.mem_get_info``) -- replaceable so that the host logic can be exercised without a GPU."""
+        if len(engines) < 1:
+            raise ValueError("LocalEnginePool needs at least one engine")
+        self.engines = list(engines)
+        self.devices = [int(e.device) for e in self.engines]
+        self.gp = (os.environ.get("UMX_WORKERS_GP", "1") != "0") if gp is None else bool(gp)
+        if peer_sum is None:
+            from .engine import peer_sum
+        self._peer_sum = peer_sum
+        self._tensor_device = tensor_device or (lambda eng: torch.device("cuda", int(eng.device)))
+        self._threads = ThreadPoolExecutor(max_workers=len(self.engines), thread_name_prefix="umx-pool")
+        self._gp_buf = None                     # per engine: (device, stream, pos, e, f) of the graph-parallel route, made at first use
+        self.natoms = int(getattr(self.engines[0], "natoms", 0) or 0)
+        self.n_exchanges = 0                    # exchange points of the most recent one-image evaluation
+        self.last_route = None                  # "batch" | "graph-parallel" | "single"
+        self.last_blocks: List[Tuple[int, int]] = []
+        self.last_all = None                    # graph-parallel route: [(E, F)] of EVERY engine (they must agree in every bit)
+        if len(set(self.devices)) < len(self.devices):
+            free = free_bytes or (lambda d: torch.cuda.mem_get_info(d)[0])
+            for eng, lim in zip(self.engines, shared_workspace_limits(self.devices, free)):
+                if lim:
+                    eng.set_workspace_limit(lim)
+
+    @classmethod
+    def create(cls, devices: Sequence[int], weights, *, precision: Optional[str] = None, engine_factory: Optional[Callable] = None,
+               **pool_kw) -> "LocalEnginePool":
+        """One engine per entry of ``devices`` (ordinals may repeat), each loaded with ``weights``; bind the system with ``set_system``."""
+        if engine_factory is None:
+            from .engine import Engine as engine_factory
+        engines = []
+        try:
+            for d in devices:
+                eng = engine_factory(int(d), precision=precision)
+                engines.append(eng)
+                eng.load_weights(weights)
+        except Exception:
+            for eng in engines:
+                eng.close()
+            raise
+        return cls(engines, **pool_kw)
+
+    def __len__(self) -> int:
+        return len(self.engines)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def close(self) -> None:
+        self._gp_buf = None
+        for eng in self.engines:
+            eng.close()
+        self.engines = []
+        self._threads.shutdown(wait=True)
+
+    # ---- the same setup on every engine ------------------------------------------------------------------------------------------
+    def set_system(self, atomic_numbers, **kw) -> None:
+        for eng in self.engines:
+            eng.set_system(atomic_numbers, **kw)
+        self.natoms = len(atomic_numbers)
+        self._gp_buf = None
+
+    def reserve_images(self, n_images: int) -> None:
+        """Batches of up to ``n_images`` images are coming: every engine is told its share (``umx_reserve_images``)."""
+        g = len(self.engines)
+        for r, eng in enumerate(self.engines):
+            lo, hi = shard_bounds(int(n_images), g, r)
+            eng.reserve_images(hi - lo)
+
+    def precision_mode(self) -> str:
+        return self.engines[0].precision_mode()
+
+    # ---- evaluation --------------------------------------------------------------------------------------------------------------
+    def _run_all(self, fn: Callable[[int], object], ranks: Sequence[int]) -> list:
+        """fn(r) for every r of ``ranks``, one host thread each; every thread has ended before this returns or raises; the error of
+        the lowest engine index wins."""
+        futs = [(r, self._threads.submit(fn, r)) for r in ranks]
+        out, first = {}, None
+        for r, fu in futs:
+            try:
+                out[r] = fu.result()
+            except BaseException as exc:      # noqa: BLE001 -- collected; the other threads are still joined
+                if first is None:
+                    first = exc
+        if first is not None:
+            raise first
+        return [out[r] for r in ranks]
+
+    def _widen_all(self, why: str) -> None:
+        for eng in self.engines:
+            if not getattr(eng, "widened", False):
+                eng.widen(why)
+
+    def energy_forces(self, pos_ang, forces: bool = True) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        """pos_ang: (K,N,3) or (N,3) Angstrom -> (E [K] eV float64, F [K,N,3] eV/A float32 | None): ``Engine.energy_forces`` over the pool."""
+        p = np.ascontiguousarray(pos_ang, dtype=np.float32)
+        if p.ndim == 2:
+            p = p[None]
+        if p.ndim != 3 or p.shape[1] != self.natoms or p.shape[2] != 3:
+            raise ValueError(f"positions must be (K,{self.natoms},3), got {p.shape}")
+        k, g = p.shape[0], len(self.engines)
+        if k == 1:
+            if self.gp and g > 1:
+                return self._graph_parallel(p[0], forces)
+            self.last_route, self.last_blocks = "single", [(0, 1)]
+            return self.engines[0].energy_forces(p, forces=forces)
+        blocks = [shard_bounds(k, g, r) for r in range(g)]
+        busy = [r for r in range(g) if blocks[r][1] > blocks[r][0]]
+        self.last_route, self.last_blocks = "batch", blocks
+        for attempt in range(2):
+            was_wide = [bool(getattr(eng, "widened", False)) for eng in self.engines]
+            res = self._run_all(lambda r: self.engines[r].energy_forces(p[blocks[r][0]: blocks[r][1]], forces=forces), busy)
+            now_wide = [bool(getattr(eng, "widened", False)) for eng in self.engines]
+            if attempt == 0 and now_wide != was_wide:
+                # an engine left the fp16 operand range and moved itself to bf16 forward planes (Engine.energy_forces): the blocks of
+                # the others are in the narrower arithmetic -- all engines move, and the WHOLE batch is evaluated again
+                self._widen_all("fp16 range violation on another engine of the local pool")
+                continue
+            break
+        e = np.concatenate([r[0] for r in res])
+        f = np.concatenate([r[1] for r in res]) if forces else None
+        return e, f
+
+    def _gp_buffers(self):
+        if self._gp_buf is None:
+            bufs = []
+            for eng in self.engines:
+                dev = self._tensor_device(eng)
+                cuda = dev.type == "cuda"
+                stream = torch.cuda.Stream(device=dev) if cuda else None
+                bufs.append((dev, stream,
+                             torch.zeros(self.natoms, 3, dtype=torch.float32, device=dev),
+                             torch.zeros(1, dtype=torch.float64, device=dev),
+                             torch.zeros(self.natoms, 3, dtype=torch.float32, device=dev)))
+                if cuda:
+                    torch.cuda.synchronize(dev)         # the fills ran on torch's current stream, the buffers are used on `stream`
+            self._gp_buf = bufs
+        return self._gp_buf
+
+    def _graph_parallel(self, pos: np.ndarray, forces: bool, _retry: bool = False):
+        if not np.isfinite(pos).all():
+            raise ValueError("non-finite position")
+        g, n = len(self.engines), self.natoms
+        bufs = self._gp_buffers()
+        host = torch.from_numpy(np.ascontiguousarray(pos, dtype=np.float32))
+        handles = []
+        for dev, stream, d_pos, _, _ in bufs:
+            if stream is not None:
+                with torch.cuda.stream(stream):
+                    d_pos.copy_(host)
+                handles.append(int(stream.cuda_stream))
+            else:
+                d_pos.copy_(host)
+                handles.append(0)
+        self.last_route, self.last_blocks = "graph-parallel", [shard_bounds(n, g, r) for r in range(g)]
+
+        def begin(r):
+            lo, hi = self.last_blocks[r]
+            _, _, d_pos, d_e, d_f = bufs[r]
+            self.engines[r].gp_begin(d_pos.data_ptr(), lo, hi, d_e.data_ptr(), d_f.data_ptr(), handles[r])
+
+        try:
+            self._run_all(begin, range(g))
+            self.n_exchanges = 0
+            while True:
+                steps = self._run_all(lambda r: self.engines[r].gp_step(), range(g))
+                done = [s[2] for s in steps]
+                if all(done):
+                    break
+                counts = {s[1] for s in steps}
+                if any(done) or len(counts) != 1:
+                    raise RuntimeError(f"local pool: the engines disagree at exchange point {self.n_exchanges} (done {done}, counts {sorted(counts)})")
+                self._peer_sum([s[0] for s in steps], counts.pop(), self.devices, handles)
+                self.n_exchanges += 1
+        except BaseException:
+            self._abandon()
+            raise
+        out = []
+        for (dev, stream, _, d_e, d_f) in bufs:
+            if stream is not None:
+                stream.synchronize()
+            out.append((d_e.cpu().numpy().copy(), d_f.cpu().numpy().copy()))
+        self.last_all = out
+        e, f = out[0]
+        if not np.isfinite(e).all():
+            # energies are complete on every engine (node-level work is replicated): collect every sticky flag, then all widen together
+            for eng in self.engines:
+                eng.take_range_error()
+            if not _retry and any([eng.widen("non-finite energy in a graph-parallel evaluation over the local pool") for eng in self.engines]):
+                return self._graph_parallel(pos, forces, _retry=True)
+            raise RuntimeError(f"non-finite energy in graph-parallel mode over the local pool (precision mode {self.precision_mode()}): "
+                               "non-finite coordinates, or an overflow that wider forward planes cannot cure")
+        return e, (f[None] if forces else None)
+
+    def _abandon(self) -> None:
+        """An error between gp_begin and the last step: let the device drain so that no engine is left waiting on a peer's event
+        (an evaluation left half-way is dropped by the engine's next gp_begin)."""
+        for buf in self._gp_buf or []:
+            if buf[1] is not None:
+                try:
+                    buf[1].synchronize()
+                except Exception:       # noqa: BLE001 -- the original error is the one to report
+                    pass

@@ -140,8 +140,10 @@ class UMAcore:
         self.workers = max(int(workers) if workers is not None else 1, 1)
         self.workers_per_node = max(int(workers_per_node) if workers_per_node is not None else 1, 1)
         # The reference's workers>1 is graph-parallel inference of ONE image (ParallelMLIPPredictUnit,
-        # :220-242).  Here images are the parallel unit (one engine per GPU, see parallel.py); inside
-        # a process `workers` only keeps the reference's side effect: no analytical Hessian.
+        # :220-242).  Here images are the parallel unit (one engine per GPU, see parallel.py).  Outside a process
+        # group `workers=G` builds G engines in THIS process when there are G devices to put them on
+        # (parallel.LocalEnginePool; UMX_LOCAL_DEVICES names them); otherwise it only keeps the reference's side
+        # effect: no analytical Hessian.
         self.parallel_predict = self.workers > 1
         self.has_torch_model = False       # no nn.Module is exposed -> analytical Hessian unavailable
         self.elem = [e.capitalize() for e in elem]
@@ -173,10 +175,26 @@ class UMAcore:
                           RuntimeWarning, stacklevel=3)
         self.z = synth.symbols_to_z(self.elem)
         W.check_merged_for(weights, self.z, charge, spin, task_name)   # a MoLE merge is valid for one system only
-        self.engine = Engine(_device_index(device), precision=precision)     # None: UMX_PRECISION (default "auto")
-        cap_pools_to_usable_cores()                       # BLAS pools sized for the machine inside a CPU-quota container starve the GPU feeder
-        self.engine.load_weights(weights)
-        self.engine.set_system(self.z, charge=charge, spin=spin, task=task_name, radius=radius, max_neigh=max_neigh)
+        self._pool = None
+        pool_devices = None
+        if self.workers > 1:
+            from . import parallel as P
+
+            if not P.process_group_active():
+                pool_devices = P.local_devices_for(self.workers)          # ValueError: UMX_LOCAL_DEVICES and workers disagree
+        if pool_devices is not None:
+            # `workers` engines in this process (ordinals may repeat: "0,0" rehearses the path on one GPU); engine 0 is `self.engine`
+            self._pool = P.LocalEnginePool.create(pool_devices, weights, precision=precision, engine_factory=Engine)
+            self.engine = self._pool.engines[0]
+            cap_pools_to_usable_cores()
+            self._pool.set_system(self.z, charge=charge, spin=spin, task=task_name, radius=radius, max_neigh=max_neigh)
+        else:
+            dev_index = _device_index(device)
+            self.engine = Engine(dev_index, precision=precision)     # None: UMX_PRECISION (default "auto")
+            cap_pools_to_usable_cores()                       # BLAS pools sized for the machine inside a CPU-quota container starve the GPU feeder
+            self.engine.load_weights(weights)
+            self.engine.set_system(self.z, charge=charge, spin=spin, task=task_name, radius=radius, max_neigh=max_neigh)
+        self.local_devices = list(pool_devices) if pool_devices is not None else [dev_index]   # ordinals in use by this core
         self._gp = None
         if self.workers > 1 and os.environ.get("UMX_WORKERS_GP", "1") != "0":
             # the reference's workers > 1 IS graph-parallel inference of one structure over `workers` processes
@@ -194,6 +212,16 @@ class UMAcore:
         import torch
         return torch.device("cuda", self.engine.device)
 
+    def close(self) -> None:
+        """Release every engine of this core (the pool's, or the one)."""
+        if getattr(self, "_pool", None) is not None:
+            self._pool.close()
+        else:
+            self.engine.close()
+
+    def reserve_images(self, n_images: int) -> None:
+        (self._pool if self._pool is not None else self.engine).reserve_images(int(n_images))
+
     def enable_graph_parallel(self, on: bool = True, group=None) -> None:
         """Evaluate every geometry with its GRAPH partitioned over the ranks of `group` (default: the world) -- the reference's
         ``workers > 1`` mode (``ParallelMLIPPredictUnit``, ``:220-242``), for single large structures when there are fewer images
@@ -203,6 +231,9 @@ class UMAcore:
         if not on:
             self._gp = None
             return
+        if self._pool is not None:
+            raise RuntimeError("enable_graph_parallel: this core evaluates on an in-process pool of engines (workers > 1 without a process "
+                               "group); the rank-level graph-parallel mode needs one engine per rank")
         from .parallel import GraphParallelEvaluator
 
         self._gp = GraphParallelEvaluator(self.engine, len(self.z), self.device, group)
@@ -231,7 +262,7 @@ class UMAcore:
         if getattr(self, "_gp", None) is not None:
             e, f = self._gp_eval(coords_ang)
             return {"energy": e, "forces": f if forces else None}
-        e, f = self.engine.energy_forces(np.asarray(coords_ang), forces=forces)
+        e, f = (getattr(self, "_pool", None) or self.engine).energy_forces(np.asarray(coords_ang), forces=forces)
         return {"energy": e, "forces": f}
 
     def compute_batch_dev(self, pos32):
@@ -266,7 +297,7 @@ class UMAcore:
         if getattr(self, "_gp", None) is not None:
             e, f = self._gp_eval(coord_ang)
         else:
-            e, f = self.engine.energy_forces(np.asarray(coord_ang, dtype=np.float64).reshape(1, -1, 3), forces=forces)
+            e, f = (getattr(self, "_pool", None) or self.engine).energy_forces(np.asarray(coord_ang, dtype=np.float64).reshape(1, -1, 3), forces=forces)
         return {"energy": float(e[0]), "forces": (f[0] if forces else None), "hessian": None}
 
 
@@ -325,23 +356,24 @@ class uma_pysis(Calculator):
         if self._core is None:
             self._core = UMAcore(elem, **self._core_kw)
             if self._reserve_images and hasattr(self._core, "engine"):
-                self._core.engine.reserve_images(self._reserve_images)
+                self._core.reserve_images(self._reserve_images)
         return self._core
 
     def reserve_images(self, n_images: int) -> None:
         """Tell the engine that batches of up to ``n_images`` images are coming (a string that will grow to that size): its workspace is
         then allocated once instead of being re-allocated at every growth -- seconds each (``umx_reserve_images``).  A hint only."""
         self._reserve_images = max(0, int(n_images))
-        eng = getattr(self._core, "engine", None)
-        if eng is not None:
-            eng.reserve_images(self._reserve_images)
+        if getattr(self._core, "engine", None) is not None:
+            (self._core if hasattr(self._core, "reserve_images") else self._core.engine).reserve_images(self._reserve_images)
 
     def close(self) -> None:
         """Release the engine (HBM workspace, weights) now instead of at garbage collection; the calculator can be used
         again afterwards (the core is rebuilt lazily on the next call)."""
         if self._core is not None:
             eng = getattr(self._core, "engine", None)
-            if eng is not None:
+            if hasattr(self._core, "close"):
+                self._core.close()                        # every engine of an in-process pool
+            elif eng is not None:
                 eng.close()
             self._core = None
 
@@ -382,12 +414,15 @@ class uma_pysis(Calculator):
         base = core.compute(coord_ang, forces=True, hessian=False)
         # the displaced geometries and their forces stay on the GPU when the core runs on the HIP engine (round 6); the graph-parallel mode and
         # stand-in cores keep the host form
-        dev_fn = core.compute_batch_dev if (getattr(core, "_gp", None) is None and hasattr(core, "compute_batch_dev")
+        # stand-in cores keep the host form; so does an in-process pool (its blocks go to the engines from the host: the same columns, bit for bit)
+        dev_fn = core.compute_batch_dev if (getattr(core, "_gp", None) is None and getattr(core, "_pool", None) is None and hasattr(core, "compute_batch_dev")
                                             and hasattr(getattr(core, "engine", None), "energy_forces_dev")
                                             and getattr(core.device, "type", "cpu") == "cuda") else None
         hess = H.fd_hessian(lambda c: core.compute_batch(c, forces=True)["forces"], coord_ang, self.freeze_atoms, device=core.device,
                             double=self.hessian_double, partial=self.return_partial_hessian, batch=FD_BATCH,
                             shard=self._hess_shard, group=self._hess_group, engine=getattr(core, "engine", None), batch_forces_dev=dev_fn)
+        # (a pool that widens in the middle of this Hessian widens ALL its engines, engine 0 -- `engine` above -- included, so fd_hessian's
+        # "compute every column again" rule sees it)
         return {"energy": base["energy"], "forces": base["forces"], "hessian": hess}
 
     # ---------- PySisyphus API --------------------------------------
