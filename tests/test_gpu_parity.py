@@ -530,6 +530,12 @@ def test_stage_by_stage_against_staged_oracle(weights, mode, monkeypatch):
             r = t[nm].reshape(-1)
             assert a.size == r.size, nm
             assert np.abs(a - r).max() <= tol * max(np.abs(r).max(), 1.0), nm
+        # the edge frames (R, D2, env, denv as the engine packs them) and dE/dvec per edge, at this test's own tolerance
+        from oracle.escn_md_oracle import wigner_blocks
+        frame = np.concatenate([t["rm"].reshape(ne, 9), wigner_blocks(st.t["rm"])[1].numpy().reshape(ne, 25), t["env"][:, None], t["denv"][:, None]], axis=1)
+        assert np.abs(engine.debug_fetch("frame").reshape(ne, 36) - frame).max() <= tol * max(np.abs(frame).max(), 1.0), "frame"
+        gvec = engine.debug_fetch("gvec").reshape(ne, 4)
+        assert np.abs(gvec[:, :3] - t["gvec"]).max() <= tol * max(np.abs(t["gvec"]).max(), 1.0) and not gvec[:, 3].any(), "gvec"
         # the FORWARD tensors alone, at float32 level in every mode: the split modes' forward products are fp32-equivalent
         # (4 fp16 / 6 bf16 plane products); only the reverse pass runs on 16-bit products
         fwd = ["x0", "rad.deg", "e_node"] + [f"{s}.{i}" for i in range(W.NUM_LAYERS) for s in ("xn", "rad", "msg", "xmid", "xn2", "gspre", "ffh", "x")]
