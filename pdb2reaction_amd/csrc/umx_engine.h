@@ -1,0 +1,320 @@
+// umx_engine.h -- host side, part 1 of 5: the engine's state (struct umx_engine) and the small types it is made of: the precision
+// descriptor, the weight views, the workspace view (WS), the launch plan (Seg / Plan), and the error / buffer helpers every other
+// host header uses.  Host headers are included by umx_api.hip only, in this order: umx_engine.h, umx_launch.h, umx_workspace.h,
+// umx_plan.h, umx_weights.h (one translation unit: every kernel template is instantiated once; they do not include one another).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <chrono>
+#include <cstring>
+#include <functional>
+#include <initializer_list>
+#include <map>
+#include <memory>
+#include <set>
+#include <string>
+#include <vector>
+
+#include "../../include/umx.h"
+#include "umx_common.h"
+#include "umx_gemm.h"
+#include "umx_gemm_pl.h"
+#include "umx_gemm_q.h"
+#include "umx_kernels_pl.h"
+#include "umx_kernels.h"
+#include "umx_radial.h"
+#include "umx_peer.h"
+
+using namespace umx;
+
+namespace {
+
+std::string g_create_err;
+
+struct Tensor { size_t off = 0; std::vector<int> shape; size_t count = 0; };
+
+struct RadialW {          // one RadialMLP (forward + transposed copies)
+  const float *w1g, *w1gT, *ln1w, *ln1b, *w2, *w2T, *b2, *ln2w, *ln2b, *w3, *w3T, *b3;
+  const double *tsd, *ttd;     // the element tables of fc1 in double (fused radial head)
+  int out;
+};
+struct LayerW {
+  const float *n1w, *n1b, *n2w, *n2b;
+  const float *c1m0, *c1m0b, *c1m0T, *c1m1, *c1m1T, *c1m2, *c1m2T;
+  const float *c2m0, *c2m0b, *c2m0T, *c2m1, *c2m1T, *c2m2, *c2m2T;
+  const float *smlp, *smlpb, *smlpT, *l1w, *l1b, *l1T, *l2w, *l2b, *l2T;       // K8 spectral feed-forward
+  const float *g1w, *g1b, *g1T, *g2w, *g2b, *g2T, *g3w, *g3b, *g3T;            // K8 grid feed-forward (ff_grid): grid_mlp.{0,2,4} (+ optional biases), transposes
+  RadialW rad;
+};
+
+struct ProfRec { hipEvent_t a, b; double flops; int M, N, K, amode, cplx, prec, gz; };
+
+// ---- precision mode ----------------------------------------------------------------------------
+// What a mode name (UMX_PRECISION / umx_set_precision) means, resolved in ONE place (resolve_precision) at umx_load_weights -- the weight
+// planes are packed in the forward operand format it selects -- and read everywhere else.
+struct Precision {
+  const char* name = "bf16x3";     // canonical name (umx_precision_mode)
+  bool planes = true;              // split-precision plane GEMMs for the large SO(2) / radial linears; false (fp32): fp32 MFMA everywhere
+  int fwd_fmt = 3;                 // forward operand format (QFmt, umx_kernels_pl.h): 1 = two fp16 planes (split-f16),
+                                   // 3 = plain float32 quad-row blocks, split into three bf16 planes by the GEMM in registers (bf16x3, split-bf16)
+  int rev_planes = 3;              // bf16 planes of the REVERSE-pass operands: 2 (3 products, 16-bit) or 3 (6 products, 24-bit: bf16x3)
+  bool fwd_f16() const { return planes && fwd_fmt == 1; }
+  bool rev_quad() const { return planes && rev_planes == 3; }   // reverse quad-row operands (g_msg, g_hg) as float32 blocks
+  // what to tell the caller of a device-pointer entry about a non-finite energy
+  const char* range_hint() const {
+    return fwd_f16() ? " (an activation beyond the fp16 operand range of the split-f16 forward planes: re-load with UMX_PRECISION=split-bf16, bf16x3 or fp32)"
+                     : " (non-finite input or an overflow in float32)";
+  }
+};
+
+// "auto" (the default) = bf16x3: the reference runs fairchem's float32 inference settings (uma_pysis.py:229,246-250), and bf16x3 is the
+// mode whose every product, forward and reverse, carries >= 24 significant bits -- the like-for-like arithmetic.  The faster split-f16
+// (22-bit forward activations, 16-bit reverse products) meets the tolerances with margin but is narrower: an explicit choice.
+bool resolve_precision(const std::string& mode, Precision* out) {
+  Precision p;
+  if (mode == "auto" || mode == "bf16x3" || mode == "split-exact") p = {"bf16x3", true, 3, 3};   // 24-bit products in BOTH passes
+  else if (mode == "split" || mode == "split-f16") p = {"split-f16", true, 1, 2};
+  else if (mode == "split-bf16") p = {"split-bf16", true, 3, 2};
+  else if (mode == "fp32") p = {"fp32", false, 3, 2};      // (the plane copies are still packed, in the bf16 form; nothing reads them)
+  else return false;
+  if (out) *out = p;
+  return true;
+}
+
+enum Pass { FWD, REV };   // which pass a split-precision product (gemm_pl) or a weight's plane copy (PlanePacker) belongs to
+
+// one plane copy of a large weight, looked up by the weight's fp32 device pointer
+struct PlaneCopy {
+  const unsigned short* ptr;       // in d_bw
+  bool quad;                       // quad-row layout (umx_gemm_q.h), else PL (umx_gemm_pl.h)
+  float scale;                     // fp16 form: the power-of-two scale folded into the planes (else 0)
+};
+
+// ---- workspace view (carved by umx_workspace.h) --------------------------------------------------
+struct WS {
+  // node level
+  int *deg, *row_ptr, *stats;
+  float* xs[2 * NL + 1];
+  float* xn[NL];
+  float *xn2, *ffhg, *xf, *pre1, *pre2, *enode;
+  float* gspre[NL];
+  float* ffh[NL];
+  float* ffg1[NL];                 // grid feed-forward: pre-activations of the two hidden layers, (nodes x G) rows x H, kept for the reverse pass
+  float* ffg2[NL];
+  float *gridA, *gridB;            // grid feed-forward: (nodes x G) x C temporaries
+  float *G0, *G1, *G2, *ggs, *n128a, *n128b;
+  // edge level
+  int *esrc, *edst, *ez, *out_ptr, *out_cur, *out_edge;
+  float *evec, *frame, *dedd, *dedd_rad, *tau, *tau2, *gvec;
+  float* h1pre[NL + 1];
+  float* h2pre[NL + 1];
+  float *ra, *rad_deg;
+  float* rad[NL];
+  float* hg[NL];
+  float* msg[NL];
+  float *xrot, *hid, *gmsg, *ghg, *gy1, *grad, *e128a;
+  unsigned short *y1pl, *hidpl, *a2pl, *gmsgpl, *ghgpl, *gradpl;   // split path: pre-split GEMM operands (forward: quad-row planes, reverse: PL)
+};
+
+// ---- launch plan (built by umx_plan.h) -----------------------------------------------------------
+// A chunk's launch sequence is recorded as a PLAN of segments instead of being issued directly.  A segment is either
+// "matrix" (a group of the large split-precision GEMMs: MFMA-bound, one LDS-filling workgroup per CU) or "stream" (everything
+// else: the HBM-bound gather / rotate / gate / reduce kernels and the small fp32 GEMMs).  With one lane the executor simply
+// issues the segments in order.  With two lanes (UMX_STREAMS=2) it issues the plans of two chunks alternately and hands a
+// TOKEN from matrix segment to matrix segment across the lanes (events), so that at any time at most one lane occupies the
+// matrix pipe while the other lane's stream segments run beside it on the same CUs -- the two bounds (MFMA and HBM)
+// overlap instead of adding up (NOTES.md section 5).
+struct Seg { bool matrix; std::function<int()> fn; float* sync_buf = nullptr; size_t sync_count = 0; };
+struct Plan {
+  std::vector<Seg> segs;
+  void stream(std::function<int()> f) { segs.push_back({false, std::move(f)}); }
+  void matrix(std::function<int()> f) { segs.push_back({true, std::move(f)}); }
+  // graph-parallel single-image mode: an exchange point -- the buffer holds this rank's partial sums over ITS edges and must be
+  // summed over the ranks (all-reduce, done by the caller between two umx_gp_step calls) before the next segment runs
+  void sync(float* buf, size_t count) { Seg sg{false, nullptr}; sg.sync_buf = buf; sg.sync_count = count; segs.push_back(std::move(sg)); }
+};
+
+}  // namespace
+
+struct umx_engine {
+  int dev = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev_done = nullptr;    // recorded at the end of every evaluation on the stream it ran on: umx_synchronize waits on THIS, never
+                                   // on a caller's stream handle kept from an earlier call (the caller may have destroyed that stream since)
+  bool ran_on_caller = false;
+  int* d_flags = nullptr;          // [0]: sticky range flag -- an image's energy was not finite (set by k_energy, read at the next host sync)
+  hipStream_t stream2 = nullptr;   // second lane: half-chunks alternate streams so HBM-bound producers overlap the other lane's GEMMs
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  hipEvent_t ev_tok[2] = {nullptr, nullptr};   // matrix-pipe token of the two lanes (run_plans_alternating)
+  // Round 5 pruned the development levers whose A/B is settled (NOTES.md sections 5, 9, 10 keep the measurements): the PL-layout forward
+  // operands, pre-split A planes, three-plane PL reverse operands, ring depth 3, two-plane fp16 weights, hardware transcendentals / fp16
+  // products inside the fused radial kernels, the side stream, the unfused radial layers, the f16x2b8 mode.  What is left below is what runs.
+  Precision prec;                  // the mode the weights were loaded in (umx_load_weights)
+  std::string precision;           // umx_set_precision: overrides UMX_PRECISION when non-empty
+  int low_sep = 3;                 // UMX_LOW_SEP (gemm_pl): which forward bf16x3 products chain their 2^-16-order plane products from zero
+  int align = 2;                   // UMX_ALIGN_PLANES (round 6): "aligned planes" -- the leading bf16 plane of both operands of a FORWARD bf16x3 product is
+                                   // quantised to its pass group (8 consecutive k of one row), so that stage 1 of the matrix core's adder (a cut TOWARD
+                                   // ZERO at 2^-24 of the pass's largest product, i.e. an error that follows the product's sign) has nothing to cut:
+                                   // umx_gemm_pl.h qf_align_magic (A, in registers), pack_planes (umx_weights.h: weights, at load).  The remainder goes
+                                   // down the planes: elements far below their group's largest keep 16-23 bits instead of 24, with an unbiased error.  2 (default): A's leading plane in the PLAIN products (fc3, conv m = 0) -- the complex m > 0
+                                   // products take rotated l >= 1 components whose signs follow the edge direction, nothing coherent to remove -- the
+                                   // weights' planes in every forward product (free); 1: A's in every forward product; 0: the plain nearest-bf16 leading
+                                   // planes of rounds 4-5.  20 000 atoms, four cases (profiles/r06_energy_bias.txt): 0: -9e-7 ... -1.63e-4 eV, 1: -1.3e-5 ...
+                                   // +3.9e-5, 2: +4e-7 ... -5.0e-5; c3 step 517.9 / 526.3 / 523.0 ms
+  float odd_sign = -1.0f;          // sign-alternating operand rows (umx_kernels_pl.h): -1 = on (default), +1 = off (UMX_ALT_ROWS=0, dev A/B)
+  bool node_ctx = false;           // set around the node-level launches (NodeCtx): only those take the float64-accumulating kernel
+  bool node_f64_on = true;         // UMX_NODE_F64=0: node-level linears (atom-wise SO(3) linears, scalar MLP, readout and their transposes) on the
+                                   // fp32 MFMA instead of the float64-accumulating kernel (k_gemm_f64acc).  Measured (round 3): the fp32-MFMA form of
+                                   // these 14 chained GEMMs shifts the energy by a one-signed -2e-8 eV per atom; the double form costs +1 % at c3
+  int n_lanes = 0;                 // UMX_STREAMS: 1 / unset = one lane, 2 = two chunks in flight (matrix segments alternating between the lanes; bitwise the
+                                   // same results).  Mid-round 5 the engine chose two lanes by itself for batches of >= 1.2 M directed edges (c3 505.2 ->
+                                   // 499.0 ms, c4 string 761.2 -> 751.4 ms, profiles/r05_lanes_ab.txt); with the LS forward kernels (one workgroup per CU)
+                                   // the gain is gone -- c3 511.1 vs 510.6 ms, c4 string 766.4 vs 773.2 ms, c2 +2 %, c1 +25 % (same file, second part) --
+                                   // so the rule is off by default; UMX_LANES_AUTO_EDGES=<n> turns it back on with that threshold
+  long lanes_auto_edges = 0;       // UMX_LANES_AUTO_EDGES (0 = no automatic choice)
+  int stream_cap = 512;            // two-lane mode caps the grids of the grid-stride streaming kernels at this many workgroups (two per CU) so
+                                   // that they run BESIDE the other lane's GEMM
+  bool throttle = false;           // set while a two-lane evaluation is being issued
+  // graph-parallel single-image mode (umx_gp_begin / umx_gp_step): this rank builds the incoming edges of targets [gp_lo, gp_hi)
+  bool gp = false; long gp_lo = 0, gp_hi = 0;
+  std::unique_ptr<Plan> gp_plan;   // the evaluation in progress ...
+  std::unique_ptr<WS> gp_ws;       // ... and its workspace view, kept alive between the steps (the plan's closures refer to it)
+  size_t gp_at = 0;
+  hipStream_t gp_stream = nullptr;
+  std::string err;
+  // weights
+  bool have_weights = false;
+  float* d_w = nullptr;          // raw blob data section
+  float* d_dw = nullptr;         // derived weights
+  double* d_dtab = nullptr;      // derived double tables (per-element fc1 contributions of every radial MLP)
+  unsigned short* d_bw = nullptr; // plane copies (bf16 / fp16) of the large SO(2)/radial weights
+  std::map<const float*, PlaneCopy> planes;   // fp32 weight ptr -> its plane copy (forward weights and their transposes)
+  std::map<std::string, Tensor> wt;
+  std::vector<float> h_w;        // host copy of the data section (needed to build derived weights)
+  RadialW rdeg{};
+  LayerW lw[NL]{};
+  const float *emb_sphere = nullptr, *normw = nullptr, *normb = nullptr, *e0 = nullptr, *e0b = nullptr, *e0T = nullptr,
+              *e2 = nullptr, *e2b = nullptr, *e2T = nullptr, *e4 = nullptr, *e4b = nullptr;
+  double rmsd = 1.0;
+  std::vector<double> elem_refs;
+  // model variant, read off the tensors of the blob (umx_load_weights; SURVEY.md section 2.4 K8 / Appendix A.5 list them as possible for UMA-S)
+  bool ff_grid = false;            // K8 = GridAtomwise (to-grid -> point-wise SiLU MLP -> from-grid) instead of SpectralAtomwise
+  int grid_G = 0;                  // grid points (rows of so3_grid.to_grid_mat / from_grid_mat)
+  int ws_grid() const { return ff_grid ? grid_G : 0; }   // what the per-node workspace scales with (0: spectral feed-forward)
+  const float *to_grid = nullptr, *from_grid = nullptr;
+  bool grid_f64 = true;            // UMX_GRID_F64=0: the grid MLP's three GEMMs on the fp32 MFMA instead of the float64-accumulating node kernel
+  int emb_type = 0;                // charge / spin embedding: 0 rand_emb (lookup tables), 1 pos_emb (sin / cos of 2 pi v W), 2 lin_emb (Linear(1 -> C))
+  int n_datasets = 5;              // rows of dataset_embedding.weight (0: the model has no dataset embedding, mix_csd takes [charge | spin])
+  std::string variant;             // "ff=...;emb=...;datasets=N" (umx_model_variant)
+  // system
+  bool have_system = false;
+  int natoms = 0;
+  float cutoff = 6.0f;
+  int max_neigh = 300;
+  int* d_z = nullptr;
+  double* d_sysemb = nullptr;    // system embedding in DOUBLE (added to every atom: a float32 copy's error would be shared by all atoms)
+  double* d_gmu = nullptr;       // gaussian centres mu_k = k * cutoff/63 in double
+  double gcoef = 0.0;
+  double refsum = 0.0;
+  // workspace
+  size_t ws_limit = 0;
+  size_t ws_cap_default = (size_t)160 << 30;
+  char* arena = nullptr;
+  size_t arena_bytes = 0;
+  long cap_nodes = 0, cap_edges = 0;
+  int* d_deg_all = nullptr; int* d_cand_all = nullptr; long deg_all_cap = 0;
+  int* d_img_edges = nullptr; long img_edges_cap = 0;
+  // partitioned evaluation of ONE oversized image on one GPU (eval_partitioned): per-partition degree arrays and partial forces
+  int force_parts = 0;             // UMX_FORCE_PARTS (dev / tests): evaluate every image in this many target-node partitions
+  int* d_part_deg = nullptr; float* d_part_f = nullptr; long part_cap = 0;
+  int last_parts = 0;              // partitions used by the most recent evaluation (0: the ordinary path)
+  int last_lanes = 1;              // lanes (chunks in flight) of the most recent evaluation (umx_last_lanes)
+  int arena_allocs = 0;            // how often the workspace has been (re-)allocated (umx_workspace_stats)
+  bool ws_eager = false;           // UMX_WS_EAGER=1: size the workspace for the whole batch at once (the behaviour before ABI v8)
+  long ws_soft_edges = 320000;     // UMX_WS_SOFT_EDGES: directed edges per chunk the workspace starts with when nothing else is known
+  double t_first_eval = -1.0;      // steady-clock seconds of the first evaluation (amortised workspace growth)
+  int hint_applied = 0;            // the hint value the workspace has been sized for already
+  int hint_images = 0;             // umx_reserve_images: size the workspace for this many images at the next growth
+  // host io staging for the host-pointer entry point
+  float* d_io_pos = nullptr; double* d_io_e = nullptr; float* d_io_f = nullptr; long io_cap = 0, io_img_cap = 0;
+  // stats / profiling / debug
+  int64_t last_edges = 0; int32_t last_maxdeg = 0;
+  bool may_truncate = true;      // the largest degree of the evaluation being planned reaches max_neigh: k_graph_fill takes its truncating (LDS) form
+  bool prof_on = false;
+  std::vector<ProfRec> prof;
+  size_t prof_used = 0;
+  bool dbg_on = false;
+  std::map<std::string, std::vector<char>> dbg;
+};
+
+namespace {
+
+#define HIPCHK(eng, expr)                                                                         \
+  do {                                                                                            \
+    hipError_t _e = (expr);                                                                       \
+    if (_e != hipSuccess) {                                                                       \
+      (eng)->err = std::string(#expr) + ": " + hipGetErrorName(_e) + " (" + hipGetErrorString(_e) + ")"; \
+      return UMX_ERR_HIP;                                                                         \
+    }                                                                                             \
+  } while (0)
+
+#define CHK(expr) do { int _s = (expr); if (_s != UMX_OK) return _s; } while (0)
+
+int fail(umx_engine* e, int code, const std::string& msg) { e->err = msg; return code; }
+
+inline unsigned nblk(long n, int per) { return (unsigned)((n + per - 1) / per); }
+
+// ---- growing a device buffer ---------------------------------------------------------------------
+// The buffers that share one capacity counter are replaced together: drain the streams that may still be using the old ones, free them,
+// clear pointers and capacity (a failed hipMalloc below must not leave a dangling pointer behind), allocate, record the capacity.
+struct DevBuf {
+  void** p; size_t bytes;
+  template <class T> DevBuf(T*& ptr, size_t count) : p(reinterpret_cast<void**>(&ptr)), bytes(count * sizeof(T)) {}
+};
+template <class Cap>
+int grow(umx_engine* eng, Cap& cap, Cap new_cap, std::initializer_list<hipStream_t> drain, std::initializer_list<DevBuf> bufs) {
+  for (hipStream_t s : drain) HIPCHK(eng, hipStreamSynchronize(s));
+  for (const DevBuf& b : bufs) if (*b.p) HIPCHK(eng, hipFree(*b.p));
+  for (const DevBuf& b : bufs) *b.p = nullptr;
+  cap = 0;
+  for (const DevBuf& b : bufs) HIPCHK(eng, hipMalloc(b.p, b.bytes));
+  cap = new_cap;
+  return UMX_OK;
+}
+// the workspace arena: the second lane may still be running in it
+int grow_arena(umx_engine* eng, hipStream_t s, size_t bytes) {
+  CHK(grow(eng, eng->arena_bytes, bytes, {s, eng->stream2}, {DevBuf(eng->arena, bytes)}));
+  ++eng->arena_allocs;
+  return UMX_OK;
+}
+
+// ---- debug captures ------------------------------------------------------------------------------
+// UMX_DEBUG_ONLY (tests): a comma-separated list of name prefixes; with captures on, only the names that start with one of them are kept
+// (a 44 k-edge system holds ~1 GB of captures per layer and pass)
+bool dbg_wanted(const std::string& name) {
+  const char* ev = std::getenv("UMX_DEBUG_ONLY");
+  if (!ev || !*ev) return true;
+  const std::string only(ev);
+  for (size_t a = 0; a <= only.size();) {
+    size_t b = only.find(',', a);
+    if (b == std::string::npos) b = only.size();
+    if (b > a && name.compare(0, b - a, only, a, b - a) == 0) return true;
+    a = b + 1;
+  }
+  return false;
+}
+
+int dbg_capture(umx_engine* eng, const std::string& name, const void* dptr, size_t bytes) {
+  if (!eng->dbg_on || !dbg_wanted(name)) return UMX_OK;
+  std::vector<char>& v = eng->dbg[name];
+  v.resize(bytes);
+  HIPCHK(eng, hipStreamSynchronize(eng->stream));
+  if (bytes) HIPCHK(eng, hipMemcpy(v.data(), dptr, bytes, hipMemcpyDeviceToHost));
+  return UMX_OK;
+}
+#define DBG(name, ptr, count) CHK(dbg_capture(eng, name, ptr, (size_t)(count) * sizeof(*(ptr))))
+
+}  // namespace

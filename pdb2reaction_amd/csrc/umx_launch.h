@@ -1,0 +1,224 @@
+// umx_launch.h -- host side, part 2 of 5: the profiling bracket and the GEMM launchers (fp32 MFMA / float64-accumulating node kernel:
+// launch_gemm; split-precision plane GEMMs: gemm_pl = choose_pl + the table of instantiations + one launch site).
+#pragma once
+
+namespace {
+
+// HIP-event bracket around one launch for umx_profile_read (prec: > 0 split-precision GEMM family, 0 fp32 GEMM, < 0 fused radial kernels).
+// *out stays null while profiling is off.
+int prof_open(umx_engine* eng, ProfRec** out, double flops, int prec, long M, int N, int K, int amode = 0, int cplx = 0, int gz = 1) {
+  *out = nullptr;
+  if (!eng->prof_on) return UMX_OK;
+  if (eng->prof_used == eng->prof.size()) {
+    ProfRec r; HIPCHK(eng, hipEventCreate(&r.a)); HIPCHK(eng, hipEventCreate(&r.b)); r.flops = 0; eng->prof.push_back(r);
+  }
+  ProfRec* pr = &eng->prof[eng->prof_used++];
+  pr->flops = flops; pr->M = (int)M; pr->N = N; pr->K = K; pr->amode = amode; pr->cplx = cplx; pr->gz = gz; pr->prec = prec;
+  HIPCHK(eng, hipEventRecord(pr->a, eng->stream));
+  *out = pr;
+  return UMX_OK;
+}
+int prof_close(umx_engine* eng, ProfRec* pr) {
+  if (pr) HIPCHK(eng, hipEventRecord(pr->b, eng->stream));
+  return UMX_OK;
+}
+// grid of a grid-stride ("virtual block") kernel: all blocks normally, capped in throttled two-lane mode
+inline unsigned vgrid(const umx_engine* eng, unsigned blocks) {
+  return (eng->throttle && eng->stream_cap > 0 && blocks > (unsigned)eng->stream_cap) ? (unsigned)eng->stream_cap : blocks;
+}
+
+// ---- fp32 GEMM launcher ------------------------------------------------------------------------
+GemmP gp_zero() { GemmP p; std::memset(&p, 0, sizeof(p)); p.conj = 1.0f; return p; }
+
+int launch_gemm(umx_engine* eng, const GemmP& p, int amode, int cplx, int epi, int gz = 1) {
+  if (p.M <= 0) return UMX_OK;
+  if (p.K % G_BK != 0) return fail(eng, UMX_ERR_ARG, "gemm: K not a multiple of 32");
+  const int bmr = cplx ? 64 : 128, bnc = cplx ? 64 : 128;
+  const long nM = (p.M + bmr - 1) / bmr, nN = (p.N + bnc - 1) / bnc;
+  const long blocks = ((nM + 7) / 8) * 8 * nN;
+  dim3 grid((unsigned)blocks, 1, (unsigned)gz), block(256);
+  ProfRec* pr;
+  CHK(prof_open(eng, &pr, cplx ? 8.0 * p.M * (double)p.N * p.K : 2.0 * p.M * (double)p.N * p.K * gz, 0, p.M, p.N, p.K, amode, cplx, gz));
+  if (eng->node_f64_on && eng->node_ctx && !cplx && epi == E_BIAS && (amode == A_PLAIN || amode == A_SILU)) {
+    const dim3 g64((unsigned)(((p.M + 63) / 64) * ((p.N + 63) / 64)), 1, (unsigned)gz);
+    if (amode == A_SILU) hipLaunchKernelGGL(k_gemm_f64acc<A_SILU>, g64, block, 0, eng->stream, p);
+    else hipLaunchKernelGGL(k_gemm_f64acc<A_PLAIN>, g64, block, 0, eng->stream, p);
+    HIPCHK(eng, hipGetLastError());
+    return prof_close(eng, pr);
+  }
+  const int key = amode * 100 + cplx * 10 + epi;
+  switch (key) {
+    case A_PLAIN * 100 + 0 + E_BIAS: hipLaunchKernelGGL((umx_gemm_kernel<A_PLAIN, 0, E_BIAS>), grid, block, 0, eng->stream, p); break;
+    case A_PLAIN * 100 + 10 + E_BIAS: hipLaunchKernelGGL((umx_gemm_kernel<A_PLAIN, 1, E_BIAS>), grid, block, 0, eng->stream, p); break;
+    case A_MODUL * 100 + 0 + E_BIAS: hipLaunchKernelGGL((umx_gemm_kernel<A_MODUL, 0, E_BIAS>), grid, block, 0, eng->stream, p); break;
+    case A_MODUL * 100 + 10 + E_BIAS: hipLaunchKernelGGL((umx_gemm_kernel<A_MODUL, 1, E_BIAS>), grid, block, 0, eng->stream, p); break;
+    case A_SILU * 100 + 0 + E_BIAS: hipLaunchKernelGGL((umx_gemm_kernel<A_SILU, 0, E_BIAS>), grid, block, 0, eng->stream, p); break;
+    default: return fail(eng, UMX_ERR_ARG, "gemm: variant not instantiated");
+  }
+  HIPCHK(eng, hipGetLastError());
+  return prof_close(eng, pr);
+}
+
+struct NodeCtx { umx_engine* e; explicit NodeCtx(umx_engine* eng) : e(eng) { e->node_ctx = true; } ~NodeCtx() { e->node_ctx = false; } };
+
+// plain C = A . B^T (+bias, +resid)
+int gemm_plain(umx_engine* eng, const float* A, long lda, int offA, const float* B, long ldb, const float* bias, float* Cp,
+               long ldc, int offC, long M, int N, int K, int amode = A_PLAIN, int gz = 1, long zA = 0, long zC = 0,
+               const float* resid = nullptr, long ldres = 0, int offRes = 0, long zRes = 0) {
+  GemmP p = gp_zero();
+  p.A = A; p.lda = lda; p.offA0 = offA; p.B = B; p.ldb = ldb; p.bias = bias; p.Cp = Cp; p.ldc = ldc; p.offC = offC;
+  p.M = (int)M; p.N = N; p.K = K; p.zA = zA; p.zC = zC; p.resid = resid; p.ldres = ldres; p.offRes = offRes; p.zRes = zRes;
+  return launch_gemm(eng, p, amode, 0, E_BIAS, gz);
+}
+
+// the same for a NODE-level linear (rows = atoms): float64 accumulation when the engine asks for it (umx_engine::node_f64_on)
+template <class... Args> int gemm_node(umx_engine* eng, Args... args) {
+  NodeCtx node(eng);
+  return gemm_plain(eng, args...);
+}
+
+// ... and for the (node x grid point) rows of the grid feed-forward: float64-accumulated like the other node-level linears unless
+// UMX_GRID_F64=0 (fp32 MFMA)
+template <class... Args> int gemm_grid(umx_engine* eng, Args... args) {
+  if (!eng->grid_f64) return gemm_plain(eng, args...);
+  NodeCtx node(eng);
+  return gemm_plain(eng, args...);
+}
+
+// SO(2) complex linear on (edge, re/im) rows
+int gemm_cplx(umx_engine* eng, const float* A, long lda, int offRe, int offIm, const float* R, long ldr, int offR, const float* B,
+              long ldb, int bHalf, float* Cp, long ldc, int offCre, int offCim, long M, int N, int K, float conj) {
+  GemmP p = gp_zero();
+  p.A = A; p.lda = lda; p.offA0 = offRe; p.offA1 = offIm; p.R = R; p.ldr = ldr; p.offR = offR; p.B = B; p.ldb = ldb; p.bHalf = bHalf;
+  p.Cp = Cp; p.ldc = ldc; p.offC = offCre; p.offCi = offCim; p.M = (int)M; p.N = N; p.K = K; p.conj = conj;
+  return launch_gemm(eng, p, R ? A_MODUL : A_PLAIN, 1, E_BIAS);
+}
+
+// SO(3) linear on l-primary node rows: ONE launch, gridDim.z = 9 coefficients, the weights of degree l(z) picked per z (zBl);
+// the bias acts on the l = 0 row only
+int so3_linear(umx_engine* eng, const float* A, const float* Wl, const float* bias, float* Cp, long nn, const float* resid) {
+  GemmP p = gp_zero();
+  p.A = A; p.lda = ROW; p.offA0 = 0; p.B = Wl; p.ldb = C; p.bias = bias; p.Cp = Cp; p.ldc = ROW; p.offC = 0;
+  p.M = (int)nn; p.N = C; p.K = C; p.zA = C; p.zC = C; p.resid = resid; p.ldres = ROW; p.offRes = 0; p.zRes = C; p.zBl = (long)C * C;
+  NodeCtx node(eng);
+  return launch_gemm(eng, p, A_PLAIN, 0, E_BIAS, S);
+}
+
+// ---- split-precision GEMM of the large SO(2) / radial linears ----------------------------------
+// Operand formats and plane counts follow the pass and the engine's precision mode:
+//   forward, bf16x3 / split-bf16 : A = float32 quad-row blocks split into three bf16 planes by the GEMM in registers, B = three bf16 planes (6 products)
+//   forward, split-f16           : A = two fp16 planes of 16 x activation, B = three exact fp16 planes (4 products)
+//   reverse, bf16x3              : conv^T: A = float32 quad-row blocks (g_msg / g_hg), B = three bf16 planes, 6 products (umx_gemm_q.h);
+//                                  fc3^T: A = float32 ROWS (g_rad, a_f32rows) split by umx_gemm_pl16_kernel<.., AF = 1>
+//   reverse, split-* modes       : A, B = two PL bf16 planes, 3 products (umx_gemm_pl.h)
+// Kernel families: Q_F16 quad-row, two fp16 planes x three fp16 weight planes; Q_BF16 quad-row, float32 A blocks x three bf16 weight
+// planes; PL3_ROWS three PL planes, A = float32 rows (bf16x3 layer fc3^T); PL3 three PL planes (bf16x3 edge-degree fc3^T); PL2_* two PL
+// planes: 256-wide tiles / narrow tiles on the 16x16x32 MFMA / narrow tiles on the 32x32x16 MFMA
+enum PlFamily { Q_F16, Q_BF16, PL3_ROWS, PL3, PL2_WIDE, PL2_M16, PL2_M32 };
+
+// every instantiated plane GEMM, exactly once.  Q_BF16 rows: ls = the low-order plane products accumulate apart, in the form that goes
+// with the tile width (template LS = 1: 256 x 256 tiles, one spare accumulator folded in every k-step; LS = 2: 256 x 128 tiles, a second
+// accumulator set for the whole k loop); al = aligned leading plane of A
+struct PlKernel { PlFamily fam; bool cplx, wide, ls, al; void (*fn)(const GemmPL); };
+#define UMX_PAIR(fam, wide, ls, al, kernel, ...) {fam, false, wide, ls, al, kernel<0, __VA_ARGS__>}, {fam, true, wide, ls, al, kernel<1, __VA_ARGS__>}
+const PlKernel pl_kernels[] = {
+    UMX_PAIR(Q_F16, false, false, false, umx_gemm_q_kernel, 0, 2, 2, 1, 4, 3),
+    UMX_PAIR(Q_F16, true, false, false, umx_gemm_q_kernel, 1, 2, 2, 1, 4, 3),
+    UMX_PAIR(Q_BF16, false, false, false, umx_gemm_q_kernel, 0, 3, 2, 0, 6, 3, 1),
+    UMX_PAIR(Q_BF16, true, false, false, umx_gemm_q_kernel, 1, 3, 2, 0, 6, 3, 1),
+    UMX_PAIR(Q_BF16, false, false, true, umx_gemm_q_kernel, 0, 3, 2, 0, 6, 3, 1, 0, 1),
+    UMX_PAIR(Q_BF16, true, false, true, umx_gemm_q_kernel, 1, 3, 2, 0, 6, 3, 1, 0, 1),
+    UMX_PAIR(Q_BF16, false, true, false, umx_gemm_q_kernel, 0, 3, 2, 0, 6, 3, 1, 2),
+    UMX_PAIR(Q_BF16, true, true, false, umx_gemm_q_kernel, 1, 3, 2, 0, 6, 3, 1, 1),
+    UMX_PAIR(Q_BF16, false, true, true, umx_gemm_q_kernel, 0, 3, 2, 0, 6, 3, 1, 2, 1),
+    UMX_PAIR(Q_BF16, true, true, true, umx_gemm_q_kernel, 1, 3, 2, 0, 6, 3, 1, 1, 1),
+    {PL3_ROWS, false, false, false, false, umx_gemm_pl16_kernel<0, 3, 2, 4, 2, 2, 2, 0, 1>},     // (an 8 x 1 wave layout measured the same)
+    {PL3, false, false, false, false, umx_gemm_pl_kernel<0, 3, 2, 4, 2, 2, 2>},
+    UMX_PAIR(PL2_WIDE, true, false, false, umx_gemm_pl16_kernel, 2, 2, 4, 2, 2, 4),
+    UMX_PAIR(PL2_M16, false, false, false, umx_gemm_pl16_kernel, 2, 3, 4, 2, 2, 2),
+    UMX_PAIR(PL2_M32, false, false, false, umx_gemm_pl_kernel, 2, 3, 4, 2, 2, 2),
+};
+#undef UMX_PAIR
+
+// which instantiation runs one product, with which grid and which leading dimensions (in 2-byte units)
+// (prec: ProfRec::prec -- 24: two fp16 planes, 4 products; 3 / 2: bf16 planes, 6 / 3 products; err: the product has no instantiation)
+struct PlChoice { PlFamily fam; bool wide = false, ls = false, al = false; unsigned blocks = 0; long lda = 0, ldb = 0; int prec = 0; const char* err = nullptr; };
+PlChoice choose_pl(const Precision& pm, Pass pass, bool w_quad, int cplx, long M, int N, int K, int a_cols, bool a_f32rows, int low_sep, int align) {
+  PlChoice c;
+  const bool fwd = pass == FWD;
+  const int P = fwd ? 3 : pm.rev_planes;
+  c.prec = (fwd && pm.fwd_fmt == 1) ? 24 : P;
+  c.lda = (long)a_cols * P; c.ldb = (long)K * P;
+  // 256 x 256 tiles (two ring stages fit the LDS) wherever N fills whole tiles: a third less L2->LDS fill per FLOP, 9-11 % faster.
+  // Small systems (c1: 50 atoms x 8 images = 13 k edges = 51 row tiles): a launch whose wide grid does not even put one workgroup on
+  // every CU is bound by ONE tile's k-loop, so the narrow tiles (twice the workgroups, half the work each) finish sooner.
+  const int bmr = cplx ? 128 : 256;
+  const long nM = (M + bmr - 1) / bmr;
+  const bool fills = nM * (N / (cplx ? 128 : 256)) >= 256;          // wide grid >= one workgroup per CU
+  // LS: the three plane products of order 2^-16 of a forward bf16x3 GEMM accumulate apart from the large ones (umx_gemm_q.h) -- on every
+  // PLAIN product (radial fc3, conv-1 / conv-2 m = 0: operands with one-signed columns -- SiLU outputs, gated scalars, element embeddings);
+  // the complex m > 0 products take rotated l >= 1 components whose signs follow the edge direction, and measured no different with it
+  // (c5 energy error, three fixtures: none +1.0e-3 eV, fc3 only +5.9e-4, plain -7e-6, all -3e-5; c3 step 497 / 500 / 511 / 522 ms).
+  // UMX_LOW_SEP (dev A/B): 0 none, 1 fc3 only, 2 every forward product, 3 the plain ones (default).
+  c.ls = fwd && pm.fwd_fmt == 3 && (low_sep == 2 || (low_sep == 3 && !cplx) || (low_sep == 1 && !cplx && K == RH));
+  // (an LS product picks its tile from N alone: the two LS forms fold the small products in at different points, and an image must get the
+  //  same bits whether it is evaluated alone or in a batch -- tests/test_gpu_graph_parallel.py, test_gpu_parity.py batch independence)
+  c.wide = N % (cplx ? 128 : 256) == 0 && (fills || c.ls);
+  int bnc = c.wide ? (cplx ? 128 : 256) : (cplx ? 64 : 128);
+  if (fwd && pm.fwd_fmt == 1) {
+    // two fp16 planes of 16 x (activations), three exact planes of s_w x (weights): C = (A' . B'^T) / (16 s_w)
+    c.fam = Q_F16; c.lda = (long)a_cols * 2; c.ldb = (long)K * 3;
+  } else if (fwd || (P == 3 && w_quad)) {
+    // A = float32 quad-row blocks, split into the three bf16 planes in registers; weights as three bf16 planes.  The 256 x 128 LS form
+    // keeps a second accumulator set for the whole k loop (190 VGPRs: one workgroup per CU instead of two -- +10 ms at c3 for conv-1 /
+    // conv-2 m = 0; deeper rings do not buy it back: S = 3 / 4 measured +5 / +6 ms.  Round 6 measured the per-k-step fold of the wide
+    // tiles there too: 167-172 VGPRs as compiled (one workgroup per CU all the same); forced into the 128 VGPRs a second workgroup needs
+    // it spills 19 registers: +40 ms, and 48 float32 folds per output instead of one move the 20 000-atom energies to -9e-5 eV on two of
+    // four cases -- profiles/r06_ls_ab.txt; removed)
+    c.fam = Q_BF16; c.lda = (long)a_cols * 3; c.ldb = (long)K * 3;
+    c.al = fwd && (align == 1 || (align == 2 && !cplx));      // aligned planes: forward products only (the weights' planes were built to match, umx_load_weights)
+  } else if (P == 3) {
+    // three-plane PL products of the bf16x3 reverse pass: the radial fc3^T of the layers (A = float32 rows, split in registers) and of the
+    // edge-degree embedding (A = three PL planes written by k_rotate_back_bwd<3, 3>); both plain, N = 128, 256 x 128 tiles
+    if (cplx || N > 128) { c.err = "gemm_pl: three-plane PL products are instantiated for the plain N <= 128 (radial fc3^T) products only"; return c; }
+    c.fam = a_f32rows ? PL3_ROWS : PL3;                       // (wide is false here: N is no multiple of 256)
+    if (a_f32rows) c.lda = (long)a_cols * 2;                  // row pitch in 2-byte units
+  } else if (c.wide) {
+    c.fam = PL2_WIDE;
+  } else {
+    // MFMA shape per GEMM (measured in the c3 pipeline): 16x16x32 wins 1-7 % on the complex SO(2) GEMMs and on K >= 512,
+    // 32x32x16 wins 5-10 % on the short-K plain ones (radial fc3^T, conv-2^T m = 0)
+    c.fam = (cplx || K >= 512) ? PL2_M16 : PL2_M32;
+  }
+  c.blocks = (unsigned)(((nM + 7) / 8) * 8 * ((N + bnc - 1) / bnc));
+  return c;
+}
+
+// Wkey = fp32 device pointer of the weight (its plane copy is looked up); a_cols = total columns of the A matrix; offsets in columns.
+int gemm_pl(umx_engine* eng, int cplx, Pass pass, const unsigned short* Apl, int a_cols, int offA0, int offA1, const float* Wkey, int bHalf,
+            const float* bias, float* Cp, long ldc, int offC, int offCi, long M, int N, int K, float conj, bool a_f32rows = false) {
+  if (M <= 0) return UMX_OK;
+  auto it = eng->planes.find(Wkey);
+  if (it == eng->planes.end()) return fail(eng, UMX_ERR_ARG, "gemm_pl: weight has no PL copy");
+  if (K % 32 != 0) return fail(eng, UMX_ERR_ARG, "gemm_pl: K not a multiple of 32");
+  const PlaneCopy& w = it->second;
+  const PlChoice c = choose_pl(eng->prec, pass, w.quad, cplx, M, N, K, a_cols, a_f32rows, eng->low_sep, eng->align);
+  if (c.err) return fail(eng, UMX_ERR_ARG, c.err);
+  const PlKernel* k = nullptr;
+  for (const PlKernel& e : pl_kernels)
+    if (e.fam == c.fam && e.cplx == (cplx != 0) && e.wide == c.wide && e.ls == c.ls && e.al == c.al) { k = &e; break; }
+  if (!k) return fail(eng, UMX_ERR_ARG, "gemm_pl: variant not instantiated");
+  GemmPL q;
+  std::memset(&q, 0, sizeof(q));
+  q.Apl = Apl; q.lda = c.lda; q.offA0 = offA0; q.offA1 = offA1; q.Bpl = w.ptr; q.ldb = c.ldb; q.bHalf = bHalf;
+  q.Cp = Cp; q.ldc = ldc; q.offC = offC; q.offCi = offCi; q.bias = bias; q.conj = conj; q.M = (int)M; q.N = N; q.K = K;
+  q.odd_sign = eng->odd_sign;
+  if (c.fam == Q_F16) q.cscale = 1.0f / (QF16_SCALE * w.scale);
+  ProfRec* pr;
+  CHK(prof_open(eng, &pr, cplx ? 8.0 * M * (double)N * K : 2.0 * M * (double)N * K, c.prec, M, N, K, 9, cplx));
+  hipLaunchKernelGGL(k->fn, dim3(c.blocks), dim3(512), 0, eng->stream, q);
+  HIPCHK(eng, hipGetLastError());
+  return prof_close(eng, pr);
+}
+
+}  // namespace

@@ -7,7 +7,7 @@ No checkpoint exists in this environment, so the engine c
 by :func:`param_shapes`.  :func:`make_synthetic_weights` fills those shapes deterministically from
 a seed; the same arrays feed the HIP engine (through :func:`pack_blob`) and the CPU oracle.
 
-Blob layout (little endian), parsed by ``csrc/umx_api.hip``::
+Blob layout (little endian), parsed by ``csrc/umx_weights.h``::
 
     char  magic[8] = "UMXW0001"
     u32   n_tensors, u32 reserved
