@@ -120,6 +120,24 @@ int umx_load_weights(umx_engine* eng, const void* blob, size_t nbytes);
  * umx_model_variant: "ff=spectral|grid(G=..);emb=rand_emb|pos_emb|lin_emb;datasets=N" of the loaded blob ("" before).                 */
 const char* umx_model_variant(const umx_engine* eng);
 
+/* EXPERT-FORM BLOBS (additive, ABI v10).  A blob whose 24 SO(2) weights blocks.<i>.edge_wise.so2_conv_{1,2}.{fc_m0, so2_m_conv.0.fc,
+ * so2_m_conv.1.fc}.weight are Mixture-of-Linear-Experts stacks (n, out, in), 1 <= n <= 64 -- all 24 with one n, or none: anything mixed is
+ * UMX_ERR_WEIGHTS -- is an expert-form blob (checkpoint.convert_experts; it also carries the routing tensors, which the engine ignores).
+ * umx_load_weights validates and uploads it, builds every derived weight that does not depend on those 24, keeps the stacks resident on
+ * the device (4.52 M x 4 B x n: 579 MB at n = 32) and leaves the engine in the state "weights loaded, experts not merged": umx_set_system
+ * and every evaluation fail with UMX_ERR_ARG and a text that names umx_set_expert_coefficients.
+ *
+ * umx_set_expert_coefficients(n, alpha): n must be the blob's expert count and every alpha finite (UMX_ERR_ARG otherwise; an engine that
+ * holds a merged blob refuses too).  Runs the merge W = sum_k alpha_k W_k on the engine's stream -- float64 products and sums in expert
+ * order, no fused multiply-add, one rounding to float32 (checkpoint.merge_mole_ordered is the definition) -- and rebuilds the reverse-pass
+ * copies and the plane copies of the 24 weights on the device.  Afterwards the engine is in exactly the state umx_load_weights of the
+ * blob merged on the host with the same alpha leaves it in (same bytes in all three weight arenas, same plane records), no system bound:
+ * call umx_set_system next.  May be called again between evaluations with other coefficients; returns when the kernels have finished.
+ * umx_expert_count: the expert count of the loaded blob, 0 for a merged one.
+ * Replaces: fairchem's MoLE merge at the first evaluation of a system, uma_pysis.py:246-250, 502-504.       */
+int umx_set_expert_coefficients(umx_engine* eng, int n, const double* alpha);
+int umx_expert_count(const umx_engine* eng);
+
 /* Precision mode for the NEXT umx_load_weights ("auto", "bf16x3" (= "split-exact"), "split" (= "split-f16"), "split-bf16", "fp32"); NULL or "" = back to
  * the UMX_PRECISION environment variable.  The Python binding uses it to re-load an engine in split-bf16 when an evaluation
  * returned UMX_ERR_RANGE (ABI v6).                                                                                   */
@@ -264,6 +282,10 @@ int umx_bond_changes(umx_engine* eng, int n, const double* r1, const double* r2,
 int umx_debug_fetch(umx_engine* eng, const char* name, void* host_buf, size_t capacity,
                     size_t* nbytes_out);
 int umx_debug_keep(umx_engine* eng, int on);
+/* umx_debug_fetch also answers, on demand and without umx_debug_keep: "weights:w", "weights:dw", "weights:bw" -- the three weight arenas
+ * as they are on the device (float32 data section, float32 derived weights, 16-bit plane copies); "weights:table" -- the tensor table of
+ * "weights:w" as text, one "<name> <first float> <floats>" per line; "experts:kernel_ms" -- one float, the milliseconds between the events
+ * around the merge and packing kernels of the last umx_set_expert_coefficients.                                                          */
 
 #ifdef __cplusplus
 }

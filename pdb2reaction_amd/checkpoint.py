@@ -183,6 +183,21 @@ def merge_mole(experts: Array, coefficients: Array) -> Array:
     return np.tensordot(a, e, axes=(0, 0))
 
 
+def merge_mole_ordered(experts: Array, coefficients: Array) -> Array:
+    """The PINNED merge, the definition ``umx_set_expert_coefficients`` reproduces bit for bit: for every element
+    ``s = 0.0; for k in 0 .. n-1: s = s + alpha[k] * float64(W_k)`` -- every product and every sum rounded to float64, no fused
+    multiply-add, experts in ascending order -- then ONE rounding to float32.  (:func:`merge_mole` leaves the order to BLAS.)"""
+    e = np.asarray(experts)
+    a = np.asarray(coefficients, dtype=np.float64).reshape(-1)
+    if e.shape[0] != a.shape[0]:
+        raise ValueError(f"MoLE merge: {e.shape[0]} experts but {a.shape[0]} coefficients")
+    s = np.zeros(e.shape[1:], dtype=np.float64)
+    for k in range(e.shape[0]):
+        p = np.multiply(a[k], e[k].astype(np.float64))        # two separate array operations: a product, rounded, then a sum, rounded
+        s = np.add(s, p)
+    return s.astype(np.float32)
+
+
 # fairchem-style module names -> the engine's flat names [3P-UNVERIFIED, from memory of fairchem-core 2.x models/uma]: the lookup tables of
 # ChgSpinEmbedding live under ``.rand_emb``, DatasetEmbedding keeps one (1, C) table per dataset NAME, the S2-grid matrices are buffers of
 # ``SO3_grid["lmax_lmax"]`` with shape (lat, long, 9).  Applied after prefix stripping and before a user ``rename``.
@@ -236,7 +251,8 @@ def from_state_dict(state: Mapping[str, object], *, prefix: str = "backbone.", c
                     rename: Optional[Union[Mapping[str, str], Callable[[str], Optional[str]]]] = None,
                     extra: Optional[Mapping[str, object]] = None, strict: bool = True,
                     dataset_list: Optional[Sequence[str]] = None, variant: Optional[Mapping[str, Any]] = None,
-                    task: Optional[str] = None, info: Optional[Dict[str, Any]] = None) -> Dict[str, Array]:
+                    task: Optional[str] = None, info: Optional[Dict[str, Any]] = None, ordered_merge: bool = False,
+                    keep_experts: bool = False) -> Dict[str, Array]:
     """Turn a (fairchem-style) state dict into the engine's parameter dict.
 
     1. keys are stripped of ``prefix`` (keys without it are kept as they are); fairchem-style module names are mapped to the engine's
@@ -247,7 +263,10 @@ def from_state_dict(state: Mapping[str, object], *, prefix: str = "backbone.", c
        as it is -- its rows then ARE in ``dataset_list`` order; (lat, long, 9) grid matrices are flattened to (G, 9));
     2. ``rename`` (dict or callable returning the new name, or None to drop the key) is applied;
     3. a key ending in ``expert_suffix`` whose tensor has one more dimension than the target is an expert stack: it is merged
-       with ``coefficients`` and stored under ``<stem> + merged_suffix``;
+       with ``coefficients`` and stored under ``<stem> + merged_suffix`` (``ordered_merge``: with :func:`merge_mole_ordered`, the merge
+       the engine does on the device, instead of :func:`merge_mole`); with ``keep_experts`` (:func:`convert_experts`) the stack is KEPT,
+       as float32 (n_experts, out, in) under the merged name -- only the 24 SO(2) weights may be stacks then -- and so are the routing
+       tensors (``composition_embedding.weight``, ``routing_mlp.<n>.{weight,bias}``);
     4. ``extra`` adds tensors that live outside the module tree: ``normalizer.rmsd``, ``element_refs`` -- or ``atom_refs`` /
        ``form_elem_refs`` as the reference obtains them (``uma_pysis.py:231-239``; :func:`element_refs_from`, needs ``task``) -- and,
        for a grid model whose SO3_Grid buffers are not in the state dict, ``so3_grid.to_grid_mat`` / ``so3_grid.from_grid_mat``
@@ -284,9 +303,17 @@ def from_state_dict(state: Mapping[str, object], *, prefix: str = "backbone.", c
         if name.endswith(expert_suffix) and (name[: -len(expert_suffix)] + merged_suffix) in loose:
             target = name[: -len(expert_suffix)] + merged_suffix
             if arr.ndim == len(loose[target]) + 1:
-                if coefficients is None:
+                if keep_experts:
+                    if target not in W.EXPERT_WEIGHT_NAMES:
+                        raise UnsupportedCheckpoint(f"{key}: an expert stack on {target!r}; the engine merges experts of the {len(W.EXPERT_WEIGHT_NAMES)} SO(2) "
+                                                    "weights only (the per-system host conversion, convert_for_system, takes such a checkpoint)")
+                    if not (1 <= arr.shape[0] <= W.MAX_EXPERTS):
+                        raise UnsupportedCheckpoint(f"{key}: {arr.shape[0]} experts; an expert-form blob holds 1..{W.MAX_EXPERTS}")
+                    name = target
+                elif coefficients is None:
                     raise ValueError(f"{key}: expert stack of {arr.shape[0]} needs MoLE coefficients")
-                arr, name = merge_mole(arr, coefficients), target
+                else:
+                    arr, name = (merge_mole_ordered if ordered_merge else merge_mole)(arr, coefficients), target
         if name in out:
             raise KeyError(f"{name} assigned twice (last from {key})")
         out[name] = arr
@@ -320,7 +347,19 @@ def from_state_dict(state: Mapping[str, object], *, prefix: str = "backbone.", c
                        "dumped from the loaded model; they are data of the checkpoint and are not re-derived here")
     shapes = W.param_shapes(**have)
     res: Dict[str, Array] = {}
+    try:
+        n_exp = W.expert_count(out) if keep_experts else 0
+    except ValueError as exc:
+        raise UnsupportedCheckpoint(str(exc)) from None
     for name, arr in out.items():
+        if keep_experts and W.is_routing_tensor(name):
+            res[name] = np.ascontiguousarray(arr, dtype=np.float32)
+            continue
+        if n_exp and name in W.EXPERT_WEIGHT_NAMES:
+            if tuple(arr.shape[1:]) != tuple(shapes[name]):
+                raise ValueError(f"{name}: expert shape {tuple(arr.shape[1:])} != expected {tuple(shapes[name])}")
+            res[name] = np.ascontiguousarray(arr, dtype=np.float32)
+            continue
         if name not in shapes:
             if strict:
                 raise KeyError(f"{name!r} is not a parameter of the UMA-S engine for this variant ({have}; see weights.param_shapes())")
@@ -431,7 +470,7 @@ def convert_for_system(state: Mapping[str, object], atomic_numbers, charge: int,
 
 
 def convert(state: Mapping[str, object], *, merged_for: Optional[Mapping[str, object]] = None,
-            model_config: Union[None, str, Mapping[str, Any]] = None, strict_unknown: bool = False, **kw) -> bytes:
+            model_config: Union[None, str, Mapping[str, Any]] = None, strict_unknown: bool = False, _experts: bool = False, **kw) -> bytes:
     """State dict -> UMXW0001 blob (``weights.pack_blob`` of ``from_state_dict``).
 
     ``model_config`` (REQUIRED): the checkpoint's own hyper-parameters (:func:`find_model_config`) -- held against the engine
@@ -466,7 +505,7 @@ def convert(state: Mapping[str, object], *, merged_for: Optional[Mapping[str, ob
     kw.setdefault("dataset_list", model.get("dataset_list") or None)
     kw.setdefault("variant", {k: model[k] for k in ENGINE_CHOICES if k in model} or None)
     info: Dict[str, Any] = {}
-    params = from_state_dict(state, info=info, **kw)
+    params = from_state_dict(state, info=info, keep_experts=_experts, **kw)
     v = W.variant_of(params)
     model.update(ff_type=v["ff_type"], chg_spin_emb_type=v["chg_spin_emb_type"])
     if v["n_datasets"] == 0:
@@ -483,9 +522,80 @@ def convert(state: Mapping[str, object], *, merged_for: Optional[Mapping[str, ob
     if v["n_datasets"] and len(model["dataset_list"]) != v["n_datasets"]:
         raise UnsupportedCheckpoint(f"dataset_list has {len(model['dataset_list'])} names, the dataset embedding {v['n_datasets']} rows")
     meta: Dict[str, Any] = {"model": model}
+    if _experts:
+        n_exp = W.expert_count(params)
+        if not n_exp:
+            raise ValueError("convert_experts: the state dict holds no expert stacks (keys ending in expert_suffix with one more dimension "
+                             "than the weight): it is a merged parameter set, convert() takes it")
+        if W.COMPOSITION_KEY not in params or not any(k.startswith(W.ROUTING_PREFIX) for k in params):
+            raise KeyError(f"convert_experts: the state dict has no routing network ({W.COMPOSITION_KEY}, {W.ROUTING_PREFIX}<n>.weight/bias): "
+                           "the coefficients of a system could not be computed from the blob")
+        meta["experts"] = n_exp
     if merged_for is not None:
         meta["merged_for"] = dict(merged_for)
     return W.pack_blob(params, meta=meta)
+
+
+def convert_experts(state: Mapping[str, object], **kw) -> bytes:
+    """State dict with MoLE experts + routing network -> EXPERT-FORM blob: the validation, renaming, variant selection and trailer of
+    :func:`convert`, but no system and no coefficients.  The 24 SO(2) weights stay float32 stacks (n_experts, out, in) under their merged
+    names, the routing tensors stay in the blob, the trailer says ``"experts": n_experts`` and carries no ``merged_for``: the engine
+    keeps the stacks on the GPU and merges them for whichever system is bound (``umx_set_expert_coefficients``, alpha from
+    :func:`expert_coefficients`).  1 <= n_experts <= 64; a stack on any other tensor raises :class:`UnsupportedCheckpoint` naming it."""
+    for bad in ("coefficients", "merged_for"):
+        if kw.get(bad) is not None:
+            raise ValueError(f"convert_experts takes no {bad}: an expert-form blob belongs to no system")
+    kw.pop("coefficients", None)
+    kw.pop("merged_for", None)
+    return convert(state, _experts=True, **kw)
+
+
+def expert_coefficients(weight_set: Mapping[str, object], atomic_numbers, charge: int, spin: int, task: str) -> Array:
+    """alpha (n_experts,) of one system from the routing tensors AS STORED in an expert-form weight set (float32 values, float64
+    arithmetic): :func:`mole_coefficients` on the blob's own names, task rows in the order of its ``dataset_list``."""
+    meta = getattr(weight_set, "meta", None) or {}
+    dl = (meta.get("model") or {}).get("dataset_list") or W.DATASET_LIST
+    return mole_coefficients(weight_set, atomic_numbers, charge, spin, task, prefix="", dataset_list=tuple(dl))
+
+
+def merge_expert_set(weight_set: Mapping[str, object], coefficients: Array, merged_for: Optional[Mapping[str, object]] = None) -> "W.WeightSet":
+    """The merged weight set an expert-form one becomes under ``coefficients``, on the host: every stack through
+    :func:`merge_mole_ordered`, routing tensors dropped, ``merged_for`` recorded when given -- what the engine's device merge is
+    compared with."""
+    meta = {k: v for k, v in (getattr(weight_set, "meta", None) or {}).items() if k != "experts"}
+    if merged_for is not None:
+        meta["merged_for"] = dict(merged_for)
+    out = W.WeightSet(meta=meta)
+    for name, arr in weight_set.items():
+        if W.is_routing_tensor(name):
+            continue
+        out[name] = merge_mole_ordered(arr, coefficients) if name in W.EXPERT_WEIGHT_NAMES and np.ndim(arr) == 3 else np.asarray(arr, dtype=np.float32)
+    return out
+
+
+def _find_state(ckpt: Mapping[str, Any], state_key: Optional[str]):
+    for key in ([state_key] if state_key else ["ema_state_dict", "state_dict", "model_state_dict", "model"]):
+        cand = ckpt.get(key)
+        if isinstance(cand, Mapping) and any(hasattr(v, "shape") for v in cand.values()):
+            return cand
+    raise KeyError("convert_checkpoint: no state dict found in the checkpoint (tried " + (state_key or "ema_state_dict, state_dict, model_state_dict, model") + ")")
+
+
+def convert_checkpoint_experts(ckpt: Mapping[str, Any], *, state_key: Optional[str] = None, **kw) -> bytes:
+    """A whole checkpoint mapping -> expert-form blob: :func:`convert_checkpoint` without a system (model config found and validated the
+    same way, state dict taken from the same keys [3P-UNVERIFIED]).  ``normalizer.rmsd`` / ``element_refs`` are taken from ``extra=``,
+    from the state dict, or from entries of those names at the top of the mapping."""
+    cfg = kw.pop("model_config", None)
+    if cfg is None:
+        cfg = find_model_config(ckpt)
+        if cfg is None:
+            raise UnsupportedCheckpoint("the checkpoint carries no model config (no mapping with 'lmax' and 'sphere_channels'): it cannot be "
+                                        f"checked against the engine; pass model_config=... (or {ASSUME_UMA_S!r}) explicitly")
+    if kw.get("extra") is None:           # normaliser / element references stored next to the state dict, under the engine's names
+        top = {k: ckpt[k] for k in ("normalizer.rmsd", "element_refs") if k in ckpt}
+        if top:
+            kw["extra"] = top
+    return convert_experts(_find_state(ckpt, state_key), model_config=cfg, **kw)
 
 
 def convert_checkpoint(ckpt: Mapping[str, Any], atomic_numbers, charge: int, spin: int, task: str, *, state_key: Optional[str] = None,

@@ -13,10 +13,13 @@
 #include "umx_workspace.h"   // carving the workspace arena
 #include "umx_plan.h"        // the launch plan of one chunk, its executors, and one evaluation as its phases
 #include "umx_weights.h"     // the weight loader
+#include "umx_experts.h"     // expert-form weights: the Mixture-of-Linear-Experts merge and its plane copies on the device
 
 // ================================================================================================
 //                                           C ABI
 // ================================================================================================
+#define NOT_MERGED "expert-form weights are loaded but not merged: call umx_set_expert_coefficients first (then umx_set_system)"
+
 extern "C" {
 
 int umx_abi_version(void) { return 10; }
@@ -77,12 +80,13 @@ int umx_destroy(umx_engine* eng) {
   (void)hipSetDevice(eng->dev);
   (void)hipStreamSynchronize(eng->stream);
   for (auto& r : eng->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-  void* ptrs[] = {eng->d_w, eng->d_dw, eng->d_bw, eng->d_gmu, eng->d_z, eng->d_sysemb, eng->arena, eng->d_deg_all, eng->d_cand_all, eng->d_img_edges, eng->d_io_pos, eng->d_io_e, eng->d_io_f, eng->d_flags, eng->d_dtab, eng->d_part_deg, eng->d_part_f};
+  void* ptrs[] = {eng->d_w, eng->d_dw, eng->d_bw, eng->d_gmu, eng->d_z, eng->d_sysemb, eng->arena, eng->d_deg_all, eng->d_cand_all, eng->d_img_edges, eng->d_io_pos, eng->d_io_e, eng->d_io_f, eng->d_flags, eng->d_dtab, eng->d_part_deg, eng->d_part_f, eng->d_ex, eng->d_mjobs, eng->d_pjobs, eng->d_mx};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   (void)hipStreamSynchronize(eng->stream2);
   (void)hipEventDestroy(eng->ev_fork); (void)hipEventDestroy(eng->ev_join);
   (void)hipEventDestroy(eng->ev_tok[0]); (void)hipEventDestroy(eng->ev_tok[1]);
   if (eng->ev_done) (void)hipEventDestroy(eng->ev_done);
+  if (eng->ev_m0) { (void)hipEventDestroy(eng->ev_m0); (void)hipEventDestroy(eng->ev_m1); }
   (void)hipStreamDestroy(eng->stream2);
   (void)hipStreamDestroy(eng->stream);
   delete eng;
@@ -100,6 +104,13 @@ int umx_load_weights(umx_engine* eng, const void* blob, size_t nbytes) {
   return load_weights_impl(eng, blob, nbytes);
 }
 
+int umx_set_expert_coefficients(umx_engine* eng, int n, const double* alpha) {
+  if (!eng) return UMX_ERR_ARG;
+  return set_expert_coefficients_impl(eng, n, alpha);
+}
+
+int umx_expert_count(const umx_engine* eng) { return eng && eng->have_weights ? eng->n_experts : 0; }
+
 const char* umx_precision_mode(const umx_engine* eng) {
   if (!eng || !eng->have_weights) return "";
   return eng->prec.name;
@@ -113,6 +124,7 @@ const char* umx_model_variant(const umx_engine* eng) {
 int umx_set_system(umx_engine* eng, int n_atoms, const int32_t* z, int charge, int spin, int task_index, float radius, int max_neigh) {
   if (!eng) return UMX_ERR_ARG;
   if (!eng->have_weights) return fail(eng, UMX_ERR_ARG, "umx_set_system: load weights first");
+  if (eng->need_merge()) return fail(eng, UMX_ERR_ARG, "umx_set_system: " NOT_MERGED);
   if (n_atoms <= 0 || !z) return fail(eng, UMX_ERR_ARG, "umx_set_system: empty system");
   if (charge < -100 || charge > 100) return fail(eng, UMX_ERR_ARG, "umx_set_system: charge outside [-100, 100]");
   if (spin < 0 || spin > 100) return fail(eng, UMX_ERR_ARG, "umx_set_system: spin multiplicity outside [0, 100]");
@@ -206,6 +218,7 @@ int umx_synchronize(umx_engine* eng) {
 
 int umx_energy_forces_dev(umx_engine* eng, int n_images, const float* d_pos, double* d_energy, float* d_forces, void* hip_stream) {
   if (!eng) return UMX_ERR_ARG;
+  if (eng->need_merge()) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: " NOT_MERGED);
   if (!eng->have_system) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: bind a system first (umx_set_system)");
   if (n_images <= 0 || !d_pos || !d_energy) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: bad arguments");
   if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
@@ -218,6 +231,7 @@ int umx_energy_forces_dev(umx_engine* eng, int n_images, const float* d_pos, dou
 
 int umx_gp_begin(umx_engine* eng, const float* d_pos, int node_lo, int node_hi, double* d_energy, float* d_forces, void* hip_stream) {
   if (!eng) return UMX_ERR_ARG;
+  if (eng->need_merge()) return fail(eng, UMX_ERR_ARG, "umx_gp_begin: " NOT_MERGED);
   if (!eng->have_system) return fail(eng, UMX_ERR_ARG, "umx_gp_begin: bind a system first (umx_set_system)");
   if (!d_pos || !d_energy || !d_forces) return fail(eng, UMX_ERR_ARG, "umx_gp_begin: bad arguments (forces are part of the exchange)");
   if (node_lo < 0 || node_hi > eng->natoms || node_lo > node_hi) return fail(eng, UMX_ERR_ARG, "umx_gp_begin: node range outside [0, n_atoms]");
@@ -340,6 +354,7 @@ int umx_peer_sum(int n_peers, float* const* d_bufs, size_t count, const int* dev
 
 int umx_energy_forces(umx_engine* eng, int n_images, const float* pos, double* energy, float* forces) {
   if (!eng) return UMX_ERR_ARG;
+  if (eng->need_merge()) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: " NOT_MERGED);
   if (!eng->have_system) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: bind a system first (umx_set_system)");
   if (n_images <= 0 || !pos || !energy) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: bad arguments");
   if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
@@ -437,6 +452,35 @@ int umx_debug_keep(umx_engine* eng, int on) {
 
 int umx_debug_fetch(umx_engine* eng, const char* name, void* host_buf, size_t capacity, size_t* nbytes_out) {
   if (!eng || !name) return UMX_ERR_ARG;
+  const std::string nm(name);
+  if (nm.rfind("weights:", 0) == 0 || nm.rfind("experts:", 0) == 0) {
+    // fetched on demand: the three weight arenas as they are on the device, the tensor table of d_w ("<name> <first float> <floats>" per
+    // line), and the kernel time of the last umx_set_expert_coefficients (one float, milliseconds between its two events)
+    if (!eng->have_weights) return fail(eng, UMX_ERR_ARG, "umx_debug_fetch: load weights first");
+    HIPCHK(eng, hipSetDevice(eng->dev));
+    HIPCHK(eng, hipStreamSynchronize(eng->stream));
+    const void* dptr = nullptr; size_t nb = 0;
+    std::string table; float ms = 0.f;
+    if (nm == "weights:w") { dptr = eng->d_w; nb = eng->n_w * sizeof(float); }
+    else if (nm == "weights:dw") { dptr = eng->d_dw; nb = eng->n_dw * sizeof(float); }
+    else if (nm == "weights:bw") { dptr = eng->d_bw; nb = eng->n_bw * sizeof(unsigned short); }
+    else if (nm == "weights:table") {
+      for (const auto& kv : eng->wt) table += kv.first + " " + std::to_string(kv.second.off) + " " + std::to_string(kv.second.count) + "\n";
+      nb = table.size();
+    } else if (nm == "experts:kernel_ms") {
+      if (!eng->experts_merged) return fail(eng, UMX_ERR_ARG, "umx_debug_fetch: no expert merge has run");
+      HIPCHK(eng, hipEventElapsedTime(&ms, eng->ev_m0, eng->ev_m1));
+      nb = sizeof(float);
+    } else return fail(eng, UMX_ERR_ARG, std::string("umx_debug_fetch: no buffer named ") + name);
+    if (nbytes_out) *nbytes_out = nb;
+    if (host_buf) {
+      if (capacity < nb) return fail(eng, UMX_ERR_ARG, "umx_debug_fetch: buffer too small");
+      if (dptr) HIPCHK(eng, hipMemcpy(host_buf, dptr, nb, hipMemcpyDeviceToHost));
+      else if (nm == "weights:table") std::memcpy(host_buf, table.data(), nb);
+      else std::memcpy(host_buf, &ms, nb);
+    }
+    return UMX_OK;
+  }
   auto it = eng->dbg.find(name);
   if (it == eng->dbg.end()) return fail(eng, UMX_ERR_ARG, std::string("umx_debug_fetch: no buffer named ") + name);
   if (nbytes_out) *nbytes_out = it->second.size();

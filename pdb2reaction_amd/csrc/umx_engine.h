@@ -93,6 +93,30 @@ struct PlaneCopy {
   float scale;                     // fp16 form: the power-of-two scale folded into the planes (else 0)
 };
 
+// ---- expert-form weights (umx_experts.h) -----------------------------------------------------------
+// A blob whose 24 SO(2) weights are Mixture-of-Linear-Experts stacks (n, out, in) keeps the stacks on the device; umx_set_expert_coefficients
+// merges them into the slots a host-merged blob would have filled (d_w, transposed copy in d_dw, plane copies in d_bw).  One record per
+// weight (MergeJob) and per plane copy (PackJob), built by umx_load_weights, read by the two kernels from device memory.
+constexpr int MAX_EXPERTS = 64;
+constexpr int N_EXPERT_W = 6 * NL;          // the SO(2) weights of conv 1 and conv 2: fc_m0, so2_m_conv.0.fc, so2_m_conv.1.fc per layer
+struct ExpertAlpha { double a[MAX_EXPERTS]; };
+struct PackScales { float s[N_EXPERT_W]; };  // fp16 forward planes: the power-of-two scale of each forward weight (from its max |w|)
+struct MergeJob {
+  const float* stack;     // (n, rows, cols) float32
+  float* w;               // merged (rows, cols) in d_w
+  float* wT;              // reverse-pass copy in d_dw: (2, cols, half) with rows = 2 * half -- or the plain transpose, half = rows
+  int rows, cols, half;
+  int blk0;               // first workgroup of this job (32 x 128 tiles)
+};
+struct PackJob {
+  const float* src;       // merged float32 weight (rows, K) in d_w or d_dw
+  unsigned short* dst;    // its plane copy in d_bw
+  int rows, K, P;         // P planes
+  int quad, alignw;       // quad-row (else PL) layout; aligned leading planes
+  int f16;                // fp16 planes of s * w, s = PackScales::s[f16 - 1] (0: bf16 planes)
+  int blk0;               // first workgroup of this job (256 lanes, one 8-k group of one row each)
+};
+
 // ---- workspace view (carved by umx_workspace.h) --------------------------------------------------
 struct WS {
   // node level
@@ -194,6 +218,17 @@ struct umx_engine {
   std::map<const float*, PlaneCopy> planes;   // fp32 weight ptr -> its plane copy (forward weights and their transposes)
   std::map<std::string, Tensor> wt;
   std::vector<float> h_w;        // host copy of the data section (needed to build derived weights)
+  size_t n_w = 0, n_dw = 0, n_bw = 0;   // elements of d_w / d_dw / d_bw (umx_debug_fetch "weights:w|dw|bw")
+  // expert form (umx_experts.h): n_experts > 0 -- the 24 SO(2) weights of d_w / d_dw / d_bw are filled by umx_set_expert_coefficients;
+  // h_w and d_w then hold the COMPACT data section (every stack takes the room of one expert, table order, 64-byte aligned)
+  int n_experts = 0;
+  bool experts_merged = false;
+  float* d_ex = nullptr;           // the expert stacks
+  MergeJob* d_mjobs = nullptr; PackJob* d_pjobs = nullptr; unsigned* d_mx = nullptr;
+  int n_mjobs = 0, n_pjobs = 0, merge_blocks = 0, pack_blocks = 0;
+  std::vector<const float*> f16_keys;   // fp16 forward planes: PackScales slot -> key of the weight's PlaneCopy (its scale follows the merge)
+  hipEvent_t ev_m0 = nullptr, ev_m1 = nullptr;   // around the merge + pack kernels of the last umx_set_expert_coefficients
+  bool need_merge() const { return n_experts > 0 && !experts_merged; }
   RadialW rdeg{};
   LayerW lw[NL]{};
   const float *emb_sphere = nullptr, *normw = nullptr, *normb = nullptr, *e0 = nullptr, *e0b = nullptr, *e0T = nullptr,

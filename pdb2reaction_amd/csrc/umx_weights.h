@@ -37,16 +37,23 @@ float from_half(unsigned short h) {
   return v;
 }
 
+// fp16 forward planes: the power of two that puts max|w| into [2^14, 2^15)
+float f16_scale(float mx) {
+  int ex = 0;
+  if (mx > 0.f && std::isfinite(mx)) { std::frexp(mx, &ex); ex = std::max(-24, std::min(40, 15 - ex)); }   // mx = f * 2^ex', f in [0.5, 1)
+  return std::ldexp(1.0f, ex);
+}
+
 // The host image of all plane copies (uploaded as d_bw) and where each weight's copy starts in it.  RNE split with exact residuals.
 struct PlanePacker {
-  struct Req { const float* dev; size_t off; bool quad; float scale; };
+  struct Req { const float* dev; size_t off; bool quad; float scale; int rows, K, P; bool fwd, f16; };
   Precision pm; int align;
   std::vector<unsigned short> bw;
   std::vector<Req> req;
-  size_t open(const float* dev, size_t count, bool quad, float scale) {
+  size_t open(const float* dev, size_t count, bool quad, float scale, int rows, int K, int P, bool fwd, bool f16) {
     const size_t off = (bw.size() + 63) & ~size_t(63);
     bw.resize(off + count);
-    req.push_back({dev, off, quad, scale});
+    req.push_back({dev, off, quad, scale, rows, K, P, fwd, f16});
     return off;
   }
   // fp16 quad-row copy of a forward weight: three half planes of s * w, s = the power of two that puts max|w| into [2^14, 2^15):
@@ -55,10 +62,8 @@ struct PlanePacker {
     const int PB = 3;
     float mx = 0.f;
     for (size_t i = 0; i < (size_t)rows * K; ++i) mx = std::max(mx, std::fabs(host[i]));
-    int ex = 0;
-    if (mx > 0.f && std::isfinite(mx)) { std::frexp(mx, &ex); ex = std::max(-24, std::min(40, 15 - ex)); }   // mx = f * 2^ex', f in [0.5, 1)
-    const float sc = std::ldexp(1.0f, ex);
-    const size_t off = open(dev, (size_t)rows * K * PB, true, sc);
+    const float sc = f16_scale(mx);
+    const size_t off = open(dev, (size_t)rows * K * PB, true, sc, rows, K, PB, true, true);
     for (int rr = 0; rr < rows; ++rr)
       for (int k = 0; k < K; ++k) {
         float x = host[(size_t)rr * K + k] * sc;
@@ -73,7 +78,7 @@ struct PlanePacker {
     const int P = fwdw ? 3 : pm.rev_planes;
     const bool quad = fwdw || (rev_quad && P == 3);
     if (fwdw && pm.fwd_fmt == 1) { pack_f16(host, dev, rows, K); return; }
-    const size_t off = open(dev, (size_t)rows * K * P, quad, 0.f);
+    const size_t off = open(dev, (size_t)rows * K * P, quad, 0.f, rows, K, P, fwdw, false);
     // aligned planes (forward bf16 weights): the value that goes into plane q < 2 is first rounded to a multiple of 2^(e_max - 12), e_max =
     // exponent of the largest magnitude of what is left of the 8 weights the matrix core sees in one pass (k = 8 g ... 8 g + 7 of one row);
     // the exact remainder goes down the planes, so w0 + w1 + w2 is what it was (umx_gemm_pl.h qf_align_magic does the same to A's leading plane)
@@ -117,6 +122,26 @@ template <class T> int upload(umx_engine* eng, T*& dst, const std::vector<T>& sr
 
 // ---- umx_load_weights ----------------------------------------------------------------------------------
 
+// the 24 SO(2) weights a Mixture-of-Linear-Experts checkpoint stacks (umx_experts.h)
+std::vector<std::string> expert_weight_names() {
+  std::vector<std::string> v;
+  for (int i = 0; i < NL; ++i)
+    for (const char* c : {"1", "2"})
+      for (const char* leaf : {".fc_m0.weight", ".so2_m_conv.0.fc.weight", ".so2_m_conv.1.fc.weight"})
+        v.push_back("blocks." + std::to_string(i) + ".edge_wise.so2_conv_" + c + leaf);
+  return v;
+}
+
+// drop what an earlier expert-form blob left on the device
+int experts_release(umx_engine* eng) {
+  HIPCHK(eng, hipStreamSynchronize(eng->stream));
+  void** ptrs[] = {(void**)&eng->d_ex, (void**)&eng->d_mjobs, (void**)&eng->d_pjobs, (void**)&eng->d_mx};
+  for (void** p : ptrs) if (*p) { HIPCHK(eng, hipFree(*p)); *p = nullptr; }
+  eng->n_experts = 0; eng->experts_merged = false; eng->n_mjobs = eng->n_pjobs = eng->merge_blocks = eng->pack_blocks = 0;
+  eng->f16_keys.clear();
+  return UMX_OK;
+}
+
 int load_weights_impl(umx_engine* eng, const void* blob, size_t nbytes) {
   HIPCHK(eng, hipSetDevice(eng->dev));
   const char* b = static_cast<const char*>(blob);
@@ -127,6 +152,7 @@ int load_weights_impl(umx_engine* eng, const void* blob, size_t nbytes) {
   if (nbytes < 16 + (size_t)n * esz) return fail(eng, UMX_ERR_WEIGHTS, "weight blob: truncated table");
   size_t pos = 16;
   eng->wt.clear();
+  std::vector<std::string> order;           // names in table order
   size_t max_end = 0;
   for (uint32_t i = 0; i < n; ++i) {
     char name[97]; std::memcpy(name, b + pos, 96); name[96] = 0;
@@ -139,15 +165,62 @@ int load_weights_impl(umx_engine* eng, const void* blob, size_t nbytes) {
     for (uint32_t d = 0; d < ndim; ++d) { t.shape.push_back((int)dims[d]); cnt *= dims[d]; }
     if (cnt != t.count) return fail(eng, UMX_ERR_WEIGHTS, std::string("weight blob: size mismatch for ") + name);
     eng->wt[name] = t;
+    order.push_back(name);
     max_end = std::max(max_end, (size_t)(off + nb));
     pos += esz;
   }
   const size_t data0 = (pos + 63) & ~size_t(63);
   if (nbytes < data0 + max_end) return fail(eng, UMX_ERR_WEIGHTS, "weight blob: truncated data");
-  eng->h_w.assign(reinterpret_cast<const float*>(b + data0), reinterpret_cast<const float*>(b + data0) + (max_end + 3) / 4);
+  const float* src = reinterpret_cast<const float*>(b + data0);
   for (const auto& kv : eng->wt)            // a non-finite parameter would only show up later as a non-finite energy
     for (size_t i = 0; i < kv.second.count; ++i)
-      if (!std::isfinite(eng->h_w[kv.second.off + i])) return fail(eng, UMX_ERR_WEIGHTS, "weight blob: non-finite value in " + kv.first);
+      if (!std::isfinite(src[kv.second.off + i])) return fail(eng, UMX_ERR_WEIGHTS, "weight blob: non-finite value in " + kv.first);
+  // ---- expert form?  The 24 SO(2) weights all stacked (n, out, in) with one n, or none of them
+  int nex = 0;
+  {
+    int stacked = 0;
+    for (const std::string& nm : expert_weight_names()) {
+      auto it = eng->wt.find(nm);
+      if (it == eng->wt.end() || it->second.shape.size() != 3) continue;
+      if (stacked && it->second.shape[0] != nex) return fail(eng, UMX_ERR_WEIGHTS, "weight blob: expert stacks of different sizes (" + nm + ")");
+      nex = it->second.shape[0];
+      ++stacked;
+    }
+    if (stacked && stacked != N_EXPERT_W)
+      return fail(eng, UMX_ERR_WEIGHTS, "weight blob: " + std::to_string(stacked) + " of the " + std::to_string(N_EXPERT_W) + " SO(2) weights are expert stacks: all of them or none");
+    if (stacked && (nex < 1 || nex > MAX_EXPERTS)) return fail(eng, UMX_ERR_WEIGHTS, "weight blob: expert count outside [1, " + std::to_string(MAX_EXPERTS) + "]");
+  }
+  CHK(experts_release(eng));
+  std::map<std::string, size_t> ex_off;      // expert form: where each stack starts in d_ex
+  if (nex == 0) {
+    eng->h_w.assign(src, src + (max_end + 3) / 4);
+  } else {
+    // the compact data section: the tensors in table order, 64-byte aligned, every stack in the room of ONE expert (what a host-merged blob
+    // of the same tensors looks like); the stacks go straight from the blob to the device
+    std::set<std::string> exn;
+    for (const std::string& nm : expert_weight_names()) exn.insert(nm);
+    size_t cur = 0, ex_total = 0;
+    for (const std::string& nm : order) if (exn.count(nm)) ex_total += eng->wt[nm].count;
+    HIPCHK(eng, hipMalloc(&eng->d_ex, ex_total * sizeof(float)));
+    std::vector<std::pair<size_t, Tensor*>> moves;
+    size_t exc = 0;
+    for (const std::string& nm : order) {
+      Tensor& t = eng->wt[nm];
+      const size_t old = t.off;
+      if (exn.count(nm)) {
+        HIPCHK(eng, hipMemcpy(eng->d_ex + exc, src + old, t.count * sizeof(float), hipMemcpyHostToDevice));
+        ex_off[nm] = exc; exc += t.count;
+        t.count /= (size_t)nex; t.shape.erase(t.shape.begin());
+        t.off = cur;
+      } else {
+        t.off = cur;
+        moves.push_back({old, &t});
+      }
+      cur += (t.count + 15) & ~size_t(15);
+    }
+    eng->h_w.assign(cur, 0.f);
+    for (const auto& mv : moves) std::copy(src + mv.first, src + mv.first + mv.second->count, eng->h_w.begin() + mv.second->off);
+  }
 
   auto need = [&](const std::string& nm, std::vector<int> shape) -> const Tensor* {
     auto it = eng->wt.find(nm);
@@ -326,6 +399,45 @@ int load_weights_impl(umx_engine* eng, const void* blob, size_t nbytes) {
   CHK(upload(eng, eng->d_bw, pk.bw));
   eng->planes.clear();
   for (const auto& r : pk.req) eng->planes[r.dev] = PlaneCopy{eng->d_bw + r.off, r.quad, r.scale};
+  eng->n_w = eng->h_w.size(); eng->n_dw = dw.size(); eng->n_bw = pk.bw.size();
+  if (nex) {
+    // the 24 weights' slots in d_w, their reverse-pass copies in d_dw and the 48 plane copies in d_bw were built from zeros above: what
+    // umx_set_expert_coefficients has to fill, as job records for its two kernels
+    std::vector<MergeJob> mj;
+    std::vector<PackJob> pj;
+    std::set<const float*> slots;
+    int mblk = 0, pblk = 0;
+    for (int i = 0; i < NL; ++i) {
+      const std::string bpre = "blocks." + std::to_string(i);
+      const std::string c1 = bpre + ".edge_wise.so2_conv_1", c2 = bpre + ".edge_wise.so2_conv_2";
+      auto job = [&](const std::string& nm, size_t toff, int rows, int cols, int half) {
+        float* w = eng->d_w + eng->wt[nm].off;
+        mj.push_back({eng->d_ex + ex_off[nm], w, eng->d_dw + toff, rows, cols, half, mblk});
+        mblk += (rows / 32) * (cols / 128);
+        slots.insert(w); slots.insert(eng->d_dw + toff);
+      };
+      job(c1 + ".fc_m0.weight", loff[i].c1m0T, 640, 768, 640); job(c1 + ".so2_m_conv.0.fc.weight", loff[i].c1m1T, 512, 512, 256);
+      job(c1 + ".so2_m_conv.1.fc.weight", loff[i].c1m2T, 256, 256, 128); job(c2 + ".fc_m0.weight", loff[i].c2m0T, 384, 384, 384);
+      job(c2 + ".so2_m_conv.0.fc.weight", loff[i].c2m1T, 512, 256, 256); job(c2 + ".so2_m_conv.1.fc.weight", loff[i].c2m2T, 256, 128, 128);
+    }
+    eng->f16_keys.clear();
+    for (const auto& r : pk.req) {
+      if (!slots.count(r.dev)) continue;
+      int f16 = 0;
+      if (r.f16) { eng->f16_keys.push_back(r.dev); f16 = (int)eng->f16_keys.size(); }
+      pj.push_back({r.dev, eng->d_bw + r.off, r.rows, r.K, r.P, r.quad ? 1 : 0, (r.fwd && eng->align != 0) ? 1 : 0, f16, pblk});
+      pblk += (int)(((size_t)r.rows * (r.K / 8) + 255) / 256);
+    }
+    if ((int)mj.size() != N_EXPERT_W || (int)pj.size() != 2 * N_EXPERT_W) return fail(eng, UMX_ERR_WEIGHTS, "weight blob: expert job table is incomplete");
+    HIPCHK(eng, hipMalloc(&eng->d_mjobs, mj.size() * sizeof(MergeJob)));
+    HIPCHK(eng, hipMalloc(&eng->d_pjobs, pj.size() * sizeof(PackJob)));
+    HIPCHK(eng, hipMalloc(&eng->d_mx, N_EXPERT_W * sizeof(unsigned)));
+    HIPCHK(eng, hipMemcpy(eng->d_mjobs, mj.data(), mj.size() * sizeof(MergeJob), hipMemcpyHostToDevice));
+    HIPCHK(eng, hipMemcpy(eng->d_pjobs, pj.data(), pj.size() * sizeof(PackJob), hipMemcpyHostToDevice));
+    eng->n_mjobs = (int)mj.size(); eng->n_pjobs = (int)pj.size(); eng->merge_blocks = mblk; eng->pack_blocks = pblk;
+    if (!eng->ev_m0) { HIPCHK(eng, hipEventCreate(&eng->ev_m0)); HIPCHK(eng, hipEventCreate(&eng->ev_m1)); }
+  }
+  eng->n_experts = nex; eng->experts_merged = false;
   auto fill_rad = [&](RadialW& r, const std::string& pre, int out) {
     const RadOff& o = roff[pre];
     r.w1g = D(o.w1g); r.w1gT = D(o.w1gT); r.w2T = D(o.w2T); r.w3T = D(o.w3T);

@@ -72,6 +72,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "umx_set_precision": ([vp, C.c_char_p], i32),
         "umx_precision_mode": ([vp], C.c_char_p),
         "umx_model_variant": ([vp], C.c_char_p),
+        "umx_set_expert_coefficients": ([vp, i32, dp], i32),
+        "umx_expert_count": ([vp], i32),
         "umx_set_system": ([vp, i32, C.POINTER(C.c_int32), i32, i32, i32, C.c_float, i32], i32),
         "umx_set_workspace_limit": ([vp, C.c_size_t], i32),
         "umx_energy_forces": ([vp, i32, fp, dp, fp], i32),
@@ -123,6 +125,7 @@ EXPORTED_SYMBOLS = (
     "umx_abi_version", "umx_build_digest", "umx_create", "umx_destroy", "umx_last_error", "umx_load_weights", "umx_set_precision", "umx_precision_mode", "umx_model_variant", "umx_set_system",
     "umx_set_workspace_limit", "umx_energy_forces", "umx_energy_forces_dev", "umx_gp_begin", "umx_gp_step", "umx_peer_sum", "umx_synchronize",
     "umx_last_graph_stats", "umx_last_partitions", "umx_last_lanes", "umx_reserve_images", "umx_workspace_stats", "umx_profile_enable", "umx_profile_read", "umx_bond_changes", "umx_debug_fetch", "umx_debug_keep",
+    "umx_set_expert_coefficients", "umx_expert_count",
 )
 
 
@@ -162,6 +165,9 @@ class Engine:
         self.widened = False            # True once an fp16 range violation moved this engine to bf16 forward planes (split-bf16 / bf16x3)
         self._blob = None
         self._system = None
+        self.n_experts = 0              # > 0: the loaded blob is in expert form; set_system merges its experts for the system it binds
+        self.expert_coefficients = None # the MoLE coefficients alpha (n_experts,) of the last set_system on an expert-form blob
+        self._routing = None            # expert form: the blob's tensors without the stacks (the routing network reads them)
         self.dataset_list = tuple(W.DATASET_LIST)      # order of the rows of the loaded blob's dataset_embedding.weight (load_weights)
         if precision is not None:
             self._chk(self.lib.umx_set_precision(self._h, precision.encode()), "umx_set_precision")
@@ -186,11 +192,22 @@ class Engine:
     # ---- setup -----------------------------------------------------------------------------------
     def load_weights(self, weights: Union[bytes, Dict[str, np.ndarray]]):
         blob = weights if isinstance(weights, (bytes, bytearray)) else W.pack_blob(weights)
-        self._blob = bytes(blob)        # kept (~27 MB) so that a range violation can re-load the engine in split-bf16
-        buf = C.create_string_buffer(self._blob, len(self._blob))
-        self._chk(self.lib.umx_load_weights(self._h, C.cast(buf, C.c_void_p), len(self._blob)), "umx_load_weights")
+        # kept so that a range violation can re-load the engine in split-bf16: ~27 MB for a merged blob; an expert-form blob is its
+        # stacks -- 18 MB per expert, 579 MB of HOST memory at 32 experts, next to the copy on the device
+        self._blob = blob if isinstance(blob, bytes) else bytes(blob)
+        # (the library only reads the blob: it is handed over in place, an expert-form one is too large to copy for the call)
+        self._chk(self.lib.umx_load_weights(self._h, C.cast(C.c_char_p(self._blob), C.c_void_p), len(self._blob)), "umx_load_weights")
         # task names -> rows of dataset_embedding.weight: the checkpoint's own dataset_list when the blob records one (checkpoint.py), else UMA's
         meta = weights.meta if hasattr(weights, "meta") else W.blob_meta(self._blob)
+        self.n_experts = int(self.lib.umx_expert_count(self._h))
+        self.expert_coefficients, self._routing = None, None
+        if meta.get("experts") is not None and int(meta["experts"]) != self.n_experts:
+            raise UmxError(f"the weight blob's trailer says {meta['experts']} experts, the engine found {self.n_experts} in its tensors")
+        if self.n_experts:
+            if isinstance(weights, (bytes, bytearray)):
+                self._routing = W.unpack_blob(self._blob, skip=W.EXPERT_WEIGHT_NAMES)
+            else:
+                self._routing = W.WeightSet(((k, v) for k, v in weights.items() if k not in W.EXPERT_WEIGHT_NAMES), meta=meta)
         self.dataset_list = tuple((meta.get("model") or {}).get("dataset_list") or W.DATASET_LIST)
         # the list must name exactly the rows the blob's dataset embedding has (a re-ordered or shorter table without a trailer would
         # otherwise map task names to the wrong rows silently); datasets=0: a model without dataset embedding takes any task name
@@ -211,6 +228,15 @@ class Engine:
         z = np.ascontiguousarray(atomic_numbers, dtype=np.int32)
         if task not in self.dataset_list:
             raise ValueError(f"task_name {task!r} not in {self.dataset_list}")
+        if self.n_experts:
+            # expert form: alpha of THIS system on the host (a 256 -> 64 -> n MLP on one vector), the merge of the 24 SO(2) weights and
+            # their plane copies on the device; binding another system later merges again
+            from .checkpoint import expert_coefficients
+
+            alpha = np.ascontiguousarray(expert_coefficients(self._routing, z, int(charge), int(spin), task), dtype=np.float64)
+            self._chk(self.lib.umx_set_expert_coefficients(self._h, len(alpha), alpha.ctypes.data_as(C.POINTER(C.c_double))),
+                      "umx_set_expert_coefficients")
+            self.expert_coefficients = alpha
         self._chk(self.lib.umx_set_system(self._h, len(z), z.ctypes.data_as(C.POINTER(C.c_int32)), int(charge), int(spin),
                                           self.dataset_list.index(task), float(radius or 0.0), int(max_neigh or 0)),
                   "umx_set_system")

@@ -23,7 +23,7 @@ library, and fails loudly otherwise.
 from __future__ import annotations
 
 import os
-from typing import Any, Dict, List, Optional, Sequence
+from typing import Any, Dict, List, Mapping, Optional, Sequence
 
 import numpy as np
 
@@ -68,10 +68,15 @@ FD_BATCH = int(os.environ.get("UMX_FD_BATCH", "64"))
 
 
 def resolve_weights(model: str) -> "W.WeightSet":
-    """Map the reference's ``model`` keyword to a merged UMA-S parameter set.
+    """Map the reference's ``model`` keyword to a UMA-S parameter set.
 
-    * a path to a ``.umxw`` blob -> loaded as is;
-    * a model name -> ``$UMX_WEIGHTS_DIR/<name>.umxw``;
+    * a path to a ``.umxw`` blob -> loaded as is, merged for one system or in EXPERT FORM (``checkpoint.convert_experts``: one file
+      for every system, the engine merges the experts on the GPU when a system is bound);
+    * a path to a checkpoint file (anything else that exists) -> ``torch.load(map_location="cpu", weights_only=True)`` and
+      ``checkpoint.convert_checkpoint_experts``: model config, state dict, normaliser and element references are taken from the
+      mapping as ``checkpoint.convert`` demands them; a file that does not unpickle under ``weights_only=True`` raises with that
+      reason (key names [3P-UNVERIFIED], like the rest of the loader);
+    * a model name -> ``$UMX_WEIGHTS_DIR/<name>.umxw``, else ``$UMX_WEIGHTS_DIR/<name>.pt`` (a checkpoint file, as above);
     * ``"synthetic"`` / ``"synthetic:<seed>"`` -> the deterministic stand-in of ``weights.make_synthetic_weights``
       (what tests and bench.py use: the real checkpoint is a gated download that does not exist here, SURVEY.md 8c);
     * anything else raises ``FileNotFoundError`` -- like the reference, which raises when the checkpoint cannot be
@@ -82,11 +87,13 @@ def resolve_weights(model: str) -> "W.WeightSet":
     if m == "synthetic" or m.startswith("synthetic:"):
         return W.make_synthetic_weights(int(m.split(":", 1)[1]) if ":" in m else int(os.environ.get("UMX_SYNTHETIC_SEED", "0")))
     if os.path.isfile(m):
-        return W.load_weights(m)
+        return _load_weight_file(m)
     wdir = os.environ.get("UMX_WEIGHTS_DIR")
     cand = os.path.join(wdir, f"{m}.umxw") if wdir else None
     if cand and os.path.isfile(cand):
         return W.load_weights(cand)
+    if wdir and os.path.isfile(os.path.join(wdir, f"{m}.pt")):
+        return _load_weight_file(os.path.join(wdir, f"{m}.pt"))
     if os.environ.get("UMX_ALLOW_SYNTHETIC", "0") == "1":
         import warnings
 
@@ -98,6 +105,25 @@ def resolve_weights(model: str) -> "W.WeightSet":
         f"UMA weights for model {m!r} not found: expected {where}, or pass model=<path to a .umxw blob> "
         "(convert a fairchem checkpoint with pdb2reaction_amd.checkpoint.convert). "
         "Use model='synthetic' or UMX_ALLOW_SYNTHETIC=1 only for tests and benchmarks.")
+
+
+def _load_weight_file(path: str) -> "W.WeightSet":
+    """A ``.umxw`` blob (by its magic) as it is; any other file as a checkpoint -> expert-form weight set."""
+    with open(path, "rb") as f:
+        magic = f.read(len(W.MAGIC))
+    if magic == W.MAGIC:
+        return W.load_weights(path)
+    import torch
+
+    from . import checkpoint as CK
+
+    try:
+        ckpt = torch.load(path, map_location="cpu", weights_only=True)
+    except Exception as exc:
+        raise CK.UnsupportedCheckpoint(f"{path}: not a .umxw blob, and torch.load(weights_only=True) does not read it as a checkpoint: {exc}") from exc
+    if not isinstance(ckpt, Mapping):
+        raise CK.UnsupportedCheckpoint(f"{path}: the checkpoint is a {type(ckpt).__name__}, not a mapping with a model config and a state dict")
+    return W.unpack_blob(CK.convert_checkpoint_experts(ckpt))
 
 
 def _device_index(device: str) -> int:

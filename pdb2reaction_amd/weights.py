@@ -61,6 +61,14 @@ TO_M = (0, 2, 6, 3, 7, 1, 5, 8, 4)
 L_OF_LP = (0, 1, 1, 1, 2, 2, 2, 2, 2)
 L_OF_MP = tuple(L_OF_LP[i] for i in TO_M)
 
+# Mixture-of-Linear-Experts: the 24 SO(2) weights an expert-form blob keeps as stacks (n_experts, out, in), and the tensors of the routing
+# network it carries next to the engine's parameters (checkpoint.convert_experts; names [3P-UNVERIFIED])
+MAX_EXPERTS = 64
+EXPERT_WEIGHT_NAMES = tuple(f"blocks.{i}.edge_wise.so2_conv_{c}.{leaf}.weight" for i in range(NUM_LAYERS) for c in (1, 2)
+                            for leaf in ("fc_m0", "so2_m_conv.0.fc", "so2_m_conv.1.fc"))
+COMPOSITION_KEY = "composition_embedding.weight"
+ROUTING_PREFIX = "routing_mlp."
+
 MAGIC = b"UMXW0001"
 META_MAGIC = b"UMXMETA1"
 
@@ -75,6 +83,23 @@ class WeightSet(OrderedDict):
         self.meta = dict(meta or {})
 
 
+def is_routing_tensor(name: str) -> bool:
+    return name == COMPOSITION_KEY or name.startswith(ROUTING_PREFIX)
+
+
+def expert_count(weights: Dict[str, Any]) -> int:
+    """Experts of an expert-form weight set (the 24 SO(2) weights stacked (n, out, in) with one n), 0 for a merged one; a set with
+    only some of them stacked, or stacks of different sizes, raises ValueError."""
+    ns = {int(np.shape(weights[k])[0]) for k in EXPERT_WEIGHT_NAMES if k in weights and np.ndim(weights[k]) == 3}
+    n_stacked = sum(1 for k in EXPERT_WEIGHT_NAMES if k in weights and np.ndim(weights[k]) == 3)
+    if not n_stacked:
+        return 0
+    if len(ns) != 1 or n_stacked != len(EXPERT_WEIGHT_NAMES):
+        raise ValueError(f"mixed weight set: {n_stacked} of the {len(EXPERT_WEIGHT_NAMES)} SO(2) weights are expert stacks (sizes {sorted(ns)}): "
+                         "all of them with one expert count, or none")
+    return ns.pop()
+
+
 def system_record(atomic_numbers: Sequence[int], charge: int, spin: int, task: str) -> Dict[str, Any]:
     """What MoLE routing depends on: the element multiset, total charge, spin multiplicity, task."""
     zs, counts = np.unique(np.asarray(atomic_numbers, dtype=np.int64), return_counts=True)
@@ -83,9 +108,11 @@ def system_record(atomic_numbers: Sequence[int], charge: int, spin: int, task: s
 
 def check_merged_for(weights: Dict[str, np.ndarray], atomic_numbers: Sequence[int], charge: int, spin: int, task: str) -> None:
     """Raise ValueError when `weights` carries a ``merged_for`` record that does not match the system about to be bound.
-    Parameter sets without the record (synthetic weights, single-expert checkpoints) fit every system."""
-    want = (getattr(weights, "meta", None) or {}).get("merged_for")
-    if not want:
+    Parameter sets without the record (synthetic weights, single-expert checkpoints) fit every system, and so does an expert-form set:
+    its experts are merged for the system at hand when it is bound (``Engine.set_system``)."""
+    meta = getattr(weights, "meta", None) or {}
+    want = meta.get("merged_for")
+    if not want or meta.get("experts"):
         return
     have = system_record(atomic_numbers, charge, spin, task)
     if have != want:
@@ -262,6 +289,30 @@ def make_synthetic_weights(seed: int = 0, ff_type: str = "spectral", chg_spin_em
     return out
 
 
+def make_synthetic_experts(n_experts: int, seed: int = 0, **variant) -> "WeightSet":
+    """Deterministic stand-in for a Mixture-of-Linear-Experts checkpoint in EXPERT FORM: :func:`make_synthetic_weights` of the variant,
+    its 24 SO(2) weights replaced by float32 stacks (n_experts, out, in) of the same scale, plus a routing network
+    (``composition_embedding.weight`` (100, C), ``routing_mlp.0`` 2C -> 64, ``routing_mlp.2`` 64 -> n_experts)."""
+    n = int(n_experts)
+    if not (1 <= n <= MAX_EXPERTS):
+        raise ValueError(f"n_experts must be in [1, {MAX_EXPERTS}]")
+    base = make_synthetic_weights(seed, **variant)
+    rng = np.random.default_rng([int(seed), n, 1201])
+    out = WeightSet(meta=dict(base.meta, experts=n))
+    for name, arr in base.items():
+        if name in EXPERT_WEIGHT_NAMES:
+            scale = np.float32((1.0 / np.sqrt(2.0) if ".so2_m_conv." in name else 1.0) / np.sqrt(arr.shape[-1]))
+            arr = rng.standard_normal((n,) + arr.shape, dtype=np.float32) * scale
+        out[name] = arr
+    c = SPHERE_CHANNELS
+    out[COMPOSITION_KEY] = rng.standard_normal((MAX_NUM_ELEMENTS, c), dtype=np.float32)
+    out[ROUTING_PREFIX + "0.weight"] = rng.standard_normal((64, 2 * c), dtype=np.float32) * np.float32(1.0 / np.sqrt(2 * c))
+    out[ROUTING_PREFIX + "0.bias"] = rng.standard_normal(64, dtype=np.float32) * np.float32(0.1)
+    out[ROUTING_PREFIX + "2.weight"] = rng.standard_normal((n, 64), dtype=np.float32) * np.float32(0.125)
+    out[ROUTING_PREFIX + "2.bias"] = rng.standard_normal(n, dtype=np.float32) * np.float32(0.1)
+    return out
+
+
 def _draw(rng, name: str, shape) -> np.ndarray:
     leaf = name.split(".")[-1]
     if name == "normalizer.rmsd":
@@ -285,11 +336,20 @@ def _draw(rng, name: str, shape) -> np.ndarray:
 
 def pack_blob(weights: Dict[str, np.ndarray], meta: Optional[Dict[str, Any]] = None) -> bytes:
     """Serialise a name->array dict into the UMXW0001 blob read by ``umx_load_weights`` (``meta`` or ``weights.meta``
-    goes into the JSON trailer)."""
+    goes into the JSON trailer).  An expert-form set (:func:`expert_count` > 0) keeps its 24 stacks as 3-dimensional tensors under
+    their merged names, and its routing tensors follow the engine's parameters in the table."""
     shapes = param_shapes(**variant_of(weights))
     missing = [k for k in shapes if k not in weights]
     if missing:
         raise KeyError(f"weights missing {len(missing)} tensors, e.g. {missing[:3]}")
+    n_exp = expert_count(weights)
+    if n_exp:
+        if not (1 <= n_exp <= MAX_EXPERTS):
+            raise ValueError(f"{n_exp} experts: an expert-form blob holds 1..{MAX_EXPERTS}")
+        shapes = OrderedDict((k, ((n_exp,) + tuple(v)) if k in EXPERT_WEIGHT_NAMES else tuple(v)) for k, v in shapes.items())
+        for k in weights:
+            if is_routing_tensor(k):
+                shapes[k] = tuple(np.shape(weights[k]))
     entries = []
     chunks = []
     off = 0
@@ -307,6 +367,8 @@ def pack_blob(weights: Dict[str, np.ndarray], meta: Optional[Dict[str, Any]] = N
     table = b"".join(entries)
     pad = (-(len(head) + len(table))) % 64
     meta = meta if meta is not None else getattr(weights, "meta", None)
+    if n_exp:
+        meta = dict(meta or {}, experts=n_exp)
     trailer = b""
     if meta:
         js = json.dumps(meta, sort_keys=True).encode()
@@ -314,7 +376,9 @@ def pack_blob(weights: Dict[str, np.ndarray], meta: Optional[Dict[str, Any]] = N
     return head + table + b"\0" * pad + b"".join(chunks) + trailer
 
 
-def unpack_blob(blob: bytes) -> "WeightSet":
+def unpack_blob(blob: bytes, skip: Sequence[str] = ()) -> "WeightSet":
+    """Blob -> WeightSet (tensors copied, trailer in ``meta``); names in ``skip`` are left out (the expert stacks of an expert-form blob
+    are most of its bytes)."""
     if blob[:8] != MAGIC:
         raise ValueError("not a UMXW0001 weight blob")
     n, _ = struct.unpack_from("<II", blob, 8)
@@ -329,6 +393,9 @@ def unpack_blob(blob: bytes) -> "WeightSet":
     out = WeightSet()
     end = data0
     for name, shape, off, nb in ents:
+        end = max(end, data0 + off + nb + ((-nb) % 64))
+        if name in skip:
+            continue
         out[name] = np.frombuffer(blob, dtype=np.float32, count=nb // 4, offset=data0 + off).reshape(shape).copy()
         end = max(end, data0 + off + nb + ((-nb) % 64))
     if blob[end:end + 8] == META_MAGIC:
