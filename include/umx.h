@@ -198,7 +198,7 @@ int umx_energy_forces_dev(umx_engine* eng, int n_images, const float* d_pos_ang,
  * 9 all-reduces of n_atoms*1152 floats and one of n_atoms*3.  Energies are complete on every rank (node-level work is replicated);
  * forces are complete after the last all-reduce.  Every precision mode (fp32 since round 3); `hip_stream` must stay
  * alive until umx_gp_step has reported *done.  A rank without edges (node_lo == node_hi, or isolated targets) takes part with
- * all-zero partial sums.                                                                                                      */
+ * all-zero partial sums.  An engine in recompute mode 2 (umx_set_recompute) is refused: this mode keeps activations stored.     */
 int umx_gp_begin(umx_engine* eng, const float* d_pos_ang, int node_lo, int node_hi, double* d_energy_ev,
                  float* d_forces_ev_ang, void* hip_stream);
 int umx_gp_step(umx_engine* eng, float** d_buf, size_t* count, int* done);
@@ -230,8 +230,33 @@ int umx_last_graph_stats(const umx_engine* eng, int64_t* n_edges_total, int32_t*
 /* Target-node partitions the most recent evaluation used per image: 0 = the ordinary path.  An image whose per-edge activations do not
  * fit the workspace budget in one piece (~120 KB per directed edge) is evaluated in 2..16 partitions that keep their own activations
  * (~72 KB per edge) and share one region for the GEMM operands, with the graph-parallel plan's exchange points summed locally (ABI v7);
- * beyond that -- ~1.5x the atoms -- UMX_ERR_CAPACITY names the multi-GPU graph-parallel mode.                                    */
+ * beyond that -- ~1.5x the atoms -- UMX_ERR_CAPACITY names the multi-GPU graph-parallel mode and the recompute switch below.      */
 int umx_last_partitions(const umx_engine* eng);
+
+/* RECOMPUTE PLANS (additive to ABI v10; opt-in, off by default).  A stored plan keeps every per-edge activation of the four layers from the
+ * forward to the reverse pass (~72 KB per directed edge), which is what bounds the size of ONE image on one GPU.  A recompute plan keeps
+ * only node-level state, the graph and the small per-edge buffers across the passes: the per-edge, per-layer activations (h1pre, h2pre,
+ * rad, hg, msg, and the edge-degree link's) share ONE slot (~18 KB per edge), each layer overwrites the last, and the reverse pass
+ * re-issues a layer's forward edge pipeline (radial MLP, gather / rotate / modulate, conv 1, gate, conv 2 -- the SAME kernels on the same
+ * stored node input, nothing node-level) just before that layer's reverse segments.  In target-node partitions the slot is shared by
+ * all partitions as well: between two exchange points one partition replays and reverses one layer, then the next; the loop over 2..16
+ * partitions finds the smallest number that fits.  Results are BITWISE those of the stored plan with the same partitioning (the kernels
+ * are deterministic), in every precision mode and with both feed-forward forms; the cost is one more forward edge pipeline per step.
+ *   mode 0 (default): stored plans only -- an image beyond them is UMX_ERR_CAPACITY;
+ *   mode 1: a recompute plan only when no stored plan fits the budget -- tried after the stored plans in one piece and in 2..16
+ *           partitions, and before UMX_ERR_CAPACITY; while the images fit, nothing changes (results, workspace, speed);
+ *   mode 2: always (a capped workspace then holds more images per chunk).
+ * The environment variable UMX_RECOMPUTE=0|1|2 is read at umx_create.  umx_last_recompute: 1 when the most recent evaluation ran a
+ * recompute plan (an energy-only call of such a plan replays nothing), else 0.  Debug captures (umx_debug_keep) name the stored buffers of
+ * every layer: with them on, plans are stored ones.  umx_gp_begin, the multi-GPU graph-parallel entry, keeps every rank's activations
+ * stored: it REFUSES an engine in mode 2 (UMX_ERR_ARG) and ignores mode 1.
+ * umx_workspace_bytes: the size arithmetic of the planner -- bytes of the workspace of a chunk of n_nodes nodes and n_edges directed edges
+ * in one piece (parts = 0), or of one image in `parts` = 2..16 partitions of equal edge counts (a lower bound: the shared region is sized
+ * for the largest partition), as a stored (recompute = 0) or a recompute plan; for the engine's loaded precision mode and feed-forward
+ * form, or, with eng = NULL (needs no device), the default mode and the spectral form.  -1 for arguments out of range.             */
+int umx_set_recompute(umx_engine* eng, int mode);
+int umx_last_recompute(const umx_engine* eng);
+int64_t umx_workspace_bytes(const umx_engine* eng, int64_t n_nodes, int64_t n_edges, int parts, int recompute);
 
 /* Lanes of the most recent evaluation (ABI v10): 2 = two chunks of images were in flight on two streams, the large-GEMM segments of one
  * beside the HBM-bound segments of the other (UMX_STREAMS=2, or UMX_LANES_AUTO_EDGES=<n>: for batches of >= n directed edges whose largest

@@ -53,6 +53,10 @@ class UMXCalculator(_AseBase):
         """workers > 1 (outside a torch.distributed process group): that many engines in this process when there are that many
         devices (``UMX_LOCAL_DEVICES`` names them), as in ``uma_pysis.UMAcore`` -- ``calculate_images`` deals its images over them,
         a single image is evaluated graph-parallel (``parallel.LocalEnginePool``); ``local_devices`` lists the ordinals in use."""
+        # not an ASE keyword: recompute plans (0 | 1 | 2; None = UMX_RECOMPUTE), as in ``uma_pysis`` (Engine.set_recompute)
+        self.recompute = kwargs.pop("recompute", None)
+        if self.recompute not in (None, 0, 1, 2):
+            raise ValueError(f"recompute must be 0, 1 or 2, got {self.recompute!r}")
         super().__init__(**kwargs)
         self.workers = max(int(workers or 1), 1)
         self.local_devices = None
@@ -83,10 +87,12 @@ class UMXCalculator(_AseBase):
                 if not P.process_group_active():
                     pool_devices = P.local_devices_for(self.workers)
             if pool_devices is not None:
-                self._engine = P.LocalEnginePool.create(pool_devices, self._weights, engine_factory=Engine)     # same methods as one engine
+                self._engine = P.LocalEnginePool.create(pool_devices, self._weights, engine_factory=Engine, recompute=self.recompute)     # same methods as one engine
             else:
                 self._engine = Engine(_device_index(self.device))
                 self._engine.load_weights(self._weights)
+                if self.recompute is not None:
+                    self._engine.set_recompute(self.recompute)
             self.local_devices = list(pool_devices) if pool_devices is not None else [_device_index(self.device)]
             from ._host import cap_pools_to_usable_cores
 

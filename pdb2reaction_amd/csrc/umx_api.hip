@@ -48,6 +48,7 @@ int umx_create(umx_engine** out, int device_ordinal) {
   if (const char* ev = std::getenv("UMX_STREAMS")) e->n_lanes = std::atoi(ev) >= 2 ? 2 : (std::atoi(ev) == 1 ? 1 : 0);
   if (const char* ev = std::getenv("UMX_LANES_AUTO_EDGES")) e->lanes_auto_edges = std::max(0L, std::atol(ev));
   if (const char* ev = std::getenv("UMX_FORCE_PARTS")) e->force_parts = std::max(0, std::min(16, std::atoi(ev)));
+  if (const char* ev = std::getenv("UMX_RECOMPUTE")) e->recompute = std::max(0, std::min(2, std::atoi(ev)));
   if (const char* ev = std::getenv("UMX_WS_GB")) e->ws_cap_default = (size_t)std::max(0L, std::atol(ev)) << 30;
   if (const char* ev = std::getenv("UMX_WS_EAGER")) e->ws_eager = std::atoi(ev) != 0;
   if (const char* ev = std::getenv("UMX_WS_SOFT_EDGES")) e->ws_soft_edges = std::max(1L, std::atol(ev));
@@ -235,6 +236,9 @@ int umx_gp_begin(umx_engine* eng, const float* d_pos, int node_lo, int node_hi, 
   if (!eng->have_system) return fail(eng, UMX_ERR_ARG, "umx_gp_begin: bind a system first (umx_set_system)");
   if (!d_pos || !d_energy || !d_forces) return fail(eng, UMX_ERR_ARG, "umx_gp_begin: bad arguments (forces are part of the exchange)");
   if (node_lo < 0 || node_hi > eng->natoms || node_lo > node_hi) return fail(eng, UMX_ERR_ARG, "umx_gp_begin: node range outside [0, n_atoms]");
+  if (eng->recompute == 2)
+    return fail(eng, UMX_ERR_ARG, "umx_gp_begin: recompute mode 2 (umx_set_recompute / UMX_RECOMPUTE=2) is a one-GPU plan; the multi-GPU graph-parallel mode "
+                                  "keeps every rank's activations stored: set mode 0 or 1 on the engines that take part");
   if (eng->gp_plan) gp_clear(eng);                       // an abandoned evaluation
   HIPCHK(eng, hipSetDevice(eng->dev));
   eng->gp = true; eng->gp_lo = node_lo; eng->gp_hi = node_hi;
@@ -397,6 +401,25 @@ int umx_last_graph_stats(const umx_engine* eng, int64_t* n_edges_total, int32_t*
 
 int umx_last_partitions(const umx_engine* eng) { return eng ? eng->last_parts : 0; }
 int umx_last_lanes(const umx_engine* eng) { return eng ? eng->last_lanes : 0; }
+
+int umx_set_recompute(umx_engine* eng, int mode) {
+  if (!eng) return UMX_ERR_ARG;
+  if (mode < 0 || mode > 2) return fail(eng, UMX_ERR_ARG, "umx_set_recompute: mode must be 0 (off), 1 (when the stored plans do not fit) or 2 (always)");
+  if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_set_recompute: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
+  eng->recompute = mode;
+  return UMX_OK;
+}
+int umx_last_recompute(const umx_engine* eng) { return eng ? eng->last_recompute : 0; }
+
+int64_t umx_workspace_bytes(const umx_engine* eng, int64_t n_nodes, int64_t n_edges, int parts, int recompute) {
+  if (n_nodes < 0 || n_edges < 0 || parts < 0 || parts == 1 || parts > 16) return -1;
+  const Precision pm = eng && eng->have_weights ? eng->prec : Precision();
+  const int grid = eng && eng->have_weights ? eng->ws_grid() : 0;
+  if (parts == 0) return (int64_t)carve(nullptr, n_nodes, n_edges, nullptr, pm, grid, recompute != 0);
+  std::vector<long> pe(parts);
+  for (int p = 0; p < parts; ++p) pe[p] = (long)(n_edges * (p + 1) / parts - n_edges * p / parts);
+  return (int64_t)part_layout(pm, grid, recompute != 0, n_nodes, pe, nullptr);
+}
 
 int umx_workspace_stats(const umx_engine* eng, int64_t* bytes, int32_t* allocations) {
   if (!eng) return UMX_ERR_ARG;

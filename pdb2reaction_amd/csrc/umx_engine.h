@@ -265,6 +265,13 @@ struct umx_engine {
   // partitioned evaluation of ONE oversized image on one GPU (eval_partitioned): per-partition degree arrays and partial forces
   int force_parts = 0;             // UMX_FORCE_PARTS (dev / tests): evaluate every image in this many target-node partitions
   int* d_part_deg = nullptr; float* d_part_f = nullptr; long part_cap = 0;
+  // recompute plans (umx_set_recompute / UMX_RECOMPUTE): keep only node-level state across the passes and replay a layer's forward edge
+  // pipeline just before its reverse segments -- one activation slot instead of one per layer (carve_acts)
+  int recompute = 0;               // 0 off, 1 when the stored plans do not fit the budget, 2 always
+  bool rc_active = false;          // the evaluation being planned is a recompute plan (read by ws_bytes and plan_chunk)
+  bool arena_rc = false;           // what cap_nodes / cap_edges of the arena were sized for
+  bool arena_keep = false;         // the caps were cleared by a change of plan kind: keep an arena that is large enough (prepare_arena)
+  int last_recompute = 0;          // 1: the most recent evaluation ran a recompute plan (umx_last_recompute)
   int last_parts = 0;              // partitions used by the most recent evaluation (0: the ordinary path)
   int last_lanes = 1;              // lanes (chunks in flight) of the most recent evaluation (umx_last_lanes)
   int arena_allocs = 0;            // how often the workspace has been (re-)allocated (umx_workspace_stats)

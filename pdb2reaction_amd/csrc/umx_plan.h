@@ -68,6 +68,7 @@ void plan_chunk(umx_engine* eng, WS& w, const float* d_pos, const int* d_deg, co
   const bool pl = eng->prec.planes;
   const bool gp = eng->gp;                                       // graph-parallel: partial sums over this rank's edges + exchange points
   const bool may_trunc = eng->may_truncate;                      // some node of this call has more candidates than max_neigh (known on the host)
+  const bool rc = eng->rc_active && d_forces != nullptr;         // recompute plan: one activation slot (carve_acts), replayed layer by layer in the reverse pass
   const bool fused_rev = eng->prec.planes || !eng->dbg_on;     // k_modrot_bwd_pl produces g_xn itself (fp32 mode with debug captures: the unfused kernels, which expose xrot / g_xrot)
   const long g_lo = gp ? eng->gp_lo : 0, g_hi = gp ? eng->gp_hi : nn;
   // every closure reads eng->stream when it RUNS (the executor points it at the lane's stream)
@@ -116,15 +117,16 @@ void plan_chunk(umx_engine* eng, WS& w, const float* d_pos, const int* d_deg, co
     });
   }
 
-  for (int i = 0; i < NL; ++i) {
+  // The edge pipeline of layer i's forward pass (radial MLP, gather / rotate / modulate, conv 1, gate, conv 2 -> rad, hg, msg, h1pre,
+  // h2pre of the layer), led by the layer's first norm.  replay (recompute plans, reverse pass): the same segments from the STORED node
+  // input xn[i] -- the norm, like everything node-level, is not issued again; no kernel of the pipeline writes node state.
+  auto edge_fwd = [&](int i, bool replay) {
     const LayerW* Lp = &eng->lw[i];
     float* xin = w.xs[2 * i];
-    float* xmid = w.xs[2 * i + 1];
-    float* xout = w.xs[2 * i + 2];
     if (ne > 0 && pl) {
       P.stream([=, &w]() -> int {
         hipStream_t s = eng->stream;
-        hipLaunchKernelGGL(k_norm_fwd, dim3(nblk(nn, 4)), B256, 0, s, xin, Lp->n1w, Lp->n1b, eng->d_sysemb, w.xn[i], nn);
+        if (!replay) hipLaunchKernelGGL(k_norm_fwd, dim3(nblk(nn, 4)), B256, 0, s, xin, Lp->n1w, Lp->n1b, eng->d_sysemb, w.xn[i], nn);
         return radial_fwd_head(eng, w, Lp->rad, i, ne);
       });
       P.matrix([=, &w]() -> int {
@@ -162,7 +164,7 @@ void plan_chunk(umx_engine* eng, WS& w, const float* d_pos, const int* d_deg, co
       P.stream([=, &w]() -> int {
         hipStream_t s = eng->stream;
         const LayerW& L = *Lp;
-        hipLaunchKernelGGL(k_norm_fwd, dim3(nblk(nn, 4)), B256, 0, s, xin, L.n1w, L.n1b, eng->d_sysemb, w.xn[i], nn);
+        if (!replay) hipLaunchKernelGGL(k_norm_fwd, dim3(nblk(nn, 4)), B256, 0, s, xin, L.n1w, L.n1b, eng->d_sysemb, w.xn[i], nn);
         if (ne > 0) {
           hipLaunchKernelGGL(k_gather_rotate, dim3(nblk(ne, 4)), B256, 0, s, w.xn[i], w.esrc, w.edst, w.frame, w.xrot, ne);
           CHK(radial_fwd(eng, w, L.rad, i, ne, w.rad[i]));
@@ -185,6 +187,13 @@ void plan_chunk(umx_engine* eng, WS& w, const float* d_pos, const int* d_deg, co
         return UMX_OK;
       });
     }
+  };
+  for (int i = 0; i < NL; ++i) {
+    const LayerW* Lp = &eng->lw[i];
+    float* xin = w.xs[2 * i];
+    float* xmid = w.xs[2 * i + 1];
+    float* xout = w.xs[2 * i + 2];
+    edge_fwd(i, false);
     if (gp) {      // partial aggregate of this rank's edges -> xn2 (free until the norm below), all-reduce, xmid = xin + sum
       P.stream([=, &w]() -> int {
         hipLaunchKernelGGL(k_rotate_back_reduce<9>, dim3(nblk(nn, 4)), B256, 0, eng->stream, w.msg[i], w.frame, w.row_ptr, (const float*)nullptr, w.xn2, nn, 1.0f,
@@ -265,6 +274,10 @@ void plan_chunk(umx_engine* eng, WS& w, const float* d_pos, const int* d_deg, co
     const LayerW* Lp = &eng->lw[i];
     float* xin = w.xs[2 * i];
     float* xmid = w.xs[2 * i + 1];
+    // recompute plan: the activation slot holds another layer (or, between exchange points, another partition): replay this layer's
+    // forward edge pipeline into it first.  Every transient operand is free here: the reverse segments of layer i + 1 are complete.
+    // (One piece: the slot still holds layer NL - 1 when the reverse pass starts.)
+    if (rc && ne > 0 && (gp || i != NL - 1)) edge_fwd(i, true);
     // atom-wise backward: G0 = dE/dx_out  (+ the first edge kernel of the layer)
     P.stream([=, &w]() -> int {
       hipStream_t s = eng->stream;
@@ -399,6 +412,10 @@ void plan_chunk(umx_engine* eng, WS& w, const float* d_pos, const int* d_deg, co
   P.stream([=, &w]() -> int {
     hipStream_t s = eng->stream;
     if (ne > 0) {
+      if (rc) {      // recompute plan: the edge-degree link's radial MLP again (h1pre / h2pre / rad_deg of the slot), not its node sum
+        CHK(radial_fwd_head(eng, w, eng->rdeg, NL, ne));
+        CHK(radial_fwd_fc3(eng, w, eng->rdeg, ne, w.rad_deg));
+      }
       // split path: the gradient of the edge-degree radial output goes straight into the PL planes of the fc3^T GEMM (gmsgpl is free here)
       const bool dpl = eng->prec.planes && eng->planes.count(eng->rdeg.w3T) != 0;
       if (dpl && eng->prec.rev_planes == 3) hipLaunchKernelGGL((k_rotate_back_bwd<3, 3>), dim3(nblk(ne, 4)), B256, 0, s, w.G0, w.rad_deg, w.frame, w.edst,
@@ -563,24 +580,16 @@ int eval_partitioned(umx_engine* eng, hipStream_t s, const float* d_pos, double*
   std::vector<int> cnt;
   CHK(read_degree_pass(eng, s, d_cnt, P, cnt, true));
   eng->may_truncate = cnt[P] >= eng->max_neigh;
-  // layout: P persistent regions, then one transient region sized for the largest partition
-  std::vector<size_t> off(P + 1, 0);
-  size_t tmax = 0;
-  for (int p = 0; p < P; ++p) {
-    Bump bp{nullptr}; WS t; carve_persist(bp, N, cnt[p], t, eng->ws_grid());
-    off[p + 1] = off[p] + bp.bytes();
-    Bump bt{nullptr}; carve_trans(bt, cnt[p], t, eng->prec);
-    tmax = std::max(tmax, bt.bytes());
-  }
-  const size_t total = off[P] + tmax;
+  // layout: P persistent regions, then one shared region sized for the largest partition -- the transient operands and, for a recompute
+  // plan, the activation slot: between two exchange points a partition replays and reverses ONE layer, then the next partition runs
+  std::vector<size_t> off;
+  const std::vector<long> pe(cnt.begin(), cnt.begin() + P);
+  const size_t total = part_layout(eng->prec, eng->ws_grid(), eng->rc_active, N, pe, &off);
   if (total > budget) return UMX_ERR_CAPACITY;              // (the caller tries more partitions)
   if (eng->arena_bytes < total) CHK(grow_arena(eng, s, total));
   eng->cap_nodes = 0; eng->cap_edges = 0;                    // the ordinary path re-carves (and re-sizes) the arena on its next call
   std::vector<WS> ws(P);
-  for (int p = 0; p < P; ++p) {
-    Bump bp{eng->arena + off[p]}; carve_persist(bp, N, cnt[p], ws[p], eng->ws_grid());
-    Bump bt{eng->arena + off[P]}; carve_trans(bt, cnt[p], ws[p], eng->prec);
-  }
+  for (int p = 0; p < P; ++p) part_carve(eng->arena, off, eng->prec, eng->ws_grid(), eng->rc_active, N, cnt[p], p, ws[p]);
   std::vector<Plan> plans(P);
   const bool gp_keep = eng->gp; const long lo_keep = eng->gp_lo, hi_keep = eng->gp_hi;
   for (int p = 0; p < P; ++p) {
@@ -629,7 +638,9 @@ int eval_images_partitioned(umx_engine* eng, hipStream_t s, long K, const float*
       stp = eval_partitioned(eng, s, d_pos + k * N * 3, d_energy + k, d_forces ? d_forces + k * N * 3 : nullptr, parts, budget, &e1, &m1);
       if (stp == UMX_OK) { etot += e1; mdeg = std::max(mdeg, m1); eng->last_parts = parts; }
     }
-    if (stp == UMX_ERR_CAPACITY) return fail(eng, UMX_ERR_CAPACITY, why + " -- and not in 16 partitions on this GPU either");
+    if (stp == UMX_ERR_CAPACITY)
+      return fail(eng, UMX_ERR_CAPACITY, why + " -- and not in 16 partitions on this GPU either" +
+                  (eng->rc_active ? " (recompute plan)" : "; umx_set_recompute / UMX_RECOMPUTE=1 lets one GPU evaluate it by recomputing the per-edge activations layer by layer"));
     if (stp != UMX_OK) return stp;
   }
   eng->last_edges = etot; eng->last_maxdeg = mdeg;
@@ -739,7 +750,10 @@ int prepare_arena(umx_engine* eng, hipStream_t s, const ImageEdges& ie, const Ch
       bytes = ws_bytes(eng, cn, ce);
     }
     if (bytes > budget) { ce = std::max(need_edges, 1L); bytes = ws_bytes(eng, cn, ce); }
-    CHK(grow_arena(eng, s, lanes * bytes));                  // one workspace per lane
+    // one workspace per lane.  (After a change of plan kind the caps were cleared, not outgrown: an arena that holds the new kind's
+    // workspace is carved anew and kept -- mode 1 may change kind at every call.)
+    if (!(eng->arena_keep && lanes * bytes <= eng->arena_bytes)) CHK(grow_arena(eng, s, lanes * bytes));
+    eng->arena_keep = false;
     eng->cap_nodes = cn; eng->cap_edges = ce;
   }
   long use_nodes = eng->cap_nodes, use_edges = eng->cap_edges;
@@ -804,17 +818,10 @@ int run_chunks(umx_engine* eng, hipStream_t s, int lanes, const ImageEdges& ie, 
   return st;
 }
 
-// Evaluate on `run_stream` (may be the legacy default stream 0).  eng->stream is swapped for the duration so that every
-// helper launches there; it is restored on every exit path.
-int energy_forces_on(umx_engine* eng, hipStream_t run_stream, int n_images, const float* d_pos, double* d_energy, float* d_forces) {
-  hipStream_t own = eng->stream;
-  eng->stream = run_stream;
-  eng->ran_on_caller = (run_stream != own);
-  struct Restore { umx_engine* e; hipStream_t s; ~Restore() { e->stream = s; } } restore{eng, own};
-  hipStream_t s = eng->stream;
-  const long K = n_images;
-  ImageEdges ie;
-  CHK(degree_pass(eng, s, K, d_pos, ie));
+// Plan and run one evaluation with the kind of plan eng->rc_active names: budget, lanes, chunks (or partitions), arena, execution.
+int evaluate_planned(umx_engine* eng, hipStream_t s, long K, const float* d_pos, double* d_energy, float* d_forces, const ImageEdges& ie) {
+  // cap_nodes / cap_edges say what the arena holds in ws_bytes of ONE kind of plan: after a change of kind it is carved (and sized) anew
+  if (eng->arena_rc != eng->rc_active) { eng->cap_nodes = 0; eng->cap_edges = 0; eng->arena_rc = eng->rc_active; eng->arena_keep = true; }
   size_t budget = 0;
   CHK(workspace_budget(eng, ie, &budget));
   int lanes = choose_lanes(eng, K, ie, budget);
@@ -849,6 +856,28 @@ int energy_forces_on(umx_engine* eng, hipStream_t run_stream, int n_images, cons
   CHK(run_chunks(eng, s, lanes, ie, chunks, wl, d_pos, d_energy, d_forces));
   HIPCHK(eng, hipEventRecord(eng->ev_done, s));
   return UMX_OK;
+}
+
+// Evaluate on `run_stream` (may be the legacy default stream 0).  eng->stream is swapped for the duration so that every
+// helper launches there; it is restored on every exit path.
+int energy_forces_on(umx_engine* eng, hipStream_t run_stream, int n_images, const float* d_pos, double* d_energy, float* d_forces) {
+  hipStream_t own = eng->stream;
+  eng->stream = run_stream;
+  eng->ran_on_caller = (run_stream != own);
+  struct Restore { umx_engine* e; hipStream_t s; ~Restore() { e->stream = s; } } restore{eng, own};
+  hipStream_t s = eng->stream;
+  ImageEdges ie;
+  CHK(degree_pass(eng, s, n_images, d_pos, ie));
+  // recompute plans: never in the multi-GPU graph-parallel mode, nor with debug captures (they name the stored buffers of every layer)
+  const bool rc_can = !eng->gp && !eng->dbg_on;
+  eng->rc_active = rc_can && eng->recompute == 2;
+  int st = evaluate_planned(eng, s, n_images, d_pos, d_energy, d_forces, ie);
+  if (st == UMX_ERR_CAPACITY && rc_can && eng->recompute == 1) {      // no stored plan fits, in one piece or in partitions
+    eng->rc_active = true;
+    st = evaluate_planned(eng, s, n_images, d_pos, d_energy, d_forces, ie);
+  }
+  if (st == UMX_OK) eng->last_recompute = eng->rc_active ? 1 : 0;
+  return st;
 }
 
 void gp_clear(umx_engine* eng) { eng->gp_plan.reset(); eng->gp_ws.reset(); eng->gp_at = 0; eng->gp = false; }

@@ -19,6 +19,10 @@ struct Bump {
 // (~48 KB per edge) and are dead at every exchange point of the plan -- which is what lets the partitions of ONE oversized image share a
 // single transient region (eval_partitioned).  gridG: the grid points of the grid feed-forward, whose per-node buffers scale with it
 // (0 = spectral feed-forward); pm: the precision mode, which decides the operand buffers of the transient region.
+// carve_persist: node-level state, the graph lists and the small per-edge buffers (~0.3 KB per edge); carve_acts: the per-edge, per-layer
+// activations -- stored for every layer (and the edge-degree link), or, for a RECOMPUTE plan (rc), ONE slot of ~18 KB per edge that every
+// layer's pointers alias: a layer overwrites the last, and the reverse pass replays a layer's forward edge pipeline into the slot just
+// before that layer's reverse segments (plan_chunk).  The slot is dead at every exchange point, like the transient region.
 void carve_persist(Bump& b, long nn, long ne, WS& t, int gridG) {
   t.deg = nullptr;  // deg comes from the per-call array
   t.row_ptr = b.take<int>(nn + 1); t.stats = b.take<int>(4);
@@ -37,6 +41,20 @@ void carve_persist(Bump& b, long nn, long ne, WS& t, int gridG) {
   t.out_ptr = b.take<int>(nn + 1); t.out_cur = b.take<int>(nn + 1);
   t.evec = b.take<float>(ne * 4); t.frame = b.take<float>(ne * FRAME); t.dedd = b.take<float>(ne); t.dedd_rad = b.take<float>(ne);
   t.tau = b.take<float>(ne * 4); t.tau2 = b.take<float>(ne * 4); t.gvec = b.take<float>(ne * 4);
+}
+void carve_acts(Bump& b, long ne, WS& t, bool rc) {
+  if (rc) {
+    static_assert(3 * C <= ROW, "the edge-degree link's radial output shares the slot's message rows");
+    float* h1 = b.take<float>(ne * RH); float* h2 = b.take<float>(ne * RH);
+    float* rad = b.take<float>(ne * RAD); float* hg = b.take<float>(ne * HG); float* msg = b.take<float>(ne * ROW);
+    for (auto& x : t.h1pre) x = h1;
+    for (auto& x : t.h2pre) x = h2;
+    for (auto& x : t.rad) x = rad;
+    for (auto& x : t.hg) x = hg;
+    for (auto& x : t.msg) x = msg;
+    t.rad_deg = msg;            // (the edge-degree link is one more "layer" of the slot: E x 384 of its E x 1152 message rows)
+    return;
+  }
   for (auto& x : t.h1pre) x = b.take<float>(ne * RH);
   for (auto& x : t.h2pre) x = b.take<float>(ne * RH);
   t.rad_deg = b.take<float>(ne * 3 * C);
@@ -64,15 +82,45 @@ void carve_trans(Bump& b, long ne, WS& t, const Precision& pm) {
     t.ghg = b.take<float>(ne * HG); t.grad = b.take<float>(ne * RAD);
   }
 }
-size_t carve(char* base, long nn, long ne, WS* w, const Precision& pm, int gridG) {
+size_t carve(char* base, long nn, long ne, WS* w, const Precision& pm, int gridG, bool rc) {
   Bump b{base};
   WS t;
   carve_persist(b, nn, ne, t, gridG);
+  carve_acts(b, ne, t, rc);
   carve_trans(b, ne, t, pm);
   if (w) *w = t;
   return b.bytes();
 }
-// bytes of the workspace of a chunk of nn nodes and ne directed edges, or (base, w) its carve-up, for this engine's model and mode
-inline size_t ws_bytes(const umx_engine* eng, long nn, long ne, char* base = nullptr, WS* w = nullptr) { return carve(base, nn, ne, w, eng->prec, eng->ws_grid()); }
+// bytes of the workspace of a chunk of nn nodes and ne directed edges, or (base, w) its carve-up, for this engine's model and mode and
+// the kind of plan (stored / recompute) of the evaluation being planned
+inline size_t ws_bytes(const umx_engine* eng, long nn, long ne, char* base = nullptr, WS* w = nullptr) { return carve(base, nn, ne, w, eng->prec, eng->ws_grid(), eng->rc_active); }
+
+// One image in `parts` target-node partitions (eval_partitioned), edges[p] directed edges each: every partition's own region, then ONE
+// region all of them share, sized for the largest partition -- the transient operands, and for a recompute plan the activation slot too.
+// off: [parts + 1] offsets of the partitions' regions, off[parts] = the shared region's; returns the total.
+size_t part_layout(const Precision& pm, int gridG, bool rc, long nn, const std::vector<long>& edges, std::vector<size_t>* off) {
+  size_t at = 0, shared = 0;
+  if (off) off->assign(edges.size() + 1, 0);
+  for (size_t p = 0; p < edges.size(); ++p) {
+    WS t;
+    Bump bp{nullptr}; carve_persist(bp, nn, edges[p], t, gridG);
+    if (!rc) carve_acts(bp, edges[p], t, false);
+    at += bp.bytes();
+    if (off) (*off)[p + 1] = at;
+    Bump bs{nullptr};
+    if (rc) carve_acts(bs, edges[p], t, true);
+    carve_trans(bs, edges[p], t, pm);
+    shared = std::max(shared, bs.bytes());
+  }
+  return at + shared;
+}
+// the views of partition p of that layout
+void part_carve(char* arena, const std::vector<size_t>& off, const Precision& pm, int gridG, bool rc, long nn, long ne, size_t p, WS& t) {
+  Bump bp{arena + off[p]}; carve_persist(bp, nn, ne, t, gridG);
+  if (!rc) carve_acts(bp, ne, t, false);
+  Bump bs{arena + off.back()};
+  if (rc) carve_acts(bs, ne, t, true);
+  carve_trans(bs, ne, t, pm);
+}
 
 }  // namespace

@@ -85,6 +85,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "umx_last_graph_stats": ([vp, i64p, C.POINTER(C.c_int32)], i32),
         "umx_last_partitions": ([vp], i32),
         "umx_last_lanes": ([vp], i32),
+        "umx_set_recompute": ([vp, i32], i32),
+        "umx_last_recompute": ([vp], i32),
+        "umx_workspace_bytes": ([vp, C.c_int64, C.c_int64, i32, i32], C.c_int64),
         "umx_reserve_images": ([vp, i32], i32),
         "umx_workspace_stats": ([vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32)], i32),
         "umx_profile_enable": ([vp, i32], i32),
@@ -125,8 +128,19 @@ EXPORTED_SYMBOLS = (
     "umx_abi_version", "umx_build_digest", "umx_create", "umx_destroy", "umx_last_error", "umx_load_weights", "umx_set_precision", "umx_precision_mode", "umx_model_variant", "umx_set_system",
     "umx_set_workspace_limit", "umx_energy_forces", "umx_energy_forces_dev", "umx_gp_begin", "umx_gp_step", "umx_peer_sum", "umx_synchronize",
     "umx_last_graph_stats", "umx_last_partitions", "umx_last_lanes", "umx_reserve_images", "umx_workspace_stats", "umx_profile_enable", "umx_profile_read", "umx_bond_changes", "umx_debug_fetch", "umx_debug_keep",
-    "umx_set_expert_coefficients", "umx_expert_count",
+    "umx_set_expert_coefficients", "umx_expert_count", "umx_set_recompute", "umx_last_recompute", "umx_workspace_bytes",
 )
+
+
+def workspace_bytes(n_nodes: int, n_edges: int, parts: int = 0, recompute: int = 0, engine: Optional["Engine"] = None) -> int:
+    """``umx_workspace_bytes``: the planner's size arithmetic -- bytes of the workspace of ``n_nodes`` nodes and ``n_edges`` directed edges
+    in one piece (``parts=0``) or in 2..16 equal partitions, as a stored or a recompute plan; for ``engine``'s loaded mode and model, or
+    (``None``: needs no GPU) the default precision mode and the spectral feed-forward."""
+    lib = load_library()
+    n = int(lib.umx_workspace_bytes(engine._h if engine is not None else None, int(n_nodes), int(n_edges), int(parts), int(recompute)))
+    if n < 0:
+        raise ValueError(f"workspace_bytes: arguments out of range (n_nodes={n_nodes}, n_edges={n_edges}, parts={parts})")
+    return n
 
 
 def peer_sum(ptrs: Sequence[int], count: int, devices: Sequence[int], streams: Sequence[int]) -> None:
@@ -150,8 +164,9 @@ def peer_sum(ptrs: Sequence[int], count: int, devices: Sequence[int], streams: S
 class Engine:
     """One UMA-S engine on one GPU (one per process/rank, or several per process in a ``parallel.LocalEnginePool``)."""
 
-    def __init__(self, device: int = 0, precision: Optional[str] = None):
-        """precision: None = the UMX_PRECISION environment variable (default "auto" = "bf16x3": 3 x 3 bf16 planes / 6 products in both
+    def __init__(self, device: int = 0, precision: Optional[str] = None, recompute: Optional[int] = None):
+        """recompute: None = the UMX_RECOMPUTE environment variable (default 0), else 0 | 1 | 2 (``set_recompute``).
+        precision: None = the UMX_PRECISION environment variable (default "auto" = "bf16x3": 3 x 3 bf16 planes / 6 products in both
         passes, the like-for-like arithmetic to float32 -- include/umx.h), else "auto" | "bf16x3" | "split" (the opt-in fast mode:
         fp16 forward planes, 16-bit reverse) | "split-bf16" | "fp32"."""
         self.lib = load_library()
@@ -171,6 +186,8 @@ class Engine:
         self.dataset_list = tuple(W.DATASET_LIST)      # order of the rows of the loaded blob's dataset_embedding.weight (load_weights)
         if precision is not None:
             self._chk(self.lib.umx_set_precision(self._h, precision.encode()), "umx_set_precision")
+        if recompute is not None:
+            self.set_recompute(recompute)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -365,6 +382,16 @@ class Engine:
     def last_partitions(self) -> int:
         """Target-node partitions per image of the most recent evaluation (0: the ordinary path; see ``umx_last_partitions``)."""
         return int(self.lib.umx_last_partitions(self._h))
+
+    def set_recompute(self, mode: int):
+        """Recompute plans (``umx_set_recompute``): 0 = off (default), 1 = only when no stored plan fits the workspace budget (after the
+        stored partitioned plans, before the capacity error), 2 = always.  A recompute plan keeps node-level state only and replays each
+        layer's forward edge pipeline before its reverse segments: bitwise the stored plan's results, one more forward edge pipeline."""
+        self._chk(self.lib.umx_set_recompute(self._h, int(mode)), "umx_set_recompute")
+
+    def last_recompute(self) -> int:
+        """1 when the most recent evaluation ran a recompute plan, else 0 (``umx_last_recompute``)."""
+        return int(self.lib.umx_last_recompute(self._h))
 
     def last_lanes(self) -> int:
         """Chunks in flight (1 or 2) of the most recent evaluation (``umx_last_lanes``)."""

@@ -422,6 +422,7 @@ class LocalEnginePool:
         self.last_route = None                  # "batch" | "graph-parallel" | "single"
         self.last_blocks: List[Tuple[int, int]] = []
         self.last_all = None                    # graph-parallel route: [(E, F)] of EVERY engine (they must agree in every bit)
+        self.recompute = None                   # what ``create`` / ``set_recompute`` gave every engine (None: the engines' own setting)
         if len(set(self.devices)) < len(self.devices):
             free = free_bytes or (lambda d: torch.cuda.mem_get_info(d)[0])
             for eng, lim in zip(self.engines, shared_workspace_limits(self.devices, free)):
@@ -430,8 +431,9 @@ class LocalEnginePool:
 
     @classmethod
     def create(cls, devices: Sequence[int], weights, *, precision: Optional[str] = None, engine_factory: Optional[Callable] = None,
-               **pool_kw) -> "LocalEnginePool":
-        """One engine per entry of ``devices`` (ordinals may repeat), each loaded with ``weights``; bind the system with ``set_system``."""
+               recompute: Optional[int] = None, **pool_kw) -> "LocalEnginePool":
+        """One engine per entry of ``devices`` (ordinals may repeat), each loaded with ``weights``; bind the system with ``set_system``.
+        recompute: None = every engine's own ``UMX_RECOMPUTE``, else 0 | 1 | 2 for every engine (``Engine.set_recompute``)."""
         if engine_factory is None:
             from .engine import Engine as engine_factory
         engines = []
@@ -439,12 +441,16 @@ class LocalEnginePool:
             for d in devices:
                 eng = engine_factory(int(d), precision=precision)
                 engines.append(eng)
+                if recompute is not None:
+                    eng.set_recompute(int(recompute))
                 eng.load_weights(weights)
         except Exception:
             for eng in engines:
                 eng.close()
             raise
-        return cls(engines, **pool_kw)
+        pool = cls(engines, **pool_kw)
+        pool.recompute = None if recompute is None else int(recompute)
+        return pool
 
     def __len__(self) -> int:
         return len(self.engines)
@@ -480,6 +486,17 @@ class LocalEnginePool:
     def precision_mode(self) -> str:
         return self.engines[0].precision_mode()
 
+    def set_recompute(self, mode: int) -> None:
+        """``Engine.set_recompute`` on every engine.  Mode 2 is a one-GPU plan: a single image then goes to engine 0 alone, not to the
+        graph-parallel route (``umx_gp_begin`` refuses an engine in mode 2)."""
+        for eng in self.engines:
+            eng.set_recompute(int(mode))
+        self.recompute = int(mode)
+
+    def last_recompute(self) -> int:
+        """1 when any engine's most recent evaluation ran a recompute plan."""
+        return int(any(eng.last_recompute() for eng in self.engines))
+
     # ---- evaluation --------------------------------------------------------------------------------------------------------------
     def _run_all(self, fn: Callable[[int], object], ranks: Sequence[int]) -> list:
         """fn(r) for every r of ``ranks``, one host thread each; every thread has ended before this returns or raises; the error of
@@ -510,7 +527,7 @@ class LocalEnginePool:
             raise ValueError(f"positions must be (K,{self.natoms},3), got {p.shape}")
         k, g = p.shape[0], len(self.engines)
         if k == 1:
-            if self.gp and g > 1:
+            if self.gp and g > 1 and self.recompute != 2:
                 return self._graph_parallel(p[0], forces)
             self.last_route, self.last_blocks = "single", [(0, 1)]
             return self.engines[0].energy_forces(p, forces=forces)

@@ -159,6 +159,7 @@ class UMAcore:
         radius: Optional[float] = None,
         r_edges: bool = False,
         precision: Optional[str] = None,
+        recompute: Optional[int] = None,
     ):
         from .engine import Engine  # raises ImportError loudly when libumx.so is missing
 
@@ -210,13 +211,15 @@ class UMAcore:
                 pool_devices = P.local_devices_for(self.workers)          # ValueError: UMX_LOCAL_DEVICES and workers disagree
         if pool_devices is not None:
             # `workers` engines in this process (ordinals may repeat: "0,0" rehearses the path on one GPU); engine 0 is `self.engine`
-            self._pool = P.LocalEnginePool.create(pool_devices, weights, precision=precision, engine_factory=Engine)
+            self._pool = P.LocalEnginePool.create(pool_devices, weights, precision=precision, engine_factory=Engine, recompute=recompute)
             self.engine = self._pool.engines[0]
             cap_pools_to_usable_cores()
             self._pool.set_system(self.z, charge=charge, spin=spin, task=task_name, radius=radius, max_neigh=max_neigh)
         else:
             dev_index = _device_index(device)
             self.engine = Engine(dev_index, precision=precision)     # None: UMX_PRECISION (default "auto")
+            if recompute is not None:                                 # None: UMX_RECOMPUTE (default 0)
+                self.engine.set_recompute(recompute)
             cap_pools_to_usable_cores()                       # BLAS pools sized for the machine inside a CPU-quota container starve the GPU feeder
             self.engine.load_weights(weights)
             self.engine.set_system(self.z, charge=charge, spin=spin, task=task_name, radius=radius, max_neigh=max_neigh)
@@ -360,11 +363,17 @@ class uma_pysis(Calculator):
         precision = kwargs.pop("precision", None)
         if precision not in (None, "auto", "split", "split-f16", "split-bf16", "bf16x3", "split-exact", "fp32"):
             raise ValueError(f"precision must be auto, split, split-bf16, bf16x3 or fp32, got {precision!r}")
+        # likewise: recompute plans (0 off | 1 when the stored plans do not fit the workspace | 2 always; None = UMX_RECOMPUTE) -- one
+        # image of any size on one GPU, at the price of one more forward edge pipeline (Engine.set_recompute)
+        recompute = kwargs.pop("recompute", None)
+        if recompute not in (None, 0, 1, 2):
+            raise ValueError(f"recompute must be 0, 1 or 2, got {recompute!r}")
         super().__init__(charge=charge, mult=spin, **kwargs)
         self._core: Optional[UMAcore] = None
         self._core_kw = dict(
             charge=charge, spin=spin, model=model, task_name=task_name, device=device, workers=workers,
             workers_per_node=workers_per_node, max_neigh=max_neigh, radius=radius, r_edges=r_edges, precision=precision,
+            recompute=recompute,
         )
         self._reserve_images = 0
         self.out_hess_torch = out_hess_torch
