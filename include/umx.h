@@ -156,6 +156,29 @@ const char* umx_precision_mode(const umx_engine* eng);
 int umx_set_system(umx_engine* eng, int n_atoms, const int32_t* atomic_numbers, int charge,
                    int spin, int task_index, float radius, int max_neigh);
 
+/* PERIODIC BOUNDARY CONDITIONS (additive to ABI v10; off by default).  cell: the three lattice vectors in Angstrom, row by row
+ * (cell[3 k + c] = component c of vector k); pbc: one flag per axis.  With a cell set, the radius graph holds every (source j,
+ * lattice translation t) with 0 < |r_j + t - r_i| <= cutoff, t over the integer combinations of the periodic lattice vectors -- an
+ * atom's own images included -- rows in ascending (source, translation index) order; max_neigh keeps the nearest candidates over all
+ * images.  Everything behind the graph is the open-boundary code.  Positions may lie anywhere: the engine wraps a scratch copy into
+ * the cell for the search, energies and forces do not depend on it.
+ *   - ONE cell for all images of a call (a string in a fixed cell).  The cell PERSISTS across umx_set_system until it is set again.
+ *   - All flags zero, or cell == NULL (or pbc == NULL): open boundaries, exactly the engine without this call.
+ *   - UMX_ERR_ARG (umx_last_error says which): a non-finite entry; a degenerate periodic sub-lattice (a periodic vector of zero
+ *     length, two that span no area, three that span no volume); a cell that needs more than 4 lattice translations per direction
+ *     along a periodic axis -- the cap: floor(cutoff / h + 1e-4) + 1 <= 4 with h the distance between that axis' lattice planes, i.e.
+ *     h > cutoff / 4 (1.5 A at the 6 A cutoff; a 5 A edge needs 2), at most 9^3 = 729 translations.  The check uses the cutoff bound
+ *     at the time (6 A before any umx_set_system) and is repeated by the evaluation when umx_set_system changed the cutoff since.  A
+ *     refused call leaves the previous cell in place.  Refused while a graph-parallel evaluation is in progress.
+ *   - The evaluation refuses (UMX_ERR_ARG) translations x n_atoms >= 2^32, and (UMX_ERR_CAPACITY) an atom with more than 1024
+ *     candidates while max_neigh binds.
+ * umx_last_graph_shifts: the number of lattice translations (table entries, the zero translation included) the most recent evaluation
+ * searched; 0 = open boundaries.  Stress / virials, per-image cells and variable-cell drivers are not provided.
+ * No reference counterpart: the reference builds its AtomicData without a cell and never sets pbc (uma_pysis.py:292-327); what
+ * fairchem's own periodic graph generation returns has not been compared [3P-UNVERIFIED].                                         */
+int umx_set_cell(umx_engine* eng, const double cell[9], const int pbc[3]);
+int umx_last_graph_shifts(const umx_engine* eng);
+
 /* Optional: cap the device workspace (bytes; 0 = automatic from free HBM).
  * How much of the cap is used (ABI v8): device memory costs ~45 ms per GiB to allocate on this driver, so the workspace is amortised.
  * Without a hint it starts at chunks of ~320 000 directed edges (UMX_WS_SOFT_EDGES; at least one image; within 3 % of the speed of the

@@ -43,8 +43,26 @@ def _numbers(atoms) -> np.ndarray:
     return np.asarray(atoms.numbers, dtype=np.int32)
 
 
+def _cell_pbc(atoms):
+    """(cell bytes, pbc flags) of an image, or None for open boundaries: ``get_cell()`` / ``get_pbc()`` of an ASE ``Atoms``, the
+    ``cell`` / ``pbc`` attributes of a duck-typed stand-in; absent attributes, or no periodic axis, mean open boundaries."""
+    pbc = atoms.get_pbc() if hasattr(atoms, "get_pbc") else getattr(atoms, "pbc", None)
+    cell = atoms.get_cell() if hasattr(atoms, "get_cell") else getattr(atoms, "cell", None)
+    if pbc is None or cell is None:
+        return None
+    flags = np.broadcast_to(np.asarray(pbc, dtype=bool), (3,))
+    if not flags.any():
+        return None
+    c = np.ascontiguousarray(np.asarray(cell, dtype=np.float64).reshape(3, 3))
+    return c.tobytes(), tuple(bool(f) for f in flags)
+
+
 class UMXCalculator(_AseBase):
-    """ASE calculator protocol on the MI355X engine (energies eV, forces eV/Angstrom)."""
+    """ASE calculator protocol on the MI355X engine (energies eV, forces eV/Angstrom).
+
+    Periodic images: the cell and the pbc flags of the ``Atoms`` reach the engine (``Engine.set_cell``), one cell for all images of a
+    ``calculate_images`` call.  Stress is NOT implemented (``implemented_properties`` stays energy and forces), so variable-cell
+    drivers cannot use this calculator."""
 
     implemented_properties = ["energy", "forces"]
 
@@ -64,7 +82,7 @@ class UMXCalculator(_AseBase):
         self.default_charge, self.default_spin = int(charge), int(spin)
         self.radius, self.max_neigh = radius, max_neigh
         self._engine = None
-        self._bound = None          # (numbers bytes, charge, spin)
+        self._bound = None          # (numbers bytes, charge, spin, (cell bytes, pbc flags) | None)
         self._last = None           # (bound key, positions, results) of the most recent single-image evaluation
         if not hasattr(self, "results"):
             self.results = {}
@@ -97,11 +115,19 @@ class UMXCalculator(_AseBase):
             from ._host import cap_pools_to_usable_cores
 
             cap_pools_to_usable_cores()          # the DMF driver's dense linear algebra between two calls must not starve the GPU feeder
-        key = (z.tobytes(), charge, spin)
-        if key != self._bound:
+        cell = _cell_pbc(atoms)
+        key = (z.tobytes(), charge, spin, cell)
+        if self._bound is None or key[:3] != self._bound[:3]:
             # merged-MoLE weights depend on (composition, charge, spin, task): refuse to re-bind them to another system
             W.check_merged_for(self._weights, z, charge, spin, self.task_name)
             self._engine.set_system(z, charge=charge, spin=spin, task=self.task_name, radius=self.radius, max_neigh=self.max_neigh)
+            self._bound = key[:3] + (None,) if self._bound is None else key[:3] + (self._bound[3],)
+        if cell != self._bound[3]:
+            # (after set_system: the engine checks the cell against the cutoff that is bound)
+            if cell is None:
+                self._engine.set_cell(None, None)
+            else:
+                self._engine.set_cell(np.frombuffer(cell[0], dtype=np.float64).reshape(3, 3), cell[1])
             self._bound = key
         return self._engine
 
@@ -138,6 +164,8 @@ class UMXCalculator(_AseBase):
         for im in images[1:]:
             if not np.array_equal(_numbers(im), z0):
                 raise ValueError("all images must share atom order and elements")
+            if _cell_pbc(im) != self._bound[3]:
+                raise ValueError("all images must share the cell and the pbc flags of the first image (one cell per call)")
         pos = np.stack([np.asarray(im.get_positions(), dtype=np.float64) for im in images])
         e, f = eng.energy_forces(pos, forces=True)
         return e, np.asarray(f, dtype=np.float64)

@@ -11,6 +11,7 @@
 #include "umx_engine.h"      // engine state, precision descriptor, WS / Plan types, error and buffer helpers
 #include "umx_launch.h"      // profiling bracket, GEMM launchers, the plane-GEMM dispatch table
 #include "umx_workspace.h"   // carving the workspace arena
+#include "umx_periodic.h"    // periodic boundary conditions: the translation table, the wrapped copy, the graph-kernel launchers
 #include "umx_plan.h"        // the launch plan of one chunk, its executors, and one evaluation as its phases
 #include "umx_weights.h"     // the weight loader
 #include "umx_experts.h"     // expert-form weights: the Mixture-of-Linear-Experts merge and its plane copies on the device
@@ -81,7 +82,7 @@ int umx_destroy(umx_engine* eng) {
   (void)hipSetDevice(eng->dev);
   (void)hipStreamSynchronize(eng->stream);
   for (auto& r : eng->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-  void* ptrs[] = {eng->d_w, eng->d_dw, eng->d_bw, eng->d_gmu, eng->d_z, eng->d_sysemb, eng->arena, eng->d_deg_all, eng->d_cand_all, eng->d_img_edges, eng->d_io_pos, eng->d_io_e, eng->d_io_f, eng->d_flags, eng->d_dtab, eng->d_part_deg, eng->d_part_f, eng->d_ex, eng->d_mjobs, eng->d_pjobs, eng->d_mx};
+  void* ptrs[] = {eng->d_w, eng->d_dw, eng->d_bw, eng->d_gmu, eng->d_z, eng->d_sysemb, eng->arena, eng->d_deg_all, eng->d_cand_all, eng->d_img_edges, eng->d_io_pos, eng->d_io_e, eng->d_io_f, eng->d_flags, eng->d_dtab, eng->d_part_deg, eng->d_part_f, eng->d_ex, eng->d_mjobs, eng->d_pjobs, eng->d_mx, eng->d_shifts, eng->d_wrap};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   (void)hipStreamSynchronize(eng->stream2);
   (void)hipEventDestroy(eng->ev_fork); (void)hipEventDestroy(eng->ev_join);
@@ -398,6 +399,13 @@ int umx_last_graph_stats(const umx_engine* eng, int64_t* n_edges_total, int32_t*
   if (max_degree) *max_degree = eng->last_maxdeg;
   return UMX_OK;
 }
+
+int umx_set_cell(umx_engine* eng, const double cell[9], const int pbc[3]) {
+  if (!eng) return UMX_ERR_ARG;
+  if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_set_cell: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
+  return set_cell_impl(eng, cell, pbc);
+}
+int umx_last_graph_shifts(const umx_engine* eng) { return eng ? eng->last_shifts : 0; }
 
 int umx_last_partitions(const umx_engine* eng) { return eng ? eng->last_parts : 0; }
 int umx_last_lanes(const umx_engine* eng) { return eng ? eng->last_lanes : 0; }

@@ -284,6 +284,14 @@ struct umx_engine {
   float* d_io_pos = nullptr; double* d_io_e = nullptr; float* d_io_f = nullptr; long io_cap = 0, io_img_cap = 0;
   // stats / profiling / debug
   int64_t last_edges = 0; int32_t last_maxdeg = 0;
+  // periodic boundary conditions (umx_set_cell, umx_periodic.h): ONE cell for all images of a call; it persists across umx_set_system
+  bool pbc_on = false;
+  double cell[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; int pbc[3] = {0, 0, 0};
+  Periodic per{};                  // what the periodic graph kernels read, built for the cutoff per_cutoff (rebuilt when umx_set_system changes it)
+  float per_cutoff = 0.f;
+  float4* d_shifts = nullptr;      // the translation table [PBC_MAX_SHIFTS]
+  float* d_wrap = nullptr; long wrap_cap = 0;   // positions wrapped into the cell: the copy the graph kernels read
+  int last_shifts = 0;             // lattice translations the most recent evaluation searched (umx_last_graph_shifts; 0: open boundaries)
   bool may_truncate = true;      // the largest degree of the evaluation being planned reaches max_neigh: k_graph_fill takes its truncating (LDS) form
   bool prof_on = false;
   std::vector<ProfRec> prof;

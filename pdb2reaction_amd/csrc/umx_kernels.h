@@ -20,6 +20,75 @@ namespace umx {
 __device__ __forceinline__ float dist2_f(float dx, float dy, float dz) { return fmaf(dz, dz, fmaf(dy, dy, dx * dx)); }
 
 // ------------------------------------------------------------------------------------------------
+// Periodic boundary conditions (umx_set_cell): what the periodic instantiations of the two graph kernels read.  Built on the host in
+// float64 from the cell (umx_periodic.h), passed by value.  A candidate of target i is (source j, translation t) with
+// 0 < |r_j + t - r_i| <= cutoff; t runs over the table, entry k = ((na + Na) (2 Nb + 1) + (nb + Nb)) (2 Nc + 1) + (nc + Nc) for
+// t = na a + nb b + nc c, |n| <= N per periodic axis (N = 0 on an open axis).  The kernels read positions WRAPPED into the cell
+// (k_wrap_cell), so the fractional coordinates of two atoms differ by less than one along every periodic axis.
+// ------------------------------------------------------------------------------------------------
+constexpr int GF_MAXC = 1024;                     // candidates the truncating fill ranks in LDS (see k_graph_fill)
+constexpr int PBC_MAX_AXIS = 4;                   // the cap: lattice translations -4 .. +4 per periodic axis
+constexpr int PBC_MAX_SHIFTS = 729;               // (2 * PBC_MAX_AXIS + 1)^3 table entries
+struct Periodic {
+  float a[3][3];          // lattice vectors (rows); zero for an open axis
+  float b[3][3];          // dual vectors of the periodic sub-lattice: fractional coordinate k = r . b[k]; zero for an open axis
+  float gmax[3];          // pruning: a translated cell whose nearest face is more than gmax[k] (fractional, cutoff / plane distance + margin) away is skipped
+  int n_shifts, zero;     // table entries, index of the zero translation
+  const float4* shifts;   // (tx, ty, tz, bits of (na + 8) | (nb + 8) << 8 | (nc + 8) << 16)
+};
+
+// one definition of the edge vector of a candidate, used by count and fill alike (see dist2_f)
+__device__ __forceinline__ void pbc_delta(const float* __restrict__ pj, float xi, float yi, float zi, const float4 sh, float& dx, float& dy, float& dz) {
+  dx = (pj[0] - xi) + sh.x; dy = (pj[1] - yi) + sh.y; dz = (pj[2] - zi) + sh.z;
+}
+
+// The translations that can reach the target at (x, y, z) within the cutoff, compacted in ascending index order into the wave's
+// LDS slice `act`; returns their number.  Wave-uniform decision per translation: the translated cell holds fractional coordinates
+// [n, n + 1) along axis k, the target sits at f, so every source of that image is at least gap = max(n - f, f - (n + 1), 0) plane
+// distances away.  The margin inside gmax covers the float32 rounding of the wrap and of f (1e-3 of a plane distance against 1e-6).
+__device__ __forceinline__ int pbc_active_shifts(const Periodic& per, float x, float y, float z, int lane, unsigned short* act) {
+  float f[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) f[k] = fmaf(z, per.b[k][2], fmaf(y, per.b[k][1], x * per.b[k][0]));
+  int na = 0;
+  for (int t0 = 0; t0 < per.n_shifts; t0 += 64) {
+    const int t = t0 + lane;
+    bool ok = t < per.n_shifts;
+    if (ok) {
+      const unsigned code = __float_as_uint(per.shifts[t].w);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const float n = (float)((int)((code >> (8 * k)) & 255u) - 8);
+        const float gap = fmaxf(fmaxf(n - f[k], f[k] - (n + 1.0f)), 0.0f);
+        ok = ok && gap <= per.gmax[k];
+      }
+    }
+    const unsigned long long m = __ballot(ok);
+    if (ok) act[na + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)t;
+    na += __popcll(m);
+  }
+  // the slice is private to this wave and its DS operations execute in order: only the compiler must not move the reads up
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  return na;
+}
+
+// wrap every atom into the cell along the periodic axes (a scratch copy only the graph kernels read: a per-atom lattice translation
+// changes no edge vector, hence no energy or force).  n = 0 leaves the coordinate bits as they are.
+__global__ void k_wrap_cell(const float* __restrict__ pos, float* __restrict__ out, long nt, const Periodic per) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nt) return;
+  const float x = pos[i * 3 + 0], y = pos[i * 3 + 1], z = pos[i * 3 + 2];
+  float n[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) n[k] = floorf(fmaf(z, per.b[k][2], fmaf(y, per.b[k][1], x * per.b[k][0])));
+  out[i * 3 + 0] = x - fmaf(n[2], per.a[2][0], fmaf(n[1], per.a[1][0], n[0] * per.a[0][0]));
+  out[i * 3 + 1] = y - fmaf(n[2], per.a[2][1], fmaf(n[1], per.a[1][1], n[0] * per.a[0][1]));
+  out[i * 3 + 2] = z - fmaf(n[2], per.a[2][2], fmaf(n[1], per.a[1][2], n[0] * per.a[0][2]));
+}
+
+// ------------------------------------------------------------------------------------------------
 // K1 radius graph: brute force inside each image, wave per target, ballot compaction (ascending
 // source order => CSR rows sorted by source).  pos: [NT][3] f32.
 // ------------------------------------------------------------------------------------------------
@@ -27,8 +96,12 @@ __device__ __forceinline__ float dist2_f(float dx, float dy, float dz) { return 
 // single-image mode, where every other node gets an empty row).
 // flag: bit 1 of the engine's sticky status word -- a non-finite coordinate (every comparison with it is false, so the atom would just
 // lose its edges); the device-pointer entries read the word right behind this kernel and refuse the evaluation (ABI v7)
+// PBC = true (umx_set_cell): candidates are (source, translation) pairs; pos is the wrapped copy.  flag bit 2: a target of the periodic
+// form has more candidates than the truncating fill can rank (GF_MAXC) while max_neigh binds -- refused by the host.
+template <bool PBC>
 __global__ __launch_bounds__(256) void k_graph_count(const float* __restrict__ pos, int natoms, long nt, float rc2, int max_neigh,
-                                                     int* __restrict__ deg, int* __restrict__ cand, long lo, long hi, int* __restrict__ flag) {
+                                                     int* __restrict__ deg, int* __restrict__ cand, long lo, long hi, int* __restrict__ flag,
+                                                     const Periodic per) {
   UMX_WAVE_ITEM(node, nt)
   const float xi = pos[node * 3 + 0], yi = pos[node * 3 + 1], zi = pos[node * 3 + 2];
   if (lane == 0 && !(isfinite(xi) && isfinite(yi) && isfinite(zi))) atomicOr(flag, 2);
@@ -38,6 +111,28 @@ __global__ __launch_bounds__(256) void k_graph_count(const float* __restrict__ p
   }
   const long base = (node / natoms) * natoms;
   int cnt = 0;
+  if constexpr (PBC) {
+    __shared__ unsigned short act_s[4][PBC_MAX_SHIFTS];
+    unsigned short* act = act_s[threadIdx.x >> 6];
+    const int na = pbc_active_shifts(per, xi, yi, zi, lane, act);
+    const int self = (int)(node - base);
+    for (int a = 0; a < na; ++a) {
+      const int t = __builtin_amdgcn_readfirstlane((int)act[a]);
+      const float4 sh = per.shifts[t];
+      for (int j0 = 0; j0 < natoms; j0 += 64) {
+        const int j = j0 + lane;
+        bool ok = false;
+        if (j < natoms) {
+          float dx, dy, dz;
+          pbc_delta(pos + (base + j) * 3, xi, yi, zi, sh, dx, dy, dz);
+          const float d2 = dist2_f(dx, dy, dz);
+          ok = (d2 <= rc2) && (d2 > 0.0f) && !(j == self && t == per.zero);   // an atom's own image (t != 0) is an edge
+        }
+        cnt += __popcll(__ballot(ok));
+      }
+    }
+    if (lane == 0 && cnt > max_neigh && cnt > GF_MAXC) atomicOr(flag, 4);
+  } else {
   for (int j0 = 0; j0 < natoms; j0 += 64) {
     const int j = j0 + lane;
     bool ok = false;
@@ -47,6 +142,7 @@ __global__ __launch_bounds__(256) void k_graph_count(const float* __restrict__ p
       ok = (d2 <= rc2) && (d2 > 0.0f) && (base + j != node);        // 0 < d <= cutoff
     }
     cnt += __popcll(__ballot(ok));
+  }
   }
   if (lane == 0) { cand[node] = cnt; deg[node] = cnt < max_neigh ? cnt : max_neigh; }
 }
@@ -82,14 +178,17 @@ __global__ __launch_bounds__(1024) void k_scan(const int* __restrict__ deg, long
 // target's candidates as 64-bit keys (d^2 bits << 32 | source: unique, ordered like the oracle's comparator) into its own LDS slice,
 // ranks each key against the others with broadcast reads (cand^2 / 64 compares per lane) and writes the kept ones in source order.
 // More than GF_MAXC candidates (> 1 atom / A^3 at a 6 A cutoff) keep the slow form.
-constexpr int GF_MAXC = 1024;
 // TRUNC = false (the common case: the host knows the batch's largest candidate count, read with the edge counts, and it is below max_neigh):
 // no truncation code and NO LDS -- the static 32-KiB key array of the truncating form would cap the resident blocks of this HBM-bound
 // kernel on every launch for a path that is never taken.
-template <bool TRUNC>
+// PBC = true: rows in ascending (source, translation index) order.  The truncating form ranks the candidates of ALL images by the
+// key (d^2 bits << 32 | translation index * natoms + source) -- equal-distance images of one source cannot tie -- finds the key of
+// rank max_neigh - 1 and keeps every candidate up to it; then (both forms) every lane counts the kept candidates of its source over
+// the active translations, a prefix sum over the lanes gives its first slot, and it writes them in translation order.
+template <bool TRUNC, bool PBC>
 __global__ __launch_bounds__(256) void k_graph_fill(const float* __restrict__ pos, int natoms, long nt, float rc2, int max_neigh,
                                                     const int* __restrict__ cand, const int* __restrict__ row_ptr, int* __restrict__ esrc,
-                                                    int* __restrict__ edst, float* __restrict__ evec, long lo, long hi) {
+                                                    int* __restrict__ edst, float* __restrict__ evec, long lo, long hi, const Periodic per) {
   UMX_WAVE_ITEM(node, nt)
   if (node < lo || node >= hi) return;           // wave-uniform: rows outside the owned target range are empty
   const long base = (node / natoms) * natoms;
@@ -97,6 +196,88 @@ __global__ __launch_bounds__(256) void k_graph_fill(const float* __restrict__ po
   const int nc = cand[node];
   const bool truncate = TRUNC && nc > max_neigh;
   int w = row_ptr[node];
+  if constexpr (PBC) {
+    __shared__ unsigned short act_s[4][PBC_MAX_SHIFTS];
+    unsigned short* act = act_s[threadIdx.x >> 6];
+    const int na = pbc_active_shifts(per, xi, yi, zi, lane, act);
+    const int self = (int)(node - base);
+    const int wend = row_ptr[node + 1];
+    unsigned long long kth = ~0ull;                                    // the largest key kept
+    // one definition of a candidate and its key for the three passes below
+    auto candidate = [&](int j, int t, const float4 sh, float& dx, float& dy, float& dz, unsigned long long& key) -> bool {
+      pbc_delta(pos + (base + j) * 3, xi, yi, zi, sh, dx, dy, dz);
+      const float d2 = dist2_f(dx, dy, dz);
+      key = ((unsigned long long)__float_as_uint(d2) << 32) | ((unsigned)t * (unsigned)natoms + (unsigned)j);
+      return (d2 <= rc2) && (d2 > 0.0f) && !(j == self && t == per.zero);
+    };
+    if constexpr (TRUNC) if (truncate) {                              // wave-uniform; nc <= GF_MAXC (else the degree pass refused)
+      __shared__ unsigned long long gf_keys[4][GF_MAXC];
+      unsigned long long* keys = gf_keys[threadIdx.x >> 6];
+      int c = 0;
+      for (int a = 0; a < na; ++a) {
+        const int t = __builtin_amdgcn_readfirstlane((int)act[a]);
+        const float4 sh = per.shifts[t];
+        for (int j0 = 0; j0 < natoms; j0 += 64) {
+          const int j = j0 + lane;
+          float dx, dy, dz;
+          unsigned long long key = 0ull;
+          const bool ok = j < natoms && candidate(j, t, sh, dx, dy, dz, key);
+          const unsigned long long m = __ballot(ok);
+          const int at = c + __popcll(m & ((1ull << lane) - 1ull));
+          if (ok && at < GF_MAXC) keys[at] = key;
+          c += __popcll(m);
+        }
+      }
+      c = c < GF_MAXC ? c : GF_MAXC;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      for (int c0 = 0; c0 < c; c0 += 64) {
+        const int ci = c0 + lane;
+        const bool have = ci < c;
+        const unsigned long long k = have ? keys[ci] : ~0ull;
+        int rank = 0;
+        for (int q = 0; q < c; ++q) rank += keys[q] < k ? 1 : 0;
+        const unsigned long long m = __ballot(have && rank == max_neigh - 1);     // keys are unique: at most one lane
+        if (m) {
+          const int from = __ffsll((long long)m) - 1;
+          const unsigned hi32 = __shfl((unsigned)(k >> 32), from, 64), lo32 = __shfl((unsigned)(k & 0xffffffffull), from, 64);
+          kth = ((unsigned long long)hi32 << 32) | lo32;
+        }
+      }
+    }
+    for (int j0 = 0; j0 < natoms; j0 += 64) {
+      const int j = j0 + lane;
+      int mine = 0;
+      if (j < natoms)
+#pragma clang loop vectorize(disable) interleave(disable)   // (two translations per lane would come out as packed-fp32 instructions: build.py refuses them)
+        for (int a = 0; a < na; ++a) {
+          const int t = act[a];
+          float dx, dy, dz;
+          unsigned long long key;
+          if (candidate(j, t, per.shifts[t], dx, dy, dz, key) && key <= kth) ++mine;
+        }
+      int incl = mine;                                                 // inclusive prefix sum over the lanes
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(incl, o, 64); if (lane >= o) incl += v; }
+      int slot = w + incl - mine;
+      if (mine)
+#pragma clang loop vectorize(disable) interleave(disable)
+        for (int a = 0; a < na; ++a) {
+          const int t = act[a];
+          float dx, dy, dz;
+          unsigned long long key;
+          if (candidate(j, t, per.shifts[t], dx, dy, dz, key) && key <= kth && slot < wend) {
+            const float d = sqrtf(__uint_as_float((unsigned)(key >> 32))), inv = 1.0f / d;
+            esrc[slot] = (int)(base + j);
+            edst[slot] = (int)node;
+            *reinterpret_cast<float4*>(evec + (long)slot * 4) = make_float4(dx * inv, dy * inv, dz * inv, d);
+            ++slot;
+          }
+        }
+      w += __shfl(incl, 63, 64);
+    }
+  } else {                                                            // open boundaries: the body below is as it was
   if constexpr (TRUNC) if (truncate && nc <= GF_MAXC) {               // wave-uniform
     __shared__ unsigned long long gf_keys[4][GF_MAXC];
     unsigned long long* keys = gf_keys[threadIdx.x >> 6];
@@ -174,6 +355,7 @@ __global__ __launch_bounds__(256) void k_graph_fill(const float* __restrict__ po
       *reinterpret_cast<float4*>(evec + (long)slot * 4) = make_float4(dx * inv, dy * inv, dz * inv, d);
     }
     w += __popcll(m);
+  }
   }
 }
 

@@ -1,0 +1,166 @@
+// umx_periodic.h -- host side: periodic boundary conditions (umx_set_cell).  The cell is turned, in float64, into what the periodic
+// instantiations of the graph kernels read (struct Periodic, umx_kernels.h): the lattice vectors, the dual vectors of the periodic
+// sub-lattice (fractional coordinates for the wrap and for pruning), and the table of lattice translations.  Also here: the wrapped
+// copy of the positions and the two launchers that pick the open-boundary or the periodic instantiation.
+//
+// Translations per periodic axis k: N_k = floor(cutoff / h_k + 1e-4) + 1, h_k the distance between the lattice planes of axis k within
+// the periodic sub-lattice -- the whole cells the cutoff spans, plus one because two wrapped atoms may be almost a cell apart (the 1e-4
+// covers the float32 rounding of the wrap).  The table holds every combination, (2 N_a + 1)(2 N_b + 1)(2 N_c + 1) entries with c
+// running fastest; N_k <= PBC_MAX_AXIS = 4, i.e. plane distances down to cutoff / 4 (1.5 A at the 6 A cutoff; a 5 A edge needs N = 2).
+#pragma once
+
+namespace {
+
+struct PeriodicHost { Periodic per{}; std::vector<float4> table; };
+
+inline void cross3(const double* u, const double* v, double* o) {
+  o[0] = u[1] * v[2] - u[2] * v[1]; o[1] = u[2] * v[0] - u[0] * v[2]; o[2] = u[0] * v[1] - u[1] * v[0];
+}
+inline double norm3(const double* u) { return std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]); }
+
+// false + *why: the cell is refused
+bool build_periodic(const double cell[9], const int pbc[3], double cutoff, PeriodicHost* out, std::string* why) {
+  const char ax[3] = {'a', 'b', 'c'};
+  for (int i = 0; i < 9; ++i)
+    if (!std::isfinite(cell[i])) { *why = "non-finite cell entry"; return false; }
+  bool on[3];
+  int np = 0;
+  double M[3][3];                      // periodic rows as given; open rows are replaced by unit vectors orthogonal to the periodic span
+  for (int k = 0; k < 3; ++k) {
+    on[k] = pbc[k] != 0;
+    np += on[k] ? 1 : 0;
+    for (int c = 0; c < 3; ++c) M[k][c] = cell[k * 3 + c];
+    if (on[k] && !(norm3(M[k]) > 0.0)) { *why = std::string("degenerate cell: lattice vector ") + ax[k] + " has zero length"; return false; }
+  }
+  if (np == 2) {
+    const int o = !on[0] ? 0 : (!on[1] ? 1 : 2), i = (o + 1) % 3, j = (o + 2) % 3;
+    double n[3];
+    cross3(M[i], M[j], n);
+    const double ln = norm3(n);
+    if (!(ln > 1e-6 * norm3(M[i]) * norm3(M[j]))) { *why = "degenerate cell: the two periodic lattice vectors span no area"; return false; }
+    for (int c = 0; c < 3; ++c) M[o][c] = n[c] / ln;
+  } else if (np == 1) {
+    const int i = on[0] ? 0 : (on[1] ? 1 : 2), p = (i + 1) % 3, q = (i + 2) % 3;
+    int least = 0;
+    for (int c = 1; c < 3; ++c) if (std::fabs(M[i][c]) < std::fabs(M[i][least])) least = c;
+    double e[3] = {0, 0, 0}, u[3], v[3];
+    e[least] = 1.0;
+    cross3(M[i], e, u);
+    const double lu = norm3(u);
+    for (int c = 0; c < 3; ++c) u[c] /= lu;
+    cross3(M[i], u, v);
+    const double lv = norm3(v);
+    for (int c = 0; c < 3; ++c) { M[p][c] = u[c]; M[q][c] = v[c] / lv; }
+  }
+  double c12[3], c20[3], c01[3];
+  cross3(M[1], M[2], c12); cross3(M[2], M[0], c20); cross3(M[0], M[1], c01);
+  const double det = M[0][0] * c12[0] + M[0][1] * c12[1] + M[0][2] * c12[2];
+  if (!(std::fabs(det) > 1e-6 * norm3(M[0]) * norm3(M[1]) * norm3(M[2]))) { *why = "degenerate cell: the periodic lattice vectors span no volume"; return false; }
+  // dual vectors: b_k . M_l = delta_kl; for a periodic k it lies in the periodic span, and 1 / |b_k| is the plane distance of axis k
+  const double* cr[3] = {c12, c20, c01};
+  double B[3][3], h[3];
+  int N[3];
+  Periodic& per = out->per;
+  per = Periodic();
+  for (int k = 0; k < 3; ++k) {
+    for (int c = 0; c < 3; ++c) B[k][c] = cr[k][c] / det;
+    h[k] = 1.0 / norm3(B[k]);
+    N[k] = 0;
+    if (!on[k]) continue;
+    const double spans = cutoff / h[k] + 1e-4;
+    if (!(spans < (double)PBC_MAX_AXIS)) {
+      char buf[256];
+      std::snprintf(buf, sizeof(buf), "the lattice planes of axis %c are %.4g A apart: a cutoff of %.4g A needs more than the %d lattice translations per direction "
+                    "this engine searches (plane distances down to cutoff / %d)", ax[k], h[k], cutoff, PBC_MAX_AXIS, PBC_MAX_AXIS);
+      *why = buf;
+      return false;
+    }
+    N[k] = (int)std::floor(spans) + 1;
+    for (int c = 0; c < 3; ++c) { per.a[k][c] = (float)cell[k * 3 + c]; per.b[k][c] = (float)B[k][c]; }
+    per.gmax[k] = (float)(1.001 * cutoff / h[k] + 1e-3);
+  }
+  out->table.clear();
+  for (int a = -N[0]; a <= N[0]; ++a)
+    for (int b = -N[1]; b <= N[1]; ++b)
+      for (int c = -N[2]; c <= N[2]; ++c) {
+        if (a == 0 && b == 0 && c == 0) per.zero = (int)out->table.size();
+        const unsigned code = (unsigned)(a + 8) | ((unsigned)(b + 8) << 8) | ((unsigned)(c + 8) << 16);
+        float w;
+        std::memcpy(&w, &code, sizeof(w));
+        out->table.push_back(make_float4((float)(a * cell[0] + b * cell[3] + c * cell[6]), (float)(a * cell[1] + b * cell[4] + c * cell[7]),
+                                         (float)(a * cell[2] + b * cell[5] + c * cell[8]), w));
+      }
+  per.n_shifts = (int)out->table.size();
+  return true;
+}
+
+// build the table of the stored cell for the bound cutoff and put it on the device
+int periodic_upload(umx_engine* eng, const PeriodicHost& ph) {
+  HIPCHK(eng, hipSetDevice(eng->dev));
+  HIPCHK(eng, hipStreamSynchronize(eng->stream));                     // no evaluation may still be reading the old table
+  if (eng->ran_on_caller) HIPCHK(eng, hipEventSynchronize(eng->ev_done));
+  if (!eng->d_shifts) HIPCHK(eng, hipMalloc(&eng->d_shifts, PBC_MAX_SHIFTS * sizeof(float4)));
+  HIPCHK(eng, hipMemcpy(eng->d_shifts, ph.table.data(), ph.table.size() * sizeof(float4), hipMemcpyHostToDevice));
+  eng->per = ph.per;
+  eng->per.shifts = eng->d_shifts;
+  eng->per_cutoff = eng->cutoff;
+  return UMX_OK;
+}
+
+int set_cell_impl(umx_engine* eng, const double* cell, const int* pbc) {
+  if (!cell || !pbc || !(pbc[0] || pbc[1] || pbc[2])) { eng->pbc_on = false; return UMX_OK; }
+  PeriodicHost ph;
+  std::string why;
+  if (!build_periodic(cell, pbc, eng->cutoff, &ph, &why)) return fail(eng, UMX_ERR_ARG, "umx_set_cell: " + why);   // (the engine keeps the cell it had)
+  CHK(periodic_upload(eng, ph));
+  std::memcpy(eng->cell, cell, sizeof(eng->cell));
+  for (int k = 0; k < 3; ++k) eng->pbc[k] = pbc[k] != 0;
+  eng->pbc_on = true;
+  return UMX_OK;
+}
+
+// Start of an evaluation.  Open boundaries: nothing.  Periodic: the table follows the bound cutoff, the positions of all images are
+// wrapped into the scratch copy, and *d_pos is pointed at it.
+int periodic_prepare(umx_engine* eng, hipStream_t s, long K, const float** d_pos) {
+  eng->last_shifts = 0;
+  if (!eng->pbc_on) return UMX_OK;
+  if (eng->per_cutoff != eng->cutoff) {          // umx_set_system changed the cutoff since umx_set_cell
+    PeriodicHost ph;
+    std::string why;
+    if (!build_periodic(eng->cell, eng->pbc, eng->cutoff, &ph, &why)) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: the cell set by umx_set_cell and the bound cutoff: " + why);
+    CHK(periodic_upload(eng, ph));
+  }
+  // the rank key of the truncating fill carries translation index * n_atoms + source in its low 32 bits
+  if ((unsigned long long)eng->per.n_shifts * (unsigned long long)eng->natoms > 0xffffffffull)
+    return fail(eng, UMX_ERR_ARG, "umx_energy_forces: " + std::to_string(eng->per.n_shifts) + " lattice translations x " + std::to_string(eng->natoms) +
+                " atoms do not fit the 32-bit candidate index of the periodic graph");
+  const long nt = K * eng->natoms;
+  if (eng->wrap_cap < nt) CHK(grow(eng, eng->wrap_cap, nt, {s}, {DevBuf(eng->d_wrap, (size_t)nt * 3)}));
+  hipLaunchKernelGGL(k_wrap_cell, dim3(nblk(nt, 256)), dim3(256), 0, s, *d_pos, eng->d_wrap, nt, eng->per);
+  HIPCHK(eng, hipGetLastError());
+  *d_pos = eng->d_wrap;
+  eng->last_shifts = eng->per.n_shifts;
+  return UMX_OK;
+}
+
+// ---- the two graph kernels, open-boundary or periodic instantiation ------------------------------------------------------------
+void launch_graph_count(umx_engine* eng, hipStream_t s, const float* d_pos, long nt, int* deg, int* cand, long lo, long hi) {
+  const float rc2 = eng->cutoff * eng->cutoff;
+  if (eng->pbc_on) hipLaunchKernelGGL(k_graph_count<true>, dim3(nblk(nt, 4)), dim3(256), 0, s, d_pos, eng->natoms, nt, rc2, eng->max_neigh, deg, cand, lo, hi, eng->d_flags, eng->per);
+  else hipLaunchKernelGGL(k_graph_count<false>, dim3(nblk(nt, 4)), dim3(256), 0, s, d_pos, eng->natoms, nt, rc2, eng->max_neigh, deg, cand, lo, hi, eng->d_flags, Periodic());
+}
+void launch_graph_fill(umx_engine* eng, hipStream_t s, bool trunc, const float* d_pos, long nn, const int* cand, const int* row_ptr, int* esrc, int* edst,
+                       float* evec, long lo, long hi) {
+  const float rc2 = eng->cutoff * eng->cutoff;
+  const dim3 grid(nblk(nn, 4)), block(256);
+  const int N = eng->natoms, mn = eng->max_neigh;
+  if (eng->pbc_on) {
+    if (trunc) hipLaunchKernelGGL((k_graph_fill<true, true>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, eng->per);
+    else hipLaunchKernelGGL((k_graph_fill<false, true>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, eng->per);
+  } else {
+    if (trunc) hipLaunchKernelGGL((k_graph_fill<true, false>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, Periodic());
+    else hipLaunchKernelGGL((k_graph_fill<false, false>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, Periodic());
+  }
+}
+
+}  // namespace

@@ -76,8 +76,7 @@ void plan_chunk(umx_engine* eng, WS& w, const float* d_pos, const int* d_deg, co
   P.stream([=, &w]() -> int {
     hipStream_t s = eng->stream;
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, d_deg, nn, w.row_ptr, w.stats);
-    if (may_trunc) hipLaunchKernelGGL(k_graph_fill<true>, dim3(nblk(nn, 4)), B256, 0, s, d_pos, N, nn, rc2, eng->max_neigh, d_cand, w.row_ptr, w.esrc, w.edst, w.evec, g_lo, g_hi);
-    else hipLaunchKernelGGL(k_graph_fill<false>, dim3(nblk(nn, 4)), B256, 0, s, d_pos, N, nn, rc2, eng->max_neigh, d_cand, w.row_ptr, w.esrc, w.edst, w.evec, g_lo, g_hi);
+    launch_graph_fill(eng, s, may_trunc, d_pos, nn, d_cand, w.row_ptr, w.esrc, w.edst, w.evec, g_lo, g_hi);
     HIPCHK(eng, hipMemsetAsync(w.out_cur, 0, (nn + 1) * sizeof(int), s));
     if (ne > 0) hipLaunchKernelGGL(k_out_count, dim3(nblk(ne, 256)), B256, 0, s, w.esrc, ne, w.out_cur);
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, w.out_cur, nn, w.out_ptr, w.stats + 2);
@@ -512,7 +511,7 @@ __global__ void k_image_edges(const int* __restrict__ deg, int natoms, int* __re
 
 // ---- degree pass -----------------------------------------------------------------------------------
 // End of a degree pass (k_graph_count + k_image_edges enqueued on s): the n edge totals followed by the largest degree come back to the
-// host together with the flag word, which is cleared when set.  Bit 1: THIS pass met a non-finite position.  Bit 0: an EARLIER
+// host together with the flag word, which is cleared when set.  Bit 1: THIS pass met a non-finite position (bit 2: see below).  Bit 0: an EARLIER
 // evaluation through a device-pointer entry produced a non-finite energy (this one has not computed an energy yet; on this stream that
 // evaluation is complete): its caller got NaN energies / forces and, most likely, derived these positions from them.  A pass that is
 // not the first of its call (own_only) leaves bit 0 to the next host sync.
@@ -523,9 +522,12 @@ int read_degree_pass(umx_engine* eng, hipStream_t s, const int* d_cnt, size_t n,
   HIPCHK(eng, hipMemcpyAsync(cnt.data(), d_cnt, (n + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(eng, hipMemcpyAsync(&flag, eng->d_flags, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(eng, hipStreamSynchronize(s));
-  if (own_only) flag &= 2;
+  if (own_only) flag &= 6;
   if (!flag) return UMX_OK;
   HIPCHK(eng, hipMemsetAsync(eng->d_flags, 0, sizeof(int), s));
+  if ((flag & 6) == 4)       // bit 2 (periodic graph only): more candidates than the truncating fill ranks
+    return fail(eng, UMX_ERR_CAPACITY, "periodic graph: an atom has more than " + std::to_string(GF_MAXC) + " candidates (source, translation) within the cutoff while "
+                "max_neigh = " + std::to_string(eng->max_neigh) + " binds; the truncating form ranks at most that many (a density beyond 1 atom per cubic Angstrom)");
   if (flag & 2)
     return fail(eng, UMX_ERR_ARG, "umx_energy_forces: non-finite position (device buffer)" +
                 std::string((flag & 1) ? "; the previous device-pointer evaluation had already produced a non-finite energy" : ""));
@@ -543,8 +545,7 @@ int degree_pass(umx_engine* eng, hipStream_t s, long K, const float* d_pos, Imag
   if (eng->deg_all_cap < nt) CHK(grow(eng, eng->deg_all_cap, nt, {s}, {DevBuf(eng->d_deg_all, nt), DevBuf(eng->d_cand_all, nt)}));
   if (eng->img_edges_cap < K + 1) CHK(grow(eng, eng->img_edges_cap, K + 1, {s}, {DevBuf(eng->d_img_edges, K + 1)}));
   HIPCHK(eng, hipMemsetAsync(eng->d_img_edges + K, 0, sizeof(int), s));
-  hipLaunchKernelGGL(k_graph_count, dim3(nblk(nt, 4)), dim3(256), 0, s, d_pos, N, nt, eng->cutoff * eng->cutoff, eng->max_neigh, eng->d_deg_all, eng->d_cand_all,
-                     eng->gp ? eng->gp_lo : 0L, eng->gp ? eng->gp_hi : nt, eng->d_flags);
+  launch_graph_count(eng, s, d_pos, nt, eng->d_deg_all, eng->d_cand_all, eng->gp ? eng->gp_lo : 0L, eng->gp ? eng->gp_hi : nt);
   hipLaunchKernelGGL(k_image_edges, dim3((unsigned)K), dim3(256), 0, s, eng->d_deg_all, N, eng->d_img_edges, eng->d_img_edges + K);
   CHK(read_degree_pass(eng, s, eng->d_img_edges, K, ie.per_image, false));
   eng->last_maxdeg = ie.per_image[K];
@@ -573,8 +574,7 @@ int eval_partitioned(umx_engine* eng, hipStream_t s, const float* d_pos, double*
   for (int p = 0; p < P; ++p) {
     lo[p] = (long)N * p / P; hi[p] = (long)N * (p + 1) / P;
     int* deg = eng->d_part_deg + (size_t)(2 * p) * N;
-    hipLaunchKernelGGL(k_graph_count, dim3(nblk(N, 4)), dim3(256), 0, s, d_pos, N, (long)N, eng->cutoff * eng->cutoff, eng->max_neigh, deg, deg + N,
-                       lo[p], hi[p], eng->d_flags);
+    launch_graph_count(eng, s, d_pos, (long)N, deg, deg + N, lo[p], hi[p]);
     hipLaunchKernelGGL(k_image_edges, dim3(1), dim3(256), 0, s, deg, N, d_cnt + p, d_cnt + P);
   }
   std::vector<int> cnt;
@@ -866,6 +866,7 @@ int energy_forces_on(umx_engine* eng, hipStream_t run_stream, int n_images, cons
   eng->ran_on_caller = (run_stream != own);
   struct Restore { umx_engine* e; hipStream_t s; ~Restore() { e->stream = s; } } restore{eng, own};
   hipStream_t s = eng->stream;
+  CHK(periodic_prepare(eng, s, n_images, &d_pos));     // periodic: from here on d_pos is the wrapped copy (only the graph kernels read positions)
   ImageEdges ie;
   CHK(degree_pass(eng, s, n_images, d_pos, ie));
   // recompute plans: never in the multi-GPU graph-parallel mode, nor with debug captures (they name the stored buffers of every layer)

@@ -83,6 +83,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "umx_peer_sum": ([i32, C.POINTER(vp), C.c_size_t, C.POINTER(i32), C.POINTER(vp)], i32),
         "umx_synchronize": ([vp], i32),
         "umx_last_graph_stats": ([vp, i64p, C.POINTER(C.c_int32)], i32),
+        "umx_set_cell": ([vp, dp, C.POINTER(C.c_int)], i32),
+        "umx_last_graph_shifts": ([vp], i32),
         "umx_last_partitions": ([vp], i32),
         "umx_last_lanes": ([vp], i32),
         "umx_set_recompute": ([vp, i32], i32),
@@ -129,6 +131,7 @@ EXPORTED_SYMBOLS = (
     "umx_set_workspace_limit", "umx_energy_forces", "umx_energy_forces_dev", "umx_gp_begin", "umx_gp_step", "umx_peer_sum", "umx_synchronize",
     "umx_last_graph_stats", "umx_last_partitions", "umx_last_lanes", "umx_reserve_images", "umx_workspace_stats", "umx_profile_enable", "umx_profile_read", "umx_bond_changes", "umx_debug_fetch", "umx_debug_keep",
     "umx_set_expert_coefficients", "umx_expert_count", "umx_set_recompute", "umx_last_recompute", "umx_workspace_bytes",
+    "umx_set_cell", "umx_last_graph_shifts",
 )
 
 
@@ -259,6 +262,23 @@ class Engine:
                   "umx_set_system")
         self.natoms = len(z)
         self._system = (z.copy(), int(charge), int(spin), task, radius, max_neigh)
+
+    def set_cell(self, cell=None, pbc=None):
+        """Periodic boundary conditions (``umx_set_cell``): ``cell`` (3,3) lattice vectors as rows in Angstrom, ``pbc`` one flag per axis
+        (a single bool means all three).  ``None`` for either, or no flag set, restores open boundaries.  ONE cell for all images of a
+        call; it persists across ``set_system`` until it is set again.  A degenerate cell, a non-finite entry or a cell whose lattice
+        planes are closer than cutoff / 4 raise ``UmxError``.  Stress is not computed."""
+        flags = None if pbc is None else np.broadcast_to(np.asarray(pbc, dtype=bool), (3,))
+        if cell is None or flags is None or not flags.any():
+            self._chk(self.lib.umx_set_cell(self._h, None, None), "umx_set_cell")
+            return
+        c = np.ascontiguousarray(np.asarray(cell, dtype=np.float64).reshape(3, 3))
+        f = np.ascontiguousarray(flags, dtype=np.intc)
+        self._chk(self.lib.umx_set_cell(self._h, c.ctypes.data_as(C.POINTER(C.c_double)), f.ctypes.data_as(C.POINTER(C.c_int))), "umx_set_cell")
+
+    def last_graph_shifts(self) -> int:
+        """Lattice translations the most recent evaluation searched (``umx_last_graph_shifts``); 0 = open boundaries."""
+        return int(self.lib.umx_last_graph_shifts(self._h))
 
     def set_workspace_limit(self, nbytes: int):
         self._chk(self.lib.umx_set_workspace_limit(self._h, int(nbytes)), "umx_set_workspace_limit")

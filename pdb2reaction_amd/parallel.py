@@ -476,6 +476,14 @@ class LocalEnginePool:
         self.natoms = len(atomic_numbers)
         self._gp_buf = None
 
+    def set_cell(self, cell=None, pbc=None) -> None:
+        """``Engine.set_cell`` on every engine: batches dealt over the pool and the graph-parallel single image see the same cell."""
+        for eng in self.engines:
+            eng.set_cell(cell, pbc)
+
+    def last_graph_shifts(self) -> int:
+        return int(self.engines[0].last_graph_shifts())
+
     def reserve_images(self, n_images: int) -> None:
         """Batches of up to ``n_images`` images are coming: every engine is told its share (``umx_reserve_images``)."""
         g = len(self.engines)
