@@ -173,7 +173,8 @@ int umx_set_system(umx_engine* eng, int n_atoms, const int32_t* atomic_numbers, 
  *   - The evaluation refuses (UMX_ERR_ARG) translations x n_atoms >= 2^32, and (UMX_ERR_CAPACITY) an atom with more than 1024
  *     candidates while max_neigh binds.
  * umx_last_graph_shifts: the number of lattice translations (table entries, the zero translation included) the most recent evaluation
- * searched; 0 = open boundaries.  Stress / virials, per-image cells and variable-cell drivers are not provided.
+ * searched; 0 = open boundaries.  Per-image cells and variable-cell drivers are not provided (the strain derivative is:
+ * umx_energy_forces_virial below).
  * No reference counterpart: the reference builds its AtomicData without a cell and never sets pbc (uma_pysis.py:292-327); what
  * fairchem's own periodic graph generation returns has not been compared [3P-UNVERIFIED].                                         */
 int umx_set_cell(umx_engine* eng, const double cell[9], const int pbc[3]);
@@ -209,6 +210,29 @@ int umx_energy_forces(umx_engine* eng, int n_images, const float* pos_ang, doubl
  * (UMX_ERR_ARG) -- it would otherwise silently drop that atom's edges.                            */
 int umx_energy_forces_dev(umx_engine* eng, int n_images, const float* d_pos_ang,
                           double* d_energy_ev, float* d_forces_ev_ang, void* hip_stream);
+
+/* STRAIN DERIVATIVE ("virial"; additive to ABI v10).  umx_energy_forces[_dev] with one more output, virial_ev: [n_images][9] float64,
+ * row-major, in eV:
+ *     W[3 a + b] = dE / d eps_ab  at eps = 0,   for the homogeneous strain  r -> r (1 + eps),  cell -> cell (1 + eps)
+ *                = rmsd * sum over the directed edges e of the image of  vec_e,a * (dE_model / dvec_e)_b ,   vec_e = r_src + t_e - r_dst,
+ * the sum over EVERY edge of the radius graph (self-image edges and repeated pairs included), products and sums in float64, in a fixed
+ * order: the bits of W do not depend on the batch an image is in, on the chunking or on the lanes (partitioned evaluation: reproducible,
+ * and the same for stored and recompute plans at the same partition count).  SIGN: the derivative of the energy itself -- positive when
+ * stretching raises the energy (tensile, ASE's convention for stress); for open boundaries W = - sum_i r_i (x) F_i.  The GRAPH IS HELD
+ * FIXED: the edge list of the unstrained geometry; the envelope takes every edge to zero smoothly at the cutoff, so this IS the derivative
+ * of E.  NO DIVISION BY A VOLUME happens here and W is not symmetrised: stress = (W + W^T) / 2 / |det cell| is the caller's (Python:
+ * Engine.energy_forces_stress).  Works with and without a cell (slabs and clusters have a virial, no volume).
+ *   - virial_ev == NULL is exactly umx_energy_forces[_dev]: no further kernel, launch or buffer.
+ *   - a virial without forces (forces_ev_ang == NULL: no reverse pass) is UMX_ERR_ARG.
+ *   - cost: two small launches behind the force kernels, 32 B read per directed edge; no arithmetic of the model path changes, energies
+ *     and forces are bitwise those of umx_energy_forces.
+ * Not provided: a virial from the graph-parallel entries (umx_gp_begin / umx_gp_step are unchanged), per-image cells, variable-cell
+ * drivers.  No reference counterpart (the reference never sets a cell, uma_pysis.py:292-327); fairchem's own stress has not been
+ * compared [3P-UNVERIFIED].                                                                                                        */
+int umx_energy_forces_virial(umx_engine* eng, int n_images, const float* pos_ang, double* energy_ev,
+                             float* forces_ev_ang, double* virial_ev);
+int umx_energy_forces_virial_dev(umx_engine* eng, int n_images, const float* d_pos_ang, double* d_energy_ev,
+                                 float* d_forces_ev_ang, double* d_virial_ev, void* hip_stream);
 
 /* Graph-parallel evaluation of ONE image across several engines / ranks (ABI v5) -- the reference's `workers > 1` semantics
  * (ParallelMLIPPredictUnit: the atoms' graph partitioned over workers, uma_pysis.py:220-242), for single large systems when there are

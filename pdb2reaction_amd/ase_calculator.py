@@ -36,6 +36,16 @@ except Exception:
             self.calculate(atoms, ["forces"], all_changes)
             return self.results["forces"]
 
+        def get_stress(self, atoms=None):
+            self.calculate(atoms, ["stress"], all_changes)
+            return self.results["stress"]
+
+
+try:  # pragma: no cover - only where ASE exists
+    from ase.calculators.calculator import PropertyNotImplementedError  # type: ignore
+except Exception:
+    PropertyNotImplementedError = NotImplementedError
+
 
 def _numbers(atoms) -> np.ndarray:
     if hasattr(atoms, "get_atomic_numbers"):
@@ -61,13 +71,22 @@ class UMXCalculator(_AseBase):
     """ASE calculator protocol on the MI355X engine (energies eV, forces eV/Angstrom).
 
     Periodic images: the cell and the pbc flags of the ``Atoms`` reach the engine (``Engine.set_cell``), one cell for all images of a
-    ``calculate_images`` call.  Stress is NOT implemented (``implemented_properties`` stays energy and forces), so variable-cell
-    drivers cannot use this calculator."""
+    ``calculate_images`` call.
+
+    Stress is opt-in: ``UMXCalculator(stress=True)`` adds ``"stress"`` to the INSTANCE's ``implemented_properties`` (the class attribute
+    stays energy and forces).  Every evaluation of an image whose three axes are periodic then goes through
+    ``Engine.energy_forces_stress`` and caches energy, forces and stress (eV/A^3, Voigt xx, yy, zz, yz, xz, xy, ASE's sign: tensile
+    positive), so ``get_potential_energy()``, ``get_forces()`` and ``get_stress()`` on an unchanged image are one evaluation, and ASE's
+    cell filters and variable-cell optimisers can drive the calculator.  The stress is the analytic strain derivative with the graph of
+    the unstrained geometry held fixed.  An image that is not fully periodic has no volume: energy and forces as before, a request
+    for ``"stress"`` raises ``PropertyNotImplementedError`` (``NotImplementedError`` where ASE is absent) -- as does any request for
+    it with ``stress=False``.  Per-image cells within one ``calculate_images`` call are not provided; a single image on a pool of
+    engines (``workers > 1``) is evaluated on engine 0 alone when the stress is on, because the graph-parallel path has none."""
 
     implemented_properties = ["energy", "forces"]
 
     def __init__(self, model: str = "uma-s-1p1", task_name: str = "omol", device: str = "auto", charge: int = 0, spin: int = 1,
-                 radius: Optional[float] = None, max_neigh: Optional[int] = None, workers: int = 1, **kwargs):
+                 radius: Optional[float] = None, max_neigh: Optional[int] = None, workers: int = 1, stress: bool = False, **kwargs):
         """workers > 1 (outside a torch.distributed process group): that many engines in this process when there are that many
         devices (``UMX_LOCAL_DEVICES`` names them), as in ``uma_pysis.UMAcore`` -- ``calculate_images`` deals its images over them,
         a single image is evaluated graph-parallel (``parallel.LocalEnginePool``); ``local_devices`` lists the ordinals in use."""
@@ -76,6 +95,9 @@ class UMXCalculator(_AseBase):
         if self.recompute not in (None, 0, 1, 2):
             raise ValueError(f"recompute must be 0, 1 or 2, got {self.recompute!r}")
         super().__init__(**kwargs)
+        self.stress = bool(stress)
+        if self.stress:
+            self.implemented_properties = ["energy", "forces", "stress"]      # on the instance: the class attribute stays as it is
         self.workers = max(int(workers or 1), 1)
         self.local_devices = None
         self.model, self.task_name, self.device = model, task_name, device
@@ -148,15 +170,30 @@ class UMXCalculator(_AseBase):
         pos = np.array(atoms.get_positions(), dtype=np.float64)
         # get_potential_energy() followed by get_forces() on an unchanged image is ONE evaluation (ASE's own base class caches by atoms
         # state; the stand-in base used where ASE is absent does not, and the engine always computes both)
+        with_stress = self.stress and self._fully_periodic()
+        if "stress" in properties and not with_stress:
+            raise PropertyNotImplementedError(
+                "stress: " + ("this calculator was built with stress=False (UMXCalculator(stress=True) turns it on)" if not self.stress
+                              else "the image is not periodic along all three axes, so there is no volume to refer a stress to"))
         if self._last is not None and self._last[0] == self._bound and np.array_equal(self._last[1], pos):
             self.results = dict(self._last[2])
             return
-        e, f = eng.energy_forces(pos[None], forces=True)
-        self.results = {"energy": float(e[0]), "forces": np.asarray(f[0], dtype=np.float64)}
+        if with_stress:
+            e, f, sv = eng.energy_forces_stress(pos[None])
+            self.results = {"energy": float(e[0]), "forces": np.asarray(f[0], dtype=np.float64), "stress": np.asarray(sv[0], dtype=np.float64)}
+        else:
+            e, f = eng.energy_forces(pos[None], forces=True)
+            self.results = {"energy": float(e[0]), "forces": np.asarray(f[0], dtype=np.float64)}
         self._last = (self._bound, pos, dict(self.results))
 
-    def calculate_images(self, images: Sequence[Any]):
-        """One batched evaluation for a list of images of the SAME system; returns (E [K] eV, F [K,N,3] eV/A)."""
+    def _fully_periodic(self) -> bool:
+        """The image bound last has a cell and all three pbc flags set."""
+        return self._bound is not None and self._bound[3] is not None and all(self._bound[3][1])
+
+    def calculate_images(self, images: Sequence[Any], stress: bool = False):
+        """One batched evaluation for a list of images of the SAME system; returns (E [K] eV, F [K,N,3] eV/A), and with ``stress=True``
+        (E, F, stress [K,6] eV/A^3 in Voigt order) -- for images that are periodic along all three axes, whatever the constructor's
+        ``stress`` says; ``PropertyNotImplementedError`` otherwise."""
         if not images:
             raise ValueError("empty image list")
         eng = self._ensure(images[0])
@@ -167,5 +204,10 @@ class UMXCalculator(_AseBase):
             if _cell_pbc(im) != self._bound[3]:
                 raise ValueError("all images must share the cell and the pbc flags of the first image (one cell per call)")
         pos = np.stack([np.asarray(im.get_positions(), dtype=np.float64) for im in images])
+        if stress:
+            if not self._fully_periodic():
+                raise PropertyNotImplementedError("stress: the images are not periodic along all three axes, so there is no volume to refer a stress to")
+            e, f, sv = eng.energy_forces_stress(pos)
+            return e, np.asarray(f, dtype=np.float64), np.asarray(sv, dtype=np.float64)
         e, f = eng.energy_forces(pos, forces=True)
         return e, np.asarray(f, dtype=np.float64)

@@ -12,6 +12,7 @@
 #include "umx_launch.h"      // profiling bracket, GEMM launchers, the plane-GEMM dispatch table
 #include "umx_workspace.h"   // carving the workspace arena
 #include "umx_periodic.h"    // periodic boundary conditions: the translation table, the wrapped copy, the graph-kernel launchers
+#include "umx_virial.h"      // the strain derivative of every image: the two reduction kernels behind k_force_edge and their launcher
 #include "umx_plan.h"        // the launch plan of one chunk, its executors, and one evaluation as its phases
 #include "umx_weights.h"     // the weight loader
 #include "umx_experts.h"     // expert-form weights: the Mixture-of-Linear-Experts merge and its plane copies on the device
@@ -82,7 +83,7 @@ int umx_destroy(umx_engine* eng) {
   (void)hipSetDevice(eng->dev);
   (void)hipStreamSynchronize(eng->stream);
   for (auto& r : eng->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-  void* ptrs[] = {eng->d_w, eng->d_dw, eng->d_bw, eng->d_gmu, eng->d_z, eng->d_sysemb, eng->arena, eng->d_deg_all, eng->d_cand_all, eng->d_img_edges, eng->d_io_pos, eng->d_io_e, eng->d_io_f, eng->d_flags, eng->d_dtab, eng->d_part_deg, eng->d_part_f, eng->d_ex, eng->d_mjobs, eng->d_pjobs, eng->d_mx, eng->d_shifts, eng->d_wrap};
+  void* ptrs[] = {eng->d_w, eng->d_dw, eng->d_bw, eng->d_gmu, eng->d_z, eng->d_sysemb, eng->arena, eng->d_deg_all, eng->d_cand_all, eng->d_img_edges, eng->d_io_pos, eng->d_io_e, eng->d_io_f, eng->d_flags, eng->d_dtab, eng->d_part_deg, eng->d_part_f, eng->d_ex, eng->d_mjobs, eng->d_pjobs, eng->d_mx, eng->d_shifts, eng->d_wrap, eng->d_vir_part, eng->d_vir_wp, eng->d_io_w};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   (void)hipStreamSynchronize(eng->stream2);
   (void)hipEventDestroy(eng->ev_fork); (void)hipEventDestroy(eng->ev_join);
@@ -219,16 +220,21 @@ int umx_synchronize(umx_engine* eng) {
 }
 
 int umx_energy_forces_dev(umx_engine* eng, int n_images, const float* d_pos, double* d_energy, float* d_forces, void* hip_stream) {
+  return umx_energy_forces_virial_dev(eng, n_images, d_pos, d_energy, d_forces, nullptr, hip_stream);
+}
+
+int umx_energy_forces_virial_dev(umx_engine* eng, int n_images, const float* d_pos, double* d_energy, float* d_forces, double* d_virial, void* hip_stream) {
   if (!eng) return UMX_ERR_ARG;
   if (eng->need_merge()) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: " NOT_MERGED);
   if (!eng->have_system) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: bind a system first (umx_set_system)");
   if (n_images <= 0 || !d_pos || !d_energy) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: bad arguments");
+  if (d_virial && !d_forces) return fail(eng, UMX_ERR_ARG, "umx_energy_forces_virial: the virial comes out of the reverse pass: ask for the forces too");
   if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
   HIPCHK(eng, hipSetDevice(eng->dev));
   // NULL = the legacy default stream (hipStream_t 0): the work is then ordered after everything the caller has enqueued on
   // the default stream (the producer of d_pos) and before whatever it enqueues next (the consumer of d_energy / d_forces),
   // exactly as with an explicit stream.  The engine's private non-blocking stream is never used for caller-owned buffers.
-  return energy_forces_on(eng, static_cast<hipStream_t>(hip_stream), n_images, d_pos, d_energy, d_forces);
+  return energy_forces_on(eng, static_cast<hipStream_t>(hip_stream), n_images, d_pos, d_energy, d_forces, d_virial);
 }
 
 int umx_gp_begin(umx_engine* eng, const float* d_pos, int node_lo, int node_hi, double* d_energy, float* d_forces, void* hip_stream) {
@@ -358,21 +364,28 @@ int umx_peer_sum(int n_peers, float* const* d_bufs, size_t count, const int* dev
 }
 
 int umx_energy_forces(umx_engine* eng, int n_images, const float* pos, double* energy, float* forces) {
+  return umx_energy_forces_virial(eng, n_images, pos, energy, forces, nullptr);
+}
+
+int umx_energy_forces_virial(umx_engine* eng, int n_images, const float* pos, double* energy, float* forces, double* virial) {
   if (!eng) return UMX_ERR_ARG;
   if (eng->need_merge()) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: " NOT_MERGED);
   if (!eng->have_system) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: bind a system first (umx_set_system)");
   if (n_images <= 0 || !pos || !energy) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: bad arguments");
+  if (virial && !forces) return fail(eng, UMX_ERR_ARG, "umx_energy_forces_virial: the virial comes out of the reverse pass: ask for the forces too");
   if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
   HIPCHK(eng, hipSetDevice(eng->dev));
   const long nt = (long)n_images * eng->natoms;
   if (eng->io_cap < nt) CHK(grow(eng, eng->io_cap, nt, {eng->stream}, {DevBuf(eng->d_io_pos, nt * 3), DevBuf(eng->d_io_f, nt * 3)}));
   if (eng->io_img_cap < n_images) CHK(grow(eng, eng->io_img_cap, (long)n_images, {eng->stream}, {DevBuf(eng->d_io_e, n_images)}));
+  if (virial && eng->io_w_cap < n_images) CHK(grow(eng, eng->io_w_cap, (long)n_images, {eng->stream}, {DevBuf(eng->d_io_w, (size_t)n_images * 9)}));
   for (long i = 0; i < nt * 3; ++i)         // a NaN coordinate would silently drop its atom from the radius graph (every comparison false)
     if (!std::isfinite(pos[i])) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: non-finite position (image " + std::to_string(i / ((long)eng->natoms * 3)) + ")");
   HIPCHK(eng, hipMemcpyAsync(eng->d_io_pos, pos, nt * 3 * sizeof(float), hipMemcpyHostToDevice, eng->stream));
-  CHK(energy_forces_on(eng, eng->stream, n_images, eng->d_io_pos, eng->d_io_e, forces ? eng->d_io_f : nullptr));
+  CHK(energy_forces_on(eng, eng->stream, n_images, eng->d_io_pos, eng->d_io_e, forces ? eng->d_io_f : nullptr, virial ? eng->d_io_w : nullptr));
   HIPCHK(eng, hipMemcpyAsync(energy, eng->d_io_e, (size_t)n_images * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
   if (forces) HIPCHK(eng, hipMemcpyAsync(forces, eng->d_io_f, nt * 3 * sizeof(float), hipMemcpyDeviceToHost, eng->stream));
+  if (virial) HIPCHK(eng, hipMemcpyAsync(virial, eng->d_io_w, (size_t)n_images * 9 * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
   HIPCHK(eng, hipStreamSynchronize(eng->stream));
   for (int k = 0; k < n_images; ++k)
     if (!std::isfinite(energy[k])) {

@@ -282,6 +282,12 @@ struct umx_engine {
   int hint_images = 0;             // umx_reserve_images: size the workspace for this many images at the next growth
   // host io staging for the host-pointer entry point
   float* d_io_pos = nullptr; double* d_io_e = nullptr; float* d_io_f = nullptr; long io_cap = 0, io_img_cap = 0;
+  // virial (umx_virial.h): the per-(image, slab) partials of the reduction, outside the arena; where the evaluation at hand writes W
+  // (nullptr: no virial was asked for) and its slots per image; the host entry's staging
+  double* d_vir_part = nullptr; long vir_cap = 0;
+  double* d_vir_wp = nullptr;      // partitioned evaluation: the partitions' own W_p, [VIR_MAX_PARTS][9]
+  double* vir_out = nullptr; int vir_slabs = 0;
+  double* d_io_w = nullptr; long io_w_cap = 0;
   // stats / profiling / debug
   int64_t last_edges = 0; int32_t last_maxdeg = 0;
   // periodic boundary conditions (umx_set_cell, umx_periodic.h): ONE cell for all images of a call; it persists across umx_set_system

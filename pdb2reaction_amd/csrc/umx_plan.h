@@ -59,8 +59,9 @@ int radial_bwd(umx_engine* eng, const WS& w, const RadialW& r, int slot, long ne
 }
 
 // ---- one chunk: nn nodes (= images * natoms), edges counted on the fly --------------------------
+// vir.out != nullptr: the chunk's final segment also takes the virial of its images (umx_virial.h)
 void plan_chunk(umx_engine* eng, WS& w, const float* d_pos, const int* d_deg, const int* d_cand, long nimg, long ne, double* d_energy,
-                float* d_forces, Plan& P) {
+                float* d_forces, Plan& P, const VirialOut vir = VirialOut()) {
   const int N = eng->natoms;
   const long nn = nimg * N;
   const float rc2 = eng->cutoff * eng->cutoff;
@@ -430,6 +431,7 @@ void plan_chunk(umx_engine* eng, WS& w, const float* d_pos, const int* d_deg, co
     }
     hipLaunchKernelGGL(k_force_node, dim3(nblk(nn, 4)), B256, 0, s, w.gvec, w.row_ptr, w.out_ptr, w.out_edge, (float)eng->rmsd, d_forces, nn);
     HIPCHK(eng, hipGetLastError());
+    if (vir.out) CHK(virial_launch(eng, w, vir, nimg, ne));       // (a partition: before the next one overwrites the shared gvec)
     DBG("dedd", w.dedd, ne); DBG("tau", w.tau, ne * 4); DBG("gvec", w.gvec, ne * 4);
     return UMX_OK;
   });
@@ -562,7 +564,7 @@ int degree_pass(umx_engine* eng, hipStream_t s, long K, const float* d_pos, Imag
 // TRANSIENT region (the producer -> GEMM operands are dead at every exchange point), and the all-reduce of an exchange point is a local
 // sum.  Memory per directed edge drops from ~120 KB to ~72 KB + 48 KB / P, i.e. a single image of up to ~1.5x the atoms fits the same
 // HBM; node-level work (< 3 %) is done P times.  Used automatically when one image exceeds the workspace budget.
-int eval_partitioned(umx_engine* eng, hipStream_t s, const float* d_pos, double* d_energy, float* d_forces, int P, size_t budget,
+int eval_partitioned(umx_engine* eng, hipStream_t s, const float* d_pos, double* d_energy, float* d_forces, double* d_virial, int P, size_t budget,
                      int64_t* edges_out, int* maxdeg_out) {
   const int N = eng->natoms;
   if (P < 2 || P > 16) return fail(eng, UMX_ERR_ARG, "eval_partitioned: 2..16 partitions");
@@ -591,11 +593,16 @@ int eval_partitioned(umx_engine* eng, hipStream_t s, const float* d_pos, double*
   std::vector<WS> ws(P);
   for (int p = 0; p < P; ++p) part_carve(eng->arena, off, eng->prec, eng->ws_grid(), eng->rc_active, N, cnt[p], p, ws[p]);
   std::vector<Plan> plans(P);
+  double* wpart = eng->d_vir_wp;                              // [VIR_MAX_PARTS][9] (virial_prepare); P <= 16 is checked above
   const bool gp_keep = eng->gp; const long lo_keep = eng->gp_lo, hi_keep = eng->gp_hi;
   for (int p = 0; p < P; ++p) {
     eng->gp = true; eng->gp_lo = lo[p]; eng->gp_hi = hi[p];
     int* deg = eng->d_part_deg + (size_t)(2 * p) * N;
-    plan_chunk(eng, ws[p], d_pos, deg, deg + N, 1, cnt[p], d_energy, d_forces ? eng->d_part_f + (size_t)p * N * 3 : nullptr, plans[p]);
+    // virial: the partition's own W_p (its edges are a contiguous range of the image's), taken in ITS final segment; the partials' slots
+    // are shared, the partitions run one after another on s
+    VirialOut vir;
+    if (d_virial && d_forces) { vir.out = wpart + (size_t)p * 9; vir.part = eng->d_vir_part; vir.slabs = eng->vir_slabs; }
+    plan_chunk(eng, ws[p], d_pos, deg, deg + N, 1, cnt[p], d_energy, d_forces ? eng->d_part_f + (size_t)p * N * 3 : nullptr, plans[p], vir);
   }
   eng->gp = gp_keep; eng->gp_lo = lo_keep; eng->gp_hi = hi_keep;
   std::vector<size_t> at(P, 0);
@@ -618,6 +625,11 @@ int eval_partitioned(umx_engine* eng, hipStream_t s, const float* d_pos, double*
     hipLaunchKernelGGL(k_sum_parts, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, pp, count, is_forces ? d_forces : (float*)nullptr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { st = fail(eng, UMX_ERR_HIP, std::string("k_sum_parts: ") + hipGetErrorName(e)); break; }
+    if (is_forces && d_virial) {                               // next to the forces: W = sum of the W_p in partition order
+      hipLaunchKernelGGL(k_virial_sum_parts, dim3(1), dim3(64), 0, s, wpart, P, d_virial);
+      e = hipGetLastError();
+      if (e != hipSuccess) { st = fail(eng, UMX_ERR_HIP, std::string("k_virial_sum_parts: ") + hipGetErrorName(e)); break; }
+    }
   }
   if (st != UMX_OK) return st;
   *edges_out = 0;
@@ -635,7 +647,8 @@ int eval_images_partitioned(umx_engine* eng, hipStream_t s, long K, const float*
     int stp = UMX_ERR_CAPACITY;
     for (int parts = eng->force_parts >= 2 ? eng->force_parts : 2; parts <= 16 && stp == UMX_ERR_CAPACITY; parts = eng->force_parts >= 2 ? 17 : parts + 1) {
       int64_t e1 = 0; int m1 = 0;
-      stp = eval_partitioned(eng, s, d_pos + k * N * 3, d_energy + k, d_forces ? d_forces + k * N * 3 : nullptr, parts, budget, &e1, &m1);
+      stp = eval_partitioned(eng, s, d_pos + k * N * 3, d_energy + k, d_forces ? d_forces + k * N * 3 : nullptr,
+                             eng->vir_out ? eng->vir_out + k * 9 : nullptr, parts, budget, &e1, &m1);
       if (stp == UMX_OK) { etot += e1; mdeg = std::max(mdeg, m1); eng->last_parts = parts; }
     }
     if (stp == UMX_ERR_CAPACITY)
@@ -779,8 +792,10 @@ int run_chunks(umx_engine* eng, hipStream_t s, int lanes, const ImageEdges& ie, 
     const long k0 = c.img[ci].first, k1 = c.img[ci].second;
     long e = 0;
     for (long k = k0; k < k1; ++k) e += ie.per_image[k];
+    VirialOut vir;       // the partials' slots follow the image's position in the call: the two lanes never share one
+    if (eng->vir_out && d_forces) { vir.out = eng->vir_out + k0 * 9; vir.part = eng->d_vir_part + k0 * eng->vir_slabs * 9; vir.slabs = eng->vir_slabs; }
     plan_chunk(eng, wl[lane], d_pos + k0 * N * 3, eng->d_deg_all + k0 * N, eng->d_cand_all + k0 * N, k1 - k0, e, d_energy + k0,
-               d_forces ? d_forces + k0 * N * 3 : nullptr, P);
+               d_forces ? d_forces + k0 * N * 3 : nullptr, P, vir);
   };
   if (lanes == 2) {          // chunks in pairs, one per lane, matrix segments alternating between the lanes (run_plans_alternating)
     // lane 1 starts after everything enqueued so far on the primary stream (degree pass, caller's work)
@@ -860,15 +875,22 @@ int evaluate_planned(umx_engine* eng, hipStream_t s, long K, const float* d_pos,
 
 // Evaluate on `run_stream` (may be the legacy default stream 0).  eng->stream is swapped for the duration so that every
 // helper launches there; it is restored on every exit path.
-int energy_forces_on(umx_engine* eng, hipStream_t run_stream, int n_images, const float* d_pos, double* d_energy, float* d_forces) {
+// d_virial: [n_images][9] float64 or nullptr (then nothing of umx_virial.h runs); never with the graph-parallel entry.
+int energy_forces_on(umx_engine* eng, hipStream_t run_stream, int n_images, const float* d_pos, double* d_energy, float* d_forces,
+                     double* d_virial = nullptr) {
   hipStream_t own = eng->stream;
   eng->stream = run_stream;
   eng->ran_on_caller = (run_stream != own);
-  struct Restore { umx_engine* e; hipStream_t s; ~Restore() { e->stream = s; } } restore{eng, own};
+  struct Restore { umx_engine* e; hipStream_t s; ~Restore() { e->stream = s; e->vir_out = nullptr; } } restore{eng, own};
   hipStream_t s = eng->stream;
   CHK(periodic_prepare(eng, s, n_images, &d_pos));     // periodic: from here on d_pos is the wrapped copy (only the graph kernels read positions)
   ImageEdges ie;
   CHK(degree_pass(eng, s, n_images, d_pos, ie));
+  if (d_virial) {
+    eng->vir_slabs = virial_slabs(ie.emax);
+    CHK(virial_prepare(eng, s, n_images, eng->vir_slabs));
+    eng->vir_out = d_virial;
+  }
   // recompute plans: never in the multi-GPU graph-parallel mode, nor with debug captures (they name the stored buffers of every layer)
   const bool rc_can = !eng->gp && !eng->dbg_on;
   eng->rc_active = rc_can && eng->recompute == 2;

@@ -78,6 +78,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "umx_set_workspace_limit": ([vp, C.c_size_t], i32),
         "umx_energy_forces": ([vp, i32, fp, dp, fp], i32),
         "umx_energy_forces_dev": ([vp, i32, vp, vp, vp, vp], i32),
+        "umx_energy_forces_virial": ([vp, i32, fp, dp, fp, dp], i32),
+        "umx_energy_forces_virial_dev": ([vp, i32, vp, vp, vp, vp, vp], i32),
         "umx_gp_begin": ([vp, vp, i32, i32, vp, vp, vp], i32),
         "umx_gp_step": ([vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(i32)], i32),
         "umx_peer_sum": ([i32, C.POINTER(vp), C.c_size_t, C.POINTER(i32), C.POINTER(vp)], i32),
@@ -131,7 +133,7 @@ EXPORTED_SYMBOLS = (
     "umx_set_workspace_limit", "umx_energy_forces", "umx_energy_forces_dev", "umx_gp_begin", "umx_gp_step", "umx_peer_sum", "umx_synchronize",
     "umx_last_graph_stats", "umx_last_partitions", "umx_last_lanes", "umx_reserve_images", "umx_workspace_stats", "umx_profile_enable", "umx_profile_read", "umx_bond_changes", "umx_debug_fetch", "umx_debug_keep",
     "umx_set_expert_coefficients", "umx_expert_count", "umx_set_recompute", "umx_last_recompute", "umx_workspace_bytes",
-    "umx_set_cell", "umx_last_graph_shifts",
+    "umx_set_cell", "umx_last_graph_shifts", "umx_energy_forces_virial", "umx_energy_forces_virial_dev",
 )
 
 
@@ -144,6 +146,14 @@ def workspace_bytes(n_nodes: int, n_edges: int, parts: int = 0, recompute: int =
     if n < 0:
         raise ValueError(f"workspace_bytes: arguments out of range (n_nodes={n_nodes}, n_edges={n_edges}, parts={parts})")
     return n
+
+
+def voigt_stress(virial: np.ndarray, volume: float) -> np.ndarray:
+    """(..., 3, 3) strain derivative W in eV and a volume in A^3 -> (..., 6) stress in eV/A^3, Voigt order xx, yy, zz, yz, xz, xy:
+    the symmetric part of W over the volume."""
+    w = np.asarray(virial, dtype=np.float64)
+    sym = 0.5 * (w + np.swapaxes(w, -1, -2)) / float(volume)
+    return np.stack([sym[..., 0, 0], sym[..., 1, 1], sym[..., 2, 2], sym[..., 1, 2], sym[..., 0, 2], sym[..., 0, 1]], axis=-1)
 
 
 def peer_sum(ptrs: Sequence[int], count: int, devices: Sequence[int], streams: Sequence[int]) -> None:
@@ -187,6 +197,7 @@ class Engine:
         self.expert_coefficients = None # the MoLE coefficients alpha (n_experts,) of the last set_system on an expert-form blob
         self._routing = None            # expert form: the blob's tensors without the stacks (the routing network reads them)
         self.dataset_list = tuple(W.DATASET_LIST)      # order of the rows of the loaded blob's dataset_embedding.weight (load_weights)
+        self._cell = None               # (cell (3,3) float64, pbc flags (3,)) the engine accepted last (set_cell), None for open boundaries
         if precision is not None:
             self._chk(self.lib.umx_set_precision(self._h, precision.encode()), "umx_set_precision")
         if recompute is not None:
@@ -267,14 +278,17 @@ class Engine:
         """Periodic boundary conditions (``umx_set_cell``): ``cell`` (3,3) lattice vectors as rows in Angstrom, ``pbc`` one flag per axis
         (a single bool means all three).  ``None`` for either, or no flag set, restores open boundaries.  ONE cell for all images of a
         call; it persists across ``set_system`` until it is set again.  A degenerate cell, a non-finite entry or a cell whose lattice
-        planes are closer than cutoff / 4 raise ``UmxError``.  Stress is not computed."""
+        planes are closer than cutoff / 4 raise ``UmxError`` and leave the previous cell in place.  The accepted cell is remembered:
+        ``energy_forces_stress`` divides by its volume."""
         flags = None if pbc is None else np.broadcast_to(np.asarray(pbc, dtype=bool), (3,))
         if cell is None or flags is None or not flags.any():
             self._chk(self.lib.umx_set_cell(self._h, None, None), "umx_set_cell")
+            self._cell = None
             return
         c = np.ascontiguousarray(np.asarray(cell, dtype=np.float64).reshape(3, 3))
         f = np.ascontiguousarray(flags, dtype=np.intc)
         self._chk(self.lib.umx_set_cell(self._h, c.ctypes.data_as(C.POINTER(C.c_double)), f.ctypes.data_as(C.POINTER(C.c_int))), "umx_set_cell")
+        self._cell = (c.copy(), tuple(bool(x) for x in flags))
 
     def last_graph_shifts(self) -> int:
         """Lattice translations the most recent evaluation searched (``umx_last_graph_shifts``); 0 = open boundaries."""
@@ -306,6 +320,51 @@ class Engine:
             self._chk(self.lib.umx_energy_forces(self._h, k, p.ctypes.data_as(fp), e.ctypes.data_as(C.POINTER(C.c_double)),
                                                  f.ctypes.data_as(fp) if forces else None), "umx_energy_forces")
         return e, f
+
+    def energy_forces_virial(self, pos_ang: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """pos_ang: (K,N,3) or (N,3) Angstrom -> (E [K] eV float64, F [K,N,3] eV/A float32, W [K,3,3] eV float64).
+
+        ``W[k, a, b] = dE_k / d eps_ab`` for the homogeneous strain r -> r (1 + eps), cell -> cell (1 + eps), the graph held fixed
+        (``umx_energy_forces_virial``, include/umx.h): not symmetrised, not divided by a volume, defined with and without a cell.
+        E and F are bitwise those of ``energy_forces``; an fp16 range violation takes the same widen-and-repeat path."""
+        p = np.ascontiguousarray(pos_ang, dtype=np.float32)
+        if p.ndim == 2:
+            p = p[None]
+        if p.ndim != 3 or p.shape[1] != self.natoms or p.shape[2] != 3:
+            raise ValueError(f"positions must be (K,{self.natoms},3), got {p.shape}")
+        k = p.shape[0]
+        e = np.empty(k, dtype=np.float64)
+        f = np.empty_like(p)
+        w = np.empty((k, 3, 3), dtype=np.float64)
+        fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
+
+        def call():
+            self._chk(self.lib.umx_energy_forces_virial(self._h, k, p.ctypes.data_as(fp), e.ctypes.data_as(dp), f.ctypes.data_as(fp),
+                                                        w.ctypes.data_as(dp)), "umx_energy_forces_virial")
+        try:
+            call()
+        except UmxError as err:
+            if getattr(err, "status", 0) != UMX_ERR_RANGE or not self._widen(str(err)):
+                raise
+            call()
+        return e, f, w
+
+    def energy_forces_stress(self, pos_ang: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """pos_ang: (K,N,3) or (N,3) Angstrom -> (E [K] eV, F [K,N,3] eV/A, stress [K,6] eV/A^3 in Voigt order xx, yy, zz, yz, xz, xy).
+
+        ``stress = (W + W^T) / 2 / |det cell|`` with W of ``energy_forces_virial`` and the cell ``set_cell`` accepted last; ASE's sign
+        convention (dE/d eps / V: tensile positive).  ``ValueError`` unless all three axes are periodic -- a slab or a cluster has no
+        volume; ``energy_forces_virial`` serves those."""
+        vol = self.cell_volume()
+        e, f, w = self.energy_forces_virial(pos_ang)
+        return e, f, voigt_stress(w, vol)
+
+    def cell_volume(self) -> float:
+        """|det cell| of the cell in force; ``ValueError`` unless all three axes are periodic."""
+        if self._cell is None or not all(self._cell[1]):
+            raise ValueError("stress needs a cell that is periodic along all three axes (set_cell): the volume is otherwise undefined; "
+                             "energy_forces_virial gives the strain derivative of a slab or a cluster")
+        return float(abs(np.linalg.det(self._cell[0])))
 
     def precision_mode(self) -> str:
         """The arithmetic the engine is in now ("bf16x3" | "split-f16" | "split-bf16" | "fp32"): what "auto" resolved to."""
@@ -349,6 +408,12 @@ class Engine:
         self._chk(self.lib.umx_energy_forces_dev(self._h, int(n_images), C.c_void_p(d_pos), C.c_void_p(d_energy),
                                                  C.c_void_p(d_forces) if d_forces else None,
                                                  C.c_void_p(stream) if stream else None), "umx_energy_forces_dev")
+
+    def energy_forces_virial_dev(self, n_images: int, d_pos: int, d_energy: int, d_forces: int, d_virial: int, stream: int = 0):
+        """``energy_forces_dev`` with the virial: ``d_virial`` is a device pointer to [n_images][9] float64 (row-major W, eV)."""
+        self._chk(self.lib.umx_energy_forces_virial_dev(self._h, int(n_images), C.c_void_p(d_pos), C.c_void_p(d_energy),
+                                                        C.c_void_p(d_forces) if d_forces else None, C.c_void_p(d_virial) if d_virial else None,
+                                                        C.c_void_p(stream) if stream else None), "umx_energy_forces_virial_dev")
 
     # ---- graph-parallel single-image mode (reference workers > 1; see parallel.GraphParallelEvaluator) -----------------
     def gp_begin(self, d_pos: int, node_lo: int, node_hi: int, d_energy: int, d_forces: int, stream: int = 0):

@@ -526,25 +526,25 @@ class LocalEnginePool:
             if not getattr(eng, "widened", False):
                 eng.widen(why)
 
-    def energy_forces(self, pos_ang, forces: bool = True) -> Tuple[np.ndarray, Optional[np.ndarray]]:
-        """pos_ang: (K,N,3) or (N,3) Angstrom -> (E [K] eV float64, F [K,N,3] eV/A float32 | None): ``Engine.energy_forces`` over the pool."""
+    def _images(self, pos_ang) -> np.ndarray:
+        """(K,N,3) float32 of what a caller passed as (K,N,3) or (N,3)."""
         p = np.ascontiguousarray(pos_ang, dtype=np.float32)
         if p.ndim == 2:
             p = p[None]
         if p.ndim != 3 or p.shape[1] != self.natoms or p.shape[2] != 3:
             raise ValueError(f"positions must be (K,{self.natoms},3), got {p.shape}")
+        return p
+
+    def _deal(self, p: np.ndarray, call: Callable) -> list:
+        """The batch route of every evaluation method: ``call(engine r, p[block r])`` for the engines with a non-empty contiguous block
+        ``shard_bounds(K, G, r)``, one host thread each; the results in engine (= image) order."""
         k, g = p.shape[0], len(self.engines)
-        if k == 1:
-            if self.gp and g > 1 and self.recompute != 2:
-                return self._graph_parallel(p[0], forces)
-            self.last_route, self.last_blocks = "single", [(0, 1)]
-            return self.engines[0].energy_forces(p, forces=forces)
         blocks = [shard_bounds(k, g, r) for r in range(g)]
         busy = [r for r in range(g) if blocks[r][1] > blocks[r][0]]
         self.last_route, self.last_blocks = "batch", blocks
         for attempt in range(2):
             was_wide = [bool(getattr(eng, "widened", False)) for eng in self.engines]
-            res = self._run_all(lambda r: self.engines[r].energy_forces(p[blocks[r][0]: blocks[r][1]], forces=forces), busy)
+            res = self._run_all(lambda r: call(self.engines[r], p[blocks[r][0]: blocks[r][1]]), busy)
             now_wide = [bool(getattr(eng, "widened", False)) for eng in self.engines]
             if attempt == 0 and now_wide != was_wide:
                 # an engine left the fp16 operand range and moved itself to bf16 forward planes (Engine.energy_forces): the blocks of
@@ -552,9 +552,41 @@ class LocalEnginePool:
                 self._widen_all("fp16 range violation on another engine of the local pool")
                 continue
             break
+        return res
+
+    def energy_forces(self, pos_ang, forces: bool = True) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        """pos_ang: (K,N,3) or (N,3) Angstrom -> (E [K] eV float64, F [K,N,3] eV/A float32 | None): ``Engine.energy_forces`` over the pool."""
+        p = self._images(pos_ang)
+        if p.shape[0] == 1:
+            if self.gp and len(self.engines) > 1 and self.recompute != 2:
+                return self._graph_parallel(p[0], forces)
+            self.last_route, self.last_blocks = "single", [(0, 1)]
+            return self.engines[0].energy_forces(p, forces=forces)
+        res = self._deal(p, lambda eng, block: eng.energy_forces(block, forces=forces))
         e = np.concatenate([r[0] for r in res])
         f = np.concatenate([r[1] for r in res]) if forces else None
         return e, f
+
+    def energy_forces_virial(self, pos_ang) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """``Engine.energy_forces_virial`` over the pool: (E [K], F [K,N,3], W [K,3,3] float64).  A batch is dealt over the engines in
+        the same contiguous blocks as ``energy_forces`` and is the single-engine result bit for bit (W does not depend on the batch an
+        image is in).  A SINGLE geometry is evaluated on engine 0 alone, as with recompute mode 2: the graph-parallel path has no
+        virial (``umx_gp_begin`` / ``umx_gp_step`` produce none)."""
+        p = self._images(pos_ang)
+        if p.shape[0] == 1:
+            self.last_route, self.last_blocks = "single", [(0, 1)]
+            return self.engines[0].energy_forces_virial(p)
+        res = self._deal(p, lambda eng, block: eng.energy_forces_virial(block))
+        return tuple(np.concatenate([r[i] for r in res]) for i in range(3))
+
+    def energy_forces_stress(self, pos_ang) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """``Engine.energy_forces_stress`` over the pool: (E [K], F [K,N,3], stress [K,6] eV/A^3, Voigt xx, yy, zz, yz, xz, xy), routed
+        as ``energy_forces_virial``; ``ValueError`` unless the cell (``set_cell``) is periodic along all three axes."""
+        from .engine import voigt_stress
+
+        vol = self.engines[0].cell_volume()
+        e, f, w = self.energy_forces_virial(pos_ang)
+        return e, f, voigt_stress(w, vol)
 
     def _gp_buffers(self):
         if self._gp_buf is None:
