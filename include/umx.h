@@ -162,7 +162,8 @@ int umx_set_system(umx_engine* eng, int n_atoms, const int32_t* atomic_numbers, 
  * atom's own images included -- rows in ascending (source, translation index) order; max_neigh keeps the nearest candidates over all
  * images.  Everything behind the graph is the open-boundary code.  Positions may lie anywhere: the engine wraps a scratch copy into
  * the cell for the search, energies and forces do not depend on it.
- *   - ONE cell for all images of a call (a string in a fixed cell).  The cell PERSISTS across umx_set_system until it is set again.
+ *   - ONE cell for all images of a call (a string in a fixed cell; one cell per image: umx_set_cells below).  The cell PERSISTS across
+ *     umx_set_system until it is set again.
  *   - All flags zero, or cell == NULL (or pbc == NULL): open boundaries, exactly the engine without this call.
  *   - UMX_ERR_ARG (umx_last_error says which): a non-finite entry; a degenerate periodic sub-lattice (a periodic vector of zero
  *     length, two that span no area, three that span no volume); a cell that needs more than 4 lattice translations per direction
@@ -173,12 +174,34 @@ int umx_set_system(umx_engine* eng, int n_atoms, const int32_t* atomic_numbers, 
  *   - The evaluation refuses (UMX_ERR_ARG) translations x n_atoms >= 2^32, and (UMX_ERR_CAPACITY) an atom with more than 1024
  *     candidates while max_neigh binds.
  * umx_last_graph_shifts: the number of lattice translations (table entries, the zero translation included) the most recent evaluation
- * searched; 0 = open boundaries.  Per-image cells and variable-cell drivers are not provided (the strain derivative is:
- * umx_energy_forces_virial below).
+ * searched (per-image cells: the largest table among the images); 0 = open boundaries.  Variable-cell drivers are not provided (the
+ * strain derivative is: umx_energy_forces_virial below).
  * No reference counterpart: the reference builds its AtomicData without a cell and never sets pbc (uma_pysis.py:292-327); what
  * fairchem's own periodic graph generation returns has not been compared [3P-UNVERIFIED].                                         */
 int umx_set_cell(umx_engine* eng, const double cell[9], const int pbc[3]);
 int umx_last_graph_shifts(const umx_engine* eng);
+
+/* PER-IMAGE CELLS (additive to ABI v10).  cells: [n_images][9] float64, every cell laid out as umx_set_cell's; cell k belongs to
+ * image k of the evaluations that follow -- a variable-cell string, an equation-of-state or elastic-constant scan, the strained copies
+ * of a finite-difference stress, all in ONE batched call.  Image k of such a batch is, bit for bit (energy, forces, virial), the
+ * single-image evaluation after umx_set_cell(cell k); K identical cells are umx_set_cell with that cell.
+ *   - ONE set of pbc flags for all images.
+ *   - The cells PERSIST across umx_set_system, until umx_set_cell or umx_set_cells is called again: each replaces the other.
+ *   - cells == NULL, pbc == NULL or no flag set (n_images is then not looked at): open boundaries, exactly the engine without the call.
+ *   - UMX_ERR_ARG: n_images <= 0 with cells given; any cell umx_set_cell would refuse (same checks, same cutoff rule) -- the WHOLE call
+ *     is then refused, umx_last_error names the image index and the reason, and the cell or cells in force before stay in force.
+ *     Refused while a graph-parallel evaluation is in progress.
+ *   - An evaluation (umx_energy_forces[_dev], umx_energy_forces_virial[_dev]) whose n_images differs from the bound count is
+ *     UMX_ERR_ARG (the message gives both numbers); nothing is evaluated.  umx_gp_begin takes per-image cells only when exactly ONE
+ *     cell is bound (it is then umx_set_cell with that cell), else UMX_ERR_ARG.
+ *   - The translation tables may differ in size from image to image (a strained cell can cross a threshold of N_k); they are kept
+ *     packed, sum of the images' entries.  translations x n_atoms >= 2^32 is checked per image.  When umx_set_system changed the
+ *     cutoff since, the next evaluation rebuilds every image's table from the stored cells; a cell that no longer fits names its image.
+ *   - cost: one stream synchronisation and two uploads per call (not per image); the graph kernels read the cell of their image
+ *     through scalar loads instead of the kernel arguments.
+ * Not provided: per-image pbc flags, device-resident cells, variable-cell drivers of our own, a virial from the graph-parallel entries.
+ * No reference counterpart (the reference never sets a cell, uma_pysis.py:292-327).                                                 */
+int umx_set_cells(umx_engine* eng, int n_images, const double* cells, const int pbc[3]);
 
 /* Optional: cap the device workspace (bytes; 0 = automatic from free HBM).
  * How much of the cap is used (ABI v8): device memory costs ~45 ms per GiB to allocate on this driver, so the workspace is amortised.
@@ -226,8 +249,8 @@ int umx_energy_forces_dev(umx_engine* eng, int n_images, const float* d_pos_ang,
  *   - a virial without forces (forces_ev_ang == NULL: no reverse pass) is UMX_ERR_ARG.
  *   - cost: two small launches behind the force kernels, 32 B read per directed edge; no arithmetic of the model path changes, energies
  *     and forces are bitwise those of umx_energy_forces.
- * Not provided: a virial from the graph-parallel entries (umx_gp_begin / umx_gp_step are unchanged), per-image cells, variable-cell
- * drivers.  No reference counterpart (the reference never sets a cell, uma_pysis.py:292-327); fairchem's own stress has not been
+ * With per-image cells (umx_set_cells) image k's W belongs to cell k.
+ * Not provided: a virial from the graph-parallel entries (umx_gp_begin / umx_gp_step are unchanged), variable-cell drivers.  No reference counterpart (the reference never sets a cell, uma_pysis.py:292-327); fairchem's own stress has not been
  * compared [3P-UNVERIFIED].                                                                                                        */
 int umx_energy_forces_virial(umx_engine* eng, int n_images, const float* pos_ang, double* energy_ev,
                              float* forces_ev_ang, double* virial_ev);

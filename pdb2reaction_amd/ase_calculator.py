@@ -71,7 +71,8 @@ class UMXCalculator(_AseBase):
     """ASE calculator protocol on the MI355X engine (energies eV, forces eV/Angstrom).
 
     Periodic images: the cell and the pbc flags of the ``Atoms`` reach the engine (``Engine.set_cell``), one cell for all images of a
-    ``calculate_images`` call.
+    ``calculate_images`` call -- or, with ``calculate_images(..., per_image_cells=True)``, every image's own cell
+    (``Engine.set_cells``: a variable-cell string, a scan over strained cells), the pbc flags still shared.
 
     Stress is opt-in: ``UMXCalculator(stress=True)`` adds ``"stress"`` to the INSTANCE's ``implemented_properties`` (the class attribute
     stays energy and forces).  Every evaluation of an image whose three axes are periodic then goes through
@@ -80,7 +81,7 @@ class UMXCalculator(_AseBase):
     cell filters and variable-cell optimisers can drive the calculator.  The stress is the analytic strain derivative with the graph of
     the unstrained geometry held fixed.  An image that is not fully periodic has no volume: energy and forces as before, a request
     for ``"stress"`` raises ``PropertyNotImplementedError`` (``NotImplementedError`` where ASE is absent) -- as does any request for
-    it with ``stress=False``.  Per-image cells within one ``calculate_images`` call are not provided; a single image on a pool of
+    it with ``stress=False``.  A single image on a pool of
     engines (``workers > 1``) is evaluated on engine 0 alone when the stress is on, because the graph-parallel path has none."""
 
     implemented_properties = ["energy", "forces"]
@@ -104,13 +105,15 @@ class UMXCalculator(_AseBase):
         self.default_charge, self.default_spin = int(charge), int(spin)
         self.radius, self.max_neigh = radius, max_neigh
         self._engine = None
-        self._bound = None          # (numbers bytes, charge, spin, (cell bytes, pbc flags) | None)
+        self._bound = None          # (numbers bytes, charge, spin, (cell bytes, pbc flags) | ("cells", bytes of all cells, pbc flags) | None)
         self._last = None           # (bound key, positions, results) of the most recent single-image evaluation
         if not hasattr(self, "results"):
             self.results = {}
 
     # ---- engine / system binding ------------------------------------------------------------------
-    def _ensure(self, atoms):
+    def _ensure(self, atoms, bind_cell: bool = True):
+        """The engine, with the system of ``atoms`` bound and (``bind_cell``) its cell; without, the cell entry of ``_bound`` is the
+        caller's to bring up to date."""
         from .engine import Engine
         from . import weights as W
         from .uma_pysis import _device_index, resolve_weights
@@ -144,7 +147,7 @@ class UMXCalculator(_AseBase):
             W.check_merged_for(self._weights, z, charge, spin, self.task_name)
             self._engine.set_system(z, charge=charge, spin=spin, task=self.task_name, radius=self.radius, max_neigh=self.max_neigh)
             self._bound = key[:3] + (None,) if self._bound is None else key[:3] + (self._bound[3],)
-        if cell != self._bound[3]:
+        if bind_cell and cell != self._bound[3]:
             # (after set_system: the engine checks the cell against the cutoff that is bound)
             if cell is None:
                 self._engine.set_cell(None, None)
@@ -188,21 +191,39 @@ class UMXCalculator(_AseBase):
 
     def _fully_periodic(self) -> bool:
         """The image bound last has a cell and all three pbc flags set."""
-        return self._bound is not None and self._bound[3] is not None and all(self._bound[3][1])
+        return self._bound is not None and self._bound[3] is not None and all(self._bound[3][-1])
 
-    def calculate_images(self, images: Sequence[Any], stress: bool = False):
+    def _bind_image_cells(self, eng, images) -> None:
+        """Every image's own cell to ``Engine.set_cells``.  ``_bound`` then names the set of cells, which no single image's cell equals:
+        the next ``calculate()`` binds its cell again, and the single-image cache is dropped."""
+        cps = [_cell_pbc(im) for im in images]
+        if any(cp is None for cp in cps):
+            raise ValueError("per_image_cells: every image needs a cell and at least one periodic axis")
+        if any(cp[1] != cps[0][1] for cp in cps):
+            raise ValueError("per_image_cells: all images must share the pbc flags of the first image (one set of flags per call)")
+        mark = ("cells", b"".join(cp[0] for cp in cps), cps[0][1])
+        if mark != self._bound[3]:
+            eng.set_cells(np.frombuffer(mark[1], dtype=np.float64).reshape(len(images), 3, 3), mark[2])
+            self._bound = self._bound[:3] + (mark,)
+        self._last = None
+
+    def calculate_images(self, images: Sequence[Any], stress: bool = False, per_image_cells: bool = False):
         """One batched evaluation for a list of images of the SAME system; returns (E [K] eV, F [K,N,3] eV/A), and with ``stress=True``
         (E, F, stress [K,6] eV/A^3 in Voigt order) -- for images that are periodic along all three axes, whatever the constructor's
-        ``stress`` says; ``PropertyNotImplementedError`` otherwise."""
+        ``stress`` says; ``PropertyNotImplementedError`` otherwise.  All images share the cell of the first one (``ValueError``
+        otherwise) unless ``per_image_cells=True``: then image k is evaluated in its own cell, and its stress refers to its own volume;
+        the images must all have a cell and agree in their pbc flags (``ValueError``)."""
         if not images:
             raise ValueError("empty image list")
-        eng = self._ensure(images[0])
+        eng = self._ensure(images[0], bind_cell=not per_image_cells)
         z0 = _numbers(images[0])
         for im in images[1:]:
             if not np.array_equal(_numbers(im), z0):
                 raise ValueError("all images must share atom order and elements")
-            if _cell_pbc(im) != self._bound[3]:
+            if not per_image_cells and _cell_pbc(im) != self._bound[3]:
                 raise ValueError("all images must share the cell and the pbc flags of the first image (one cell per call)")
+        if per_image_cells:
+            self._bind_image_cells(eng, images)
         pos = np.stack([np.asarray(im.get_positions(), dtype=np.float64) for im in images])
         if stress:
             if not self._fully_periodic():

@@ -83,7 +83,7 @@ int umx_destroy(umx_engine* eng) {
   (void)hipSetDevice(eng->dev);
   (void)hipStreamSynchronize(eng->stream);
   for (auto& r : eng->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-  void* ptrs[] = {eng->d_w, eng->d_dw, eng->d_bw, eng->d_gmu, eng->d_z, eng->d_sysemb, eng->arena, eng->d_deg_all, eng->d_cand_all, eng->d_img_edges, eng->d_io_pos, eng->d_io_e, eng->d_io_f, eng->d_flags, eng->d_dtab, eng->d_part_deg, eng->d_part_f, eng->d_ex, eng->d_mjobs, eng->d_pjobs, eng->d_mx, eng->d_shifts, eng->d_wrap, eng->d_vir_part, eng->d_vir_wp, eng->d_io_w};
+  void* ptrs[] = {eng->d_w, eng->d_dw, eng->d_bw, eng->d_gmu, eng->d_z, eng->d_sysemb, eng->arena, eng->d_deg_all, eng->d_cand_all, eng->d_img_edges, eng->d_io_pos, eng->d_io_e, eng->d_io_f, eng->d_flags, eng->d_dtab, eng->d_part_deg, eng->d_part_f, eng->d_ex, eng->d_mjobs, eng->d_pjobs, eng->d_mx, eng->d_shifts, eng->d_cells, eng->d_shifts_pk, eng->d_wrap, eng->d_vir_part, eng->d_vir_wp, eng->d_io_w};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   (void)hipStreamSynchronize(eng->stream2);
   (void)hipEventDestroy(eng->ev_fork); (void)hipEventDestroy(eng->ev_join);
@@ -230,6 +230,7 @@ int umx_energy_forces_virial_dev(umx_engine* eng, int n_images, const float* d_p
   if (n_images <= 0 || !d_pos || !d_energy) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: bad arguments");
   if (d_virial && !d_forces) return fail(eng, UMX_ERR_ARG, "umx_energy_forces_virial: the virial comes out of the reverse pass: ask for the forces too");
   if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
+  CHK(periodic_check_images(eng, n_images, "umx_energy_forces"));
   HIPCHK(eng, hipSetDevice(eng->dev));
   // NULL = the legacy default stream (hipStream_t 0): the work is then ordered after everything the caller has enqueued on
   // the default stream (the producer of d_pos) and before whatever it enqueues next (the consumer of d_energy / d_forces),
@@ -246,6 +247,9 @@ int umx_gp_begin(umx_engine* eng, const float* d_pos, int node_lo, int node_hi, 
   if (eng->recompute == 2)
     return fail(eng, UMX_ERR_ARG, "umx_gp_begin: recompute mode 2 (umx_set_recompute / UMX_RECOMPUTE=2) is a one-GPU plan; the multi-GPU graph-parallel mode "
                                   "keeps every rank's activations stored: set mode 0 or 1 on the engines that take part");
+  if (eng->pbc_on && eng->n_cells > 1)
+    return fail(eng, UMX_ERR_ARG, "umx_gp_begin: one image, but umx_set_cells bound cells for " + std::to_string(eng->n_cells) +
+                                  " images: the graph-parallel mode takes per-image cells only when exactly one is bound");
   if (eng->gp_plan) gp_clear(eng);                       // an abandoned evaluation
   HIPCHK(eng, hipSetDevice(eng->dev));
   eng->gp = true; eng->gp_lo = node_lo; eng->gp_hi = node_hi;
@@ -374,6 +378,7 @@ int umx_energy_forces_virial(umx_engine* eng, int n_images, const float* pos, do
   if (n_images <= 0 || !pos || !energy) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: bad arguments");
   if (virial && !forces) return fail(eng, UMX_ERR_ARG, "umx_energy_forces_virial: the virial comes out of the reverse pass: ask for the forces too");
   if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
+  CHK(periodic_check_images(eng, n_images, "umx_energy_forces"));
   HIPCHK(eng, hipSetDevice(eng->dev));
   const long nt = (long)n_images * eng->natoms;
   if (eng->io_cap < nt) CHK(grow(eng, eng->io_cap, nt, {eng->stream}, {DevBuf(eng->d_io_pos, nt * 3), DevBuf(eng->d_io_f, nt * 3)}));
@@ -417,6 +422,11 @@ int umx_set_cell(umx_engine* eng, const double cell[9], const int pbc[3]) {
   if (!eng) return UMX_ERR_ARG;
   if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_set_cell: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
   return set_cell_impl(eng, cell, pbc);
+}
+int umx_set_cells(umx_engine* eng, int n_images, const double* cells, const int pbc[3]) {
+  if (!eng) return UMX_ERR_ARG;
+  if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_set_cells: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
+  return set_cells_impl(eng, n_images, cells, pbc);
 }
 int umx_last_graph_shifts(const umx_engine* eng) { return eng ? eng->last_shifts : 0; }
 

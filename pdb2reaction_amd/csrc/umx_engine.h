@@ -290,12 +290,18 @@ struct umx_engine {
   double* d_io_w = nullptr; long io_w_cap = 0;
   // stats / profiling / debug
   int64_t last_edges = 0; int32_t last_maxdeg = 0;
-  // periodic boundary conditions (umx_set_cell, umx_periodic.h): ONE cell for all images of a call; it persists across umx_set_system
+  // periodic boundary conditions (umx_periodic.h): ONE cell for all images of a call (umx_set_cell), or one cell per image
+  // (umx_set_cells, n_cells > 0: then `cell` / `per` / `d_shifts` are not in use); either persists across umx_set_system
   bool pbc_on = false;
   double cell[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; int pbc[3] = {0, 0, 0};
   Periodic per{};                  // what the periodic graph kernels read, built for the cutoff per_cutoff (rebuilt when umx_set_system changes it)
   float per_cutoff = 0.f;
   float4* d_shifts = nullptr;      // the translation table [PBC_MAX_SHIFTS]
+  int n_cells = 0;                 // umx_set_cells: the images the bound cells belong to (0: one shared cell, or open boundaries)
+  std::vector<double> cells;       // [n_cells][9], kept for a rebuild at another cutoff
+  std::vector<int> cell_shifts;    // [n_cells] table entries of every image
+  Periodic* d_cells = nullptr; long cells_cap = 0;          // [n_cells] what the per-image instantiations read; `shifts` points into d_shifts_pk
+  float4* d_shifts_pk = nullptr; long shifts_pk_cap = 0;    // the images' tables, packed: sum of n_shifts entries
   float* d_wrap = nullptr; long wrap_cap = 0;   // positions wrapped into the cell: the copy the graph kernels read
   int last_shifts = 0;             // lattice translations the most recent evaluation searched (umx_last_graph_shifts; 0: open boundaries)
   bool may_truncate = true;      // the largest degree of the evaluation being planned reaches max_neigh: k_graph_fill takes its truncating (LDS) form

@@ -21,7 +21,7 @@ __device__ __forceinline__ float dist2_f(float dx, float dy, float dz) { return 
 
 // ------------------------------------------------------------------------------------------------
 // Periodic boundary conditions (umx_set_cell): what the periodic instantiations of the two graph kernels read.  Built on the host in
-// float64 from the cell (umx_periodic.h), passed by value.  A candidate of target i is (source j, translation t) with
+// float64 from the cell (umx_periodic.h), passed by value (one cell) or read from an array with one entry per image (umx_set_cells).  A candidate of target i is (source j, translation t) with
 // 0 < |r_j + t - r_i| <= cutoff; t runs over the table, entry k = ((na + Na) (2 Nb + 1) + (nb + Nb)) (2 Nc + 1) + (nc + Nc) for
 // t = na a + nb b + nc c, |n| <= N per periodic axis (N = 0 on an open axis).  The kernels read positions WRAPPED into the cell
 // (k_wrap_cell), so the fractional coordinates of two atoms differ by less than one along every periodic axis.
@@ -36,6 +36,25 @@ struct Periodic {
   int n_shifts, zero;     // table entries, index of the zero translation
   const float4* shifts;   // (tx, ty, tz, bits of (na + 8) | (nb + 8) << 8 | (nc + 8) << 16)
 };
+// Per-image cells (umx_set_cells): one Periodic per image of the call in device memory, every entry's `shifts` pointing into one packed
+// table buffer.  img0: the index within the call of the first image the launch covers (a chunk, a lane, one partitioned image).
+struct PeriodicImages {
+  const Periodic* cells;
+  int img0;
+};
+// what a graph kernel takes as its last argument: the one cell by value (IMG = false; also the unused argument of the open-boundary
+// instantiations), or the array of cells (IMG = true)
+template <bool IMG> struct PeriodicArgOf { using type = Periodic; };
+template <> struct PeriodicArgOf<true> { using type = PeriodicImages; };
+template <bool IMG> using PeriodicArg = typename PeriodicArgOf<IMG>::type;
+
+// The cell of the wave's node.  IMG: the image index is wave-uniform, and taken through readfirstlane so that the struct (and, through
+// its `shifts`, the table entries) arrive through scalar loads, as the kernel argument does.
+__device__ __forceinline__ Periodic periodic_of_node(const Periodic& arg, long, int) { return arg; }
+__device__ __forceinline__ Periodic periodic_of_node(const PeriodicImages& arg, long node, int natoms) {
+  const int img = __builtin_amdgcn_readfirstlane(arg.img0 + (int)(node / natoms));
+  return arg.cells[img];
+}
 
 // one definition of the edge vector of a candidate, used by count and fill alike (see dist2_f)
 __device__ __forceinline__ void pbc_delta(const float* __restrict__ pj, float xi, float yi, float zi, const float4 sh, float& dx, float& dy, float& dz) {
@@ -76,9 +95,16 @@ __device__ __forceinline__ int pbc_active_shifts(const Periodic& per, float x, f
 
 // wrap every atom into the cell along the periodic axes (a scratch copy only the graph kernels read: a per-atom lattice translation
 // changes no edge vector, hence no energy or force).  n = 0 leaves the coordinate bits as they are.
-__global__ void k_wrap_cell(const float* __restrict__ pos, float* __restrict__ out, long nt, const Periodic per) {
+// IMG (umx_set_cells): atom i is wrapped into the cell of its image i / natoms (a thread per atom: a wave may span two images, so
+// here the cell comes in through vector loads).
+template <bool IMG>
+__global__ void k_wrap_cell(const float* __restrict__ pos, float* __restrict__ out, long nt, int natoms, const PeriodicArg<IMG> parg) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nt) return;
+  const Periodic* pp;
+  if constexpr (IMG) pp = parg.cells + (parg.img0 + (int)(i / natoms));
+  else pp = &parg;
+  const Periodic& per = *pp;
   const float x = pos[i * 3 + 0], y = pos[i * 3 + 1], z = pos[i * 3 + 2];
   float n[3];
 #pragma unroll
@@ -98,11 +124,14 @@ __global__ void k_wrap_cell(const float* __restrict__ pos, float* __restrict__ o
 // lose its edges); the device-pointer entries read the word right behind this kernel and refuse the evaluation (ABI v7)
 // PBC = true (umx_set_cell): candidates are (source, translation) pairs; pos is the wrapped copy.  flag bit 2: a target of the periodic
 // form has more candidates than the truncating fill can rank (GF_MAXC) while max_neigh binds -- refused by the host.
-template <bool PBC>
+// IMG = true (umx_set_cells, PBC only): the cell is that of the node's image, read from the array behind parg.
+template <bool PBC, bool IMG = false>
 __global__ __launch_bounds__(256) void k_graph_count(const float* __restrict__ pos, int natoms, long nt, float rc2, int max_neigh,
                                                      int* __restrict__ deg, int* __restrict__ cand, long lo, long hi, int* __restrict__ flag,
-                                                     const Periodic per) {
+                                                     const PeriodicArg<IMG> parg) {
+  static_assert(PBC || !IMG, "per-image cells are periodic");
   UMX_WAVE_ITEM(node, nt)
+  const Periodic per = periodic_of_node(parg, node, natoms);
   const float xi = pos[node * 3 + 0], yi = pos[node * 3 + 1], zi = pos[node * 3 + 2];
   if (lane == 0 && !(isfinite(xi) && isfinite(yi) && isfinite(zi))) atomicOr(flag, 2);
   if (node < lo || node >= hi) {                 // wave-uniform
@@ -185,12 +214,16 @@ __global__ __launch_bounds__(1024) void k_scan(const int* __restrict__ deg, long
 // key (d^2 bits << 32 | translation index * natoms + source) -- equal-distance images of one source cannot tie -- finds the key of
 // rank max_neigh - 1 and keeps every candidate up to it; then (both forms) every lane counts the kept candidates of its source over
 // the active translations, a prefix sum over the lanes gives its first slot, and it writes them in translation order.
-template <bool TRUNC, bool PBC>
+// IMG = true (umx_set_cells, PBC only): the cell of the node's image, as in k_graph_count -- both take the image index from the same
+// (img0, node / natoms), so the rows the count sized are the rows the fill writes.
+template <bool TRUNC, bool PBC, bool IMG = false>
 __global__ __launch_bounds__(256) void k_graph_fill(const float* __restrict__ pos, int natoms, long nt, float rc2, int max_neigh,
                                                     const int* __restrict__ cand, const int* __restrict__ row_ptr, int* __restrict__ esrc,
-                                                    int* __restrict__ edst, float* __restrict__ evec, long lo, long hi, const Periodic per) {
+                                                    int* __restrict__ edst, float* __restrict__ evec, long lo, long hi, const PeriodicArg<IMG> parg) {
+  static_assert(PBC || !IMG, "per-image cells are periodic");
   UMX_WAVE_ITEM(node, nt)
   if (node < lo || node >= hi) return;           // wave-uniform: rows outside the owned target range are empty
+  const Periodic per = periodic_of_node(parg, node, natoms);
   const long base = (node / natoms) * natoms;
   const float xi = pos[node * 3 + 0], yi = pos[node * 3 + 1], zi = pos[node * 3 + 2];
   const int nc = cand[node];

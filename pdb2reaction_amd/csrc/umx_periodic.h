@@ -1,4 +1,4 @@
-// umx_periodic.h -- host side: periodic boundary conditions (umx_set_cell).  The cell is turned, in float64, into what the periodic
+// umx_periodic.h -- host side: periodic boundary conditions (umx_set_cell, umx_set_cells).  A cell is turned, in float64, into what the periodic
 // instantiations of the graph kernels read (struct Periodic, umx_kernels.h): the lattice vectors, the dual vectors of the periodic
 // sub-lattice (fractional coordinates for the wrap and for pruning), and the table of lattice translations.  Also here: the wrapped
 // copy of the positions and the two launchers that pick the open-boundary or the periodic instantiation.
@@ -108,7 +108,7 @@ int periodic_upload(umx_engine* eng, const PeriodicHost& ph) {
 }
 
 int set_cell_impl(umx_engine* eng, const double* cell, const int* pbc) {
-  if (!cell || !pbc || !(pbc[0] || pbc[1] || pbc[2])) { eng->pbc_on = false; return UMX_OK; }
+  if (!cell || !pbc || !(pbc[0] || pbc[1] || pbc[2])) { eng->pbc_on = false; eng->n_cells = 0; return UMX_OK; }
   PeriodicHost ph;
   std::string why;
   if (!build_periodic(cell, pbc, eng->cutoff, &ph, &why)) return fail(eng, UMX_ERR_ARG, "umx_set_cell: " + why);   // (the engine keeps the cell it had)
@@ -116,45 +116,128 @@ int set_cell_impl(umx_engine* eng, const double* cell, const int* pbc) {
   std::memcpy(eng->cell, cell, sizeof(eng->cell));
   for (int k = 0; k < 3; ++k) eng->pbc[k] = pbc[k] != 0;
   eng->pbc_on = true;
+  eng->n_cells = 0;
   return UMX_OK;
 }
 
-// Start of an evaluation.  Open boundaries: nothing.  Periodic: the table follows the bound cutoff, the positions of all images are
-// wrapped into the scratch copy, and *d_pos is pointed at it.
+// ---- per-image cells (umx_set_cells) -----------------------------------------------------------------------------------------------
+// every cell through build_periodic for the bound cutoff; false + *why (which names the image): one of them is refused
+bool build_periodic_images(int n, const double* cells, const int pbc[3], double cutoff, std::vector<PeriodicHost>* out, std::string* why) {
+  out->resize(n);
+  for (int k = 0; k < n; ++k) {
+    std::string w;
+    if (!build_periodic(cells + (size_t)k * 9, pbc, cutoff, &(*out)[k], &w)) { *why = "image " + std::to_string(k) + ": " + w; return false; }
+  }
+  return true;
+}
+
+// put the images' structs and their tables, packed one behind the other, on the device
+int periodic_upload_images(umx_engine* eng, const std::vector<PeriodicHost>& ph) {
+  const long n = (long)ph.size();
+  long total = 0;
+  for (const PeriodicHost& h : ph) total += (long)h.table.size();
+  HIPCHK(eng, hipSetDevice(eng->dev));
+  HIPCHK(eng, hipStreamSynchronize(eng->stream));                     // no evaluation may still be reading the old tables
+  if (eng->ran_on_caller) HIPCHK(eng, hipEventSynchronize(eng->ev_done));
+  if (eng->cells_cap < n) CHK(grow(eng, eng->cells_cap, n, {}, {DevBuf(eng->d_cells, (size_t)n)}));
+  if (eng->shifts_pk_cap < total) CHK(grow(eng, eng->shifts_pk_cap, total, {}, {DevBuf(eng->d_shifts_pk, (size_t)total)}));
+  std::vector<Periodic> pers(n);
+  std::vector<float4> table;
+  table.reserve(total);
+  eng->cell_shifts.resize(n);
+  for (long k = 0; k < n; ++k) {
+    pers[k] = ph[k].per;
+    pers[k].shifts = eng->d_shifts_pk + table.size();
+    eng->cell_shifts[k] = ph[k].per.n_shifts;
+    table.insert(table.end(), ph[k].table.begin(), ph[k].table.end());
+  }
+  HIPCHK(eng, hipMemcpy(eng->d_shifts_pk, table.data(), table.size() * sizeof(float4), hipMemcpyHostToDevice));
+  HIPCHK(eng, hipMemcpy(eng->d_cells, pers.data(), pers.size() * sizeof(Periodic), hipMemcpyHostToDevice));
+  eng->per_cutoff = eng->cutoff;
+  return UMX_OK;
+}
+
+int set_cells_impl(umx_engine* eng, int n_images, const double* cells, const int* pbc) {
+  if (!cells || !pbc || !(pbc[0] || pbc[1] || pbc[2])) { eng->pbc_on = false; eng->n_cells = 0; return UMX_OK; }
+  if (n_images <= 0) return fail(eng, UMX_ERR_ARG, "umx_set_cells: n_images must be positive when cells are given");
+  std::vector<PeriodicHost> ph;
+  std::string why;
+  if (!build_periodic_images(n_images, cells, pbc, eng->cutoff, &ph, &why)) return fail(eng, UMX_ERR_ARG, "umx_set_cells: " + why);   // (the cells in force stay)
+  CHK(periodic_upload_images(eng, ph));
+  eng->cells.assign(cells, cells + (size_t)n_images * 9);
+  for (int k = 0; k < 3; ++k) eng->pbc[k] = pbc[k] != 0;
+  eng->pbc_on = true;
+  eng->n_cells = n_images;
+  return UMX_OK;
+}
+
+// Per-image cells bound for another number of images than the evaluation holds: refused before anything runs (`who`: the entry).
+int periodic_check_images(umx_engine* eng, long K, const char* who) {
+  if (!eng->pbc_on || eng->n_cells == 0 || K == eng->n_cells) return UMX_OK;
+  return fail(eng, UMX_ERR_ARG, std::string(who) + ": " + std::to_string(K) + " images, but umx_set_cells bound cells for " + std::to_string(eng->n_cells) +
+              " (cell k belongs to image k: bind one cell per image, or one cell for all with umx_set_cell)");
+}
+
+// Start of an evaluation.  Open boundaries: nothing.  Periodic: the table(s) follow the bound cutoff, the positions of all images are
+// wrapped into the scratch copy (every image into its own cell, if umx_set_cells bound them), and *d_pos is pointed at it.
 int periodic_prepare(umx_engine* eng, hipStream_t s, long K, const float** d_pos) {
   eng->last_shifts = 0;
   if (!eng->pbc_on) return UMX_OK;
-  if (eng->per_cutoff != eng->cutoff) {          // umx_set_system changed the cutoff since umx_set_cell
-    PeriodicHost ph;
+  const bool img = eng->n_cells > 0;
+  CHK(periodic_check_images(eng, K, "umx_energy_forces"));
+  if (eng->per_cutoff != eng->cutoff) {          // umx_set_system changed the cutoff since umx_set_cell / umx_set_cells
     std::string why;
-    if (!build_periodic(eng->cell, eng->pbc, eng->cutoff, &ph, &why)) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: the cell set by umx_set_cell and the bound cutoff: " + why);
-    CHK(periodic_upload(eng, ph));
+    if (img) {
+      std::vector<PeriodicHost> ph;
+      if (!build_periodic_images(eng->n_cells, eng->cells.data(), eng->pbc, eng->cutoff, &ph, &why))
+        return fail(eng, UMX_ERR_ARG, "umx_energy_forces: the cells set by umx_set_cells and the bound cutoff: " + why);
+      CHK(periodic_upload_images(eng, ph));
+    } else {
+      PeriodicHost ph;
+      if (!build_periodic(eng->cell, eng->pbc, eng->cutoff, &ph, &why)) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: the cell set by umx_set_cell and the bound cutoff: " + why);
+      CHK(periodic_upload(eng, ph));
+    }
   }
   // the rank key of the truncating fill carries translation index * n_atoms + source in its low 32 bits
-  if ((unsigned long long)eng->per.n_shifts * (unsigned long long)eng->natoms > 0xffffffffull)
-    return fail(eng, UMX_ERR_ARG, "umx_energy_forces: " + std::to_string(eng->per.n_shifts) + " lattice translations x " + std::to_string(eng->natoms) +
-                " atoms do not fit the 32-bit candidate index of the periodic graph");
+  int most = eng->per.n_shifts, most_at = -1;
+  if (img) {
+    most_at = (int)(std::max_element(eng->cell_shifts.begin(), eng->cell_shifts.end()) - eng->cell_shifts.begin());   // (the largest table decides for every image)
+    most = eng->cell_shifts[most_at];
+  }
+  if ((unsigned long long)most * (unsigned long long)eng->natoms > 0xffffffffull)
+    return fail(eng, UMX_ERR_ARG, "umx_energy_forces: " + (img ? "image " + std::to_string(most_at) + ": " : std::string()) + std::to_string(most) + " lattice translations x " +
+                std::to_string(eng->natoms) + " atoms do not fit the 32-bit candidate index of the periodic graph");
   const long nt = K * eng->natoms;
   if (eng->wrap_cap < nt) CHK(grow(eng, eng->wrap_cap, nt, {s}, {DevBuf(eng->d_wrap, (size_t)nt * 3)}));
-  hipLaunchKernelGGL(k_wrap_cell, dim3(nblk(nt, 256)), dim3(256), 0, s, *d_pos, eng->d_wrap, nt, eng->per);
+  if (img) hipLaunchKernelGGL(k_wrap_cell<true>, dim3(nblk(nt, 256)), dim3(256), 0, s, *d_pos, eng->d_wrap, nt, eng->natoms, PeriodicImages{eng->d_cells, 0});
+  else hipLaunchKernelGGL(k_wrap_cell<false>, dim3(nblk(nt, 256)), dim3(256), 0, s, *d_pos, eng->d_wrap, nt, eng->natoms, eng->per);
   HIPCHK(eng, hipGetLastError());
   *d_pos = eng->d_wrap;
-  eng->last_shifts = eng->per.n_shifts;
+  eng->last_shifts = most;
   return UMX_OK;
 }
 
-// ---- the two graph kernels, open-boundary or periodic instantiation ------------------------------------------------------------
-void launch_graph_count(umx_engine* eng, hipStream_t s, const float* d_pos, long nt, int* deg, int* cand, long lo, long hi) {
+// ---- the two graph kernels: open-boundary, one-cell or per-image instantiation ---------------------------------------------------
+// img0: the index within the call of the image d_pos starts at (per-image cells: image img0 + node / natoms reads cell img0 + node / natoms)
+void launch_graph_count(umx_engine* eng, hipStream_t s, const float* d_pos, long nt, int* deg, int* cand, long lo, long hi, long img0) {
   const float rc2 = eng->cutoff * eng->cutoff;
-  if (eng->pbc_on) hipLaunchKernelGGL(k_graph_count<true>, dim3(nblk(nt, 4)), dim3(256), 0, s, d_pos, eng->natoms, nt, rc2, eng->max_neigh, deg, cand, lo, hi, eng->d_flags, eng->per);
-  else hipLaunchKernelGGL(k_graph_count<false>, dim3(nblk(nt, 4)), dim3(256), 0, s, d_pos, eng->natoms, nt, rc2, eng->max_neigh, deg, cand, lo, hi, eng->d_flags, Periodic());
+  const dim3 grid(nblk(nt, 4)), block(256);
+  const int N = eng->natoms, mn = eng->max_neigh;
+  if (eng->pbc_on && eng->n_cells > 0)
+    hipLaunchKernelGGL((k_graph_count<true, true>), grid, block, 0, s, d_pos, N, nt, rc2, mn, deg, cand, lo, hi, eng->d_flags, PeriodicImages{eng->d_cells, (int)img0});
+  else if (eng->pbc_on) hipLaunchKernelGGL(k_graph_count<true>, grid, block, 0, s, d_pos, N, nt, rc2, mn, deg, cand, lo, hi, eng->d_flags, eng->per);
+  else hipLaunchKernelGGL(k_graph_count<false>, grid, block, 0, s, d_pos, N, nt, rc2, mn, deg, cand, lo, hi, eng->d_flags, Periodic());
 }
 void launch_graph_fill(umx_engine* eng, hipStream_t s, bool trunc, const float* d_pos, long nn, const int* cand, const int* row_ptr, int* esrc, int* edst,
-                       float* evec, long lo, long hi) {
+                       float* evec, long lo, long hi, long img0) {
   const float rc2 = eng->cutoff * eng->cutoff;
   const dim3 grid(nblk(nn, 4)), block(256);
   const int N = eng->natoms, mn = eng->max_neigh;
-  if (eng->pbc_on) {
+  if (eng->pbc_on && eng->n_cells > 0) {
+    const PeriodicImages pi{eng->d_cells, (int)img0};
+    if (trunc) hipLaunchKernelGGL((k_graph_fill<true, true, true>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, pi);
+    else hipLaunchKernelGGL((k_graph_fill<false, true, true>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, pi);
+  } else if (eng->pbc_on) {
     if (trunc) hipLaunchKernelGGL((k_graph_fill<true, true>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, eng->per);
     else hipLaunchKernelGGL((k_graph_fill<false, true>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, eng->per);
   } else {

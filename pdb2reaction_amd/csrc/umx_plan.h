@@ -60,7 +60,9 @@ int radial_bwd(umx_engine* eng, const WS& w, const RadialW& r, int slot, long ne
 
 // ---- one chunk: nn nodes (= images * natoms), edges counted on the fly --------------------------
 // vir.out != nullptr: the chunk's final segment also takes the virial of its images (umx_virial.h)
-void plan_chunk(umx_engine* eng, WS& w, const float* d_pos, const int* d_deg, const int* d_cand, long nimg, long ne, double* d_energy,
+// img0: the index within the call of the chunk's first image (d_pos, d_deg, d_cand and the outputs start there; per-image cells are
+// indexed by it)
+void plan_chunk(umx_engine* eng, WS& w, const float* d_pos, const int* d_deg, const int* d_cand, long img0, long nimg, long ne, double* d_energy,
                 float* d_forces, Plan& P, const VirialOut vir = VirialOut()) {
   const int N = eng->natoms;
   const long nn = nimg * N;
@@ -77,7 +79,7 @@ void plan_chunk(umx_engine* eng, WS& w, const float* d_pos, const int* d_deg, co
   P.stream([=, &w]() -> int {
     hipStream_t s = eng->stream;
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, d_deg, nn, w.row_ptr, w.stats);
-    launch_graph_fill(eng, s, may_trunc, d_pos, nn, d_cand, w.row_ptr, w.esrc, w.edst, w.evec, g_lo, g_hi);
+    launch_graph_fill(eng, s, may_trunc, d_pos, nn, d_cand, w.row_ptr, w.esrc, w.edst, w.evec, g_lo, g_hi, img0);
     HIPCHK(eng, hipMemsetAsync(w.out_cur, 0, (nn + 1) * sizeof(int), s));
     if (ne > 0) hipLaunchKernelGGL(k_out_count, dim3(nblk(ne, 256)), B256, 0, s, w.esrc, ne, w.out_cur);
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, w.out_cur, nn, w.out_ptr, w.stats + 2);
@@ -547,7 +549,7 @@ int degree_pass(umx_engine* eng, hipStream_t s, long K, const float* d_pos, Imag
   if (eng->deg_all_cap < nt) CHK(grow(eng, eng->deg_all_cap, nt, {s}, {DevBuf(eng->d_deg_all, nt), DevBuf(eng->d_cand_all, nt)}));
   if (eng->img_edges_cap < K + 1) CHK(grow(eng, eng->img_edges_cap, K + 1, {s}, {DevBuf(eng->d_img_edges, K + 1)}));
   HIPCHK(eng, hipMemsetAsync(eng->d_img_edges + K, 0, sizeof(int), s));
-  launch_graph_count(eng, s, d_pos, nt, eng->d_deg_all, eng->d_cand_all, eng->gp ? eng->gp_lo : 0L, eng->gp ? eng->gp_hi : nt);
+  launch_graph_count(eng, s, d_pos, nt, eng->d_deg_all, eng->d_cand_all, eng->gp ? eng->gp_lo : 0L, eng->gp ? eng->gp_hi : nt, 0);
   hipLaunchKernelGGL(k_image_edges, dim3((unsigned)K), dim3(256), 0, s, eng->d_deg_all, N, eng->d_img_edges, eng->d_img_edges + K);
   CHK(read_degree_pass(eng, s, eng->d_img_edges, K, ie.per_image, false));
   eng->last_maxdeg = ie.per_image[K];
@@ -564,7 +566,8 @@ int degree_pass(umx_engine* eng, hipStream_t s, long K, const float* d_pos, Imag
 // TRANSIENT region (the producer -> GEMM operands are dead at every exchange point), and the all-reduce of an exchange point is a local
 // sum.  Memory per directed edge drops from ~120 KB to ~72 KB + 48 KB / P, i.e. a single image of up to ~1.5x the atoms fits the same
 // HBM; node-level work (< 3 %) is done P times.  Used automatically when one image exceeds the workspace budget.
-int eval_partitioned(umx_engine* eng, hipStream_t s, const float* d_pos, double* d_energy, float* d_forces, double* d_virial, int P, size_t budget,
+// img: the image's index within the call (d_pos and the outputs are the image's own)
+int eval_partitioned(umx_engine* eng, hipStream_t s, long img, const float* d_pos, double* d_energy, float* d_forces, double* d_virial, int P, size_t budget,
                      int64_t* edges_out, int* maxdeg_out) {
   const int N = eng->natoms;
   if (P < 2 || P > 16) return fail(eng, UMX_ERR_ARG, "eval_partitioned: 2..16 partitions");
@@ -576,7 +579,7 @@ int eval_partitioned(umx_engine* eng, hipStream_t s, const float* d_pos, double*
   for (int p = 0; p < P; ++p) {
     lo[p] = (long)N * p / P; hi[p] = (long)N * (p + 1) / P;
     int* deg = eng->d_part_deg + (size_t)(2 * p) * N;
-    launch_graph_count(eng, s, d_pos, (long)N, deg, deg + N, lo[p], hi[p]);
+    launch_graph_count(eng, s, d_pos, (long)N, deg, deg + N, lo[p], hi[p], img);
     hipLaunchKernelGGL(k_image_edges, dim3(1), dim3(256), 0, s, deg, N, d_cnt + p, d_cnt + P);
   }
   std::vector<int> cnt;
@@ -602,7 +605,7 @@ int eval_partitioned(umx_engine* eng, hipStream_t s, const float* d_pos, double*
     // are shared, the partitions run one after another on s
     VirialOut vir;
     if (d_virial && d_forces) { vir.out = wpart + (size_t)p * 9; vir.part = eng->d_vir_part; vir.slabs = eng->vir_slabs; }
-    plan_chunk(eng, ws[p], d_pos, deg, deg + N, 1, cnt[p], d_energy, d_forces ? eng->d_part_f + (size_t)p * N * 3 : nullptr, plans[p], vir);
+    plan_chunk(eng, ws[p], d_pos, deg, deg + N, img, 1, cnt[p], d_energy, d_forces ? eng->d_part_f + (size_t)p * N * 3 : nullptr, plans[p], vir);
   }
   eng->gp = gp_keep; eng->gp_lo = lo_keep; eng->gp_hi = hi_keep;
   std::vector<size_t> at(P, 0);
@@ -647,7 +650,7 @@ int eval_images_partitioned(umx_engine* eng, hipStream_t s, long K, const float*
     int stp = UMX_ERR_CAPACITY;
     for (int parts = eng->force_parts >= 2 ? eng->force_parts : 2; parts <= 16 && stp == UMX_ERR_CAPACITY; parts = eng->force_parts >= 2 ? 17 : parts + 1) {
       int64_t e1 = 0; int m1 = 0;
-      stp = eval_partitioned(eng, s, d_pos + k * N * 3, d_energy + k, d_forces ? d_forces + k * N * 3 : nullptr,
+      stp = eval_partitioned(eng, s, k, d_pos + k * N * 3, d_energy + k, d_forces ? d_forces + k * N * 3 : nullptr,
                              eng->vir_out ? eng->vir_out + k * 9 : nullptr, parts, budget, &e1, &m1);
       if (stp == UMX_OK) { etot += e1; mdeg = std::max(mdeg, m1); eng->last_parts = parts; }
     }
@@ -794,7 +797,7 @@ int run_chunks(umx_engine* eng, hipStream_t s, int lanes, const ImageEdges& ie, 
     for (long k = k0; k < k1; ++k) e += ie.per_image[k];
     VirialOut vir;       // the partials' slots follow the image's position in the call: the two lanes never share one
     if (eng->vir_out && d_forces) { vir.out = eng->vir_out + k0 * 9; vir.part = eng->d_vir_part + k0 * eng->vir_slabs * 9; vir.slabs = eng->vir_slabs; }
-    plan_chunk(eng, wl[lane], d_pos + k0 * N * 3, eng->d_deg_all + k0 * N, eng->d_cand_all + k0 * N, k1 - k0, e, d_energy + k0,
+    plan_chunk(eng, wl[lane], d_pos + k0 * N * 3, eng->d_deg_all + k0 * N, eng->d_cand_all + k0 * N, k0, k1 - k0, e, d_energy + k0,
                d_forces ? d_forces + k0 * N * 3 : nullptr, P, vir);
   };
   if (lanes == 2) {          // chunks in pairs, one per lane, matrix segments alternating between the lanes (run_plans_alternating)
@@ -864,7 +867,7 @@ int evaluate_planned(umx_engine* eng, hipStream_t s, long K, const float* d_pos,
     // every exchange point.  The workspace view must outlive this call (the closures hold a reference to it).
     eng->gp_ws = std::make_unique<WS>(wl[0]);
     eng->gp_plan = std::make_unique<Plan>();
-    plan_chunk(eng, *eng->gp_ws, d_pos, eng->d_deg_all, eng->d_cand_all, 1, ie.per_image[0], d_energy, d_forces, *eng->gp_plan);
+    plan_chunk(eng, *eng->gp_ws, d_pos, eng->d_deg_all, eng->d_cand_all, 0, 1, ie.per_image[0], d_energy, d_forces, *eng->gp_plan);
     eng->gp_at = 0; eng->gp_stream = s;
     return UMX_OK;
   }

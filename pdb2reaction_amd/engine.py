@@ -86,6 +86,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "umx_synchronize": ([vp], i32),
         "umx_last_graph_stats": ([vp, i64p, C.POINTER(C.c_int32)], i32),
         "umx_set_cell": ([vp, dp, C.POINTER(C.c_int)], i32),
+        "umx_set_cells": ([vp, C.c_int, dp, C.POINTER(C.c_int)], i32),
         "umx_last_graph_shifts": ([vp], i32),
         "umx_last_partitions": ([vp], i32),
         "umx_last_lanes": ([vp], i32),
@@ -133,7 +134,7 @@ EXPORTED_SYMBOLS = (
     "umx_set_workspace_limit", "umx_energy_forces", "umx_energy_forces_dev", "umx_gp_begin", "umx_gp_step", "umx_peer_sum", "umx_synchronize",
     "umx_last_graph_stats", "umx_last_partitions", "umx_last_lanes", "umx_reserve_images", "umx_workspace_stats", "umx_profile_enable", "umx_profile_read", "umx_bond_changes", "umx_debug_fetch", "umx_debug_keep",
     "umx_set_expert_coefficients", "umx_expert_count", "umx_set_recompute", "umx_last_recompute", "umx_workspace_bytes",
-    "umx_set_cell", "umx_last_graph_shifts", "umx_energy_forces_virial", "umx_energy_forces_virial_dev",
+    "umx_set_cell", "umx_set_cells", "umx_last_graph_shifts", "umx_energy_forces_virial", "umx_energy_forces_virial_dev",
 )
 
 
@@ -148,11 +149,11 @@ def workspace_bytes(n_nodes: int, n_edges: int, parts: int = 0, recompute: int =
     return n
 
 
-def voigt_stress(virial: np.ndarray, volume: float) -> np.ndarray:
+def voigt_stress(virial: np.ndarray, volume) -> np.ndarray:
     """(..., 3, 3) strain derivative W in eV and a volume in A^3 -> (..., 6) stress in eV/A^3, Voigt order xx, yy, zz, yz, xz, xy:
-    the symmetric part of W over the volume."""
+    the symmetric part of W over the volume.  ``volume``: one number, or one per leading index of W (per-image cells)."""
     w = np.asarray(virial, dtype=np.float64)
-    sym = 0.5 * (w + np.swapaxes(w, -1, -2)) / float(volume)
+    sym = 0.5 * (w + np.swapaxes(w, -1, -2)) / np.asarray(volume, dtype=np.float64)[..., None, None]
     return np.stack([sym[..., 0, 0], sym[..., 1, 1], sym[..., 2, 2], sym[..., 1, 2], sym[..., 0, 2], sym[..., 0, 1]], axis=-1)
 
 
@@ -197,6 +198,7 @@ class Engine:
         self.expert_coefficients = None # the MoLE coefficients alpha (n_experts,) of the last set_system on an expert-form blob
         self._routing = None            # expert form: the blob's tensors without the stacks (the routing network reads them)
         self.dataset_list = tuple(W.DATASET_LIST)      # order of the rows of the loaded blob's dataset_embedding.weight (load_weights)
+        self._cells = None              # (cells (K,3,3) float64, pbc flags (3,)) set_cells accepted last; it and _cell exclude each other
         self._cell = None               # (cell (3,3) float64, pbc flags (3,)) the engine accepted last (set_cell), None for open boundaries
         if precision is not None:
             self._chk(self.lib.umx_set_precision(self._h, precision.encode()), "umx_set_precision")
@@ -283,12 +285,32 @@ class Engine:
         flags = None if pbc is None else np.broadcast_to(np.asarray(pbc, dtype=bool), (3,))
         if cell is None or flags is None or not flags.any():
             self._chk(self.lib.umx_set_cell(self._h, None, None), "umx_set_cell")
-            self._cell = None
+            self._cell = self._cells = None
             return
         c = np.ascontiguousarray(np.asarray(cell, dtype=np.float64).reshape(3, 3))
         f = np.ascontiguousarray(flags, dtype=np.intc)
         self._chk(self.lib.umx_set_cell(self._h, c.ctypes.data_as(C.POINTER(C.c_double)), f.ctypes.data_as(C.POINTER(C.c_int))), "umx_set_cell")
-        self._cell = (c.copy(), tuple(bool(x) for x in flags))
+        self._cell, self._cells = (c.copy(), tuple(bool(x) for x in flags)), None
+
+    def set_cells(self, cells=None, pbc=None):
+        """Per-image cells (``umx_set_cells``): ``cells`` (K,3,3), cell k for image k of the evaluations that follow, ``pbc`` as for
+        ``set_cell`` and shared by all images.  ``None`` for either, or no flag set, restores open boundaries.  The cells persist across
+        ``set_system`` until ``set_cells`` or ``set_cell`` is called again (each replaces the other); an evaluation of another number of
+        images than K raises ``UmxError``.  If any cell is refused (see ``set_cell``) the call raises ``UmxError`` naming the image and
+        what was in force before stays in force.  The accepted cells are remembered: ``energy_forces_stress`` divides image k by the
+        volume of cell k."""
+        flags = None if pbc is None else np.broadcast_to(np.asarray(pbc, dtype=bool), (3,))
+        if cells is None or flags is None or not flags.any():
+            self._chk(self.lib.umx_set_cells(self._h, 0, None, None), "umx_set_cells")
+            self._cell = self._cells = None
+            return
+        c = np.ascontiguousarray(np.asarray(cells, dtype=np.float64))
+        if c.ndim != 3 or c.shape[1:] != (3, 3) or c.shape[0] == 0:
+            raise ValueError(f"cells must be (K,3,3) with K >= 1, got {c.shape}")
+        f = np.ascontiguousarray(flags, dtype=np.intc)
+        self._chk(self.lib.umx_set_cells(self._h, c.shape[0], c.ctypes.data_as(C.POINTER(C.c_double)), f.ctypes.data_as(C.POINTER(C.c_int))),
+                  "umx_set_cells")
+        self._cell, self._cells = None, (c.copy(), tuple(bool(x) for x in flags))
 
     def last_graph_shifts(self) -> int:
         """Lattice translations the most recent evaluation searched (``umx_last_graph_shifts``); 0 = open boundaries."""
@@ -352,12 +374,23 @@ class Engine:
     def energy_forces_stress(self, pos_ang: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """pos_ang: (K,N,3) or (N,3) Angstrom -> (E [K] eV, F [K,N,3] eV/A, stress [K,6] eV/A^3 in Voigt order xx, yy, zz, yz, xz, xy).
 
-        ``stress = (W + W^T) / 2 / |det cell|`` with W of ``energy_forces_virial`` and the cell ``set_cell`` accepted last; ASE's sign
-        convention (dE/d eps / V: tensile positive).  ``ValueError`` unless all three axes are periodic -- a slab or a cluster has no
-        volume; ``energy_forces_virial`` serves those."""
-        vol = self.cell_volume()
+        ``stress = (W + W^T) / 2 / |det cell|`` with W of ``energy_forces_virial`` and the cell ``set_cell`` accepted last -- with per-image
+        cells (``set_cells``), image k over the volume of cell k; ASE's sign convention (dE/d eps / V: tensile positive).  ``ValueError``
+        unless all three axes are periodic -- a slab or a cluster has no volume; ``energy_forces_virial`` serves those."""
+        vol = self.cell_volumes() if getattr(self, "_cells", None) is not None else self.cell_volume()
         e, f, w = self.energy_forces_virial(pos_ang)
         return e, f, voigt_stress(w, vol)
+
+    def cell_volumes(self) -> np.ndarray:
+        """[K] float64: |det cell_k| of the per-image cells in force (``set_cells``); with one shared cell (``set_cell``) that volume, [1].
+        ``ValueError`` unless all three axes are periodic."""
+        cells = getattr(self, "_cells", None)
+        if cells is None:
+            return np.array([self.cell_volume()], dtype=np.float64)
+        if not all(cells[1]):
+            raise ValueError("stress needs cells that are periodic along all three axes (set_cells): the volume is otherwise undefined; "
+                             "energy_forces_virial gives the strain derivative of a slab or a cluster")
+        return np.abs(np.linalg.det(cells[0])).astype(np.float64)
 
     def cell_volume(self) -> float:
         """|det cell| of the cell in force; ``ValueError`` unless all three axes are periodic."""

@@ -422,6 +422,8 @@ class LocalEnginePool:
         self.last_route = None                  # "batch" | "graph-parallel" | "single"
         self.last_blocks: List[Tuple[int, int]] = []
         self.last_all = None                    # graph-parallel route: [(E, F)] of EVERY engine (they must agree in every bit)
+        self._cells = None                      # per-image cells (``set_cells``): (cells (K,3,3) float64, pbc flags (3,)), else None
+        self._cells_on = [None] * len(self.engines)   # what engine r has bound of them: its block (lo, hi), or "single" for cells[0] alone
         self.recompute = None                   # what ``create`` / ``set_recompute`` gave every engine (None: the engines' own setting)
         if len(set(self.devices)) < len(self.devices):
             free = free_bytes or (lambda d: torch.cuda.mem_get_info(d)[0])
@@ -480,6 +482,47 @@ class LocalEnginePool:
         """``Engine.set_cell`` on every engine: batches dealt over the pool and the graph-parallel single image see the same cell."""
         for eng in self.engines:
             eng.set_cell(cell, pbc)
+        self._cells, self._cells_on = None, [None] * len(self.engines)
+
+    def set_cells(self, cells=None, pbc=None) -> None:
+        """Per-image cells (``Engine.set_cells``) for the batches that follow: cell k belongs to image k.  The pool keeps them and gives
+        every engine the cells of its contiguous block right before that engine evaluates (once, for as long as the blocks stay the
+        same); a single geometry binds ``cells[0]`` with ``set_cell`` on every engine.  ``None`` for either argument, or no flag set:
+        open boundaries on every engine."""
+        flags = None if pbc is None else np.broadcast_to(np.asarray(pbc, dtype=bool), (3,))
+        if cells is None or flags is None or not flags.any():
+            self.set_cell(None, None)
+            return
+        c = np.array(cells, dtype=np.float64)
+        if c.ndim != 3 or c.shape[1:] != (3, 3) or c.shape[0] == 0:
+            raise ValueError(f"cells must be (K,3,3) with K >= 1, got {c.shape}")
+        self._cells, self._cells_on = (c, tuple(bool(x) for x in flags)), [None] * len(self.engines)
+
+    def _bind_cells(self, k: int, blocks) -> None:
+        """Per-image cells: make every engine hold what it needs for a call of ``k`` images dealt in ``blocks`` (None: one geometry)."""
+        if self._cells is None:
+            return
+        cells, flags = self._cells
+        if len(cells) != k:
+            raise ValueError(f"{k} images, but set_cells bound cells for {len(cells)} (cell k belongs to image k)")
+        for r, eng in enumerate(self.engines):
+            want = "single" if blocks is None else tuple(blocks[r])
+            if want == self._cells_on[r] or (blocks is not None and want[1] <= want[0]):
+                continue
+            self._cells_on[r] = None
+            if blocks is None:
+                eng.set_cell(cells[0], flags)
+            else:
+                eng.set_cells(cells[want[0]: want[1]], flags)
+            self._cells_on[r] = want
+
+    def cell_volumes(self) -> np.ndarray:
+        """[K] |det cell_k| of the per-image cells (``set_cells``), else engine 0's one volume; ``ValueError`` unless fully periodic."""
+        if self._cells is None:
+            return np.array([self.engines[0].cell_volume()], dtype=np.float64)
+        if not all(self._cells[1]):
+            raise ValueError("stress needs cells that are periodic along all three axes (set_cells): the volume is otherwise undefined")
+        return np.abs(np.linalg.det(self._cells[0])).astype(np.float64)
 
     def last_graph_shifts(self) -> int:
         return int(self.engines[0].last_graph_shifts())
@@ -542,6 +585,7 @@ class LocalEnginePool:
         blocks = [shard_bounds(k, g, r) for r in range(g)]
         busy = [r for r in range(g) if blocks[r][1] > blocks[r][0]]
         self.last_route, self.last_blocks = "batch", blocks
+        self._bind_cells(k, blocks)
         for attempt in range(2):
             was_wide = [bool(getattr(eng, "widened", False)) for eng in self.engines]
             res = self._run_all(lambda r: call(self.engines[r], p[blocks[r][0]: blocks[r][1]]), busy)
@@ -558,6 +602,7 @@ class LocalEnginePool:
         """pos_ang: (K,N,3) or (N,3) Angstrom -> (E [K] eV float64, F [K,N,3] eV/A float32 | None): ``Engine.energy_forces`` over the pool."""
         p = self._images(pos_ang)
         if p.shape[0] == 1:
+            self._bind_cells(1, None)
             if self.gp and len(self.engines) > 1 and self.recompute != 2:
                 return self._graph_parallel(p[0], forces)
             self.last_route, self.last_blocks = "single", [(0, 1)]
@@ -574,6 +619,7 @@ class LocalEnginePool:
         virial (``umx_gp_begin`` / ``umx_gp_step`` produce none)."""
         p = self._images(pos_ang)
         if p.shape[0] == 1:
+            self._bind_cells(1, None)
             self.last_route, self.last_blocks = "single", [(0, 1)]
             return self.engines[0].energy_forces_virial(p)
         res = self._deal(p, lambda eng, block: eng.energy_forces_virial(block))
@@ -581,10 +627,11 @@ class LocalEnginePool:
 
     def energy_forces_stress(self, pos_ang) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """``Engine.energy_forces_stress`` over the pool: (E [K], F [K,N,3], stress [K,6] eV/A^3, Voigt xx, yy, zz, yz, xz, xy), routed
-        as ``energy_forces_virial``; ``ValueError`` unless the cell (``set_cell``) is periodic along all three axes."""
+        as ``energy_forces_virial``; ``ValueError`` unless the cell (``set_cell``) is periodic along all three axes.  With per-image
+        cells (``set_cells``) image k is divided by the volume of cell k."""
         from .engine import voigt_stress
 
-        vol = self.engines[0].cell_volume()
+        vol = self.engines[0].cell_volume() if self._cells is None else self.cell_volumes()
         e, f, w = self.energy_forces_virial(pos_ang)
         return e, f, voigt_stress(w, vol)
 
