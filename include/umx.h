@@ -199,7 +199,7 @@ int umx_last_graph_shifts(const umx_engine* eng);
  *     cutoff since, the next evaluation rebuilds every image's table from the stored cells; a cell that no longer fits names its image.
  *   - cost: one stream synchronisation and two uploads per call (not per image); the graph kernels read the cell of their image
  *     through scalar loads instead of the kernel arguments.
- * Not provided: per-image pbc flags, device-resident cells, variable-cell drivers of our own, a virial from the graph-parallel entries.
+ * Not provided: per-image pbc flags, device-resident cells, variable-cell drivers of our own.
  * No reference counterpart (the reference never sets a cell, uma_pysis.py:292-327).                                                 */
 int umx_set_cells(umx_engine* eng, int n_images, const double* cells, const int pbc[3]);
 
@@ -250,7 +250,8 @@ int umx_energy_forces_dev(umx_engine* eng, int n_images, const float* d_pos_ang,
  *   - cost: two small launches behind the force kernels, 32 B read per directed edge; no arithmetic of the model path changes, energies
  *     and forces are bitwise those of umx_energy_forces.
  * With per-image cells (umx_set_cells) image k's W belongs to cell k.
- * Not provided: a virial from the graph-parallel entries (umx_gp_begin / umx_gp_step are unchanged), variable-cell drivers.  No reference counterpart (the reference never sets a cell, uma_pysis.py:292-327); fairchem's own stress has not been
+ * One image split over several engines: umx_gp_begin_virial below gives every rank its share of W.
+ * Not provided: variable-cell drivers.  No reference counterpart (the reference never sets a cell, uma_pysis.py:292-327); fairchem's own stress has not been
  * compared [3P-UNVERIFIED].                                                                                                        */
 int umx_energy_forces_virial(umx_engine* eng, int n_images, const float* pos_ang, double* energy_ev,
                              float* forces_ev_ang, double* virial_ev);
@@ -272,6 +273,29 @@ int umx_energy_forces_virial_dev(umx_engine* eng, int n_images, const float* d_p
 int umx_gp_begin(umx_engine* eng, const float* d_pos_ang, int node_lo, int node_hi, double* d_energy_ev,
                  float* d_forces_ev_ang, void* hip_stream);
 int umx_gp_step(umx_engine* eng, float** d_buf, size_t* count, int* done);
+
+/* STRAIN DERIVATIVE OF A GRAPH-PARALLEL EVALUATION (additive to ABI v10).  umx_gp_begin with one more output, d_virial_ev: nine float64
+ * on the device.  Once umx_gp_step has reported *done (and the stream has got there) it holds THIS RANK'S PARTIAL of W,
+ *     W_r[3 a + b] = rmsd * sum over the directed edges e whose TARGET lies in [node_lo, node_hi) of  vec_e,a * (dE_model / dvec_e)_b ,
+ * row-major, float64 products and sums, sign and meaning as umx_energy_forces_virial: not symmetrised, not divided by a volume.  Every
+ * directed edge of the image -- self-image edges and repeated pairs included -- is built by exactly one rank, so
+ *     W = W_0 + W_1 + ... + W_(R-1) .
+ * THE SUM OVER THE RANKS IS THE CALLER'S JOB, and it must be taken IN RANK ORDER (float64 addition does not associate): then every rank
+ * that adds the same nine-double partials in that order holds the same bits, and a run repeats bit for bit.  Python:
+ * parallel.GraphParallelEvaluator(virial=True) gathers the partials once and adds them in rank order on every rank;
+ * parallel.LocalEnginePool adds them in engine order on the host.
+ *   - d_virial_ev == NULL is exactly umx_gp_begin: no further kernel, launch or buffer.  umx_gp_begin itself is unchanged.
+ *   - the two reduction launches of umx_energy_forces_virial sit behind the edge-force kernel in the segment in front of the force
+ *     exchange.  The partial needs no exchange point of its own: umx_gp_step reports the same float32 buffers, in number and size.
+ *   - a rank without edges (node_lo == node_hi, or isolated targets) writes nine zeros and reads no edge buffer.
+ *   - energies and forces are bitwise those of umx_gp_begin with the same ranks, ranges and precision mode.
+ *   - refused as umx_gp_begin refuses: recompute mode 2, more than one bound per-image cell.  A rank's plan is always in one piece
+ *     (the graph-parallel entries never fall back to target-node partitions on the rank).
+ *   - the partial slots are sized from the rank's own edge count.
+ * Against the one-engine W the sum differs as the graph-parallel forces do (float32 summation order of the exchanged node sums).  More
+ * than one physical device has never run (see umx_peer_sum): ranks on one device show the arithmetic and the call sequence only.     */
+int umx_gp_begin_virial(umx_engine* eng, const float* d_pos_ang, int node_lo, int node_hi, double* d_energy_ev,
+                        float* d_forces_ev_ang, double* d_virial_ev, void* hip_stream);
 
 /* In-process exchange for graph-parallel participants that live in ONE process (parallel.LocalEnginePool: G engines, one host thread;
  * no reference counterpart -- the reference's workers exchange through Ray / torch.distributed, uma_pysis.py:228-242).  Sums the

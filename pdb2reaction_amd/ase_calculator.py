@@ -82,21 +82,27 @@ class UMXCalculator(_AseBase):
     the unstrained geometry held fixed.  An image that is not fully periodic has no volume: energy and forces as before, a request
     for ``"stress"`` raises ``PropertyNotImplementedError`` (``NotImplementedError`` where ASE is absent) -- as does any request for
     it with ``stress=False``.  A single image on a pool of
-    engines (``workers > 1``) is evaluated on engine 0 alone when the stress is on, because the graph-parallel path has none."""
+    engines (``workers > 1``) is evaluated on engine 0 alone when the stress is on, unless ``gp_stress=True``: then it goes graph-parallel
+    over the whole pool (``LocalEnginePool.energy_forces_stress(graph_parallel=True)``), every engine adding its share of the strain
+    derivative -- for a cell too large for one GPU."""
 
     implemented_properties = ["energy", "forces"]
 
     def __init__(self, model: str = "uma-s-1p1", task_name: str = "omol", device: str = "auto", charge: int = 0, spin: int = 1,
-                 radius: Optional[float] = None, max_neigh: Optional[int] = None, workers: int = 1, stress: bool = False, **kwargs):
+                 radius: Optional[float] = None, max_neigh: Optional[int] = None, workers: int = 1, stress: bool = False, gp_stress: bool = False,
+                 **kwargs):
         """workers > 1 (outside a torch.distributed process group): that many engines in this process when there are that many
         devices (``UMX_LOCAL_DEVICES`` names them), as in ``uma_pysis.UMAcore`` -- ``calculate_images`` deals its images over them,
-        a single image is evaluated graph-parallel (``parallel.LocalEnginePool``); ``local_devices`` lists the ordinals in use."""
+        a single image is evaluated graph-parallel (``parallel.LocalEnginePool``); ``local_devices`` lists the ordinals in use.
+        gp_stress: with ``stress=True`` and such a pool, single-image evaluations take the pool's graph-parallel virial instead of
+        engine 0 alone (default off: engine 0, the single-engine stress bit for bit); without a pool it changes nothing."""
         # not an ASE keyword: recompute plans (0 | 1 | 2; None = UMX_RECOMPUTE), as in ``uma_pysis`` (Engine.set_recompute)
         self.recompute = kwargs.pop("recompute", None)
         if self.recompute not in (None, 0, 1, 2):
             raise ValueError(f"recompute must be 0, 1 or 2, got {self.recompute!r}")
         super().__init__(**kwargs)
         self.stress = bool(stress)
+        self.gp_stress = bool(gp_stress)
         if self.stress:
             self.implemented_properties = ["energy", "forces", "stress"]      # on the instance: the class attribute stays as it is
         self.workers = max(int(workers or 1), 1)
@@ -182,12 +188,16 @@ class UMXCalculator(_AseBase):
             self.results = dict(self._last[2])
             return
         if with_stress:
-            e, f, sv = eng.energy_forces_stress(pos[None])
+            e, f, sv = eng.energy_forces_stress(pos[None], **self._stress_kw())
             self.results = {"energy": float(e[0]), "forces": np.asarray(f[0], dtype=np.float64), "stress": np.asarray(sv[0], dtype=np.float64)}
         else:
             e, f = eng.energy_forces(pos[None], forces=True)
             self.results = {"energy": float(e[0]), "forces": np.asarray(f[0], dtype=np.float64)}
         self._last = (self._bound, pos, dict(self.results))
+
+    def _stress_kw(self) -> dict:
+        """What ``energy_forces_stress`` is called with: the graph-parallel opt-in when this calculator runs a pool of engines."""
+        return {"graph_parallel": True} if self.gp_stress and len(self.local_devices or []) > 1 else {}
 
     def _fully_periodic(self) -> bool:
         """The image bound last has a cell and all three pbc flags set."""
@@ -228,7 +238,7 @@ class UMXCalculator(_AseBase):
         if stress:
             if not self._fully_periodic():
                 raise PropertyNotImplementedError("stress: the images are not periodic along all three axes, so there is no volume to refer a stress to")
-            e, f, sv = eng.energy_forces_stress(pos)
+            e, f, sv = eng.energy_forces_stress(pos, **self._stress_kw())
             return e, np.asarray(f, dtype=np.float64), np.asarray(sv, dtype=np.float64)
         e, f = eng.energy_forces(pos, forces=True)
         return e, np.asarray(f, dtype=np.float64)

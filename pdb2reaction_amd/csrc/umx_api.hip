@@ -239,6 +239,11 @@ int umx_energy_forces_virial_dev(umx_engine* eng, int n_images, const float* d_p
 }
 
 int umx_gp_begin(umx_engine* eng, const float* d_pos, int node_lo, int node_hi, double* d_energy, float* d_forces, void* hip_stream) {
+  return umx_gp_begin_virial(eng, d_pos, node_lo, node_hi, d_energy, d_forces, nullptr, hip_stream);
+}
+
+// d_virial: this rank's share of W (nine float64), or nullptr -- then the plan is umx_gp_begin's, launch for launch
+int umx_gp_begin_virial(umx_engine* eng, const float* d_pos, int node_lo, int node_hi, double* d_energy, float* d_forces, double* d_virial, void* hip_stream) {
   if (!eng) return UMX_ERR_ARG;
   if (eng->need_merge()) return fail(eng, UMX_ERR_ARG, "umx_gp_begin: " NOT_MERGED);
   if (!eng->have_system) return fail(eng, UMX_ERR_ARG, "umx_gp_begin: bind a system first (umx_set_system)");
@@ -253,7 +258,7 @@ int umx_gp_begin(umx_engine* eng, const float* d_pos, int node_lo, int node_hi, 
   if (eng->gp_plan) gp_clear(eng);                       // an abandoned evaluation
   HIPCHK(eng, hipSetDevice(eng->dev));
   eng->gp = true; eng->gp_lo = node_lo; eng->gp_hi = node_hi;
-  const int st = energy_forces_on(eng, static_cast<hipStream_t>(hip_stream), 1, d_pos, d_energy, d_forces);
+  const int st = energy_forces_on(eng, static_cast<hipStream_t>(hip_stream), 1, d_pos, d_energy, d_forces, d_virial);
   if (st != UMX_OK) gp_clear(eng);
   return st;
 }

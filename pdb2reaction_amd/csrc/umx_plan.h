@@ -867,7 +867,11 @@ int evaluate_planned(umx_engine* eng, hipStream_t s, long K, const float* d_pos,
     // every exchange point.  The workspace view must outlive this call (the closures hold a reference to it).
     eng->gp_ws = std::make_unique<WS>(wl[0]);
     eng->gp_plan = std::make_unique<Plan>();
-    plan_chunk(eng, *eng->gp_ws, d_pos, eng->d_deg_all, eng->d_cand_all, 0, 1, ie.per_image[0], d_energy, d_forces, *eng->gp_plan);
+    // virial: this rank's share of W -- its edge list is exactly the edges whose target it owns -- taken behind k_force_edge, in the
+    // segment in front of the force exchange; the share needs no exchange point of its own (the caller adds nine doubles per rank)
+    VirialOut vir;
+    if (eng->vir_out && d_forces) { vir.out = eng->vir_out; vir.part = eng->d_vir_part; vir.slabs = eng->vir_slabs; }
+    plan_chunk(eng, *eng->gp_ws, d_pos, eng->d_deg_all, eng->d_cand_all, 0, 1, ie.per_image[0], d_energy, d_forces, *eng->gp_plan, vir);
     eng->gp_at = 0; eng->gp_stream = s;
     return UMX_OK;
   }
@@ -878,7 +882,8 @@ int evaluate_planned(umx_engine* eng, hipStream_t s, long K, const float* d_pos,
 
 // Evaluate on `run_stream` (may be the legacy default stream 0).  eng->stream is swapped for the duration so that every
 // helper launches there; it is restored on every exit path.
-// d_virial: [n_images][9] float64 or nullptr (then nothing of umx_virial.h runs); never with the graph-parallel entry.
+// d_virial: [n_images][9] float64 or nullptr (then nothing of umx_virial.h runs).  Graph-parallel entry (eng->gp): the degree pass
+// below counts this rank's own edges only, so the partial slots are sized for the rank's share, and d_virial receives that share.
 int energy_forces_on(umx_engine* eng, hipStream_t run_stream, int n_images, const float* d_pos, double* d_energy, float* d_forces,
                      double* d_virial = nullptr) {
   hipStream_t own = eng->stream;

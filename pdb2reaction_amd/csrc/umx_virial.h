@@ -9,6 +9,10 @@
 // partial covers, and the order in which everything is added, depend on the image's own edge list only: the bits of W do not depend on
 // which batch the image is in, on how the batch is chunked, or on the lanes.  The partials live outside the workspace arena
 // (umx_engine::d_vir_part), indexed by the image's position in the CALL, so two chunks in flight never share a slot.
+//
+// Graph-parallel entry (umx_gp_begin_virial): every target node outside the rank's range has an empty CSR row, so "the image's edges" of
+// the rank's plan are exactly the edges whose target it owns, and the same two launches give the rank's share of W.  The shares are
+// disjoint and cover the image; adding them over the ranks, in rank order, is the caller's (include/umx.h).
 #pragma once
 
 namespace umx {

@@ -81,6 +81,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "umx_energy_forces_virial": ([vp, i32, fp, dp, fp, dp], i32),
         "umx_energy_forces_virial_dev": ([vp, i32, vp, vp, vp, vp, vp], i32),
         "umx_gp_begin": ([vp, vp, i32, i32, vp, vp, vp], i32),
+        "umx_gp_begin_virial": ([vp, vp, i32, i32, vp, vp, vp, vp], i32),
         "umx_gp_step": ([vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(i32)], i32),
         "umx_peer_sum": ([i32, C.POINTER(vp), C.c_size_t, C.POINTER(i32), C.POINTER(vp)], i32),
         "umx_synchronize": ([vp], i32),
@@ -135,6 +136,7 @@ EXPORTED_SYMBOLS = (
     "umx_last_graph_stats", "umx_last_partitions", "umx_last_lanes", "umx_reserve_images", "umx_workspace_stats", "umx_profile_enable", "umx_profile_read", "umx_bond_changes", "umx_debug_fetch", "umx_debug_keep",
     "umx_set_expert_coefficients", "umx_expert_count", "umx_set_recompute", "umx_last_recompute", "umx_workspace_bytes",
     "umx_set_cell", "umx_set_cells", "umx_last_graph_shifts", "umx_energy_forces_virial", "umx_energy_forces_virial_dev",
+    "umx_gp_begin_virial",
 )
 
 
@@ -449,7 +451,14 @@ class Engine:
                                                         C.c_void_p(stream) if stream else None), "umx_energy_forces_virial_dev")
 
     # ---- graph-parallel single-image mode (reference workers > 1; see parallel.GraphParallelEvaluator) -----------------
-    def gp_begin(self, d_pos: int, node_lo: int, node_hi: int, d_energy: int, d_forces: int, stream: int = 0):
+    def gp_begin(self, d_pos: int, node_lo: int, node_hi: int, d_energy: int, d_forces: int, stream: int = 0, d_virial: int = 0):
+        """``umx_gp_begin``; with ``d_virial`` (a device pointer to nine float64) ``umx_gp_begin_virial``: once ``gp_step`` reports done
+        it holds THIS engine's share of W -- the sum over the engines, in engine order, is the caller's."""
+        if d_virial:
+            self._chk(self.lib.umx_gp_begin_virial(self._h, C.c_void_p(d_pos), int(node_lo), int(node_hi), C.c_void_p(d_energy),
+                                                   C.c_void_p(d_forces), C.c_void_p(d_virial), C.c_void_p(stream) if stream else None),
+                      "umx_gp_begin_virial")
+            return
         self._chk(self.lib.umx_gp_begin(self._h, C.c_void_p(d_pos), int(node_lo), int(node_hi), C.c_void_p(d_energy), C.c_void_p(d_forces),
                                         C.c_void_p(stream) if stream else None), "umx_gp_begin")
 

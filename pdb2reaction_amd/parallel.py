@@ -196,10 +196,15 @@ class GraphParallelEvaluator:
     all-reduce when the group is gloo (rehearsal of the N > 1 path with several ranks on one GPU).  Energies are complete
     on every rank (node-level work is replicated), forces after the last all-reduce.  Payload per evaluation:
     9 x N x 1152 x 4 B + N x 12 B (92 MB per all-reduce at 20 000 atoms).
+
+    ``virial=True``: the call returns ``(E, F, W)`` with ``W`` (3, 3) float64 = dE/d eps (``umx_gp_begin_virial``).  Every rank's engine
+    leaves its own share of W -- the edges whose target it owns -- next to the forces; after the last step ONE ``all_gather`` of the
+    (9,) float64 shares follows and every rank adds them in rank order: the same bits on all ranks, no further collective.
+    ``virial=False`` is the evaluator without any of it, call for call.
     """
 
     def __init__(self, engine, n_atoms: int, device: torch.device, group: Optional["dist.ProcessGroup"] = None,
-                 force_collective: bool = False):
+                 force_collective: bool = False, virial: bool = False):
         """force_collective: issue the all-reduces even in a one-rank group (they are the identity there) -- exercises the in-place
         RCCL call on the engine's own workspace memory where only one GPU is available."""
         self.engine, self.n_atoms, self.device, self.group = engine, int(n_atoms), device, group
@@ -212,13 +217,36 @@ class GraphParallelEvaluator:
         self.n_exchanges = 0
         self._e = torch.zeros(1, dtype=torch.float64, device=device)
         self._f = torch.zeros(self.n_atoms, 3, dtype=torch.float32, device=device)
+        self.virial = bool(virial)
+        self._w = torch.zeros(9, dtype=torch.float64, device=device) if self.virial else None
+        self.last_partials = None               # virial: (world, 9) float64, the ranks' shares as gathered (rank order)
 
-    def __call__(self, pos_ang: torch.Tensor, _retry: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    def _sum_partials(self) -> torch.Tensor:
+        """W (3, 3) on the device: this rank's share, gathered over the ranks once and added in rank order."""
+        if not self.distributed:
+            parts = self._w.reshape(1, 9).clone()
+        elif self._stage_cpu:
+            rows = [torch.empty(9, dtype=torch.float64) for _ in range(self.world)]
+            dist.all_gather(rows, self._w.cpu(), group=self.group)
+            parts = torch.stack(rows).to(self.device)
+        else:
+            parts = torch.empty(self.world, 9, dtype=torch.float64, device=self.device)
+            dist.all_gather_into_tensor(parts.reshape(-1), self._w, group=self.group)
+        w = parts[0].clone()
+        for r in range(1, parts.shape[0]):          # rank order: float64 addition does not associate
+            w = w + parts[r]
+        self.last_partials = parts
+        return w.reshape(3, 3)
+
+    def __call__(self, pos_ang: torch.Tensor, _retry: bool = False):
         pos = pos_ang.to(device=self.device, dtype=torch.float32).contiguous()
         if pos.shape != (self.n_atoms, 3):
             raise ValueError(f"positions must be ({self.n_atoms}, 3), got {tuple(pos.shape)}")
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        self.engine.gp_begin(pos.data_ptr(), self.lo, self.hi, self._e.data_ptr(), self._f.data_ptr(), stream)
+        if self.virial:
+            self.engine.gp_begin(pos.data_ptr(), self.lo, self.hi, self._e.data_ptr(), self._f.data_ptr(), stream, d_virial=self._w.data_ptr())
+        else:
+            self.engine.gp_begin(pos.data_ptr(), self.lo, self.hi, self._e.data_ptr(), self._f.data_ptr(), stream)
         self.n_exchanges = 0
         while True:
             ptr, count, done = self.engine.gp_step()
@@ -241,6 +269,8 @@ class GraphParallelEvaluator:
                 return self(pos_ang, _retry=True)
             raise RuntimeError(f"non-finite energy in graph-parallel mode (precision mode {self.engine.precision_mode()}): non-finite "
                                "coordinates, or an overflow that wider forward planes cannot cure")
+        if self.virial:
+            return self._e.clone(), self._f.clone(), self._sum_partials()
         return self._e.clone(), self._f.clone()
 
 
@@ -392,6 +422,9 @@ class LocalEnginePool:
       When engines raise, all threads are joined first and the error of the lowest engine index is raised.  An fp16 range violation
       (fast split-f16 mode) that widened one engine widens ALL of them and the whole batch is evaluated again, so that one result
       never mixes two arithmetics.
+    * K == 1 with a virial (``energy_forces_virial`` / ``energy_forces_stress``): engine 0 alone by default; ``graph_parallel=True``
+      takes the route below with ``umx_gp_begin_virial`` -- every engine's share of W comes back with its forces and the shares are
+      added in engine order in float64 on the host.
     * K == 1: graph-parallel over the pool (unless ``gp=False`` / ``UMX_WORKERS_GP=0``: engine 0 alone).  Engine r builds the incoming
       edges of the target nodes ``shard_bounds(N, G, r)``; all engines step to the next exchange point, ``umx_peer_sum`` adds their
       partial-sum buffers in place in engine order, and so on until done (10 exchanges).  Energies and forces are then complete --
@@ -422,6 +455,8 @@ class LocalEnginePool:
         self.last_route = None                  # "batch" | "graph-parallel" | "single"
         self.last_blocks: List[Tuple[int, int]] = []
         self.last_all = None                    # graph-parallel route: [(E, F)] of EVERY engine (they must agree in every bit)
+        self.last_partials = None               # graph-parallel route with a virial: [W_r (9,) float64] of every engine, its own share
+        self._gp_wbuf = None                    # per engine: the (9,) float64 device buffer of that share, made at first use
         self._cells = None                      # per-image cells (``set_cells``): (cells (K,3,3) float64, pbc flags (3,)), else None
         self._cells_on = [None] * len(self.engines)   # what engine r has bound of them: its block (lo, hi), or "single" for cells[0] alone
         self.recompute = None                   # what ``create`` / ``set_recompute`` gave every engine (None: the engines' own setting)
@@ -465,7 +500,7 @@ class LocalEnginePool:
         return False
 
     def close(self) -> None:
-        self._gp_buf = None
+        self._gp_buf = self._gp_wbuf = None
         for eng in self.engines:
             eng.close()
         self.engines = []
@@ -476,7 +511,7 @@ class LocalEnginePool:
         for eng in self.engines:
             eng.set_system(atomic_numbers, **kw)
         self.natoms = len(atomic_numbers)
-        self._gp_buf = None
+        self._gp_buf = self._gp_wbuf = None
 
     def set_cell(self, cell=None, pbc=None) -> None:
         """``Engine.set_cell`` on every engine: batches dealt over the pool and the graph-parallel single image see the same cell."""
@@ -612,27 +647,37 @@ class LocalEnginePool:
         f = np.concatenate([r[1] for r in res]) if forces else None
         return e, f
 
-    def energy_forces_virial(self, pos_ang) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def energy_forces_virial(self, pos_ang, graph_parallel: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """``Engine.energy_forces_virial`` over the pool: (E [K], F [K,N,3], W [K,3,3] float64).  A batch is dealt over the engines in
         the same contiguous blocks as ``energy_forces`` and is the single-engine result bit for bit (W does not depend on the batch an
-        image is in).  A SINGLE geometry is evaluated on engine 0 alone, as with recompute mode 2: the graph-parallel path has no
-        virial (``umx_gp_begin`` / ``umx_gp_step`` produce none)."""
+        image is in).  A SINGLE geometry is evaluated on engine 0 alone by default (``last_route == "single"``: the single-engine W, bit
+        for bit).  ``graph_parallel=True`` with more than one engine sends it over the whole pool instead (``umx_gp_begin_virial``,
+        ``last_route == "graph-parallel"``): an image that needs the pool's combined memory, all engines at work; every engine's share
+        of W (``last_partials``) is added in engine order in float64 on the host.  That W differs from engine 0's as the graph-parallel
+        forces do, at float32 summation order.  The opt-in cannot run with recompute mode 2 (a one-GPU plan): ``ValueError``, no silent
+        fallback.  It says nothing about batches."""
         p = self._images(pos_ang)
         if p.shape[0] == 1:
+            if graph_parallel and len(self.engines) > 1:
+                if self.recompute == 2:
+                    raise ValueError("graph_parallel=True: the graph-parallel virial cannot run with recompute mode 2 (a one-GPU plan; "
+                                     "umx_gp_begin refuses it) -- set mode 0 or 1 on the pool, or leave graph_parallel off")
+                self._bind_cells(1, None)
+                return self._graph_parallel(p[0], True, virial=True)
             self._bind_cells(1, None)
             self.last_route, self.last_blocks = "single", [(0, 1)]
             return self.engines[0].energy_forces_virial(p)
         res = self._deal(p, lambda eng, block: eng.energy_forces_virial(block))
         return tuple(np.concatenate([r[i] for r in res]) for i in range(3))
 
-    def energy_forces_stress(self, pos_ang) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def energy_forces_stress(self, pos_ang, graph_parallel: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """``Engine.energy_forces_stress`` over the pool: (E [K], F [K,N,3], stress [K,6] eV/A^3, Voigt xx, yy, zz, yz, xz, xy), routed
-        as ``energy_forces_virial``; ``ValueError`` unless the cell (``set_cell``) is periodic along all three axes.  With per-image
-        cells (``set_cells``) image k is divided by the volume of cell k."""
+        as ``energy_forces_virial`` (``graph_parallel`` included); ``ValueError`` unless the cell (``set_cell``) is periodic along all
+        three axes.  With per-image cells (``set_cells``) image k is divided by the volume of cell k."""
         from .engine import voigt_stress
 
         vol = self.engines[0].cell_volume() if self._cells is None else self.cell_volumes()
-        e, f, w = self.energy_forces_virial(pos_ang)
+        e, f, w = self.energy_forces_virial(pos_ang, graph_parallel=True) if graph_parallel else self.energy_forces_virial(pos_ang)
         return e, f, voigt_stress(w, vol)
 
     def _gp_buffers(self):
@@ -651,11 +696,21 @@ class LocalEnginePool:
             self._gp_buf = bufs
         return self._gp_buf
 
-    def _graph_parallel(self, pos: np.ndarray, forces: bool, _retry: bool = False):
+    def _gp_virial_buffers(self, bufs):
+        if self._gp_wbuf is None:
+            self._gp_wbuf = [torch.zeros(9, dtype=torch.float64, device=dev) for dev, *_ in bufs]
+            for dev, *_ in bufs:
+                if dev.type == "cuda":
+                    torch.cuda.synchronize(dev)         # as in _gp_buffers: filled on torch's current stream, used on the engine's
+        return self._gp_wbuf
+
+    def _graph_parallel(self, pos: np.ndarray, forces: bool, _retry: bool = False, virial: bool = False):
+        """virial: every engine also leaves its share of W (``umx_gp_begin_virial``); returns (E [1], F [1,N,3], W [1,3,3])."""
         if not np.isfinite(pos).all():
             raise ValueError("non-finite position")
         g, n = len(self.engines), self.natoms
         bufs = self._gp_buffers()
+        wbufs = self._gp_virial_buffers(bufs) if virial else None
         host = torch.from_numpy(np.ascontiguousarray(pos, dtype=np.float32))
         handles = []
         for dev, stream, d_pos, _, _ in bufs:
@@ -671,7 +726,10 @@ class LocalEnginePool:
         def begin(r):
             lo, hi = self.last_blocks[r]
             _, _, d_pos, d_e, d_f = bufs[r]
-            self.engines[r].gp_begin(d_pos.data_ptr(), lo, hi, d_e.data_ptr(), d_f.data_ptr(), handles[r])
+            if virial:
+                self.engines[r].gp_begin(d_pos.data_ptr(), lo, hi, d_e.data_ptr(), d_f.data_ptr(), handles[r], d_virial=wbufs[r].data_ptr())
+            else:
+                self.engines[r].gp_begin(d_pos.data_ptr(), lo, hi, d_e.data_ptr(), d_f.data_ptr(), handles[r])
 
         try:
             self._run_all(begin, range(g))
@@ -695,15 +753,21 @@ class LocalEnginePool:
                 stream.synchronize()
             out.append((d_e.cpu().numpy().copy(), d_f.cpu().numpy().copy()))
         self.last_all = out
+        self.last_partials = [wb.cpu().numpy().copy() for wb in wbufs] if virial else None      # (behind the stream synchronisations above)
         e, f = out[0]
         if not np.isfinite(e).all():
             # energies are complete on every engine (node-level work is replicated): collect every sticky flag, then all widen together
             for eng in self.engines:
                 eng.take_range_error()
             if not _retry and any([eng.widen("non-finite energy in a graph-parallel evaluation over the local pool") for eng in self.engines]):
-                return self._graph_parallel(pos, forces, _retry=True)
+                return self._graph_parallel(pos, forces, _retry=True, virial=virial)
             raise RuntimeError(f"non-finite energy in graph-parallel mode over the local pool (precision mode {self.precision_mode()}): "
                                "non-finite coordinates, or an overflow that wider forward planes cannot cure")
+        if virial:
+            w = self.last_partials[0].copy()
+            for part in self.last_partials[1:]:         # engine order: float64 addition does not associate
+                w = w + part
+            return e, f[None], w.reshape(1, 3, 3)
         return e, (f[None] if forces else None)
 
     def _abandon(self) -> None:
