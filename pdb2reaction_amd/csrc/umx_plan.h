@@ -224,11 +224,13 @@ void plan_chunk(umx_engine* eng, WS& w, const float* d_pos, const int* d_deg, co
         const int G = eng->grid_G;
         const long ng = nn * G;
         hipLaunchKernelGGL(k_grid_expand, dim3(nblk(nn, 4)), B256, 0, s, w.xn2, eng->to_grid, G, w.gridA, nn);
+        if (eng->dbg_on) DBG("gridin" + t, w.gridA, ng * C);      // (debug) the to-grid projection: gridA is overwritten by the third GEMM
         CHK(gemm_grid(eng, w.gridA, C, 0, L.g1w, C, L.g1b, w.ffg1[i], H, 0, ng, H, C));
         CHK(gemm_grid(eng, w.ffg1[i], H, 0, L.g2w, H, L.g2b, w.ffg2[i], H, 0, ng, H, H, A_SILU));
         CHK(gemm_grid(eng, w.ffg2[i], H, 0, L.g3w, H, L.g3b, w.gridA, C, 0, ng, C, H, A_SILU));
         hipLaunchKernelGGL(k_grid_contract, dim3(nblk(nn, 4)), B256, 0, s, w.gridA, eng->from_grid, G, xmid, xout, nn);
         HIPCHK(eng, hipGetLastError());
+        if (eng->dbg_on) DBG("gridout" + t, w.gridA, ng * C);     // (debug) the grid MLP's output, from-grid's input
         DBG("xn2" + t, w.xn2, nn * ROW); DBG("ffg1" + t, w.ffg1[i], ng * H); DBG("ffg2" + t, w.ffg2[i], ng * H); DBG("x" + t, xout, nn * ROW);
         return UMX_OK;
       }
@@ -238,6 +240,7 @@ void plan_chunk(umx_engine* eng, WS& w, const float* d_pos, const int* d_deg, co
       CHK(so3_linear(eng, w.ffhg, L.l2w, L.l2b, xout, nn, xmid));
       HIPCHK(eng, hipGetLastError());
       DBG("xn2" + t, w.xn2, nn * ROW); DBG("gspre" + t, w.gspre[i], nn * 2 * H); DBG("ffh" + t, w.ffh[i], nn * ROW); DBG("x" + t, xout, nn * ROW);
+      if (eng->dbg_on) DBG("ffhg" + t, w.ffhg, nn * ROW);         // (debug) the gated hidden rows: one buffer for all layers
       return UMX_OK;
     });
   }
@@ -252,6 +255,7 @@ void plan_chunk(umx_engine* eng, WS& w, const float* d_pos, const int* d_deg, co
     hipLaunchKernelGGL(k_energy, dim3((unsigned)nimg), B256, 0, s, w.enode, N, eng->rmsd, eng->refsum, d_energy, eng->d_flags);
     HIPCHK(eng, hipGetLastError());
     DBG("e_node", w.enode, nn); DBG("pre1", w.pre1, nn * H); DBG("pre2", w.pre2, nn * H);
+    if (eng->dbg_on) DBG("xf", w.xf, nn * ROW);
     if (!d_forces) return UMX_OK;
     // ---------------- K10: analytic reverse pass ----------------
     if (ne > 0) {
@@ -260,11 +264,17 @@ void plan_chunk(umx_engine* eng, WS& w, const float* d_pos, const int* d_deg, co
       HIPCHK(eng, hipMemsetAsync(w.tau, 0, ne * 4 * sizeof(float), s));
       HIPCHK(eng, hipMemsetAsync(w.tau2, 0, ne * 4 * sizeof(float), s));
     }
+    // (debug) every capture of the reverse node links sits directly behind the launch that writes its buffer: n128a / n128b, G0 / G1 / G2,
+    // ggs and gridA / gridB are reused from link to link
     hipLaunchKernelGGL(k_silu_bwd, dim3(nblk(nn * H, 256)), B256, 0, s, eng->e4, 0L, w.pre2, w.n128a, nn, H);
+    if (eng->dbg_on) DBG("g_pre2", w.n128a, nn * H);
     CHK(gemm_node(eng, w.n128a, H, 0, eng->e2T, H, nullptr, w.n128b, H, 0, nn, H, H));
+    if (eng->dbg_on) DBG("g_sil1", w.n128b, nn * H);              // dE / d silu(pre1)
     hipLaunchKernelGGL(k_silu_bwd, dim3(nblk(nn * H, 256)), B256, 0, s, w.n128b, (long)H, w.pre1, w.n128a, nn, H);
+    if (eng->dbg_on) DBG("g_pre1", w.n128a, nn * H);
     HIPCHK(eng, hipMemsetAsync(w.G1, 0, nn * ROW * sizeof(float), s));
     CHK(gemm_node(eng, w.n128a, H, 0, eng->e0T, H, nullptr, w.G1, ROW, 0, nn, C, H));
+    if (eng->dbg_on) DBG("g_xf", w.G1, nn * ROW);                 // the whole row: the columns of l > 0 must still be zero
     hipLaunchKernelGGL(k_norm_bwd, dim3(nblk(nn, 4)), B256, 0, s, w.G1, xlast, eng->normw, (const float*)nullptr, w.G0, nn);
     HIPCHK(eng, hipGetLastError());
     DBG("g_xfinal", w.G0, nn * ROW);
@@ -290,17 +300,28 @@ void plan_chunk(umx_engine* eng, WS& w, const float* d_pos, const int* d_deg, co
         const int G = eng->grid_G;
         const long ng = nn * G;
         hipLaunchKernelGGL(k_grid_expand, dim3(nblk(nn, 4)), B256, 0, s, w.G0, eng->from_grid, G, w.gridA, nn);
+        if (eng->dbg_on) DBG("g_gridout" + t, w.gridA, ng * C);
         CHK(gemm_grid(eng, w.gridA, C, 0, L.g3T, C, nullptr, w.gridB, H, 0, ng, H, C));
+        if (eng->dbg_on) DBG("g_gsil2" + t, w.gridB, ng * H);       // dE / d silu(ffg2)
         hipLaunchKernelGGL(k_silu_bwd, dim3(nblk(ng * H, 256)), B256, 0, s, w.gridB, (long)H, w.ffg2[i], w.gridA, ng, H);
+        if (eng->dbg_on) DBG("g_ffg2" + t, w.gridA, ng * H);
         CHK(gemm_grid(eng, w.gridA, H, 0, L.g2T, H, nullptr, w.gridB, H, 0, ng, H, H));
+        if (eng->dbg_on) DBG("g_gsil1" + t, w.gridB, ng * H);       // dE / d silu(ffg1)
         hipLaunchKernelGGL(k_silu_bwd, dim3(nblk(ng * H, 256)), B256, 0, s, w.gridB, (long)H, w.ffg1[i], w.gridA, ng, H);
+        if (eng->dbg_on) DBG("g_ffg1" + t, w.gridA, ng * H);
         CHK(gemm_grid(eng, w.gridA, H, 0, L.g1T, H, nullptr, w.gridB, C, 0, ng, C, H));
+        if (eng->dbg_on) DBG("g_gridin" + t, w.gridB, ng * C);
         hipLaunchKernelGGL(k_grid_contract, dim3(nblk(nn, 4)), B256, 0, s, w.gridB, eng->to_grid, G, (const float*)nullptr, w.G1, nn);     // G1 = g_xn2
+        if (eng->dbg_on) DBG("g_xn2" + t, w.G1, nn * ROW);
       } else {
       CHK(so3_linear(eng, w.G0, L.l2T, nullptr, w.G1, nn, nullptr));                         // G1 = g_ffhg
+      if (eng->dbg_on) DBG("g_ffhg" + t, w.G1, nn * ROW);
       hipLaunchKernelGGL(k_gate_node_bwd, dim3(nblk(nn * H, 256)), B256, 0, s, w.G1, w.ffh[i], w.gspre[i], w.G2, w.ggs, nn);
+      if (eng->dbg_on) { DBG("g_ffh" + t, w.G2, nn * ROW); DBG("g_gs" + t, w.ggs, nn * 2 * H); }
       CHK(so3_linear(eng, w.G2, L.l1T, nullptr, w.G1, nn, nullptr));                         // G1 = g_xn2
+      if (eng->dbg_on) DBG("g_xn2a" + t, w.G1, nn * ROW);         // before the scalar MLP's share lands in the l = 0 columns
       CHK(gemm_node(eng, w.ggs, 2 * H, 0, L.smlpT, 2 * H, nullptr, w.G1, ROW, 0, nn, C, 2 * H, A_PLAIN, 1, 0, 0, w.G1, ROW, 0, 0));
+      if (eng->dbg_on) DBG("g_xn2" + t, w.G1, nn * ROW);
       }
       hipLaunchKernelGGL(k_norm_bwd, dim3(nblk(nn, 4)), B256, 0, s, w.G1, xmid, L.n2w, w.G0, w.G2, nn);   // G2 = g_xmid
       HIPCHK(eng, hipGetLastError());

@@ -491,7 +491,10 @@ def test_device_pointer_entry_is_stream_ordered(engine):
 @pytest.mark.parametrize("mode", ["fp32", "split", "split-bf16", "bf16x3"])
 def test_stage_by_stage_against_staged_oracle(weights, mode, monkeypatch):
     """Every intermediate of the forward AND of the analytic reverse pass vs oracle/staged.py, in both precision modes
-    (the split-bf16 path keeps its GEMM operands as bf16 planes, so fewer fp32 intermediates exist there)."""
+    (the split-bf16 path keeps its GEMM operands as bf16 planes, so fewer fp32 intermediates exist there).
+    One size (26 atoms) and a tolerance against each tensor's largest element: the links themselves are held one by one, per element and at
+    the sizes where the kernels change shape, by tests/test_gpu_reverse_links.py (reverse GEMMs), tests/test_gpu_edge_links.py (edge kernels)
+    and tests/test_gpu_node_links.py (norms, node linears, gates, readout and their reverse)."""
     from oracle.staged import Staged
     from pdb2reaction_amd.engine import Engine
 

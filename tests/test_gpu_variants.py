@@ -95,7 +95,8 @@ def test_task_names_follow_the_blob_s_dataset_list(monkeypatch):
 @pytest.mark.parametrize("mode", ["bf16x3", "fp32"])
 def test_grid_block_stage_by_stage(mode, monkeypatch):
     """The grid feed-forward's forward activations (both hidden pre-activations on the 42-point grid, the block output) and the
-    gradients that leave its hand-derived reverse (g_xmid, and everything downstream) vs oracle/staged.py."""
+    gradients that leave its hand-derived reverse (g_xmid, and everything downstream) vs oracle/staged.py.  Every link of the block, the
+    reverse ones included, is held on its own (per element, at 3 ... 257 atoms, both GEMM bodies) by tests/test_gpu_node_links.py."""
     from oracle.staged import Staged
 
     w, eng, _ = make("grid_bias", mode, monkeypatch)
