@@ -258,6 +258,32 @@ int umx_energy_forces_virial(umx_engine* eng, int n_images, const float* pos_ang
 int umx_energy_forces_virial_dev(umx_engine* eng, int n_images, const float* d_pos_ang, double* d_energy_ev,
                                  float* d_forces_ev_ang, double* d_virial_ev, void* hip_stream);
 
+/* FLOAT64 POSITIONS (additive to ABI v10; opt-in).  umx_energy_forces_virial[_dev] with pos_ang / d_pos_ang as float64:
+ * [n_images][n_atoms][3] float64 Angstrom.  The entries above round the caller's geometry to float32 at the door, which moves a
+ * coordinate by up to half a float32 ulp: 2e-6 A at 32-64 A from the origin, 3e-5 A at 512-1024 A -- an ABSOLUTE error, set by where the
+ * frame sits, in every edge vector.  Here the radius-graph kernels, the only ones that read positions, form every edge vector as the float64 difference
+ *     vec = r_src + t - r_dst      (t = n_a a + n_b b + n_c c in float64 from the float64 cell of umx_set_cell / umx_set_cells)
+ * and round it ONCE to float32: the vector carries float32's RELATIVE precision, whatever the frame.  From that rounded vector on the
+ * arithmetic is that of the float entries -- the squared distance, the test 0 < d^2 <= cutoff^2, the max_neigh ranking by (d^2, source),
+ * the row order, the stored unit vector and distance, and everything behind the graph.  So:
+ *   - for float32-representable positions whose differences float32 forms exactly, E, F and W are bitwise those of the float entries;
+ *   - a rigid translation that float64 adds exactly (and that changes no float64 difference) changes no bit of E, F or W;
+ *   - periodic: the scratch copy is wrapped in float64 with the float64 lattice and dual vectors; the pruning of translated cells stays
+ *     a float32 filter with its margin; image k of a per-image-cell batch is bitwise the single evaluation after umx_set_cell(cell k).
+ * Outputs keep their types (E float64, F float32, W float64).  forces_ev_ang and virial_ev may be NULL as in the entries above (NULL for
+ * both: energies only; a virial without forces is UMX_ERR_ARG).  A non-finite float64 coordinate is refused as a non-finite float32 one
+ * is (host entry: before anything runs; device entry: by the radius-graph kernel, status bit 2), the range guard and the sticky status
+ * word are those of the float entries.  Chunks, two lanes, target-node partitions, recompute plans and the virial all take them.
+ * Cost: the three graph kernels (under 1 % of a step) in float64 differences, 24 instead of 12 bytes per atom read; nothing else.
+ * Not provided: float64 positions for the graph-parallel entries (umx_gp_begin[_virial] stay float32), float64 forces, float64
+ * positions by default.
+ * Extends: the reference hands fairchem float32 positions (AtomicData.pos, uma_pysis.py:312-322); its callers hold float64
+ * (uma_pysis.py:506-513).  No reference counterpart for the float64 path itself.                                                     */
+int umx_energy_forces_f64(umx_engine* eng, int n_images, const double* pos_ang, double* energy_ev,
+                          float* forces_ev_ang, double* virial_ev);
+int umx_energy_forces_f64_dev(umx_engine* eng, int n_images, const double* d_pos_ang, double* d_energy_ev,
+                              float* d_forces_ev_ang, double* d_virial_ev, void* hip_stream);
+
 /* Graph-parallel evaluation of ONE image across several engines / ranks (ABI v5) -- the reference's `workers > 1` semantics
  * (ParallelMLIPPredictUnit: the atoms' graph partitioned over workers, uma_pysis.py:220-242), for single large systems when there are
  * fewer images than GPUs.  Every rank passes the FULL positions; rank r builds the incoming edges of the

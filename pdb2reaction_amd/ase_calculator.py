@@ -84,13 +84,18 @@ class UMXCalculator(_AseBase):
     it with ``stress=False``.  A single image on a pool of
     engines (``workers > 1``) is evaluated on engine 0 alone when the stress is on, unless ``gp_stress=True``: then it goes graph-parallel
     over the whole pool (``LocalEnginePool.energy_forces_stress(graph_parallel=True)``), every engine adding its share of the strain
-    derivative -- for a cell too large for one GPU."""
+    derivative -- for a cell too large for one GPU.
+
+    ``UMXCalculator(double_positions=True)`` hands the float64 positions of the ``Atoms`` to the engine as they are
+    (``Engine.energy_forces(..., double_positions=True)``: edge vectors from float64 differences, results independent of where the
+    frame sits) in ``calculate`` and ``calculate_images``, with and without stress and per-image cells.  Off by default: positions are
+    then rounded to float32 first, as the reference's model input is.  Not together with ``gp_stress`` (``ValueError`` from the pool)."""
 
     implemented_properties = ["energy", "forces"]
 
     def __init__(self, model: str = "uma-s-1p1", task_name: str = "omol", device: str = "auto", charge: int = 0, spin: int = 1,
                  radius: Optional[float] = None, max_neigh: Optional[int] = None, workers: int = 1, stress: bool = False, gp_stress: bool = False,
-                 **kwargs):
+                 double_positions: bool = False, **kwargs):
         """workers > 1 (outside a torch.distributed process group): that many engines in this process when there are that many
         devices (``UMX_LOCAL_DEVICES`` names them), as in ``uma_pysis.UMAcore`` -- ``calculate_images`` deals its images over them,
         a single image is evaluated graph-parallel (``parallel.LocalEnginePool``); ``local_devices`` lists the ordinals in use.
@@ -103,6 +108,7 @@ class UMXCalculator(_AseBase):
         super().__init__(**kwargs)
         self.stress = bool(stress)
         self.gp_stress = bool(gp_stress)
+        self.double_positions = bool(double_positions)
         if self.stress:
             self.implemented_properties = ["energy", "forces", "stress"]      # on the instance: the class attribute stays as it is
         self.workers = max(int(workers or 1), 1)
@@ -188,16 +194,20 @@ class UMXCalculator(_AseBase):
             self.results = dict(self._last[2])
             return
         if with_stress:
-            e, f, sv = eng.energy_forces_stress(pos[None], **self._stress_kw())
+            e, f, sv = eng.energy_forces_stress(pos[None], **self._stress_kw(), **self._dp_kw())
             self.results = {"energy": float(e[0]), "forces": np.asarray(f[0], dtype=np.float64), "stress": np.asarray(sv[0], dtype=np.float64)}
         else:
-            e, f = eng.energy_forces(pos[None], forces=True)
+            e, f = eng.energy_forces(pos[None], forces=True, **self._dp_kw())
             self.results = {"energy": float(e[0]), "forces": np.asarray(f[0], dtype=np.float64)}
         self._last = (self._bound, pos, dict(self.results))
 
     def _stress_kw(self) -> dict:
         """What ``energy_forces_stress`` is called with: the graph-parallel opt-in when this calculator runs a pool of engines."""
         return {"graph_parallel": True} if self.gp_stress and len(self.local_devices or []) > 1 else {}
+
+    def _dp_kw(self) -> dict:
+        """``double_positions=True`` for the engine when this calculator was built with it; nothing otherwise (the calls as they were)."""
+        return {"double_positions": True} if self.double_positions else {}
 
     def _fully_periodic(self) -> bool:
         """The image bound last has a cell and all three pbc flags set."""
@@ -238,7 +248,7 @@ class UMXCalculator(_AseBase):
         if stress:
             if not self._fully_periodic():
                 raise PropertyNotImplementedError("stress: the images are not periodic along all three axes, so there is no volume to refer a stress to")
-            e, f, sv = eng.energy_forces_stress(pos, **self._stress_kw())
+            e, f, sv = eng.energy_forces_stress(pos, **self._stress_kw(), **self._dp_kw())
             return e, np.asarray(f, dtype=np.float64), np.asarray(sv, dtype=np.float64)
-        e, f = eng.energy_forces(pos, forces=True)
+        e, f = eng.energy_forces(pos, forces=True, **self._dp_kw())
         return e, np.asarray(f, dtype=np.float64)

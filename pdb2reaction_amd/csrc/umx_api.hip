@@ -22,6 +22,63 @@
 // ================================================================================================
 #define NOT_MERGED "expert-form weights are loaded but not merged: call umx_set_expert_coefficients first (then umx_set_system)"
 
+// ---- the evaluation entries, once for float and once for double positions (umx_energy_forces_f64[_dev]) ---------------------------
+namespace {
+// the device-pointer entries, for float or double positions
+int energy_forces_dev_impl(umx_engine* eng, int n_images, const PosPtr d_pos, double* d_energy, float* d_forces, double* d_virial, void* hip_stream) {
+  if (!eng) return UMX_ERR_ARG;
+  if (eng->need_merge()) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: " NOT_MERGED);
+  if (!eng->have_system) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: bind a system first (umx_set_system)");
+  if (n_images <= 0 || !(d_pos.f || d_pos.d) || !d_energy) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: bad arguments");
+  if (d_virial && !d_forces) return fail(eng, UMX_ERR_ARG, "umx_energy_forces_virial: the virial comes out of the reverse pass: ask for the forces too");
+  if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
+  CHK(periodic_check_images(eng, n_images, "umx_energy_forces"));
+  HIPCHK(eng, hipSetDevice(eng->dev));
+  // NULL = the legacy default stream (hipStream_t 0): the work is then ordered after everything the caller has enqueued on
+  // the default stream (the producer of d_pos) and before whatever it enqueues next (the consumer of d_energy / d_forces),
+  // exactly as with an explicit stream.  The engine's private non-blocking stream is never used for caller-owned buffers.
+  return energy_forces_on(eng, static_cast<hipStream_t>(hip_stream), n_images, d_pos, d_energy, d_forces, d_virial);
+}
+
+// the host-pointer entries, for float or double positions: P* pos is staged in the device buffer of its own type
+template <typename P>
+int energy_forces_host_impl(umx_engine* eng, int n_images, const P* pos, double* energy, float* forces, double* virial) {
+  if (!eng) return UMX_ERR_ARG;
+  if (eng->need_merge()) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: " NOT_MERGED);
+  if (!eng->have_system) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: bind a system first (umx_set_system)");
+  if (n_images <= 0 || !pos || !energy) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: bad arguments");
+  if (virial && !forces) return fail(eng, UMX_ERR_ARG, "umx_energy_forces_virial: the virial comes out of the reverse pass: ask for the forces too");
+  if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
+  CHK(periodic_check_images(eng, n_images, "umx_energy_forces"));
+  HIPCHK(eng, hipSetDevice(eng->dev));
+  const long nt = (long)n_images * eng->natoms;
+  if (eng->io_cap < nt) CHK(grow(eng, eng->io_cap, nt, {eng->stream}, {DevBuf(eng->d_io_pos, nt * 3), DevBuf(eng->d_io_f, nt * 3)}));
+  if (eng->io_img_cap < n_images) CHK(grow(eng, eng->io_img_cap, (long)n_images, {eng->stream}, {DevBuf(eng->d_io_e, n_images)}));
+  if (virial && eng->io_w_cap < n_images) CHK(grow(eng, eng->io_w_cap, (long)n_images, {eng->stream}, {DevBuf(eng->d_io_w, (size_t)n_images * 9)}));
+  P* d_stage;
+  if constexpr (std::is_same_v<P, double>) {          // the float64 positions' own staging, grown as the float one above
+    if (eng->io64_cap < nt) CHK(grow(eng, eng->io64_cap, nt, {eng->stream}, {DevBuf(eng->d_io_pos64, nt * 3)}));
+    d_stage = eng->d_io_pos64;
+  } else d_stage = eng->d_io_pos;
+  for (long i = 0; i < nt * 3; ++i)         // a NaN coordinate would silently drop its atom from the radius graph (every comparison false)
+    if (!std::isfinite(pos[i])) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: non-finite position (image " + std::to_string(i / ((long)eng->natoms * 3)) + ")");
+  HIPCHK(eng, hipMemcpyAsync(d_stage, pos, nt * 3 * sizeof(P), hipMemcpyHostToDevice, eng->stream));
+  CHK(energy_forces_on(eng, eng->stream, n_images, PosPtr(d_stage), eng->d_io_e, forces ? eng->d_io_f : nullptr, virial ? eng->d_io_w : nullptr));
+  HIPCHK(eng, hipMemcpyAsync(energy, eng->d_io_e, (size_t)n_images * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+  if (forces) HIPCHK(eng, hipMemcpyAsync(forces, eng->d_io_f, nt * 3 * sizeof(float), hipMemcpyDeviceToHost, eng->stream));
+  if (virial) HIPCHK(eng, hipMemcpyAsync(virial, eng->d_io_w, (size_t)n_images * 9 * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+  HIPCHK(eng, hipStreamSynchronize(eng->stream));
+  for (int k = 0; k < n_images; ++k)
+    if (!std::isfinite(energy[k])) {
+      (void)hipMemset(eng->d_flags, 0, sizeof(int));         // reported right here: do not fail the NEXT call for it as well
+      return fail(eng, UMX_ERR_RANGE, "image " + std::to_string(k) + ": non-finite energy" +
+                  (eng->prec.fwd_f16() ? " (an activation beyond the fp16 operand range of UMX_PRECISION=split: try split-bf16, bf16x3 or fp32)"
+                                      : " (an overflow in float32)"));
+    }
+  return UMX_OK;
+}
+}  // namespace
+
 extern "C" {
 
 int umx_abi_version(void) { return 10; }
@@ -83,7 +140,7 @@ int umx_destroy(umx_engine* eng) {
   (void)hipSetDevice(eng->dev);
   (void)hipStreamSynchronize(eng->stream);
   for (auto& r : eng->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-  void* ptrs[] = {eng->d_w, eng->d_dw, eng->d_bw, eng->d_gmu, eng->d_z, eng->d_sysemb, eng->arena, eng->d_deg_all, eng->d_cand_all, eng->d_img_edges, eng->d_io_pos, eng->d_io_e, eng->d_io_f, eng->d_flags, eng->d_dtab, eng->d_part_deg, eng->d_part_f, eng->d_ex, eng->d_mjobs, eng->d_pjobs, eng->d_mx, eng->d_shifts, eng->d_cells, eng->d_shifts_pk, eng->d_wrap, eng->d_vir_part, eng->d_vir_wp, eng->d_io_w};
+  void* ptrs[] = {eng->d_w, eng->d_dw, eng->d_bw, eng->d_gmu, eng->d_z, eng->d_sysemb, eng->arena, eng->d_deg_all, eng->d_cand_all, eng->d_img_edges, eng->d_io_pos, eng->d_io_e, eng->d_io_f, eng->d_flags, eng->d_dtab, eng->d_part_deg, eng->d_part_f, eng->d_ex, eng->d_mjobs, eng->d_pjobs, eng->d_mx, eng->d_shifts, eng->d_cells, eng->d_shifts_pk, eng->d_wrap, eng->d_wrap64, eng->d_lats, eng->d_io_pos64, eng->d_vir_part, eng->d_vir_wp, eng->d_io_w};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   (void)hipStreamSynchronize(eng->stream2);
   (void)hipEventDestroy(eng->ev_fork); (void)hipEventDestroy(eng->ev_join);
@@ -224,18 +281,11 @@ int umx_energy_forces_dev(umx_engine* eng, int n_images, const float* d_pos, dou
 }
 
 int umx_energy_forces_virial_dev(umx_engine* eng, int n_images, const float* d_pos, double* d_energy, float* d_forces, double* d_virial, void* hip_stream) {
-  if (!eng) return UMX_ERR_ARG;
-  if (eng->need_merge()) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: " NOT_MERGED);
-  if (!eng->have_system) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: bind a system first (umx_set_system)");
-  if (n_images <= 0 || !d_pos || !d_energy) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: bad arguments");
-  if (d_virial && !d_forces) return fail(eng, UMX_ERR_ARG, "umx_energy_forces_virial: the virial comes out of the reverse pass: ask for the forces too");
-  if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
-  CHK(periodic_check_images(eng, n_images, "umx_energy_forces"));
-  HIPCHK(eng, hipSetDevice(eng->dev));
-  // NULL = the legacy default stream (hipStream_t 0): the work is then ordered after everything the caller has enqueued on
-  // the default stream (the producer of d_pos) and before whatever it enqueues next (the consumer of d_energy / d_forces),
-  // exactly as with an explicit stream.  The engine's private non-blocking stream is never used for caller-owned buffers.
-  return energy_forces_on(eng, static_cast<hipStream_t>(hip_stream), n_images, d_pos, d_energy, d_forces, d_virial);
+  return energy_forces_dev_impl(eng, n_images, PosPtr(d_pos), d_energy, d_forces, d_virial, hip_stream);
+}
+
+int umx_energy_forces_f64_dev(umx_engine* eng, int n_images, const double* d_pos, double* d_energy, float* d_forces, double* d_virial, void* hip_stream) {
+  return energy_forces_dev_impl(eng, n_images, PosPtr(d_pos), d_energy, d_forces, d_virial, hip_stream);
 }
 
 int umx_gp_begin(umx_engine* eng, const float* d_pos, int node_lo, int node_hi, double* d_energy, float* d_forces, void* hip_stream) {
@@ -377,34 +427,11 @@ int umx_energy_forces(umx_engine* eng, int n_images, const float* pos, double* e
 }
 
 int umx_energy_forces_virial(umx_engine* eng, int n_images, const float* pos, double* energy, float* forces, double* virial) {
-  if (!eng) return UMX_ERR_ARG;
-  if (eng->need_merge()) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: " NOT_MERGED);
-  if (!eng->have_system) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: bind a system first (umx_set_system)");
-  if (n_images <= 0 || !pos || !energy) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: bad arguments");
-  if (virial && !forces) return fail(eng, UMX_ERR_ARG, "umx_energy_forces_virial: the virial comes out of the reverse pass: ask for the forces too");
-  if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
-  CHK(periodic_check_images(eng, n_images, "umx_energy_forces"));
-  HIPCHK(eng, hipSetDevice(eng->dev));
-  const long nt = (long)n_images * eng->natoms;
-  if (eng->io_cap < nt) CHK(grow(eng, eng->io_cap, nt, {eng->stream}, {DevBuf(eng->d_io_pos, nt * 3), DevBuf(eng->d_io_f, nt * 3)}));
-  if (eng->io_img_cap < n_images) CHK(grow(eng, eng->io_img_cap, (long)n_images, {eng->stream}, {DevBuf(eng->d_io_e, n_images)}));
-  if (virial && eng->io_w_cap < n_images) CHK(grow(eng, eng->io_w_cap, (long)n_images, {eng->stream}, {DevBuf(eng->d_io_w, (size_t)n_images * 9)}));
-  for (long i = 0; i < nt * 3; ++i)         // a NaN coordinate would silently drop its atom from the radius graph (every comparison false)
-    if (!std::isfinite(pos[i])) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: non-finite position (image " + std::to_string(i / ((long)eng->natoms * 3)) + ")");
-  HIPCHK(eng, hipMemcpyAsync(eng->d_io_pos, pos, nt * 3 * sizeof(float), hipMemcpyHostToDevice, eng->stream));
-  CHK(energy_forces_on(eng, eng->stream, n_images, eng->d_io_pos, eng->d_io_e, forces ? eng->d_io_f : nullptr, virial ? eng->d_io_w : nullptr));
-  HIPCHK(eng, hipMemcpyAsync(energy, eng->d_io_e, (size_t)n_images * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
-  if (forces) HIPCHK(eng, hipMemcpyAsync(forces, eng->d_io_f, nt * 3 * sizeof(float), hipMemcpyDeviceToHost, eng->stream));
-  if (virial) HIPCHK(eng, hipMemcpyAsync(virial, eng->d_io_w, (size_t)n_images * 9 * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
-  HIPCHK(eng, hipStreamSynchronize(eng->stream));
-  for (int k = 0; k < n_images; ++k)
-    if (!std::isfinite(energy[k])) {
-      (void)hipMemset(eng->d_flags, 0, sizeof(int));         // reported right here: do not fail the NEXT call for it as well
-      return fail(eng, UMX_ERR_RANGE, "image " + std::to_string(k) + ": non-finite energy" +
-                  (eng->prec.fwd_f16() ? " (an activation beyond the fp16 operand range of UMX_PRECISION=split: try split-bf16, bf16x3 or fp32)"
-                                      : " (an overflow in float32)"));
-    }
-  return UMX_OK;
+  return energy_forces_host_impl(eng, n_images, pos, energy, forces, virial);
+}
+
+int umx_energy_forces_f64(umx_engine* eng, int n_images, const double* pos, double* energy, float* forces, double* virial) {
+  return energy_forces_host_impl(eng, n_images, pos, energy, forces, virial);
 }
 
 int umx_set_precision(umx_engine* eng, const char* mode) {

@@ -16,6 +16,7 @@
 #include <memory>
 #include <set>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/umx.h"
@@ -48,6 +49,16 @@ struct LayerW {
   const float *smlp, *smlpb, *smlpT, *l1w, *l1b, *l1T, *l2w, *l2b, *l2T;       // K8 spectral feed-forward
   const float *g1w, *g1b, *g1T, *g2w, *g2b, *g2T, *g3w, *g3b, *g3T;            // K8 grid feed-forward (ff_grid): grid_mlp.{0,2,4} (+ optional biases), transposes
   RadialW rad;
+};
+
+// The positions of an evaluation as the graph kernels read them -- nothing else does: float32 (every entry but umx_energy_forces_f64[_dev])
+// or float64, on the device.  Carried from the entry down to the two launchers of umx_periodic.h, which pick the instantiation.
+struct PosPtr {
+  const float* f = nullptr;
+  const double* d = nullptr;
+  PosPtr(const float* p) : f(p) {}
+  PosPtr(const double* p) : d(p) {}
+  PosPtr atom(long i) const { return d ? PosPtr(d + i * 3) : PosPtr(f + i * 3); }   // the same positions from atom i on
 };
 
 struct ProfRec { hipEvent_t a, b; double flops; int M, N, K, amode, cplx, prec, gz; };
@@ -282,6 +293,7 @@ struct umx_engine {
   int hint_images = 0;             // umx_reserve_images: size the workspace for this many images at the next growth
   // host io staging for the host-pointer entry point
   float* d_io_pos = nullptr; double* d_io_e = nullptr; float* d_io_f = nullptr; long io_cap = 0, io_img_cap = 0;
+  double* d_io_pos64 = nullptr; long io64_cap = 0;   // umx_energy_forces_f64: the float64 positions (forces and energies use the buffers above)
   // virial (umx_virial.h): the per-(image, slab) partials of the reduction, outside the arena; where the evaluation at hand writes W
   // (nullptr: no virial was asked for) and its slots per image; the host entry's staging
   double* d_vir_part = nullptr; long vir_cap = 0;
@@ -294,6 +306,7 @@ struct umx_engine {
   // (umx_set_cells, n_cells > 0: then `cell` / `per` / `d_shifts` are not in use); either persists across umx_set_system
   bool pbc_on = false;
   double cell[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; int pbc[3] = {0, 0, 0};
+  Lattice64 lat{};                 // the float64 lattice and dual vectors of `cell`: what the double-position kernels read next to `per`
   Periodic per{};                  // what the periodic graph kernels read, built for the cutoff per_cutoff (rebuilt when umx_set_system changes it)
   float per_cutoff = 0.f;
   float4* d_shifts = nullptr;      // the translation table [PBC_MAX_SHIFTS]
@@ -301,8 +314,10 @@ struct umx_engine {
   std::vector<double> cells;       // [n_cells][9], kept for a rebuild at another cutoff
   std::vector<int> cell_shifts;    // [n_cells] table entries of every image
   Periodic* d_cells = nullptr; long cells_cap = 0;          // [n_cells] what the per-image instantiations read; `shifts` points into d_shifts_pk
+  Lattice64* d_lats = nullptr;                              // [n_cells] their float64 lattices (double positions), grown with d_cells
   float4* d_shifts_pk = nullptr; long shifts_pk_cap = 0;    // the images' tables, packed: sum of n_shifts entries
   float* d_wrap = nullptr; long wrap_cap = 0;   // positions wrapped into the cell: the copy the graph kernels read
+  double* d_wrap64 = nullptr; long wrap64_cap = 0;   // the same for double positions, wrapped in float64
   int last_shifts = 0;             // lattice translations the most recent evaluation searched (umx_last_graph_shifts; 0: open boundaries)
   bool may_truncate = true;      // the largest degree of the evaluation being planned reaches max_neigh: k_graph_fill takes its truncating (LDS) form
   bool prof_on = false;

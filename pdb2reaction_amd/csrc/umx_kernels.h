@@ -42,11 +42,27 @@ struct PeriodicImages {
   const Periodic* cells;
   int img0;
 };
+// Double positions (umx_energy_forces_f64; P = double below): the lattice and the dual vectors once more, in float64, next to the
+// float32 Periodic.  The wrap and the translation of a candidate are formed from these; the table, the pruning and everything that is
+// decided on the rounded edge vector stay with the float32 struct.
+struct Lattice64 {
+  double a[3][3];         // lattice vectors (rows); zero for an open axis
+  double b[3][3];         // dual vectors, as Periodic::b
+};
+struct NoLattice {};      // P = float: the table entry IS the translation
+struct Periodic64 { Periodic per; Lattice64 lat; };
+struct PeriodicImages64 {
+  const Periodic* cells;
+  const Lattice64* lats;  // one per image, next to cells
+  int img0;
+};
 // what a graph kernel takes as its last argument: the one cell by value (IMG = false; also the unused argument of the open-boundary
-// instantiations), or the array of cells (IMG = true)
-template <bool IMG> struct PeriodicArgOf { using type = Periodic; };
-template <> struct PeriodicArgOf<true> { using type = PeriodicImages; };
-template <bool IMG> using PeriodicArg = typename PeriodicArgOf<IMG>::type;
+// instantiations), or the array of cells (IMG = true); P = double: the same with the float64 lattice
+template <bool IMG, typename P = float> struct PeriodicArgOf { using type = Periodic; };
+template <> struct PeriodicArgOf<true, float> { using type = PeriodicImages; };
+template <> struct PeriodicArgOf<false, double> { using type = Periodic64; };
+template <> struct PeriodicArgOf<true, double> { using type = PeriodicImages64; };
+template <bool IMG, typename P = float> using PeriodicArg = typename PeriodicArgOf<IMG, P>::type;
 
 // The cell of the wave's node.  IMG: the image index is wave-uniform, and taken through readfirstlane so that the struct (and, through
 // its `shifts`, the table entries) arrive through scalar loads, as the kernel argument does.
@@ -55,11 +71,36 @@ __device__ __forceinline__ Periodic periodic_of_node(const PeriodicImages& arg, 
   const int img = __builtin_amdgcn_readfirstlane(arg.img0 + (int)(node / natoms));
   return arg.cells[img];
 }
+__device__ __forceinline__ Periodic periodic_of_node(const Periodic64& arg, long, int) { return arg.per; }
+__device__ __forceinline__ Periodic periodic_of_node(const PeriodicImages64& arg, long node, int natoms) {
+  const int img = __builtin_amdgcn_readfirstlane(arg.img0 + (int)(node / natoms));
+  return arg.cells[img];
+}
+// The float64 lattice of the wave's node (double positions), through the same wave-uniform image index; nothing for float positions.
+__device__ __forceinline__ NoLattice lattice_of_node(const Periodic&, long, int) { return NoLattice(); }
+__device__ __forceinline__ NoLattice lattice_of_node(const PeriodicImages&, long, int) { return NoLattice(); }
+__device__ __forceinline__ Lattice64 lattice_of_node(const Periodic64& arg, long, int) { return arg.lat; }
+__device__ __forceinline__ Lattice64 lattice_of_node(const PeriodicImages64& arg, long node, int natoms) {
+  const int img = __builtin_amdgcn_readfirstlane(arg.img0 + (int)(node / natoms));
+  return arg.lats[img];
+}
 
 // one definition of the edge vector of a candidate, used by count and fill alike (see dist2_f)
-__device__ __forceinline__ void pbc_delta(const float* __restrict__ pj, float xi, float yi, float zi, const float4 sh, float& dx, float& dy, float& dz) {
+__device__ __forceinline__ void pbc_delta(const float* __restrict__ pj, float xi, float yi, float zi, const float4 sh, const NoLattice&, float& dx, float& dy, float& dz) {
   dx = (pj[0] - xi) + sh.x; dy = (pj[1] - yi) + sh.y; dz = (pj[2] - zi) + sh.z;
 }
+// double positions: the translation n_a a + n_b b + n_c c in float64 from the integer triple packed in sh.w and the float64 lattice,
+// r_j + t - r_i in float64, ONE rounding to float32 -- from there on the candidate is decided and stored as above
+__device__ __forceinline__ void pbc_delta(const double* __restrict__ pj, double xi, double yi, double zi, const float4 sh, const Lattice64& lat, float& dx, float& dy, float& dz) {
+  const unsigned code = __float_as_uint(sh.w);
+  const double na = (double)((int)(code & 255u) - 8), nb = (double)((int)((code >> 8) & 255u) - 8), nc = (double)((int)((code >> 16) & 255u) - 8);
+  dx = (float)((pj[0] + fma(nc, lat.a[2][0], fma(nb, lat.a[1][0], na * lat.a[0][0]))) - xi);
+  dy = (float)((pj[1] + fma(nc, lat.a[2][1], fma(nb, lat.a[1][1], na * lat.a[0][1]))) - yi);
+  dz = (float)((pj[2] + fma(nc, lat.a[2][2], fma(nb, lat.a[1][2], na * lat.a[0][2]))) - zi);
+}
+// open boundaries: the difference in the positions' own type, rounded to float32 (P = float: today's subtraction, nothing to round)
+template <typename P>
+__device__ __forceinline__ float open_delta(P a, P b) { return (float)(a - b); }
 
 // The translations that can reach the target at (x, y, z) within the cutoff, compacted in ascending index order into the wave's
 // LDS slice `act`; returns their number.  Wave-uniform decision per translation: the translated cell holds fractional coordinates
@@ -97,10 +138,24 @@ __device__ __forceinline__ int pbc_active_shifts(const Periodic& per, float x, f
 // changes no edge vector, hence no energy or force).  n = 0 leaves the coordinate bits as they are.
 // IMG (umx_set_cells): atom i is wrapped into the cell of its image i / natoms (a thread per atom: a wave may span two images, so
 // here the cell comes in through vector loads).
-template <bool IMG>
-__global__ void k_wrap_cell(const float* __restrict__ pos, float* __restrict__ out, long nt, int natoms, const PeriodicArg<IMG> parg) {
+// P = double: the same wrap in float64 with the float64 lattice and dual vectors, into a float64 copy.
+template <bool IMG, typename P = float>
+__global__ void k_wrap_cell(const P* __restrict__ pos, P* __restrict__ out, long nt, int natoms, const PeriodicArg<IMG, P> parg) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nt) return;
+  if constexpr (std::is_same_v<P, double>) {
+    const Lattice64* lp;
+    if constexpr (IMG) lp = parg.lats + (parg.img0 + (int)(i / natoms));
+    else lp = &parg.lat;
+    const Lattice64& lat = *lp;
+    const double x = pos[i * 3 + 0], y = pos[i * 3 + 1], z = pos[i * 3 + 2];
+    double n[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) n[k] = floor(fma(z, lat.b[k][2], fma(y, lat.b[k][1], x * lat.b[k][0])));
+    out[i * 3 + 0] = x - fma(n[2], lat.a[2][0], fma(n[1], lat.a[1][0], n[0] * lat.a[0][0]));
+    out[i * 3 + 1] = y - fma(n[2], lat.a[2][1], fma(n[1], lat.a[1][1], n[0] * lat.a[0][1]));
+    out[i * 3 + 2] = z - fma(n[2], lat.a[2][2], fma(n[1], lat.a[1][2], n[0] * lat.a[0][2]));
+  } else {                                                            // float positions: the body below is as it was
   const Periodic* pp;
   if constexpr (IMG) pp = parg.cells + (parg.img0 + (int)(i / natoms));
   else pp = &parg;
@@ -112,11 +167,14 @@ __global__ void k_wrap_cell(const float* __restrict__ pos, float* __restrict__ o
   out[i * 3 + 0] = x - fmaf(n[2], per.a[2][0], fmaf(n[1], per.a[1][0], n[0] * per.a[0][0]));
   out[i * 3 + 1] = y - fmaf(n[2], per.a[2][1], fmaf(n[1], per.a[1][1], n[0] * per.a[0][1]));
   out[i * 3 + 2] = z - fmaf(n[2], per.a[2][2], fmaf(n[1], per.a[1][2], n[0] * per.a[0][2]));
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
 // K1 radius graph: brute force inside each image, wave per target, ballot compaction (ascending
-// source order => CSR rows sorted by source).  pos: [NT][3] f32.
+// source order => CSR rows sorted by source).  pos: [NT][3] f32 -- or f64 (P = double, umx_energy_forces_f64): the edge vector is then
+// the float64 difference rounded once to float32, and everything decided on it (d^2, the cutoff test, the rank key) is the float32
+// arithmetic below, unchanged.
 // ------------------------------------------------------------------------------------------------
 // [lo, hi): the target nodes whose incoming edges this engine builds (all of them normally; one rank's share in the graph-parallel
 // single-image mode, where every other node gets an empty row).
@@ -125,14 +183,14 @@ __global__ void k_wrap_cell(const float* __restrict__ pos, float* __restrict__ o
 // PBC = true (umx_set_cell): candidates are (source, translation) pairs; pos is the wrapped copy.  flag bit 2: a target of the periodic
 // form has more candidates than the truncating fill can rank (GF_MAXC) while max_neigh binds -- refused by the host.
 // IMG = true (umx_set_cells, PBC only): the cell is that of the node's image, read from the array behind parg.
-template <bool PBC, bool IMG = false>
-__global__ __launch_bounds__(256) void k_graph_count(const float* __restrict__ pos, int natoms, long nt, float rc2, int max_neigh,
+template <bool PBC, bool IMG = false, typename P = float>
+__global__ __launch_bounds__(256) void k_graph_count(const P* __restrict__ pos, int natoms, long nt, float rc2, int max_neigh,
                                                      int* __restrict__ deg, int* __restrict__ cand, long lo, long hi, int* __restrict__ flag,
-                                                     const PeriodicArg<IMG> parg) {
+                                                     const PeriodicArg<IMG, P> parg) {
   static_assert(PBC || !IMG, "per-image cells are periodic");
   UMX_WAVE_ITEM(node, nt)
   const Periodic per = periodic_of_node(parg, node, natoms);
-  const float xi = pos[node * 3 + 0], yi = pos[node * 3 + 1], zi = pos[node * 3 + 2];
+  const P xi = pos[node * 3 + 0], yi = pos[node * 3 + 1], zi = pos[node * 3 + 2];
   if (lane == 0 && !(isfinite(xi) && isfinite(yi) && isfinite(zi))) atomicOr(flag, 2);
   if (node < lo || node >= hi) {                 // wave-uniform
     if (lane == 0) { cand[node] = 0; deg[node] = 0; }
@@ -143,7 +201,8 @@ __global__ __launch_bounds__(256) void k_graph_count(const float* __restrict__ p
   if constexpr (PBC) {
     __shared__ unsigned short act_s[4][PBC_MAX_SHIFTS];
     unsigned short* act = act_s[threadIdx.x >> 6];
-    const int na = pbc_active_shifts(per, xi, yi, zi, lane, act);
+    const auto lat = lattice_of_node(parg, node, natoms);
+    const int na = pbc_active_shifts(per, (float)xi, (float)yi, (float)zi, lane, act);   // (a conservative filter: on the rounded coordinate for P = double)
     const int self = (int)(node - base);
     for (int a = 0; a < na; ++a) {
       const int t = __builtin_amdgcn_readfirstlane((int)act[a]);
@@ -153,7 +212,7 @@ __global__ __launch_bounds__(256) void k_graph_count(const float* __restrict__ p
         bool ok = false;
         if (j < natoms) {
           float dx, dy, dz;
-          pbc_delta(pos + (base + j) * 3, xi, yi, zi, sh, dx, dy, dz);
+          pbc_delta(pos + (base + j) * 3, xi, yi, zi, sh, lat, dx, dy, dz);
           const float d2 = dist2_f(dx, dy, dz);
           ok = (d2 <= rc2) && (d2 > 0.0f) && !(j == self && t == per.zero);   // an atom's own image (t != 0) is an edge
         }
@@ -166,7 +225,7 @@ __global__ __launch_bounds__(256) void k_graph_count(const float* __restrict__ p
     const int j = j0 + lane;
     bool ok = false;
     if (j < natoms) {
-      const float dx = pos[(base + j) * 3 + 0] - xi, dy = pos[(base + j) * 3 + 1] - yi, dz = pos[(base + j) * 3 + 2] - zi;
+      const float dx = open_delta(pos[(base + j) * 3 + 0], xi), dy = open_delta(pos[(base + j) * 3 + 1], yi), dz = open_delta(pos[(base + j) * 3 + 2], zi);
       const float d2 = dist2_f(dx, dy, dz);
       ok = (d2 <= rc2) && (d2 > 0.0f) && (base + j != node);        // 0 < d <= cutoff
     }
@@ -216,29 +275,31 @@ __global__ __launch_bounds__(1024) void k_scan(const int* __restrict__ deg, long
 // the active translations, a prefix sum over the lanes gives its first slot, and it writes them in translation order.
 // IMG = true (umx_set_cells, PBC only): the cell of the node's image, as in k_graph_count -- both take the image index from the same
 // (img0, node / natoms), so the rows the count sized are the rows the fill writes.
-template <bool TRUNC, bool PBC, bool IMG = false>
-__global__ __launch_bounds__(256) void k_graph_fill(const float* __restrict__ pos, int natoms, long nt, float rc2, int max_neigh,
+// P = double: as in k_graph_count -- both form a candidate's edge vector through the same pbc_delta / open_delta, so they decide alike.
+template <bool TRUNC, bool PBC, bool IMG = false, typename P = float>
+__global__ __launch_bounds__(256) void k_graph_fill(const P* __restrict__ pos, int natoms, long nt, float rc2, int max_neigh,
                                                     const int* __restrict__ cand, const int* __restrict__ row_ptr, int* __restrict__ esrc,
-                                                    int* __restrict__ edst, float* __restrict__ evec, long lo, long hi, const PeriodicArg<IMG> parg) {
+                                                    int* __restrict__ edst, float* __restrict__ evec, long lo, long hi, const PeriodicArg<IMG, P> parg) {
   static_assert(PBC || !IMG, "per-image cells are periodic");
   UMX_WAVE_ITEM(node, nt)
   if (node < lo || node >= hi) return;           // wave-uniform: rows outside the owned target range are empty
   const Periodic per = periodic_of_node(parg, node, natoms);
   const long base = (node / natoms) * natoms;
-  const float xi = pos[node * 3 + 0], yi = pos[node * 3 + 1], zi = pos[node * 3 + 2];
+  const P xi = pos[node * 3 + 0], yi = pos[node * 3 + 1], zi = pos[node * 3 + 2];
   const int nc = cand[node];
   const bool truncate = TRUNC && nc > max_neigh;
   int w = row_ptr[node];
   if constexpr (PBC) {
     __shared__ unsigned short act_s[4][PBC_MAX_SHIFTS];
     unsigned short* act = act_s[threadIdx.x >> 6];
-    const int na = pbc_active_shifts(per, xi, yi, zi, lane, act);
+    const auto lat = lattice_of_node(parg, node, natoms);
+    const int na = pbc_active_shifts(per, (float)xi, (float)yi, (float)zi, lane, act);
     const int self = (int)(node - base);
     const int wend = row_ptr[node + 1];
     unsigned long long kth = ~0ull;                                    // the largest key kept
     // one definition of a candidate and its key for the three passes below
     auto candidate = [&](int j, int t, const float4 sh, float& dx, float& dy, float& dz, unsigned long long& key) -> bool {
-      pbc_delta(pos + (base + j) * 3, xi, yi, zi, sh, dx, dy, dz);
+      pbc_delta(pos + (base + j) * 3, xi, yi, zi, sh, lat, dx, dy, dz);
       const float d2 = dist2_f(dx, dy, dz);
       key = ((unsigned long long)__float_as_uint(d2) << 32) | ((unsigned)t * (unsigned)natoms + (unsigned)j);
       return (d2 <= rc2) && (d2 > 0.0f) && !(j == self && t == per.zero);
@@ -320,7 +381,7 @@ __global__ __launch_bounds__(256) void k_graph_fill(const float* __restrict__ po
       bool ok = false;
       float d2 = 0.f;
       if (j < natoms) {
-        const float dx = pos[(base + j) * 3 + 0] - xi, dy = pos[(base + j) * 3 + 1] - yi, dz = pos[(base + j) * 3 + 2] - zi;
+        const float dx = open_delta(pos[(base + j) * 3 + 0], xi), dy = open_delta(pos[(base + j) * 3 + 1], yi), dz = open_delta(pos[(base + j) * 3 + 2], zi);
         d2 = dist2_f(dx, dy, dz);
         ok = (d2 <= rc2) && (d2 > 0.0f) && (base + j != node);
       }
@@ -342,7 +403,7 @@ __global__ __launch_bounds__(256) void k_graph_fill(const float* __restrict__ po
       const unsigned long long m = __ballot(keep);
       if (keep) {
         const int j = (int)(unsigned)(k & 0xffffffffull);
-        const float dx = pos[(base + j) * 3 + 0] - xi, dy = pos[(base + j) * 3 + 1] - yi, dz = pos[(base + j) * 3 + 2] - zi;
+        const float dx = open_delta(pos[(base + j) * 3 + 0], xi), dy = open_delta(pos[(base + j) * 3 + 1], yi), dz = open_delta(pos[(base + j) * 3 + 2], zi);
         const float d = sqrtf(__uint_as_float((unsigned)(k >> 32))), inv = 1.0f / d;
         const int slot = w + __popcll(m & ((1ull << lane) - 1ull));
         esrc[slot] = (int)(base + j);
@@ -358,7 +419,7 @@ __global__ __launch_bounds__(256) void k_graph_fill(const float* __restrict__ po
     bool ok = false;
     float dx = 0.f, dy = 0.f, dz = 0.f, d2 = 0.f;
     if (j < natoms) {
-      dx = pos[(base + j) * 3 + 0] - xi; dy = pos[(base + j) * 3 + 1] - yi; dz = pos[(base + j) * 3 + 2] - zi;
+      dx = open_delta(pos[(base + j) * 3 + 0], xi); dy = open_delta(pos[(base + j) * 3 + 1], yi); dz = open_delta(pos[(base + j) * 3 + 2], zi);
       d2 = dist2_f(dx, dy, dz);
       ok = (d2 <= rc2) && (d2 > 0.0f) && (base + j != node);
     }
@@ -368,7 +429,7 @@ __global__ __launch_bounds__(256) void k_graph_fill(const float* __restrict__ po
         const int q = q0 + lane;
         float e2 = -1.0f;                                             // -1 marks "not a candidate"
         if (q < natoms && base + q != node) {
-          const float ex = pos[(base + q) * 3 + 0] - xi, ey = pos[(base + q) * 3 + 1] - yi, ez = pos[(base + q) * 3 + 2] - zi;
+          const float ex = open_delta(pos[(base + q) * 3 + 0], xi), ey = open_delta(pos[(base + q) * 3 + 1], yi), ez = open_delta(pos[(base + q) * 3 + 2], zi);
           const float t = dist2_f(ex, ey, ez);
           if (t <= rc2 && t > 0.0f) e2 = t;
         }

@@ -11,7 +11,7 @@
 
 namespace {
 
-struct PeriodicHost { Periodic per{}; std::vector<float4> table; };
+struct PeriodicHost { Periodic per{}; Lattice64 lat{}; std::vector<float4> table; };   // lat: what the double-position kernels read next to per
 
 inline void cross3(const double* u, const double* v, double* o) {
   o[0] = u[1] * v[2] - u[2] * v[1]; o[1] = u[2] * v[0] - u[0] * v[2]; o[2] = u[0] * v[1] - u[1] * v[0];
@@ -62,6 +62,7 @@ bool build_periodic(const double cell[9], const int pbc[3], double cutoff, Perio
   int N[3];
   Periodic& per = out->per;
   per = Periodic();
+  out->lat = Lattice64();
   for (int k = 0; k < 3; ++k) {
     for (int c = 0; c < 3; ++c) B[k][c] = cr[k][c] / det;
     h[k] = 1.0 / norm3(B[k]);
@@ -77,6 +78,7 @@ bool build_periodic(const double cell[9], const int pbc[3], double cutoff, Perio
     }
     N[k] = (int)std::floor(spans) + 1;
     for (int c = 0; c < 3; ++c) { per.a[k][c] = (float)cell[k * 3 + c]; per.b[k][c] = (float)B[k][c]; }
+    for (int c = 0; c < 3; ++c) { out->lat.a[k][c] = cell[k * 3 + c]; out->lat.b[k][c] = B[k][c]; }
     per.gmax[k] = (float)(1.001 * cutoff / h[k] + 1e-3);
   }
   out->table.clear();
@@ -103,6 +105,7 @@ int periodic_upload(umx_engine* eng, const PeriodicHost& ph) {
   HIPCHK(eng, hipMemcpy(eng->d_shifts, ph.table.data(), ph.table.size() * sizeof(float4), hipMemcpyHostToDevice));
   eng->per = ph.per;
   eng->per.shifts = eng->d_shifts;
+  eng->lat = ph.lat;
   eng->per_cutoff = eng->cutoff;
   return UMX_OK;
 }
@@ -139,13 +142,15 @@ int periodic_upload_images(umx_engine* eng, const std::vector<PeriodicHost>& ph)
   HIPCHK(eng, hipSetDevice(eng->dev));
   HIPCHK(eng, hipStreamSynchronize(eng->stream));                     // no evaluation may still be reading the old tables
   if (eng->ran_on_caller) HIPCHK(eng, hipEventSynchronize(eng->ev_done));
-  if (eng->cells_cap < n) CHK(grow(eng, eng->cells_cap, n, {}, {DevBuf(eng->d_cells, (size_t)n)}));
+  if (eng->cells_cap < n) CHK(grow(eng, eng->cells_cap, n, {}, {DevBuf(eng->d_cells, (size_t)n), DevBuf(eng->d_lats, (size_t)n)}));
   if (eng->shifts_pk_cap < total) CHK(grow(eng, eng->shifts_pk_cap, total, {}, {DevBuf(eng->d_shifts_pk, (size_t)total)}));
   std::vector<Periodic> pers(n);
+  std::vector<Lattice64> lats(n);
   std::vector<float4> table;
   table.reserve(total);
   eng->cell_shifts.resize(n);
   for (long k = 0; k < n; ++k) {
+    lats[k] = ph[k].lat;
     pers[k] = ph[k].per;
     pers[k].shifts = eng->d_shifts_pk + table.size();
     eng->cell_shifts[k] = ph[k].per.n_shifts;
@@ -153,6 +158,7 @@ int periodic_upload_images(umx_engine* eng, const std::vector<PeriodicHost>& ph)
   }
   HIPCHK(eng, hipMemcpy(eng->d_shifts_pk, table.data(), table.size() * sizeof(float4), hipMemcpyHostToDevice));
   HIPCHK(eng, hipMemcpy(eng->d_cells, pers.data(), pers.size() * sizeof(Periodic), hipMemcpyHostToDevice));
+  HIPCHK(eng, hipMemcpy(eng->d_lats, lats.data(), lats.size() * sizeof(Lattice64), hipMemcpyHostToDevice));
   eng->per_cutoff = eng->cutoff;
   return UMX_OK;
 }
@@ -179,8 +185,9 @@ int periodic_check_images(umx_engine* eng, long K, const char* who) {
 }
 
 // Start of an evaluation.  Open boundaries: nothing.  Periodic: the table(s) follow the bound cutoff, the positions of all images are
-// wrapped into the scratch copy (every image into its own cell, if umx_set_cells bound them), and *d_pos is pointed at it.
-int periodic_prepare(umx_engine* eng, hipStream_t s, long K, const float** d_pos) {
+// wrapped into the scratch copy (every image into its own cell, if umx_set_cells bound them), and *d_pos is pointed at it -- a float64
+// copy, wrapped in float64, for double positions.
+int periodic_prepare(umx_engine* eng, hipStream_t s, long K, PosPtr* d_pos) {
   eng->last_shifts = 0;
   if (!eng->pbc_on) return UMX_OK;
   const bool img = eng->n_cells > 0;
@@ -208,42 +215,72 @@ int periodic_prepare(umx_engine* eng, hipStream_t s, long K, const float** d_pos
     return fail(eng, UMX_ERR_ARG, "umx_energy_forces: " + (img ? "image " + std::to_string(most_at) + ": " : std::string()) + std::to_string(most) + " lattice translations x " +
                 std::to_string(eng->natoms) + " atoms do not fit the 32-bit candidate index of the periodic graph");
   const long nt = K * eng->natoms;
+  if (d_pos->d) {
+    if (eng->wrap64_cap < nt) CHK(grow(eng, eng->wrap64_cap, nt, {s}, {DevBuf(eng->d_wrap64, (size_t)nt * 3)}));
+    if (img) hipLaunchKernelGGL((k_wrap_cell<true, double>), dim3(nblk(nt, 256)), dim3(256), 0, s, d_pos->d, eng->d_wrap64, nt, eng->natoms, PeriodicImages64{eng->d_cells, eng->d_lats, 0});
+    else hipLaunchKernelGGL((k_wrap_cell<false, double>), dim3(nblk(nt, 256)), dim3(256), 0, s, d_pos->d, eng->d_wrap64, nt, eng->natoms, Periodic64{eng->per, eng->lat});
+    HIPCHK(eng, hipGetLastError());
+    *d_pos = PosPtr(eng->d_wrap64);
+    eng->last_shifts = most;
+    return UMX_OK;
+  }
   if (eng->wrap_cap < nt) CHK(grow(eng, eng->wrap_cap, nt, {s}, {DevBuf(eng->d_wrap, (size_t)nt * 3)}));
-  if (img) hipLaunchKernelGGL(k_wrap_cell<true>, dim3(nblk(nt, 256)), dim3(256), 0, s, *d_pos, eng->d_wrap, nt, eng->natoms, PeriodicImages{eng->d_cells, 0});
-  else hipLaunchKernelGGL(k_wrap_cell<false>, dim3(nblk(nt, 256)), dim3(256), 0, s, *d_pos, eng->d_wrap, nt, eng->natoms, eng->per);
+  if (img) hipLaunchKernelGGL(k_wrap_cell<true>, dim3(nblk(nt, 256)), dim3(256), 0, s, d_pos->f, eng->d_wrap, nt, eng->natoms, PeriodicImages{eng->d_cells, 0});
+  else hipLaunchKernelGGL(k_wrap_cell<false>, dim3(nblk(nt, 256)), dim3(256), 0, s, d_pos->f, eng->d_wrap, nt, eng->natoms, eng->per);
   HIPCHK(eng, hipGetLastError());
-  *d_pos = eng->d_wrap;
+  *d_pos = PosPtr(eng->d_wrap);
   eng->last_shifts = most;
   return UMX_OK;
 }
 
-// ---- the two graph kernels: open-boundary, one-cell or per-image instantiation ---------------------------------------------------
+// ---- the two graph kernels: open-boundary, one-cell or per-image instantiation, for float or double positions ---------------------
+// the last argument of an instantiation for the cell(s) in force: PeriodicArg<IMG, P> (umx_kernels.h)
+template <bool IMG, typename P> PeriodicArg<IMG, P> periodic_arg(const umx_engine* eng, long img0, bool on = true);
+template <> Periodic periodic_arg<false, float>(const umx_engine* eng, long, bool on) { return on ? eng->per : Periodic(); }
+template <> PeriodicImages periodic_arg<true, float>(const umx_engine* eng, long img0, bool) { return PeriodicImages{eng->d_cells, (int)img0}; }
+template <> Periodic64 periodic_arg<false, double>(const umx_engine* eng, long, bool on) { return on ? Periodic64{eng->per, eng->lat} : Periodic64(); }
+template <> PeriodicImages64 periodic_arg<true, double>(const umx_engine* eng, long img0, bool) { return PeriodicImages64{eng->d_cells, eng->d_lats, (int)img0}; }
+
 // img0: the index within the call of the image d_pos starts at (per-image cells: image img0 + node / natoms reads cell img0 + node / natoms)
-void launch_graph_count(umx_engine* eng, hipStream_t s, const float* d_pos, long nt, int* deg, int* cand, long lo, long hi, long img0) {
+template <typename P>
+void launch_graph_count_of(umx_engine* eng, hipStream_t s, const P* d_pos, long nt, int* deg, int* cand, long lo, long hi, long img0) {
   const float rc2 = eng->cutoff * eng->cutoff;
   const dim3 grid(nblk(nt, 4)), block(256);
   const int N = eng->natoms, mn = eng->max_neigh;
   if (eng->pbc_on && eng->n_cells > 0)
-    hipLaunchKernelGGL((k_graph_count<true, true>), grid, block, 0, s, d_pos, N, nt, rc2, mn, deg, cand, lo, hi, eng->d_flags, PeriodicImages{eng->d_cells, (int)img0});
-  else if (eng->pbc_on) hipLaunchKernelGGL(k_graph_count<true>, grid, block, 0, s, d_pos, N, nt, rc2, mn, deg, cand, lo, hi, eng->d_flags, eng->per);
-  else hipLaunchKernelGGL(k_graph_count<false>, grid, block, 0, s, d_pos, N, nt, rc2, mn, deg, cand, lo, hi, eng->d_flags, Periodic());
+    hipLaunchKernelGGL((k_graph_count<true, true, P>), grid, block, 0, s, d_pos, N, nt, rc2, mn, deg, cand, lo, hi, eng->d_flags, periodic_arg<true, P>(eng, img0));
+  else if (eng->pbc_on) hipLaunchKernelGGL((k_graph_count<true, false, P>), grid, block, 0, s, d_pos, N, nt, rc2, mn, deg, cand, lo, hi, eng->d_flags, periodic_arg<false, P>(eng, 0));
+  else hipLaunchKernelGGL((k_graph_count<false, false, P>), grid, block, 0, s, d_pos, N, nt, rc2, mn, deg, cand, lo, hi, eng->d_flags, periodic_arg<false, P>(eng, 0, false));
 }
-void launch_graph_fill(umx_engine* eng, hipStream_t s, bool trunc, const float* d_pos, long nn, const int* cand, const int* row_ptr, int* esrc, int* edst,
-                       float* evec, long lo, long hi, long img0) {
+void launch_graph_count(umx_engine* eng, hipStream_t s, PosPtr d_pos, long nt, int* deg, int* cand, long lo, long hi, long img0) {
+  if (d_pos.d) launch_graph_count_of(eng, s, d_pos.d, nt, deg, cand, lo, hi, img0);
+  else launch_graph_count_of(eng, s, d_pos.f, nt, deg, cand, lo, hi, img0);
+}
+template <typename P>
+void launch_graph_fill_of(umx_engine* eng, hipStream_t s, bool trunc, const P* d_pos, long nn, const int* cand, const int* row_ptr, int* esrc, int* edst,
+                          float* evec, long lo, long hi, long img0) {
   const float rc2 = eng->cutoff * eng->cutoff;
   const dim3 grid(nblk(nn, 4)), block(256);
   const int N = eng->natoms, mn = eng->max_neigh;
   if (eng->pbc_on && eng->n_cells > 0) {
-    const PeriodicImages pi{eng->d_cells, (int)img0};
-    if (trunc) hipLaunchKernelGGL((k_graph_fill<true, true, true>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, pi);
-    else hipLaunchKernelGGL((k_graph_fill<false, true, true>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, pi);
-  } else if (eng->pbc_on) {
-    if (trunc) hipLaunchKernelGGL((k_graph_fill<true, true>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, eng->per);
-    else hipLaunchKernelGGL((k_graph_fill<false, true>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, eng->per);
+    const auto pi = periodic_arg<true, P>(eng, img0);
+    if (trunc) hipLaunchKernelGGL((k_graph_fill<true, true, true, P>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, pi);
+    else hipLaunchKernelGGL((k_graph_fill<false, true, true, P>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, pi);
   } else {
-    if (trunc) hipLaunchKernelGGL((k_graph_fill<true, false>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, Periodic());
-    else hipLaunchKernelGGL((k_graph_fill<false, false>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, Periodic());
+    const auto per = periodic_arg<false, P>(eng, 0, eng->pbc_on);
+    if (eng->pbc_on) {
+      if (trunc) hipLaunchKernelGGL((k_graph_fill<true, true, false, P>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, per);
+      else hipLaunchKernelGGL((k_graph_fill<false, true, false, P>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, per);
+    } else {
+      if (trunc) hipLaunchKernelGGL((k_graph_fill<true, false, false, P>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, per);
+      else hipLaunchKernelGGL((k_graph_fill<false, false, false, P>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, per);
+    }
   }
+}
+void launch_graph_fill(umx_engine* eng, hipStream_t s, bool trunc, PosPtr d_pos, long nn, const int* cand, const int* row_ptr, int* esrc, int* edst,
+                       float* evec, long lo, long hi, long img0) {
+  if (d_pos.d) launch_graph_fill_of(eng, s, trunc, d_pos.d, nn, cand, row_ptr, esrc, edst, evec, lo, hi, img0);
+  else launch_graph_fill_of(eng, s, trunc, d_pos.f, nn, cand, row_ptr, esrc, edst, evec, lo, hi, img0);
 }
 
 }  // namespace

@@ -62,7 +62,7 @@ int radial_bwd(umx_engine* eng, const WS& w, const RadialW& r, int slot, long ne
 // vir.out != nullptr: the chunk's final segment also takes the virial of its images (umx_virial.h)
 // img0: the index within the call of the chunk's first image (d_pos, d_deg, d_cand and the outputs start there; per-image cells are
 // indexed by it)
-void plan_chunk(umx_engine* eng, WS& w, const float* d_pos, const int* d_deg, const int* d_cand, long img0, long nimg, long ne, double* d_energy,
+void plan_chunk(umx_engine* eng, WS& w, const PosPtr d_pos, const int* d_deg, const int* d_cand, long img0, long nimg, long ne, double* d_energy,
                 float* d_forces, Plan& P, const VirialOut vir = VirialOut()) {
   const int N = eng->natoms;
   const long nn = nimg * N;
@@ -564,7 +564,7 @@ int read_degree_pass(umx_engine* eng, hipStream_t s, const int* d_cnt, size_t n,
 struct ImageEdges { std::vector<int> per_image; long emax = 0, etot = 0; };
 
 // degrees of every node of every image, per-image edge totals; sets last_edges / last_maxdeg / may_truncate
-int degree_pass(umx_engine* eng, hipStream_t s, long K, const float* d_pos, ImageEdges& ie) {
+int degree_pass(umx_engine* eng, hipStream_t s, long K, const PosPtr d_pos, ImageEdges& ie) {
   const int N = eng->natoms;
   const long nt = K * N;
   if (eng->deg_all_cap < nt) CHK(grow(eng, eng->deg_all_cap, nt, {s}, {DevBuf(eng->d_deg_all, nt), DevBuf(eng->d_cand_all, nt)}));
@@ -588,7 +588,7 @@ int degree_pass(umx_engine* eng, hipStream_t s, long K, const float* d_pos, Imag
 // sum.  Memory per directed edge drops from ~120 KB to ~72 KB + 48 KB / P, i.e. a single image of up to ~1.5x the atoms fits the same
 // HBM; node-level work (< 3 %) is done P times.  Used automatically when one image exceeds the workspace budget.
 // img: the image's index within the call (d_pos and the outputs are the image's own)
-int eval_partitioned(umx_engine* eng, hipStream_t s, long img, const float* d_pos, double* d_energy, float* d_forces, double* d_virial, int P, size_t budget,
+int eval_partitioned(umx_engine* eng, hipStream_t s, long img, const PosPtr d_pos, double* d_energy, float* d_forces, double* d_virial, int P, size_t budget,
                      int64_t* edges_out, int* maxdeg_out) {
   const int N = eng->natoms;
   if (P < 2 || P > 16) return fail(eng, UMX_ERR_ARG, "eval_partitioned: 2..16 partitions");
@@ -664,14 +664,14 @@ int eval_partitioned(umx_engine* eng, hipStream_t s, long img, const float* d_po
 
 // partition fallback: one image does not fit the budget in one piece (or UMX_FORCE_PARTS) -- image by image, in as few target-node
 // partitions as fit.  `why`: the capacity message of the ordinary planning.
-int eval_images_partitioned(umx_engine* eng, hipStream_t s, long K, const float* d_pos, double* d_energy, float* d_forces, size_t budget, const std::string why) {
+int eval_images_partitioned(umx_engine* eng, hipStream_t s, long K, const PosPtr d_pos, double* d_energy, float* d_forces, size_t budget, const std::string why) {
   const int N = eng->natoms;
   int64_t etot = 0; int mdeg = 0;
   for (long k = 0; k < K; ++k) {
     int stp = UMX_ERR_CAPACITY;
     for (int parts = eng->force_parts >= 2 ? eng->force_parts : 2; parts <= 16 && stp == UMX_ERR_CAPACITY; parts = eng->force_parts >= 2 ? 17 : parts + 1) {
       int64_t e1 = 0; int m1 = 0;
-      stp = eval_partitioned(eng, s, k, d_pos + k * N * 3, d_energy + k, d_forces ? d_forces + k * N * 3 : nullptr,
+      stp = eval_partitioned(eng, s, k, d_pos.atom(k * N), d_energy + k, d_forces ? d_forces + k * N * 3 : nullptr,
                              eng->vir_out ? eng->vir_out + k * 9 : nullptr, parts, budget, &e1, &m1);
       if (stp == UMX_OK) { etot += e1; mdeg = std::max(mdeg, m1); eng->last_parts = parts; }
     }
@@ -809,7 +809,7 @@ int prepare_arena(umx_engine* eng, hipStream_t s, const ImageEdges& ie, const Ch
 
 // ---- execution ---------------------------------------------------------------------------------------
 // issue the chunks' plans: one after another on s, or in pairs on the two lanes
-int run_chunks(umx_engine* eng, hipStream_t s, int lanes, const ImageEdges& ie, const Chunks& c, WS (&wl)[2], const float* d_pos, double* d_energy, float* d_forces) {
+int run_chunks(umx_engine* eng, hipStream_t s, int lanes, const ImageEdges& ie, const Chunks& c, WS (&wl)[2], const PosPtr d_pos, double* d_energy, float* d_forces) {
   const int N = eng->natoms;
   int st = UMX_OK;
   auto plan_of = [&](size_t ci, int lane, Plan& P) {
@@ -818,7 +818,7 @@ int run_chunks(umx_engine* eng, hipStream_t s, int lanes, const ImageEdges& ie, 
     for (long k = k0; k < k1; ++k) e += ie.per_image[k];
     VirialOut vir;       // the partials' slots follow the image's position in the call: the two lanes never share one
     if (eng->vir_out && d_forces) { vir.out = eng->vir_out + k0 * 9; vir.part = eng->d_vir_part + k0 * eng->vir_slabs * 9; vir.slabs = eng->vir_slabs; }
-    plan_chunk(eng, wl[lane], d_pos + k0 * N * 3, eng->d_deg_all + k0 * N, eng->d_cand_all + k0 * N, k0, k1 - k0, e, d_energy + k0,
+    plan_chunk(eng, wl[lane], d_pos.atom(k0 * N), eng->d_deg_all + k0 * N, eng->d_cand_all + k0 * N, k0, k1 - k0, e, d_energy + k0,
                d_forces ? d_forces + k0 * N * 3 : nullptr, P, vir);
   };
   if (lanes == 2) {          // chunks in pairs, one per lane, matrix segments alternating between the lanes (run_plans_alternating)
@@ -858,7 +858,7 @@ int run_chunks(umx_engine* eng, hipStream_t s, int lanes, const ImageEdges& ie, 
 }
 
 // Plan and run one evaluation with the kind of plan eng->rc_active names: budget, lanes, chunks (or partitions), arena, execution.
-int evaluate_planned(umx_engine* eng, hipStream_t s, long K, const float* d_pos, double* d_energy, float* d_forces, const ImageEdges& ie) {
+int evaluate_planned(umx_engine* eng, hipStream_t s, long K, const PosPtr d_pos, double* d_energy, float* d_forces, const ImageEdges& ie) {
   // cap_nodes / cap_edges say what the arena holds in ws_bytes of ONE kind of plan: after a change of kind it is carved (and sized) anew
   if (eng->arena_rc != eng->rc_active) { eng->cap_nodes = 0; eng->cap_edges = 0; eng->arena_rc = eng->rc_active; eng->arena_keep = true; }
   size_t budget = 0;
@@ -905,7 +905,7 @@ int evaluate_planned(umx_engine* eng, hipStream_t s, long K, const float* d_pos,
 // helper launches there; it is restored on every exit path.
 // d_virial: [n_images][9] float64 or nullptr (then nothing of umx_virial.h runs).  Graph-parallel entry (eng->gp): the degree pass
 // below counts this rank's own edges only, so the partial slots are sized for the rank's share, and d_virial receives that share.
-int energy_forces_on(umx_engine* eng, hipStream_t run_stream, int n_images, const float* d_pos, double* d_energy, float* d_forces,
+int energy_forces_on(umx_engine* eng, hipStream_t run_stream, int n_images, PosPtr d_pos, double* d_energy, float* d_forces,
                      double* d_virial = nullptr) {
   hipStream_t own = eng->stream;
   eng->stream = run_stream;

@@ -41,7 +41,7 @@ def mask_frozen(forces: np.ndarray, frozen: Sequence[int]) -> np.ndarray:
 @with_small_host_math
 def fd_hessian(batch_forces: Callable[[np.ndarray], np.ndarray], coord_ang: np.ndarray, frozen: Sequence[int], *, device,
                double: bool, partial: bool, batch: int = 64, step: float = FD_STEP_ANG, shard: bool = False, group=None, engine=None,
-               batch_forces_dev: Optional[Callable] = None):
+               batch_forces_dev: Optional[Callable] = None, double_positions: bool = False):
     """Central-difference Hessian in eV/A^2 as a torch tensor (n_out, 3, n_out, 3) on `device`.
 
     batch_forces(coords[K,N,3]) -> forces [K,N,3] float32.  Columns of frozen DOF stay zero (full output) or are
@@ -51,6 +51,11 @@ def fd_hessian(batch_forces: Callable[[np.ndarray], np.ndarray], coord_ang: np.n
     float32 [K,N,3] on `device```.  With it the displaced geometries are built on the device (float64 base point +- step, rounded to the
     model's float32 positions exactly as the host path rounds them) and forces never leave it: no PCIe copy of 2 x 64 x N x 3 floats per
     call (``UMAcore.compute_batch_dev``: the engine's device-pointer entry on torch's current stream).  Same columns, bit for bit.
+
+    double_positions: False (default) -- the displaced geometries are rounded to the model's float32 positions, so the realised
+    displacement is `step` only to half an ulp of the coordinate (a fraction of a percent of a column at 50 A from the origin, several
+    percent at 1000 A).  True -- they stay float64 on both paths (`batch_forces` receives the float64 array it always did and must not
+    round it; `batch_forces_dev` receives a float64 tensor): the displacement is `step` to float64's rounding wherever the frame sits.
 
     Multi-GPU is OPT-IN: ``shard=True`` makes this call a COLLECTIVE over `group` (default: the world).
     Every rank of the group must enter it with the same geometry and frozen set; active columns are dealt round-robin
@@ -109,7 +114,8 @@ def fd_hessian(batch_forces: Callable[[np.ndarray], np.ndarray], coord_ang: np.n
                 rows = torch.arange(m, device=device)
                 disp_t[2 * rows, ct] += step
                 disp_t[2 * rows + 1, ct] -= step
-                f = batch_forces_dev(disp_t.reshape(2 * m, n, 3).to(torch.float32)).reshape(2 * m, dof).to(dtype)
+                disp_t = disp_t.reshape(2 * m, n, 3)
+                f = batch_forces_dev(disp_t if double_positions else disp_t.to(torch.float32)).reshape(2 * m, dof).to(dtype)
                 hess[:, ct] = (-(f[0::2] - f[1::2]) / (2.0 * step)).T
                 continue
             disp = np.repeat(x0[None], 2 * len(cols), axis=0)

@@ -413,6 +413,10 @@ def shared_workspace_limits(devices: Sequence[int], free_bytes: Callable[[int], 
     return out
 
 
+GP_FLOAT32_ONLY = ("graph_parallel=True with double_positions=True: the graph-parallel entries (umx_gp_begin[_virial]) take float32 "
+                   "positions only -- leave one of the two off (a single geometry with double positions runs on engine 0)")
+
+
 class LocalEnginePool:
     """G engines owned by ONE process, one per listed device ordinal, all with the same weights, precision mode and system.
 
@@ -604,9 +608,9 @@ class LocalEnginePool:
             if not getattr(eng, "widened", False):
                 eng.widen(why)
 
-    def _images(self, pos_ang) -> np.ndarray:
-        """(K,N,3) float32 of what a caller passed as (K,N,3) or (N,3)."""
-        p = np.ascontiguousarray(pos_ang, dtype=np.float32)
+    def _images(self, pos_ang, double_positions: bool = False) -> np.ndarray:
+        """(K,N,3) float32 -- float64 with ``double_positions`` -- of what a caller passed as (K,N,3) or (N,3)."""
+        p = np.ascontiguousarray(pos_ang, dtype=np.float64 if double_positions else np.float32)
         if p.ndim == 2:
             p = p[None]
         if p.ndim != 3 or p.shape[1] != self.natoms or p.shape[2] != 3:
@@ -633,21 +637,28 @@ class LocalEnginePool:
             break
         return res
 
-    def energy_forces(self, pos_ang, forces: bool = True) -> Tuple[np.ndarray, Optional[np.ndarray]]:
-        """pos_ang: (K,N,3) or (N,3) Angstrom -> (E [K] eV float64, F [K,N,3] eV/A float32 | None): ``Engine.energy_forces`` over the pool."""
-        p = self._images(pos_ang)
+    def energy_forces(self, pos_ang, forces: bool = True, double_positions: bool = False) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        """pos_ang: (K,N,3) or (N,3) Angstrom -> (E [K] eV float64, F [K,N,3] eV/A float32 | None): ``Engine.energy_forces`` over the pool.
+
+        double_positions (``Engine.energy_forces``): batches are dealt as before, every engine taking its block as float64.  A SINGLE
+        geometry is then evaluated on engine 0 alone (``last_route == "single"``), not graph-parallel: the graph-parallel entry
+        (``umx_gp_begin``) takes float32 positions only."""
+        from .engine import dp_kw
+
+        p = self._images(pos_ang, double_positions)
+        kw = dp_kw(double_positions)
         if p.shape[0] == 1:
             self._bind_cells(1, None)
-            if self.gp and len(self.engines) > 1 and self.recompute != 2:
+            if self.gp and len(self.engines) > 1 and self.recompute != 2 and not double_positions:
                 return self._graph_parallel(p[0], forces)
             self.last_route, self.last_blocks = "single", [(0, 1)]
-            return self.engines[0].energy_forces(p, forces=forces)
-        res = self._deal(p, lambda eng, block: eng.energy_forces(block, forces=forces))
+            return self.engines[0].energy_forces(p, forces=forces, **kw)
+        res = self._deal(p, lambda eng, block: eng.energy_forces(block, forces=forces, **kw))
         e = np.concatenate([r[0] for r in res])
         f = np.concatenate([r[1] for r in res]) if forces else None
         return e, f
 
-    def energy_forces_virial(self, pos_ang, graph_parallel: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def energy_forces_virial(self, pos_ang, graph_parallel: bool = False, double_positions: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """``Engine.energy_forces_virial`` over the pool: (E [K], F [K,N,3], W [K,3,3] float64).  A batch is dealt over the engines in
         the same contiguous blocks as ``energy_forces`` and is the single-engine result bit for bit (W does not depend on the batch an
         image is in).  A SINGLE geometry is evaluated on engine 0 alone by default (``last_route == "single"``: the single-engine W, bit
@@ -655,8 +666,15 @@ class LocalEnginePool:
         ``last_route == "graph-parallel"``): an image that needs the pool's combined memory, all engines at work; every engine's share
         of W (``last_partials``) is added in engine order in float64 on the host.  That W differs from engine 0's as the graph-parallel
         forces do, at float32 summation order.  The opt-in cannot run with recompute mode 2 (a one-GPU plan): ``ValueError``, no silent
-        fallback.  It says nothing about batches."""
-        p = self._images(pos_ang)
+        fallback.  It says nothing about batches.
+        double_positions (``Engine.energy_forces_virial``): batches as before; a single geometry on engine 0.  Together with
+        ``graph_parallel=True`` it raises ``ValueError``: the graph-parallel entries take float32 positions only."""
+        from .engine import dp_kw
+
+        if graph_parallel and double_positions:
+            raise ValueError(GP_FLOAT32_ONLY)
+        p = self._images(pos_ang, double_positions)
+        kw = dp_kw(double_positions)
         if p.shape[0] == 1:
             if graph_parallel and len(self.engines) > 1:
                 if self.recompute == 2:
@@ -666,18 +684,20 @@ class LocalEnginePool:
                 return self._graph_parallel(p[0], True, virial=True)
             self._bind_cells(1, None)
             self.last_route, self.last_blocks = "single", [(0, 1)]
-            return self.engines[0].energy_forces_virial(p)
-        res = self._deal(p, lambda eng, block: eng.energy_forces_virial(block))
+            return self.engines[0].energy_forces_virial(p, **kw)
+        res = self._deal(p, lambda eng, block: eng.energy_forces_virial(block, **kw))
         return tuple(np.concatenate([r[i] for r in res]) for i in range(3))
 
-    def energy_forces_stress(self, pos_ang, graph_parallel: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def energy_forces_stress(self, pos_ang, graph_parallel: bool = False, double_positions: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """``Engine.energy_forces_stress`` over the pool: (E [K], F [K,N,3], stress [K,6] eV/A^3, Voigt xx, yy, zz, yz, xz, xy), routed
         as ``energy_forces_virial`` (``graph_parallel`` included); ``ValueError`` unless the cell (``set_cell``) is periodic along all
-        three axes.  With per-image cells (``set_cells``) image k is divided by the volume of cell k."""
-        from .engine import voigt_stress
+        three axes.  With per-image cells (``set_cells``) image k is divided by the volume of cell k.  ``double_positions`` as there."""
+        from .engine import dp_kw, voigt_stress
 
+        if graph_parallel and double_positions:
+            raise ValueError(GP_FLOAT32_ONLY)                                 # before the cell is looked at, as energy_forces_virial says it
         vol = self.engines[0].cell_volume() if self._cells is None else self.cell_volumes()
-        e, f, w = self.energy_forces_virial(pos_ang, graph_parallel=True) if graph_parallel else self.energy_forces_virial(pos_ang)
+        e, f, w = self.energy_forces_virial(pos_ang, graph_parallel=graph_parallel, **dp_kw(double_positions))
         return e, f, voigt_stress(w, vol)
 
     def _gp_buffers(self):

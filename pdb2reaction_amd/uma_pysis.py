@@ -160,6 +160,7 @@ class UMAcore:
         r_edges: bool = False,
         precision: Optional[str] = None,
         recompute: Optional[int] = None,
+        double_positions: bool = False,
     ):
         from .engine import Engine  # raises ImportError loudly when libumx.so is missing
 
@@ -180,6 +181,9 @@ class UMAcore:
         self._max_neigh_user = max_neigh
         self._radius_user = radius
         self._r_edges_user = r_edges
+        # False: positions are rounded to float32 before the engine sees them (the reference's AtomicData.pos, :312-322).  True: the float64
+        # geometry goes through (Engine.energy_forces(double_positions=True)): edge vectors from float64 differences
+        self.double_positions = bool(double_positions)
 
         weights = resolve_weights(model)                    # raises FileNotFoundError before any GPU work
         # graph defaults come from the MODEL, as in the reference (backbone.cutoff / backbone.max_neighbors, fallback 6.0 A;
@@ -260,6 +264,9 @@ class UMAcore:
         if not on:
             self._gp = None
             return
+        if getattr(self, "double_positions", False):
+            raise ValueError("enable_graph_parallel: double_positions=True cannot be combined with the graph-parallel mode -- its entry "
+                             "(umx_gp_begin) takes float32 positions only")
         if self._pool is not None:
             raise RuntimeError("enable_graph_parallel: this core evaluates on an in-process pool of engines (workers > 1 without a process "
                                "group); the rank-level graph-parallel mode needs one engine per rank")
@@ -291,22 +298,33 @@ class UMAcore:
         if getattr(self, "_gp", None) is not None:
             e, f = self._gp_eval(coords_ang)
             return {"energy": e, "forces": f if forces else None}
-        e, f = (getattr(self, "_pool", None) or self.engine).energy_forces(np.asarray(coords_ang), forces=forces)
+        e, f = (getattr(self, "_pool", None) or self.engine).energy_forces(np.asarray(coords_ang), forces=forces, **self._dp_kw())
         return {"energy": e, "forces": f}
+
+    def _dp_kw(self) -> dict:
+        """``double_positions=True`` for the engine (or pool) when this core was built with it; nothing otherwise (the calls as they were)."""
+        return {"double_positions": True} if getattr(self, "double_positions", False) else {}
 
     def compute_batch_dev(self, pos32):
         """Device form of :meth:`compute_batch` for loops that stay on the GPU (the batched FD Hessian): ``pos32`` torch float32 [K,N,3] on
         the engine's device -> forces torch float32 [K,N,3] on the same device, through the engine's device-pointer entry on torch's
         current stream.  That entry is asynchronous and cannot refuse a non-finite energy itself, so the energies are looked at here (one
-        scalar read per call); a range violation of the fast split-f16 mode widens the engine and repeats the call, as the host entry does."""
+        scalar read per call); a range violation of the fast split-f16 mode widens the engine and repeats the call, as the host entry does.
+        A core built with ``double_positions=True`` takes a torch float64 tensor instead (``umx_energy_forces_f64_dev``).  The pointer
+        entry cannot see the type behind its pointer, so the tensor's dtype is held to the flag here: ``TypeError`` otherwise."""
         import torch
 
+        dp = self._dp_kw()
+        want = torch.float64 if dp else torch.float32
+        if pos32.dtype != want:
+            raise TypeError(f"compute_batch_dev: positions are {pos32.dtype}, this core takes {want} "
+                            f"(double_positions={bool(dp)})")
         k = int(pos32.shape[0])
         pos32 = pos32.contiguous()
         e = torch.empty(k, dtype=torch.float64, device=pos32.device)
         f = torch.empty(k, pos32.shape[1], 3, dtype=torch.float32, device=pos32.device)
         for attempt in range(2):
-            self.engine.energy_forces_dev(k, pos32.data_ptr(), e.data_ptr(), f.data_ptr(), stream=torch.cuda.current_stream(pos32.device).cuda_stream)
+            self.engine.energy_forces_dev(k, pos32.data_ptr(), e.data_ptr(), f.data_ptr(), stream=torch.cuda.current_stream(pos32.device).cuda_stream, **dp)
             if bool(torch.isfinite(e).all()):
                 return f
             self.engine.take_range_error()
@@ -326,7 +344,8 @@ class UMAcore:
         if getattr(self, "_gp", None) is not None:
             e, f = self._gp_eval(coord_ang)
         else:
-            e, f = (getattr(self, "_pool", None) or self.engine).energy_forces(np.asarray(coord_ang, dtype=np.float64).reshape(1, -1, 3), forces=forces)
+            e, f = (getattr(self, "_pool", None) or self.engine).energy_forces(np.asarray(coord_ang, dtype=np.float64).reshape(1, -1, 3), forces=forces,
+                                                                               **self._dp_kw())
         return {"energy": float(e[0]), "forces": (f[0] if forces else None), "hessian": None}
 
 
@@ -368,6 +387,10 @@ class uma_pysis(Calculator):
         recompute = kwargs.pop("recompute", None)
         if recompute not in (None, 0, 1, 2):
             raise ValueError(f"recompute must be 0, 1 or 2, got {recompute!r}")
+        # likewise: False (default) keeps the reference's float32 positions (AtomicData.pos, :312-322); True passes the float64 geometry
+        # through get_energy / get_forces / get_forces_batch / get_hessian to the engine (edge vectors from float64 differences, FD
+        # displacements realised in float64).  Not with the graph-parallel mode.
+        self.double_positions = bool(kwargs.pop("double_positions", False))
         super().__init__(charge=charge, mult=spin, **kwargs)
         self._core: Optional[UMAcore] = None
         self._core_kw = dict(
@@ -375,6 +398,8 @@ class uma_pysis(Calculator):
             workers_per_node=workers_per_node, max_neigh=max_neigh, radius=radius, r_edges=r_edges, precision=precision,
             recompute=recompute,
         )
+        if self.double_positions:                 # (only then: a stand-in core keeps the reference's signature)
+            self._core_kw["double_positions"] = True
         self._reserve_images = 0
         self.out_hess_torch = out_hess_torch
         self.hessian_calc_mode = hessian_calc_mode
@@ -455,7 +480,8 @@ class uma_pysis(Calculator):
                                             and getattr(core.device, "type", "cpu") == "cuda") else None
         hess = H.fd_hessian(lambda c: core.compute_batch(c, forces=True)["forces"], coord_ang, self.freeze_atoms, device=core.device,
                             double=self.hessian_double, partial=self.return_partial_hessian, batch=FD_BATCH,
-                            shard=self._hess_shard, group=self._hess_group, engine=getattr(core, "engine", None), batch_forces_dev=dev_fn)
+                            shard=self._hess_shard, group=self._hess_group, engine=getattr(core, "engine", None), batch_forces_dev=dev_fn,
+                            **({"double_positions": True} if self.double_positions else {}))
         # (a pool that widens in the middle of this Hessian widens ALL its engines, engine 0 -- `engine` above -- included, so fd_hessian's
         # "compute every column again" rule sees it)
         return {"energy": base["energy"], "forces": base["forces"], "hessian": hess}
