@@ -69,6 +69,7 @@ __device__ __forceinline__ void q3_issue(const unsigned char* A, const unsigned 
 //   fp16, 2 x 3 planes, 4 products: hh, hl, lh and A_hi . B_lo2 -- the weights (B, 33 bits in three half planes) are EXACT, so their
 //         rounding cannot bias every atom the same way (two-plane weights shift the c3 energy by +2.5e-8 eV/atom, NOTES.md section 5);
 //         the activations keep 22 bits with unbiased per-element rounding; dropped: A_lo . B_mid (2^-22, random sign) and below
+//         (hl, lh and A_hi . B_lo2 are summed apart per k-step and join the hh accumulator through one float32 add, see the k loop)
 //   fp16, 2 x 2 planes, 3 or 4 products: hh, hl, lh (+ ll)
 __host__ __device__ constexpr bool q_use_product(int PA, int PB, int NPROD, int qa, int qb) {
   if (PA == 3 && PB == 3) return qa + qb < 3;
@@ -256,6 +257,33 @@ __global__ __launch_bounds__(512, 1) void umx_gemm_q_kernel(const GemmPL p) {
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][0], acc[i][j], 0, 0, 0);
 #pragma unroll
           for (int r = 0; r < 16; ++r) {      // scalar adds (an opaque asm per element): a vector add would be selected as v_pk_add_f32 (NOTES 5 item 14)
+            float v = lo[r];
+            asm("" : "+v"(v));
+            acc[i][j][r] += v;
+          }
+        }
+    } else if constexpr (F16 && P == 2 && PB == 3 && NPROD == 4) {
+      // The engine's fp16 form.  The three small products of a k-step -- A_hi . B_mid, A_lo . B_hi (2^-11 of the leading one) and
+      // A_hi . B_lo2 (the last bits of the float32 weight: about 2^-24 of it, below half an ulp of the running sum) -- are summed in a zero
+      // accumulator `lo`; only A_hi . B_hi goes straight into acc, and lo joins it through ONE float32 add per k-step.  Why, as for LS above:
+      // v_mfma_f32_32x32x16_f16 aligns its 16 products to the largest addend and cuts them towards zero a few bits below that addend's ulp
+      // (csrc/mfma_bias.hip, f16 rows).  Beside an accumulator that carries all earlier k-tiles and the bias, most bits of an A_hi . B_lo2
+      // product fall under the cut; in lo the largest addend is 2^-11 of the sum and the cut lies far below every product.  The add rounds to
+      // nearest, and A_hi . B_lo2 has to reach it TOGETHER with the 2^-11-order products: their low bits spread lo evenly over the
+      // accumulator's grid, so the rounding passes a term smaller than half an ulp without bias, whereas that term alone, added to a value
+      // on the grid, would round away whole.  Figures: profiles/forward_links.txt.  Both tile widths fold at the same point, every k-step:
+      // an image gets the same bits alone and in a batch (choose_pl picks the width from M).
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < TNW; ++j) {
+          f32x16 lo = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+          lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a[i][0]), __builtin_bit_cast(f16x8_t, b[j][2]), lo, 0, 0, 0);
+          lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a[i][0]), __builtin_bit_cast(f16x8_t, b[j][1]), lo, 0, 0, 0);
+          lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a[i][1]), __builtin_bit_cast(f16x8_t, b[j][0]), lo, 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a[i][0]), __builtin_bit_cast(f16x8_t, b[j][0]), acc[i][j], 0, 0, 0);
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {      // scalar adds (an opaque asm per element: no v_pk_add_f32, NOTES 5 item 14)
             float v = lo[r];
             asm("" : "+v"(v));
             acc[i][j][r] += v;

@@ -31,6 +31,7 @@ int radial_fwd_fc3(umx_engine* eng, const WS& w, const RadialW& r, long ne, floa
 }
 int radial_fwd(umx_engine* eng, const WS& w, const RadialW& r, int slot, long ne, float* rad_out) {
   CHK(radial_fwd_head(eng, w, r, slot, ne));
+  if (eng->dbg_on && !eng->prec.planes) DBG("a2." + std::to_string(slot), w.ra, ne * RH);       // (debug) fp32 mode: the fc3 operand rows behind the head
   return radial_fwd_fc3(eng, w, r, ne, rad_out);
 }
 
@@ -98,6 +99,10 @@ void plan_chunk(umx_engine* eng, WS& w, const PosPtr d_pos, const int* d_deg, co
       // (debug) the fc3 A operand exactly as the GEMM reads it: float32 quad-row blocks, odd rows negated -- tests/test_gpu_mfma_model.py holds the
       // GEMM's output against the bit-exact model of the matrix core on exactly these bits
       if (eng->prec.planes && eng->prec.fwd_fmt == 3) DBG("a2q.deg", reinterpret_cast<const float*>(w.a2pl), (ne + 3) / 4 * 4 * RH);
+      // (debug) the fast mode's operand: the raw halves of the two-plane "Q2H" blocks (umx_kernels_pl.h), 4-row-padded rows x columns x 2;
+      // fp32 mode: the float32 rows of the fc3 operand -- tests/test_gpu_forward_links.py
+      if (eng->prec.planes && eng->prec.fwd_fmt == 1) DBG("a2h.deg", w.a2pl, (ne + 3) / 4 * 4 * RH * 2);
+      if (!eng->prec.planes) DBG("a2.deg", w.ra, ne * RH);
       CHK(radial_fwd_fc3(eng, w, eng->rdeg, ne, w.rad_deg));
     }
     // x0 = node init + sum over incoming edges (one kernel, the base added in double); graph-parallel: the bare partial sum goes to G1 and is
@@ -133,6 +138,7 @@ void plan_chunk(umx_engine* eng, WS& w, const PosPtr d_pos, const int* d_deg, co
       });
       P.matrix([=, &w]() -> int {
         if (eng->prec.fwd_fmt == 3) DBG("a2q." + std::to_string(i), reinterpret_cast<const float*>(w.a2pl), (ne + 3) / 4 * 4 * RH);
+        if (eng->prec.fwd_fmt == 1) DBG("a2h." + std::to_string(i), w.a2pl, (ne + 3) / 4 * 4 * RH * 2);
         return radial_fwd_fc3(eng, w, Lp->rad, ne, w.rad[i]);
       });
       P.stream([=, &w]() -> int {
@@ -145,6 +151,7 @@ void plan_chunk(umx_engine* eng, WS& w, const PosPtr d_pos, const int* d_deg, co
       // SO(2) conv 1 on the pre-modulated planes -> hg = [gate | hpre]
       P.matrix([=, &w]() -> int {
         if (eng->prec.fwd_fmt == 3) DBG("y1q." + std::to_string(i), reinterpret_cast<const float*>(w.y1pl), (ne + 3) / 4 * 4 * XROT);     // (debug) conv-1's A operand as the GEMMs read it
+        if (eng->prec.fwd_fmt == 1) DBG("y1h." + std::to_string(i), w.y1pl, (ne + 3) / 4 * 4 * XROT * 2);
         CHK(gemm_pl(eng, 0, FWD, w.y1pl, XROT, 0, 0, Lp->c1m0, 0, Lp->c1m0b, w.hg[i], HG, 0, 0, ne, 640, 768, 1.0f));
         CHK(gemm_pl(eng, 1, FWD, w.y1pl, XROT, 768, 1280, Lp->c1m1, 256, nullptr, w.hg[i], HG, 640, 896, ne, 256, 512, 1.0f));
         return gemm_pl(eng, 1, FWD, w.y1pl, XROT, 1792, 2048, Lp->c1m2, 128, nullptr, w.hg[i], HG, 1152, 1280, ne, 128, 256, 1.0f);
@@ -158,6 +165,7 @@ void plan_chunk(umx_engine* eng, WS& w, const PosPtr d_pos, const int* d_deg, co
       });
       P.matrix([=, &w]() -> int {
         if (eng->prec.fwd_fmt == 3) DBG("hidq." + std::to_string(i), reinterpret_cast<const float*>(w.hidpl), (ne + 3) / 4 * 4 * ROW);      // (debug) conv-2's A operand
+        if (eng->prec.fwd_fmt == 1) DBG("hidh." + std::to_string(i), w.hidpl, (ne + 3) / 4 * 4 * ROW * 2);
         CHK(gemm_pl(eng, 0, FWD, w.hidpl, ROW, 0, 0, Lp->c2m0, 0, Lp->c2m0b, w.msg[i], ROW, 0, 0, ne, 384, 384, 1.0f));
         CHK(gemm_pl(eng, 1, FWD, w.hidpl, ROW, 384, 640, Lp->c2m1, 256, nullptr, w.msg[i], ROW, 384, 640, ne, 256, 256, 1.0f));
         return gemm_pl(eng, 1, FWD, w.hidpl, ROW, 896, 1024, Lp->c2m2, 128, nullptr, w.msg[i], ROW, 896, 1024, ne, 128, 128, 1.0f);

@@ -22,7 +22,7 @@ oracle/staged.py spells them) or are written plainly below; none is transcribed 
 
 Modes: bf16x3 (float32 quad-row operands, the fused k_modrot_bwd_pl<0> that production runs in every mode), split-bf16 (the same forward
 kernels: its reverse links only, two PL planes), fp32 (the plain row kernels; with captures on its reverse pass is the unfused one).  The
-fast mode's fp16 forward operands (k_*_q3<1>) have no capture and are out of scope.
+fast mode's fp16 forward operands (k_*_q3<1>) are held by tests/test_gpu_forward_links.py, with the links of this file.
 
 Sizes (preconditions asserted from the captured row_ptr / out_ptr / ne): S = 40 atoms, 1142 edges; L = 700 atoms, 44404 edges, layers 0 and
 3 only; T1 = 17 atoms with max_neigh 3 (51 edges, two nodes without out-edges) and T2 = 13 atoms with max_neigh 5 (65 edges): truncated
