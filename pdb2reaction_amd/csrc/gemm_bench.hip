@@ -1,5 +1,5 @@
 // gemm_bench.hip -- dev micro-benchmark / correctness check for the GEMM kernels (not part of libumx.so).
-// usage: gemm_bench M N K
+// usage: gemm_bench M N K | gemm_bench f16 M N K | gemm_bench half [M]
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -321,7 +321,63 @@ static int f16_mode(long M, int N, int K) {
   return 0;
 }
 
+// ---- `gemm_bench half [M]`: the half-height forms of the engine's forward bf16x3 kernels (umx_gemm_q.h MW = 2: 128-row tiles, 256 threads, two
+// workgroups per CU) beside the 256-row forms at the c3 shapes -- conv-1 m = 0 (N 640, K 768) and conv-2 m = 0 (384, 384) on the narrow LS = 2
+// kernel, fc3 (1536, 128) on the wide LS = 1 kernel, one complex product (N 256, K 512) -- time per launch and a count of differing output words
+__global__ void k_count_diff(const unsigned int* __restrict__ a, const unsigned int* __restrict__ b, long n, unsigned long long* __restrict__ out) {
+  unsigned long long d = 0;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) d += a[i] != b[i];
+  if (d) atomicAdd(out, d);
+}
+static int half_mode(long M) {
+  struct Shape { const char* name; int cplx, wide, N, K, a_cols, offA1, bHalf, ldc, offCi; void (*full)(const GemmPL); void (*half)(const GemmPL); };
+  const Shape shapes[] = {
+      {"conv-1 m0  plain 256x128 LS=2", 0, 0, 640, 768, 768, 0, 0, 640, 0, umx_gemm_q_kernel<0, 0, 3, 2, 0, 6, 3, 1, 2, 1>, umx_gemm_q_kernel<0, 0, 3, 2, 0, 6, 3, 1, 2, 1, 2>},
+      {"conv-2 m0  plain 256x128 LS=2", 0, 0, 384, 384, 384, 0, 0, 384, 0, umx_gemm_q_kernel<0, 0, 3, 2, 0, 6, 3, 1, 2, 1>, umx_gemm_q_kernel<0, 0, 3, 2, 0, 6, 3, 1, 2, 1, 2>},
+      {"fc3        plain 256x256 LS=1", 0, 1, 1536, 128, 128, 0, 0, 1536, 0, umx_gemm_q_kernel<0, 1, 3, 2, 0, 6, 3, 1, 1, 1>, umx_gemm_q_kernel<0, 1, 3, 2, 0, 6, 3, 1, 1, 1, 2>},
+      {"conv m>0   complex 256x256", 1, 1, 256, 512, 1024, 512, 256, 512, 256, umx_gemm_q_kernel<1, 1, 3, 2, 0, 6, 3, 1>, umx_gemm_q_kernel<1, 1, 3, 2, 0, 6, 3, 1, 0, 0, 2>},
+  };
+  const long Mp = (M + 3) / 4 * 4;
+  std::vector<float> h((size_t)1 << 22); for (auto& v : h) v = (rand() / (float)RAND_MAX) * 2 - 1;
+  unsigned long long* d_nd; CK(hipMalloc(&d_nd, 8));
+  for (const Shape& sh : shapes) {
+    const int brows = sh.cplx ? 2 * sh.bHalf : sh.N;            // weight rows: complex = (A half | B half) x channel
+    float *A, *B, *C0, *C1, *bias; unsigned char *Aqf, *Bq;
+    const size_t an = (size_t)M * sh.a_cols, bn = (size_t)brows * sh.K, cn = (size_t)M * sh.ldc;
+    CK(hipMalloc(&A, an * 4)); CK(hipMalloc(&B, bn * 4)); CK(hipMalloc(&C0, cn * 4)); CK(hipMalloc(&C1, cn * 4)); CK(hipMalloc(&bias, sh.N * 4));
+    CK(hipMalloc(&Aqf, (size_t)Mp * sh.a_cols * 4)); CK(hipMalloc(&Bq, bn * 6));
+    for (size_t o = 0; o < an; o += h.size() - 977) CK(hipMemcpy(A + o, h.data() + (o % 977), std::min(h.size() - 977, an - o) * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(B, h.data() + 13, bn * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(bias, h.data() + 5, sh.N * 4, hipMemcpyHostToDevice));
+    CK(hipMemset(Aqf, 0, (size_t)Mp * sh.a_cols * 4));
+    hipLaunchKernelGGL(k_copy_qf, dim3((unsigned)((an + 255) / 256)), dim3(256), 0, 0, A, M, (long)sh.a_cols, sh.a_cols, Aqf);
+    hipLaunchKernelGGL(k_split_q<3>, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, 0, B, (long)brows, (long)sh.K, sh.K, Bq);
+    CK(hipDeviceSynchronize());
+    GemmPL g; std::memset(&g, 0, sizeof(g)); g.conj = 1.f; g.cscale = 1.f; g.odd_sign = -1.f;
+    g.Apl = reinterpret_cast<const unsigned short*>(Aqf); g.lda = 3L * sh.a_cols; g.offA0 = 0; g.offA1 = sh.offA1;
+    g.Bpl = reinterpret_cast<const unsigned short*>(Bq); g.ldb = 3L * sh.K; g.bHalf = sh.bHalf; g.bias = sh.cplx ? nullptr : bias;
+    g.ldc = sh.ldc; g.offC = 0; g.offCi = sh.offCi; g.M = (int)M; g.N = sh.N; g.K = sh.K;
+    const int bnc = (sh.wide ? 256 : 128) / (sh.cplx ? 2 : 1), nN = (sh.N + bnc - 1) / bnc;
+    auto grid = [&](int bm) { const int bmr = sh.cplx ? bm / 2 : bm; const long nM = (M + bmr - 1) / bmr; return dim3((unsigned)(((nM + 7) / 8) * 8 * nN)); };
+    GemmPL g0 = g, g1 = g; g0.Cp = C0; g1.Cp = C1;
+    CK(hipMemset(C0, 0, cn * 4)); CK(hipMemset(C1, 0xff, cn * 4));
+    const float t0 = timeit([&] { hipLaunchKernelGGL(sh.full, grid(256), dim3(512), 0, 0, g0); });
+    const float t1 = timeit([&] { hipLaunchKernelGGL(sh.half, grid(128), dim3(256), 0, 0, g1); });
+    const float t0b = timeit([&] { hipLaunchKernelGGL(sh.full, grid(256), dim3(512), 0, 0, g0); });
+    const float t1b = timeit([&] { hipLaunchKernelGGL(sh.half, grid(128), dim3(256), 0, 0, g1); });
+    CK(hipMemset(d_nd, 0, 8));
+    hipLaunchKernelGGL(k_count_diff, dim3(4096), dim3(256), 0, 0, reinterpret_cast<const unsigned int*>(C0), reinterpret_cast<const unsigned int*>(C1), (long)cn, d_nd);
+    unsigned long long nd = 0; CK(hipMemcpy(&nd, d_nd, 8, hipMemcpyDeviceToHost));
+    const double fl = (sh.cplx ? 8.0 : 2.0) * M * sh.N * sh.K * 6;       // executed plane products
+    printf("%-32s M %ld N %4d K %4d   256-row %7.3f / %7.3f ms (%6.0f TF/s executed)   128-row x2 %7.3f / %7.3f ms (%6.0f TF/s)   %+5.1f %%   differing output words %llu of %zu\n",
+           sh.name, M, sh.N, sh.K, t0, t0b, fl / std::min(t0, t0b) / 1e9, t1, t1b, fl / std::min(t1, t1b) / 1e9, 100.0 * (std::min(t1, t1b) / std::min(t0, t0b) - 1.0), nd, cn);
+    fflush(stdout);
+    CK(hipFree(A)); CK(hipFree(B)); CK(hipFree(C0)); CK(hipFree(C1)); CK(hipFree(bias)); CK(hipFree(Aqf)); CK(hipFree(Bq));
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && !strcmp(argv[1], "half")) return half_mode(argc > 2 ? atol(argv[2]) : 1140000);
   if (argc > 1 && !strcmp(argv[1], "f16")) return f16_mode(argc > 2 ? atol(argv[2]) : 569632, argc > 3 ? atoi(argv[3]) : 512, argc > 4 ? atoi(argv[4]) : 512);
   const long M = argc > 1 ? atol(argv[1]) : 569632; const int N = argc > 2 ? atoi(argv[2]) : 640, K = argc > 3 ? atoi(argv[3]) : 768;
   const long lda = 2304;

@@ -115,6 +115,7 @@ int umx_create(umx_engine** out, int device_ordinal) {
   if (const char* ev = std::getenv("UMX_GRID_F64")) e->grid_f64 = std::atoi(ev) != 0;
   if (const char* ev = std::getenv("UMX_ALT_ROWS")) e->odd_sign = std::atoi(ev) != 0 ? -1.0f : 1.0f;
   if (const char* ev = std::getenv("UMX_LOW_SEP")) e->low_sep = std::atoi(ev);
+  if (const char* ev = std::getenv("UMX_GEMM_HALF")) e->gemm_half = std::atoi(ev);
   if (const char* ev = std::getenv("UMX_ALIGN_PLANES")) e->align = std::atoi(ev);
   // stream2 (the second lane) is created with the highest priority (as measured in rounds 3-5; priorities change little on this pool)
   int prio_lo = 0, prio_hi = 0;

@@ -25,6 +25,7 @@
 // 64 rows x (BN/2) columns of 32x32x16 MFMA tiles; CPLX as there (rows = (re/im, edge), weight rows = (A/B half, channel)).
 // WIDE = 1: 256 x 256 tile (N must fill whole tiles); WIDE = 0: 256 x 128.
 #pragma once
+#include <type_traits>
 #include "umx_gemm_pl.h"
 
 namespace umx {
@@ -37,18 +38,33 @@ template <int P> __device__ __forceinline__ int q_row_off(int row) { return (row
 template <int P> __device__ __forceinline__ int q_swz(int g) { return P == 3 ? ((g >> 2) & 1) : ((g >> 1) & 3); }
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 
-template <int JA, int JBF, int BHALF_ROUND, int A_BYTES, int TAG>
-__device__ __forceinline__ void q3_issue(const unsigned char* A, const unsigned char* B, unsigned char* sbase, const long (&a_off)[JA],
-                                         const long (&b_off)[JBF + BHALF_ROUND], long kofs_a, long kofs_b, int piece, bool b_tail) {
+// BO = type of the per-lane offsets: long, or unsigned int where the registers count (half-height tiles: B takes twice the rounds; the
+// weight planes are far below 4 GB and A is then the workgroup's own row tile, and a 32-bit lane offset beside a uniform base is an
+// addressing mode of the load itself)
+template <int JA, int JBF, int BHALF_ROUND, int A_BYTES, int TAG, int RND = 8192, class BO = long>
+__device__ __forceinline__ void q3_issue(const unsigned char* A, const unsigned char* B, unsigned char* sbase, const BO (&a_off)[JA],
+                                         const BO (&b_off)[JBF + BHALF_ROUND], long kofs_a, long kofs_b, int piece, bool b_tail) {
+  BO ao[JA];
+#pragma unroll
+  for (int j = 0; j < JA; ++j) {
+    ao[j] = a_off[j];
+    if constexpr (sizeof(BO) == 4) asm("" : "+v"(ao[j]));   // opaque: the 32-bit offsets stay 32-bit registers (hoisted out of the k loop they would be widened to pairs)
+  }
 #pragma unroll
   for (int j = 0; j < JA; ++j)
-    __builtin_amdgcn_global_load_lds(A + a_off[j] + kofs_a, (__attribute__((address_space(3))) void*)(sbase + piece + j * 8192), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((A + kofs_a) + ao[j], (__attribute__((address_space(3))) void*)(sbase + piece + j * RND), 16, 0, 0);
+  BO bo[JBF + BHALF_ROUND];
+#pragma unroll
+  for (int j = 0; j < JBF + BHALF_ROUND; ++j) {
+    bo[j] = b_off[j];
+    if constexpr (sizeof(BO) == 4) asm("" : "+v"(bo[j]));
+  }
 #pragma unroll
   for (int j = 0; j < JBF; ++j)
-    __builtin_amdgcn_global_load_lds(B + b_off[j] + kofs_b, (__attribute__((address_space(3))) void*)(sbase + A_BYTES + piece + j * 8192), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((B + kofs_b) + bo[j], (__attribute__((address_space(3))) void*)(sbase + A_BYTES + piece + j * RND), 16, 0, 0);
   if constexpr (BHALF_ROUND != 0)
-    if (b_tail)                   // wave-uniform: the first four waves fetch the last half round
-      __builtin_amdgcn_global_load_lds(B + b_off[JBF] + kofs_b, (__attribute__((address_space(3))) void*)(sbase + A_BYTES + piece + JBF * 8192), 16, 0, 0);
+    if (b_tail)                   // wave-uniform: the first half of the waves fetch the last half round
+      __builtin_amdgcn_global_load_lds((B + kofs_b) + bo[JBF], (__attribute__((address_space(3))) void*)(sbase + A_BYTES + piece + JBF * RND), 16, 0, 0);
 }
 
 // (Round 4 also had an "X8" form -- two fp16 planes + two bf8 planes of the activations, the two 2^-22-order products on
@@ -82,24 +98,30 @@ __host__ __device__ constexpr bool q_use_product(int PA, int PB, int NPROD, int 
 // (bf16x3 / split-bf16: A as float32, AF) and <.., 2, 2, 1, 4, 3> (split: fp16 planes, exact weights); the other forms are gemm_bench's.
 // S = ring stages (2: request tile kt+1 while tile kt is consumed; 3: two tiles in flight -- more tolerant of HBM latency when
 // other kernels load the memory system, at 144 KB of LDS for the wide tile).
+// MW = waves along M.  4: 256-row tiles, 8 waves, one workgroup per CU.  2: the HALF-HEIGHT form -- 128-row tiles (CPLX: 64 edges), 4 waves,
+// TWO workgroups per CU.  The per-wave tile (64 rows x BN/2 columns), its accumulators and its k order are the same, so every output element
+// is the same bits in either form; the DMA rounds are half as long (4 KB) and B takes twice as many.  What the second workgroup buys: it
+// runs its k loop while the first one waits for its prologue's DMA round trip or drains its stores (NOTES.md section 13).
 // AL = 1 (AF kernels, forward products): "aligned planes" -- the leading plane of A is quantised to the lane's pass group (qf_align_magic,
 // umx_gemm_pl.h); the weights' leading plane is quantised the same way when the planes are built (umx_api.hip).
-template <int CPLX, int WIDE, int P = 3, int S = 2, int F16 = 0, int NPROD = (P == 3 ? 6 : 3), int PB = P, int AF = 0, int LS = 0, int AL = 0>
-__global__ __launch_bounds__(512, 1) void umx_gemm_q_kernel(const GemmPL p) {
+template <int CPLX, int WIDE, int P = 3, int S = 2, int F16 = 0, int NPROD = (P == 3 ? 6 : 3), int PB = P, int AF = 0, int LS = 0, int AL = 0, int MW = 4>
+__global__ __launch_bounds__(MW * 128, MW == 4 ? 1 : 2) void umx_gemm_q_kernel(const GemmPL p) {
   static_assert(!AL || AF, "AL: the float32-A kernels");
   static_assert(!LS || (P == 3 && PB == 3 && !F16 && NPROD == 6), "LS: the six-product bf16 form");
   static_assert(LS != 2 || !WIDE, "LS = 2 (second accumulator set): 256 x 128 tiles only");
+  static_assert(MW == 4 || MW == 2, "waves along M: 4 (256-row tiles) or 2 (half-height tiles, two workgroups per CU)");
   static_assert(!AF || (P == 3 && PB == 3 && F16 == 0), "AF: the six-product bf16 form with A as float32");
   static_assert((P == 3 && PB == 3 && NPROD == 6) || (P == 2 && PB == 2 && (NPROD == 3 || NPROD == 4)) || (P == 2 && PB == 3 && (NPROD == 4 || NPROD == 5)), "plane products");
-  constexpr int BM = 256, BN = WIDE ? 256 : 128;
+  constexpr int NT = MW * 128, RND = NT * 16;             // threads; bytes of one DMA round (every lane 16 B)
+  constexpr int BM = 64 * MW, BN = WIDE ? 256 : 128;
   constexpr int BMR = CPLX ? BM / 2 : BM, BNC = CPLX ? BN / 2 : BN;
   constexpr int BLK = AF ? 256 : 128 * P, CPB = AF ? 16 : 8 * P;   // A: bytes per block, 16-B chunks per block (32 P bytes per row per block; AF: 64)
   constexpr int BLKB = 128 * PB, CPBB = 8 * PB;           // B likewise
   constexpr int A_BYTES = AF ? BM * 64 : BM * 32 * P, B_BYTES = BN * 32 * PB, STAGE = A_BYTES + B_BYTES;
   constexpr int TNW = WIDE ? 4 : 2;                       // 32-column MFMA tiles per wave
-  constexpr int JA = A_BYTES / 8192;                      // DMA rounds of the whole block (512 lanes x 16 B)
-  constexpr int JBF = B_BYTES / 8192, BHR = (B_BYTES % 8192) ? 1 : 0;
-  static_assert(S * STAGE <= 160 * 1024 && A_BYTES % 8192 == 0 && (B_BYTES % 8192 == 0 || B_BYTES % 8192 == 4096), "tile geometry");
+  constexpr int JA = A_BYTES / RND;                       // DMA rounds of the whole block (NT lanes x 16 B)
+  constexpr int JBF = B_BYTES / RND, BHR = (B_BYTES % RND) ? 1 : 0;
+  static_assert(S * STAGE * (MW == 4 ? 1 : 2) <= 160 * 1024 && A_BYTES % RND == 0 && (B_BYTES % RND == 0 || B_BYTES % RND == RND / 2), "tile geometry");
   static_assert((P == 2 || P == 3) && (PB == 2 || PB == 3), "two or three planes");
   static_assert(S >= 2 && S <= 4, "ring depth");
   __shared__ __attribute__((aligned(1024))) unsigned char ring[S * STAGE];
@@ -118,27 +140,29 @@ __global__ __launch_bounds__(512, 1) void umx_gemm_q_kernel(const GemmPL p) {
   const long b_blocks = p.K / 16;                          // (ldb is implied: K * PB)
   const long gA = ((long)p.M + 3) / 4;                     // row groups that exist (rows are padded to 4)
   const int gN = p.N / 4;
-  long a_off[JA], b_off[JBF + BHR];
+  typedef typename std::conditional<MW == 4, long, unsigned int>::type BOff;
+  BOff a_off[JA], b_off[JBF + BHR];
+  const long a_tile = MW == 4 ? 0 : (long)mt * (BMR / 4) * a_blocks * BLK;    // half-height: A offsets count from the workgroup's row tile
 #pragma unroll
   for (int j = 0; j < JA; ++j) {
-    const int c = tid + 512 * j, g = c / CPB, s = c % CPB;
+    const int c = tid + NT * j, g = c / CPB, s = c % CPB;
     long grp; int offA;
     if (CPLX) { grp = (long)mt * (BMR / 4) + (g % (BMR / 4)); offA = (g / (BMR / 4)) ? p.offA1 : p.offA0; }
     else      { grp = (long)mt * (BM / 4) + g;                offA = p.offA0; }
     if (grp >= gA) grp = gA - 1;
-    if (AF) a_off[j] = (grp * a_blocks + offA / 16) * BLK + (s >> 2) * 64 + (((s & 3) ^ (g & 3)) * 16);   // s = row in group * 4 + piece
-    else    a_off[j] = (grp * a_blocks + offA / 16) * BLK + (s ^ q_swz<P>(g)) * 16;          // the 16-B half is the LSB of the chunk index
+    if (AF) a_off[j] = (BOff)((grp * a_blocks + offA / 16) * BLK - a_tile + (s >> 2) * 64 + (((s & 3) ^ (g & 3)) * 16));   // s = row in group * 4 + piece
+    else    a_off[j] = (BOff)((grp * a_blocks + offA / 16) * BLK - a_tile + (s ^ q_swz<P>(g)) * 16);          // the 16-B half is the LSB of the chunk index
   }
 #pragma unroll
   for (int j = 0; j < JBF + BHR; ++j) {
-    const int c = tid + 512 * j, g = (c / CPBB) % (BN / 4), s = c % CPBB; // (% keeps the unused lanes of a half round in range)
+    const int c = tid + NT * j, g = (c / CPBB) % (BN / 4), s = c % CPBB; // (% keeps the unused lanes of a half round in range)
     long grp;
     if (CPLX) { int cg = nt * (BNC / 4) + (g % (BNC / 4)); if (cg >= gN) cg = gN - 1; grp = (long)(g / (BNC / 4)) * (p.bHalf / 4) + cg; }
     else      { int cg = nt * (BN / 4) + g; if (cg >= gN) cg = gN - 1; grp = cg; }
-    b_off[j] = grp * b_blocks * BLKB + (s ^ q_swz<PB>(g)) * 16;
+    b_off[j] = (BOff)(grp * b_blocks * BLKB + (s ^ q_swz<PB>(g)) * 16);
   }
   const int piece = __builtin_amdgcn_readfirstlane(wave * 1024);
-  const bool b_tail = __builtin_amdgcn_readfirstlane(wave < 4 ? 1 : 0) != 0;
+  const bool b_tail = __builtin_amdgcn_readfirstlane(wave < MW ? 1 : 0) != 0;
 
   // The accumulators START from the bias (real GEMMs; scaled and signed the way the epilogue un-scales them, both exact): a bias added
   // to the finished float32 sum is "a value on the float32 grid plus a constant", whose rounding error is the SAME for every row whose
@@ -187,11 +211,11 @@ __global__ __launch_bounds__(512, 1) void umx_gemm_q_kernel(const GemmPL p) {
   }
 
   const int nk = p.K / 16;
-  constexpr int TAG = 9000 + S * 100 + P * 10 + CPLX * 2 + WIDE + F16 * 1000 + NPROD * 10000 + PB * 100000 + AF * 10000000 + LS * 100000000 + AL * 500000000;   // one q3_issue instance per kernel
+  constexpr int TAG = 9000 + S * 100 + P * 10 + CPLX * 2 + WIDE + F16 * 1000 + NPROD * 10000 + PB * 100000 + AF * 10000000 + LS * 100000000 + AL * 500000000 + (MW == 2 ? 1000000000 : 0);   // one q3_issue instance per kernel
   constexpr int GI = JA + JBF;                            // DMA instructions per tile per wave (+1 for the waves that fetch the half round)
 #pragma unroll
   for (int t = 0; t < S - 1; ++t)
-    if (t < nk) q3_issue<JA, JBF, BHR, A_BYTES, TAG>(Ab, Bb, ring + t * STAGE, a_off, b_off, (long)t * BLK, (long)t * BLKB, piece, b_tail);
+    if (t < nk) q3_issue<JA, JBF, BHR, A_BYTES, TAG, RND, BOff>(Ab + a_tile, Bb, ring + t * STAGE, a_off, b_off, (long)t * BLK, (long)t * BLKB, piece, b_tail);
   int st_cur = 0, st_nxt = S - 1;
   for (int kt = 0; kt < nk; ++kt) {
     // tile kt has landed once at most the requests of the S-2 younger tiles are outstanding (fewer near the tail: wait for all)
@@ -199,7 +223,7 @@ __global__ __launch_bounds__(512, 1) void umx_gemm_q_kernel(const GemmPL p) {
     else if (BHR != 0 && b_tail) wait_vmcnt<(S - 2) * (GI + 1)>();
     else wait_vmcnt<(S - 2) * GI>();
     __builtin_amdgcn_s_barrier();   // tile kt landed everywhere; everyone finished reading tile kt-1
-    if (kt + S - 1 < nk) q3_issue<JA, JBF, BHR, A_BYTES, TAG>(Ab, Bb, ring + st_nxt * STAGE, a_off, b_off, (long)(kt + S - 1) * BLK, (long)(kt + S - 1) * BLKB, piece, b_tail);
+    if (kt + S - 1 < nk) q3_issue<JA, JBF, BHR, A_BYTES, TAG, RND, BOff>(Ab + a_tile, Bb, ring + st_nxt * STAGE, a_off, b_off, (long)(kt + S - 1) * BLK, (long)(kt + S - 1) * BLKB, piece, b_tail);
     const unsigned char* sb = ring + st_cur * STAGE;
     st_cur = st_cur + 1 == S ? 0 : st_cur + 1;
     st_nxt = st_nxt + 1 == S ? 0 : st_nxt + 1;

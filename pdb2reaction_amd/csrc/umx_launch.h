@@ -118,9 +118,12 @@ enum PlFamily { Q_F16, Q_BF16, PL3_ROWS, PL3, PL2_WIDE, PL2_M16, PL2_M32 };
 
 // every instantiated plane GEMM, exactly once.  Q_BF16 rows: ls = the low-order plane products accumulate apart, in the form that goes
 // with the tile width (template LS = 1: 256 x 256 tiles, one spare accumulator folded in every k-step; LS = 2: 256 x 128 tiles, a second
-// accumulator set for the whole k loop); al = aligned leading plane of A
-struct PlKernel { PlFamily fam; bool cplx, wide, ls, al; void (*fn)(const GemmPL); };
-#define UMX_PAIR(fam, wide, ls, al, kernel, ...) {fam, false, wide, ls, al, kernel<0, __VA_ARGS__>}, {fam, true, wide, ls, al, kernel<1, __VA_ARGS__>}
+// accumulator set for the whole k loop); al = aligned leading plane of A; half = the half-height form (template MW = 2: 128-row tiles,
+// 256 threads, two workgroups per CU) -- every Q_BF16 kernel has one, bit for bit its full-height form (UMX_HALF rows)
+struct PlKernel { PlFamily fam; bool cplx, wide, ls, al, half; void (*fn)(const GemmPL); };
+#define UMX_PAIR(fam, wide, ls, al, kernel, ...) {fam, false, wide, ls, al, false, kernel<0, __VA_ARGS__>}, {fam, true, wide, ls, al, false, kernel<1, __VA_ARGS__>}
+#define UMX_HALF(wide, ls, al, LS) {Q_BF16, false, wide, ls, al, true, umx_gemm_q_kernel<0, wide, 3, 2, 0, 6, 3, 1, LS, al, 2>}, \
+                                   {Q_BF16, true, wide, ls, al, true, umx_gemm_q_kernel<1, wide, 3, 2, 0, 6, 3, 1, LS, al, 2>}
 const PlKernel pl_kernels[] = {
     UMX_PAIR(Q_F16, false, false, false, umx_gemm_q_kernel, 0, 2, 2, 1, 4, 3),
     UMX_PAIR(Q_F16, true, false, false, umx_gemm_q_kernel, 1, 2, 2, 1, 4, 3),
@@ -132,18 +135,21 @@ const PlKernel pl_kernels[] = {
     UMX_PAIR(Q_BF16, true, true, false, umx_gemm_q_kernel, 1, 3, 2, 0, 6, 3, 1, 1),
     UMX_PAIR(Q_BF16, false, true, true, umx_gemm_q_kernel, 0, 3, 2, 0, 6, 3, 1, 2, 1),
     UMX_PAIR(Q_BF16, true, true, true, umx_gemm_q_kernel, 1, 3, 2, 0, 6, 3, 1, 1, 1),
-    {PL3_ROWS, false, false, false, false, umx_gemm_pl16_kernel<0, 3, 2, 4, 2, 2, 2, 0, 1>},     // (an 8 x 1 wave layout measured the same)
-    {PL3, false, false, false, false, umx_gemm_pl_kernel<0, 3, 2, 4, 2, 2, 2>},
+    UMX_HALF(0, 0, 0, 0), UMX_HALF(1, 0, 0, 0), UMX_HALF(0, 0, 1, 0), UMX_HALF(1, 0, 1, 0),
+    UMX_HALF(0, 1, 0, 2), UMX_HALF(1, 1, 0, 1), UMX_HALF(0, 1, 1, 2), UMX_HALF(1, 1, 1, 1),
+    {PL3_ROWS, false, false, false, false, false, umx_gemm_pl16_kernel<0, 3, 2, 4, 2, 2, 2, 0, 1>},     // (an 8 x 1 wave layout measured the same)
+    {PL3, false, false, false, false, false, umx_gemm_pl_kernel<0, 3, 2, 4, 2, 2, 2>},
     UMX_PAIR(PL2_WIDE, true, false, false, umx_gemm_pl16_kernel, 2, 2, 4, 2, 2, 4),
     UMX_PAIR(PL2_M16, false, false, false, umx_gemm_pl16_kernel, 2, 3, 4, 2, 2, 2),
     UMX_PAIR(PL2_M32, false, false, false, umx_gemm_pl_kernel, 2, 3, 4, 2, 2, 2),
 };
 #undef UMX_PAIR
+#undef UMX_HALF
 
 // which instantiation runs one product, with which grid and which leading dimensions (in 2-byte units)
 // (prec: ProfRec::prec -- 24: two fp16 planes, 4 products; 3 / 2: bf16 planes, 6 / 3 products; err: the product has no instantiation)
-struct PlChoice { PlFamily fam; bool wide = false, ls = false, al = false; unsigned blocks = 0; long lda = 0, ldb = 0; int prec = 0; const char* err = nullptr; };
-PlChoice choose_pl(const Precision& pm, Pass pass, bool w_quad, int cplx, long M, int N, int K, int a_cols, bool a_f32rows, int low_sep, int align) {
+struct PlChoice { PlFamily fam; bool wide = false, ls = false, al = false, half = false; unsigned blocks = 0; long lda = 0, ldb = 0; int prec = 0; const char* err = nullptr; };
+PlChoice choose_pl(const Precision& pm, Pass pass, bool w_quad, int cplx, long M, int N, int K, int a_cols, bool a_f32rows, int low_sep, int align, int half) {
   PlChoice c;
   const bool fwd = pass == FWD;
   const int P = fwd ? 3 : pm.rev_planes;
@@ -170,8 +176,9 @@ PlChoice choose_pl(const Precision& pm, Pass pass, bool w_quad, int cplx, long M
     c.fam = Q_F16; c.lda = (long)a_cols * 2; c.ldb = (long)K * 3;
   } else if (fwd || (P == 3 && w_quad)) {
     // A = float32 quad-row blocks, split into the three bf16 planes in registers; weights as three bf16 planes.  The 256 x 128 LS form
-    // keeps a second accumulator set for the whole k loop (190 VGPRs: one workgroup per CU instead of two -- +10 ms at c3 for conv-1 /
-    // conv-2 m = 0; deeper rings do not buy it back: S = 3 / 4 measured +5 / +6 ms.  Round 6 measured the per-k-step fold of the wide
+    // keeps a second accumulator set for the whole k loop (190 VGPRs: one 8-wave workgroup per CU instead of two -- +10 ms at c3 for conv-1 /
+    // conv-2 m = 0 when it went in; deeper rings do not buy it back: S = 3 / 4 measured +5 / +6 ms, and neither do two 4-wave workgroups
+    // of half the height, which fit the same registers: -0.1 ms, see UMX_GEMM_HALF below -- the 10 ms are not tile turnover.  Round 6 measured the per-k-step fold of the wide
     // tiles there too: 167-172 VGPRs as compiled (one workgroup per CU all the same); forced into the 128 VGPRs a second workgroup needs
     // it spills 19 registers: +40 ms, and 48 float32 folds per output instead of one move the 20 000-atom energies to -9e-5 eV on two of
     // four cases -- profiles/r06_ls_ab.txt; removed)
@@ -190,7 +197,21 @@ PlChoice choose_pl(const Precision& pm, Pass pass, bool w_quad, int cplx, long M
     // 32x32x16 wins 5-10 % on the short-K plain ones (radial fc3^T, conv-2^T m = 0)
     c.fam = (cplx || K >= 512) ? PL2_M16 : PL2_M32;
   }
-  c.blocks = (unsigned)(((nM + 7) / 8) * 8 * ((N + bnc - 1) / bnc));
+  // Half-height tiles (umx_gemm_q.h MW = 2; Q_BF16 only): two 4-wave workgroups per CU, each running while the other waits for its
+  // prologue or drains its stores, at the price of fetching the B tile twice as often.  The bits are the same in either form, so this
+  // choice MAY depend on M (unlike the LS tile width above) -- and half tiles would also suit the small-M rule (`fills`), which is left as
+  // measured.  UMX_GEMM_HALF (dev A/B): 0 none, 1 the forward LS products on narrow tiles (conv-1 / conv-2 m = 0, edge-degree fc3), 2 + the
+  // forward LS products on wide tiles (fc3), 3 every Q_BF16 product, 4 the complex (m > 0) products only, 5 (default) the products that
+  // measured a gain: those WITHOUT LS and with K >= 256 -- the complex m > 0 products of both passes (c3, per launch: N 256 K 512 -4.2 %,
+  // 256 x 256 -2.5 %, 512 x 256 -1.5 ... -3.3 %, 128 x 256 -1 %) and the plain conv^T m = 0 products of the bf16x3 reverse pass (768 x 640
+  // -3.9 %); the short-K complex products lose (128 x 128 +4 %, 256 x 128 +-0).  The forward LS products, for which the second workgroup
+  // was expected to pay (their 190 / 239 VGPRs cost them their co-resident partner in round 5), measured NO gain: c3 step -0.1 ms
+  // (narrow) / -0.4 ms (+ fc3) against an A/A spread of 0.8 ms; every Q_BF16 product -6.4 ms, complex only -5.1 ms
+  // (profiles/half_tile_ab.txt; NOTES.md section 13).
+  c.half = c.fam == Q_BF16 && (half == 3 || (half == 4 && cplx) || (half == 5 && !c.ls && K >= 256) ||
+                               (fwd && c.ls && (half == 2 || (half == 1 && !c.wide))));
+  const long nMf = c.half ? (M + bmr / 2 - 1) / (bmr / 2) : nM;     // row tiles of the form that runs
+  c.blocks = (unsigned)(((nMf + 7) / 8) * 8 * ((N + bnc - 1) / bnc));
   return c;
 }
 
@@ -202,11 +223,11 @@ int gemm_pl(umx_engine* eng, int cplx, Pass pass, const unsigned short* Apl, int
   if (it == eng->planes.end()) return fail(eng, UMX_ERR_ARG, "gemm_pl: weight has no PL copy");
   if (K % 32 != 0) return fail(eng, UMX_ERR_ARG, "gemm_pl: K not a multiple of 32");
   const PlaneCopy& w = it->second;
-  const PlChoice c = choose_pl(eng->prec, pass, w.quad, cplx, M, N, K, a_cols, a_f32rows, eng->low_sep, eng->align);
+  const PlChoice c = choose_pl(eng->prec, pass, w.quad, cplx, M, N, K, a_cols, a_f32rows, eng->low_sep, eng->align, eng->gemm_half);
   if (c.err) return fail(eng, UMX_ERR_ARG, c.err);
   const PlKernel* k = nullptr;
   for (const PlKernel& e : pl_kernels)
-    if (e.fam == c.fam && e.cplx == (cplx != 0) && e.wide == c.wide && e.ls == c.ls && e.al == c.al) { k = &e; break; }
+    if (e.fam == c.fam && e.cplx == (cplx != 0) && e.wide == c.wide && e.ls == c.ls && e.al == c.al && e.half == c.half) { k = &e; break; }
   if (!k) return fail(eng, UMX_ERR_ARG, "gemm_pl: variant not instantiated");
   GemmPL q;
   std::memset(&q, 0, sizeof(q));
@@ -216,7 +237,7 @@ int gemm_pl(umx_engine* eng, int cplx, Pass pass, const unsigned short* Apl, int
   if (c.fam == Q_F16) q.cscale = 1.0f / (QF16_SCALE * w.scale);
   ProfRec* pr;
   CHK(prof_open(eng, &pr, cplx ? 8.0 * M * (double)N * K : 2.0 * M * (double)N * K, c.prec, M, N, K, 9, cplx));
-  hipLaunchKernelGGL(k->fn, dim3(c.blocks), dim3(512), 0, eng->stream, q);
+  hipLaunchKernelGGL(k->fn, dim3(c.blocks), dim3(k->half ? 256 : 512), 0, eng->stream, q);
   HIPCHK(eng, hipGetLastError());
   return prof_close(eng, pr);
 }
