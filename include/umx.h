@@ -284,6 +284,40 @@ int umx_energy_forces_f64(umx_engine* eng, int n_images, const double* pos_ang, 
 int umx_energy_forces_f64_dev(umx_engine* eng, int n_images, const double* d_pos_ang, double* d_energy_ev,
                               float* d_forces_ev_ang, double* d_virial_ev, void* hip_stream);
 
+/* PINNED NEIGHBOUR GRAPH (additive to ABI v10; opt-in).  Every evaluation rebuilds the radius graph from the positions it is given.  The
+ * model is a smooth function of the positions only while the edge set stays the same: an edge that crosses the cutoff is harmless (the
+ * envelope takes it to zero with two vanishing derivatives), an edge that enters or leaves through the max_neigh cap is not -- a rank
+ * swap removes one edge of full weight and adds another.  Whatever differences evaluations of nearby geometries (a finite-difference
+ * Hessian, Lanczos and dimer probes, line searches, strain scans) wants ONE edge set.
+ * umx_pin_graph[_f64]: pos_ang is ONE image, [n_atoms][3] float32 (float64), HOST pointer.  The engine builds the graph of that image
+ * with the radius, max_neigh, cell and pbc flags in force -- exactly what an evaluation of it builds -- and keeps its structure: per
+ * directed edge the source, the target and the lattice translation as an integer triple; per atom the wrap offset used; the rows' order.
+ * While a graph is pinned EVERY image of EVERY evaluation (all entries above, host and device pointers, float and double positions) uses
+ * that edge set: only the edge vectors are recomputed, vec = r_src + t - r_dst with t = the edge's triple times the cell in force for
+ * that image.  No cutoff test, no ranking: an edge that has grown beyond the cutoff stays in the list with envelope 0; two pinned
+ * neighbours that come to coincide give a non-finite energy (UMX_ERR_RANGE).  The float entries use the expression of the unpinned
+ * float graph on positions shifted by the stored wrap offsets; the double entries one float64 difference rounded once.  So an
+ * evaluation of the reference image itself -- through the entry of the type it was pinned with -- is bitwise (E, F, W) the unpinned one,
+ * and the strain derivative W "with the graph held fixed" can be checked by finite differences on that very graph.
+ *   - No device-to-host read happens in a pinned evaluation (the host knows every image's edge count): umx_last_graph_stats reports
+ *     n_images x the reference's edges; umx_last_graph_shifts the number of distinct translations among the pinned edges.
+ *   - Chunks, two lanes, recompute plans and the virial run as they are; target-node partitions take contiguous row ranges of the pin.
+ *   - A non-finite coordinate: host entries refuse before launch as ever; device-pointer entries set the sticky status word and
+ *     umx_synchronize reports it (UMX_ERR_RANGE), as for a non-finite energy.
+ *   - umx_unpin_graph restores the ordinary behaviour, bit for bit.  With nothing pinned no kernel, launch or result differs.
+ *   - umx_pinned_graph: directed edges and largest in-degree of the pinned graph; zeros when nothing is pinned.
+ * Rules (UMX_ERR_ARG): pinning requires a bound system and, with per-image cells, exactly one bound cell; umx_set_system unpins;
+ * umx_set_cell / umx_set_cells keep the pin while the pbc flags are those of pin time (the translations follow the new cells) and unpin
+ * otherwise; umx_gp_begin[_virial] refuse while a graph is pinned; pinning while a graph-parallel evaluation is in progress is refused;
+ * a non-finite reference position is refused.  A failed pin leaves the previous state (pinned or not).  Pinning again replaces the pin.
+ * Not provided: a pin for the graph-parallel entries, automatic re-pinning or a skin criterion, one graph per image of a batch.
+ * Corresponds to: what the reference's hessian_calc_mode="Analytical" differentiates -- autograd at the graph of the geometry it was
+ * given (uma_pysis.py:394-417).                                                                                                      */
+int umx_pin_graph(umx_engine* eng, const float* pos_ang);
+int umx_pin_graph_f64(umx_engine* eng, const double* pos_ang);
+int umx_unpin_graph(umx_engine* eng);
+int umx_pinned_graph(const umx_engine* eng, int64_t* n_edges, int32_t* max_degree);
+
 /* Graph-parallel evaluation of ONE image across several engines / ranks (ABI v5) -- the reference's `workers > 1` semantics
  * (ParallelMLIPPredictUnit: the atoms' graph partitioned over workers, uma_pysis.py:220-242), for single large systems when there are
  * fewer images than GPUs.  Every rank passes the FULL positions; rank r builds the incoming edges of the

@@ -201,6 +201,17 @@ class UMXCalculator(_AseBase):
             self.results = {"energy": float(e[0]), "forces": np.asarray(f[0], dtype=np.float64)}
         self._last = (self._bound, pos, dict(self.results))
 
+    def pinned(self, atoms):
+        """``with calc.pinned(atoms): ...`` -- the neighbour graph of ``atoms`` (its positions, cell and pbc flags; ``Engine.pin_graph``)
+        is pinned for the block and unpinned on the way out, also on an exception: every ``calculate`` / ``calculate_images`` inside --
+        the displaced or strained copies of ``atoms`` -- is evaluated on that one edge set.  Images with other pbc flags, or of another
+        system, end the pin early (the engine's rules)."""
+        from .engine import _Pinned
+
+        eng = self._ensure(atoms)
+        self._last = None                # a result cached without the pin is not the pinned one
+        return _Pinned(eng, np.array(atoms.get_positions(), dtype=np.float64), self._dp_kw())
+
     def _stress_kw(self) -> dict:
         """What ``energy_forces_stress`` is called with: the graph-parallel opt-in when this calculator runs a pool of engines."""
         return {"graph_parallel": True} if self.gp_stress and len(self.local_devices or []) > 1 else {}

@@ -77,6 +77,109 @@ int energy_forces_host_impl(umx_engine* eng, int n_images, const P* pos, double*
     }
   return UMX_OK;
 }
+
+// ---- pinned graph (umx_pin_graph[_f64]) -----------------------------------------------------------------------------------------------
+void pin_clear(umx_engine* eng) { eng->pin_on = false; }     // (the buffers stay: the next pin replaces them, umx_destroy frees them)
+
+// umx_set_cell / umx_set_cells under a pin: the pbc flags of pin time keep it -- the pinned edges' translations are formed anew for the
+// cell(s) now in force -- any other flags unpin
+int pin_after_cell(umx_engine* eng) {
+  if (!eng->pin_on) return UMX_OK;
+  bool same = eng->pbc_on == eng->pin_pbc_on;
+  for (int k = 0; k < 3 && same && eng->pbc_on; ++k) same = eng->pbc[k] == eng->pin_pbc[k];
+  if (!same) { pin_clear(eng); return UMX_OK; }
+  const int st = pin_upload_shifts(eng, eng->pin_codes, &eng->d_pin_shifts, &eng->pin_shifts_cap);
+  if (st != UMX_OK) pin_clear(eng);
+  return st;
+}
+
+// Build the graph of ONE reference image exactly as an evaluation of it does -- wrapped copy, degree pass, scan, fill -- with the
+// translation of every edge as one more output of the fill, and keep its structure.  Everything that can fail happens on new buffers:
+// a failed pin leaves the previous state.
+template <typename P>
+int pin_graph_impl(umx_engine* eng, const P* pos) {
+  if (!eng) return UMX_ERR_ARG;
+  if (eng->need_merge()) return fail(eng, UMX_ERR_ARG, "umx_pin_graph: " NOT_MERGED);
+  if (!eng->have_system) return fail(eng, UMX_ERR_ARG, "umx_pin_graph: bind a system first (umx_set_system)");
+  if (!pos) return fail(eng, UMX_ERR_ARG, "umx_pin_graph: bad arguments");
+  if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_pin_graph: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
+  CHK(periodic_check_images(eng, 1, "umx_pin_graph"));
+  const int N = eng->natoms;
+  for (long i = 0; i < (long)N * 3; ++i)
+    if (!std::isfinite(pos[i])) return fail(eng, UMX_ERR_ARG, "umx_pin_graph: non-finite position");
+  HIPCHK(eng, hipSetDevice(eng->dev));
+  hipStream_t s = eng->stream;
+  HIPCHK(eng, hipStreamSynchronize(s));                              // no evaluation may still be replaying the graph this one replaces
+  if (eng->ran_on_caller) HIPCHK(eng, hipEventSynchronize(eng->ev_done));
+  if (eng->io_cap < N) CHK(grow(eng, eng->io_cap, (long)N, {s}, {DevBuf(eng->d_io_pos, (size_t)N * 3), DevBuf(eng->d_io_f, (size_t)N * 3)}));
+  P* d_stage;
+  if constexpr (std::is_same_v<P, double>) {
+    if (eng->io64_cap < N) CHK(grow(eng, eng->io64_cap, (long)N, {s}, {DevBuf(eng->d_io_pos64, (size_t)N * 3)}));
+    d_stage = eng->d_io_pos64;
+  } else d_stage = eng->d_io_pos;
+  HIPCHK(eng, hipMemcpyAsync(d_stage, pos, (size_t)N * 3 * sizeof(P), hipMemcpyHostToDevice, s));
+  // the ordinary graph of the image: the pin in force (if any) stands aside, and what the engine reports of its last evaluation stays
+  struct Keep {
+    umx_engine* e; bool pin; int64_t edges; int32_t maxdeg; int shifts; bool trunc;
+    ~Keep() { e->pin_on = pin; e->last_edges = edges; e->last_maxdeg = maxdeg; e->last_shifts = shifts; e->may_truncate = trunc; }
+  } keep{eng, eng->pin_on, eng->last_edges, eng->last_maxdeg, eng->last_shifts, eng->may_truncate};
+  eng->pin_on = false;
+  PosPtr dp(d_stage);
+  CHK(periodic_prepare(eng, s, 1, &dp));
+  ImageEdges ie;
+  CHK(degree_pass(eng, s, 1, dp, ie));
+  const long E = ie.etot;
+  const bool trunc = eng->may_truncate;
+  // new buffers: source, target, translation (first the packed triple, then its index), wrap offsets; scratch: row_ptr, edge vectors
+  int *n_src = nullptr, *n_dst = nullptr, *n_tix = nullptr, *n_wrap = nullptr, *t_row = nullptr;
+  float* t_evec = nullptr;
+  float4* n_shifts = nullptr; long n_shifts_cap = 0;
+  struct Bufs { void** p[7]; bool drop = true; ~Bufs() { if (drop) for (void** q : p) if (*q) (void)hipFree(*q); } }
+      bufs{{(void**)&n_src, (void**)&n_dst, (void**)&n_tix, (void**)&n_wrap, (void**)&t_row, (void**)&t_evec, (void**)&n_shifts}};
+  const size_t eb = (size_t)std::max(E, 1L);
+  HIPCHK(eng, hipMalloc(&n_src, eb * sizeof(int)));
+  HIPCHK(eng, hipMalloc(&n_dst, eb * sizeof(int)));
+  HIPCHK(eng, hipMalloc(&n_tix, eb * sizeof(int)));
+  HIPCHK(eng, hipMalloc(&n_wrap, (size_t)N * 3 * sizeof(int)));
+  HIPCHK(eng, hipMalloc(&t_row, ((size_t)N + 3) * sizeof(int)));
+  HIPCHK(eng, hipMalloc(&t_evec, eb * 4 * sizeof(float)));
+  HIPCHK(eng, hipMemsetAsync(n_tix, 0, eb * sizeof(int), s));
+  HIPCHK(eng, hipMemsetAsync(n_wrap, 0, (size_t)N * 3 * sizeof(int), s));
+  hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, eng->d_deg_all, (long)N, t_row, t_row + N + 1);
+  launch_graph_fill_pin(eng, s, trunc, dp, (long)N, eng->d_cand_all, t_row, n_src, n_dst, t_evec, n_tix);
+  if (eng->pbc_on) launch_wrap_index_of(eng, s, d_stage, n_wrap);
+  HIPCHK(eng, hipGetLastError());
+  std::vector<int> deg((size_t)N), code(eb);
+  HIPCHK(eng, hipMemcpyAsync(deg.data(), eng->d_deg_all, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (E > 0) HIPCHK(eng, hipMemcpyAsync(code.data(), n_tix, (size_t)E * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(eng, hipStreamSynchronize(s));
+  std::vector<long> row((size_t)N + 1, 0);
+  int maxdeg = 0;
+  for (int i = 0; i < N; ++i) { row[i + 1] = row[i] + deg[i]; maxdeg = std::max(maxdeg, deg[i]); }
+  if (row[N] != E) return fail(eng, UMX_ERR_HIP, "umx_pin_graph: the degrees and the edge count of the reference graph disagree");
+  // the distinct translations, in ascending order of their packed triple, and every edge's index among them
+  std::vector<unsigned> codes;
+  if (eng->pbc_on && E > 0) {
+    const std::set<unsigned> uniq(code.begin(), code.begin() + E);
+    codes.assign(uniq.begin(), uniq.end());
+    for (long e = 0; e < E; ++e) code[e] = (int)(std::lower_bound(codes.begin(), codes.end(), (unsigned)code[e]) - codes.begin());
+    HIPCHK(eng, hipMemcpy(n_tix, code.data(), (size_t)E * sizeof(int), hipMemcpyHostToDevice));
+  }
+  CHK(pin_upload_shifts(eng, codes, &n_shifts, &n_shifts_cap));
+  // nothing below fails: the new graph replaces the old one
+  bufs.drop = false;
+  void* old[] = {eng->d_pin_src, eng->d_pin_dst, eng->d_pin_tix, eng->d_pin_wrap, eng->d_pin_shifts, eng->d_pin_deg, t_row, t_evec};
+  for (void* q : old) if (q) (void)hipFree(q);
+  eng->d_pin_src = n_src; eng->d_pin_dst = n_dst; eng->d_pin_tix = n_tix; eng->d_pin_wrap = n_wrap;
+  eng->d_pin_shifts = n_shifts; eng->pin_shifts_cap = n_shifts_cap;
+  eng->d_pin_deg = nullptr; eng->pin_deg_imgs = 0;
+  eng->pin_deg = std::move(deg); eng->pin_row = std::move(row); eng->pin_codes = std::move(codes);
+  eng->pin_edges = E; eng->pin_maxdeg = maxdeg;
+  eng->pin_pbc_on = eng->pbc_on;
+  for (int k = 0; k < 3; ++k) eng->pin_pbc[k] = eng->pbc_on ? eng->pbc[k] : 0;
+  keep.pin = true;
+  return UMX_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -141,7 +244,7 @@ int umx_destroy(umx_engine* eng) {
   (void)hipSetDevice(eng->dev);
   (void)hipStreamSynchronize(eng->stream);
   for (auto& r : eng->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-  void* ptrs[] = {eng->d_w, eng->d_dw, eng->d_bw, eng->d_gmu, eng->d_z, eng->d_sysemb, eng->arena, eng->d_deg_all, eng->d_cand_all, eng->d_img_edges, eng->d_io_pos, eng->d_io_e, eng->d_io_f, eng->d_flags, eng->d_dtab, eng->d_part_deg, eng->d_part_f, eng->d_ex, eng->d_mjobs, eng->d_pjobs, eng->d_mx, eng->d_shifts, eng->d_cells, eng->d_shifts_pk, eng->d_wrap, eng->d_wrap64, eng->d_lats, eng->d_io_pos64, eng->d_vir_part, eng->d_vir_wp, eng->d_io_w};
+  void* ptrs[] = {eng->d_w, eng->d_dw, eng->d_bw, eng->d_gmu, eng->d_z, eng->d_sysemb, eng->arena, eng->d_deg_all, eng->d_cand_all, eng->d_img_edges, eng->d_io_pos, eng->d_io_e, eng->d_io_f, eng->d_flags, eng->d_dtab, eng->d_part_deg, eng->d_part_f, eng->d_ex, eng->d_mjobs, eng->d_pjobs, eng->d_mx, eng->d_shifts, eng->d_cells, eng->d_shifts_pk, eng->d_wrap, eng->d_wrap64, eng->d_lats, eng->d_io_pos64, eng->d_vir_part, eng->d_vir_wp, eng->d_io_w, eng->d_pin_src, eng->d_pin_dst, eng->d_pin_tix, eng->d_pin_wrap, eng->d_pin_deg, eng->d_pin_shifts};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   (void)hipStreamSynchronize(eng->stream2);
   (void)hipEventDestroy(eng->ev_fork); (void)hipEventDestroy(eng->ev_join);
@@ -198,6 +301,7 @@ int umx_set_system(umx_engine* eng, int n_atoms, const int32_t* z, int charge, i
     rs += eng->elem_refs[z[i]];
   }
   HIPCHK(eng, hipStreamSynchronize(eng->stream));
+  pin_clear(eng);                                         // a pinned graph belongs to the system it was built for
   if (eng->d_z) { HIPCHK(eng, hipFree(eng->d_z)); eng->d_z = nullptr; }
   HIPCHK(eng, hipMalloc(&eng->d_z, n_atoms * sizeof(int)));
   HIPCHK(eng, hipMemcpy(eng->d_z, z, n_atoms * sizeof(int), hipMemcpyHostToDevice));
@@ -272,7 +376,9 @@ int umx_synchronize(umx_engine* eng) {
   HIPCHK(eng, hipMemcpy(&flag, eng->d_flags, sizeof(int), hipMemcpyDeviceToHost));
   if (flag) {
     HIPCHK(eng, hipMemset(eng->d_flags, 0, sizeof(int)));
-    return fail(eng, UMX_ERR_RANGE, std::string("a device-pointer evaluation produced a non-finite energy") + eng->prec.range_hint());
+    // (bit 1 can be left only by the replay of a pinned graph: every other evaluation reads it behind its own degree pass)
+    return fail(eng, UMX_ERR_RANGE, std::string("a device-pointer evaluation produced a non-finite energy") +
+                ((flag & 2) ? " (a non-finite position reached an evaluation on the pinned graph)" : eng->prec.range_hint()));
   }
   return UMX_OK;
 }
@@ -303,6 +409,8 @@ int umx_gp_begin_virial(umx_engine* eng, const float* d_pos, int node_lo, int no
   if (eng->recompute == 2)
     return fail(eng, UMX_ERR_ARG, "umx_gp_begin: recompute mode 2 (umx_set_recompute / UMX_RECOMPUTE=2) is a one-GPU plan; the multi-GPU graph-parallel mode "
                                   "keeps every rank's activations stored: set mode 0 or 1 on the engines that take part");
+  if (eng->pin_on)
+    return fail(eng, UMX_ERR_ARG, "umx_gp_begin: a graph is pinned (umx_pin_graph) and the graph-parallel entries build their own: call umx_unpin_graph first");
   if (eng->pbc_on && eng->n_cells > 1)
     return fail(eng, UMX_ERR_ARG, "umx_gp_begin: one image, but umx_set_cells bound cells for " + std::to_string(eng->n_cells) +
                                   " images: the graph-parallel mode takes per-image cells only when exactly one is bound");
@@ -454,14 +562,30 @@ int umx_last_graph_stats(const umx_engine* eng, int64_t* n_edges_total, int32_t*
 int umx_set_cell(umx_engine* eng, const double cell[9], const int pbc[3]) {
   if (!eng) return UMX_ERR_ARG;
   if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_set_cell: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
-  return set_cell_impl(eng, cell, pbc);
+  CHK(set_cell_impl(eng, cell, pbc));
+  return pin_after_cell(eng);
 }
 int umx_set_cells(umx_engine* eng, int n_images, const double* cells, const int pbc[3]) {
   if (!eng) return UMX_ERR_ARG;
   if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_set_cells: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
-  return set_cells_impl(eng, n_images, cells, pbc);
+  CHK(set_cells_impl(eng, n_images, cells, pbc));
+  return pin_after_cell(eng);
 }
 int umx_last_graph_shifts(const umx_engine* eng) { return eng ? eng->last_shifts : 0; }
+
+int umx_pin_graph(umx_engine* eng, const float* pos_ang) { return pin_graph_impl(eng, pos_ang); }
+int umx_pin_graph_f64(umx_engine* eng, const double* pos_ang) { return pin_graph_impl(eng, pos_ang); }
+int umx_unpin_graph(umx_engine* eng) {
+  if (!eng) return UMX_ERR_ARG;
+  pin_clear(eng);
+  return UMX_OK;
+}
+int umx_pinned_graph(const umx_engine* eng, int64_t* n_edges, int32_t* max_degree) {
+  if (!eng) return UMX_ERR_ARG;
+  if (n_edges) *n_edges = eng->pin_on ? (int64_t)eng->pin_edges : 0;
+  if (max_degree) *max_degree = eng->pin_on ? (int32_t)eng->pin_maxdeg : 0;
+  return UMX_OK;
+}
 
 int umx_last_partitions(const umx_engine* eng) { return eng ? eng->last_parts : 0; }
 int umx_last_lanes(const umx_engine* eng) { return eng ? eng->last_lanes : 0; }

@@ -276,11 +276,15 @@ __global__ __launch_bounds__(1024) void k_scan(const int* __restrict__ deg, long
 // IMG = true (umx_set_cells, PBC only): the cell of the node's image, as in k_graph_count -- both take the image index from the same
 // (img0, node / natoms), so the rows the count sized are the rows the fill writes.
 // P = double: as in k_graph_count -- both form a candidate's edge vector through the same pbc_delta / open_delta, so they decide alike.
-template <bool TRUNC, bool PBC, bool IMG = false, typename P = float>
+// TOUT = true (PBC only; the pinning call umx_pin_graph alone): etr[slot] receives the translation the edge took, as the bits of its
+// table entry's w ((na + 8) | (nb + 8) << 8 | (nc + 8) << 16).  Every other instantiation ignores etr and keeps its code.
+template <bool TRUNC, bool PBC, bool IMG = false, typename P = float, bool TOUT = false>
 __global__ __launch_bounds__(256) void k_graph_fill(const P* __restrict__ pos, int natoms, long nt, float rc2, int max_neigh,
                                                     const int* __restrict__ cand, const int* __restrict__ row_ptr, int* __restrict__ esrc,
-                                                    int* __restrict__ edst, float* __restrict__ evec, long lo, long hi, const PeriodicArg<IMG, P> parg) {
+                                                    int* __restrict__ edst, float* __restrict__ evec, long lo, long hi, const PeriodicArg<IMG, P> parg,
+                                                    int* __restrict__ etr = nullptr) {
   static_assert(PBC || !IMG, "per-image cells are periodic");
+  static_assert(PBC || !TOUT, "open boundaries have no translation to report");
   UMX_WAVE_ITEM(node, nt)
   if (node < lo || node >= hi) return;           // wave-uniform: rows outside the owned target range are empty
   const Periodic per = periodic_of_node(parg, node, natoms);
@@ -366,6 +370,7 @@ __global__ __launch_bounds__(256) void k_graph_fill(const P* __restrict__ pos, i
             esrc[slot] = (int)(base + j);
             edst[slot] = (int)node;
             *reinterpret_cast<float4*>(evec + (long)slot * 4) = make_float4(dx * inv, dy * inv, dz * inv, d);
+            if constexpr (TOUT) etr[slot] = (int)__float_as_uint(per.shifts[t].w);
             ++slot;
           }
         }
@@ -451,6 +456,105 @@ __global__ __launch_bounds__(256) void k_graph_fill(const P* __restrict__ pos, i
     w += __popcll(m);
   }
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Pinned graph (umx_pin_graph): the edge set of ONE reference image, kept and replayed for every image of every evaluation while the
+// pin holds.  Per directed edge of the reference the engine keeps the source and the target (atom indices within the image), and an
+// index into the distinct lattice translations the reference edges took; per atom the integer wrap offset n of k_wrap_cell at pin time.
+// ------------------------------------------------------------------------------------------------
+// the wrap offsets of k_wrap_cell (the same expressions), as integers: out[3 i + k] = n_k of atom i.  Run once, by the pinning call.
+template <bool IMG, typename P = float>
+__global__ void k_wrap_index(const P* __restrict__ pos, int* __restrict__ out, long nt, int natoms, const PeriodicArg<IMG, P> parg) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nt) return;
+  if constexpr (std::is_same_v<P, double>) {
+    const Lattice64* lp;
+    if constexpr (IMG) lp = parg.lats + (parg.img0 + (int)(i / natoms));
+    else lp = &parg.lat;
+    const Lattice64& lat = *lp;
+    const double x = pos[i * 3 + 0], y = pos[i * 3 + 1], z = pos[i * 3 + 2];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[i * 3 + k] = (int)floor(fma(z, lat.b[k][2], fma(y, lat.b[k][1], x * lat.b[k][0])));
+  } else {
+    const Periodic* pp;
+    if constexpr (IMG) pp = parg.cells + (parg.img0 + (int)(i / natoms));
+    else pp = &parg;
+    const Periodic& per = *pp;
+    const float x = pos[i * 3 + 0], y = pos[i * 3 + 1], z = pos[i * 3 + 2];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[i * 3 + k] = (int)floorf(fmaf(z, per.b[k][2], fmaf(y, per.b[k][1], x * per.b[k][0])));
+  }
+}
+
+// a position shifted by the stored wrap offset n in the cell at hand: the expressions of k_wrap_cell
+__device__ __forceinline__ void wrap_by(const Periodic& per, const int* __restrict__ n, float& x, float& y, float& z) {
+  const float n0 = (float)n[0], n1 = (float)n[1], n2 = (float)n[2];
+  x = x - fmaf(n2, per.a[2][0], fmaf(n1, per.a[1][0], n0 * per.a[0][0]));
+  y = y - fmaf(n2, per.a[2][1], fmaf(n1, per.a[1][1], n0 * per.a[0][1]));
+  z = z - fmaf(n2, per.a[2][2], fmaf(n1, per.a[1][2], n0 * per.a[0][2]));
+}
+__device__ __forceinline__ void wrap_by(const Lattice64& lat, const int* __restrict__ n, double& x, double& y, double& z) {
+  const double n0 = (double)n[0], n1 = (double)n[1], n2 = (double)n[2];
+  x = x - fma(n2, lat.a[2][0], fma(n1, lat.a[1][0], n0 * lat.a[0][0]));
+  y = y - fma(n2, lat.a[2][1], fma(n1, lat.a[1][1], n0 * lat.a[0][1]));
+  z = z - fma(n2, lat.a[2][2], fma(n1, lat.a[1][2], n0 * lat.a[0][2]));
+}
+
+// The replay: one thread per edge of the chunk.  Reference edges [e0, e0 + ecnt) -- all of them, or the contiguous rows of one
+// target-node partition -- are written for each of the chunk's images: output edge k * ecnt + (e - e0) of image k gets source and target
+// with the image's node offset, and the edge vector r_src + t - r_dst of the image's positions.  No cutoff test, no ranking: an edge
+// that has grown beyond the cutoff stays, k_edge_geom gives it envelope 0.
+// BC: 0 open boundaries, 1 one cell (umx_set_cell), 2 per-image cells (umx_set_cells; cell parg.img0 + k for image k).
+// P = float: the expression of the float k_graph_fill (pbc_delta / open_delta) on positions shifted by the stored wrap offsets, with
+// the translation read from pshift -- [cells][nd] entries the host forms with the routine that fills the translation table, so at the
+// pin-time cell they are the table's bits.  P = double: one float64 difference rounded once, as k_graph_fill<..., double>.
+// flag: bit 1 of the sticky status word for a non-finite coordinate, as k_graph_count sets it.
+template <int BC, typename P = float>
+__global__ __launch_bounds__(256) void k_graph_replay(const P* __restrict__ pos, int natoms, long e0, long ecnt, long total,
+                                                      const int* __restrict__ psrc, const int* __restrict__ pdst, const int* __restrict__ ptix,
+                                                      const int* __restrict__ pwrap, const float4* __restrict__ pshift, int nd,
+                                                      int* __restrict__ esrc, int* __restrict__ edst, float* __restrict__ evec, int* __restrict__ flag,
+                                                      const PeriodicArg<BC == 2, P> parg) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const long img = i / ecnt;
+  const long e = e0 + (i - img * ecnt);
+  const int js = psrc[e], jd = pdst[e];
+  const long base = img * natoms;
+  const P* ps = pos + (base + js) * 3;
+  const P* pd = pos + (base + jd) * 3;
+  P sx = ps[0], sy = ps[1], sz = ps[2], xi = pd[0], yi = pd[1], zi = pd[2];
+  if (!(isfinite(sx) && isfinite(sy) && isfinite(sz) && isfinite(xi) && isfinite(yi) && isfinite(zi))) atomicOr(flag, 2);
+  float dx, dy, dz;
+  if constexpr (BC == 0) {
+    dx = open_delta(sx, xi); dy = open_delta(sy, yi); dz = open_delta(sz, zi);
+  } else {
+    int cell = 0;
+    if constexpr (BC == 2) cell = parg.img0 + (int)img;
+    const float4 sh = pshift[(long)cell * nd + ptix[e]];
+    if constexpr (std::is_same_v<P, double>) {
+      const Lattice64* lp;
+      if constexpr (BC == 2) lp = parg.lats + cell;
+      else lp = &parg.lat;
+      wrap_by(*lp, pwrap + js * 3, sx, sy, sz);
+      wrap_by(*lp, pwrap + jd * 3, xi, yi, zi);
+      const double pj[3] = {sx, sy, sz};
+      pbc_delta(pj, xi, yi, zi, sh, *lp, dx, dy, dz);
+    } else {
+      const Periodic* pp;
+      if constexpr (BC == 2) pp = parg.cells + cell;
+      else pp = &parg;
+      wrap_by(*pp, pwrap + js * 3, sx, sy, sz);
+      wrap_by(*pp, pwrap + jd * 3, xi, yi, zi);
+      const float pj[3] = {sx, sy, sz};
+      pbc_delta(pj, xi, yi, zi, sh, NoLattice(), dx, dy, dz);
+    }
+  }
+  const float d = sqrtf(dist2_f(dx, dy, dz)), inv = 1.0f / d;
+  esrc[i] = (int)(base + js);
+  edst[i] = (int)(base + jd);
+  *reinterpret_cast<float4*>(evec + i * 4) = make_float4(dx * inv, dy * inv, dz * inv, d);
 }
 
 // CSR by SOURCE (out-edges), valid for any graph (max_neigh truncation makes it asymmetric): count, scan (k_scan), fill

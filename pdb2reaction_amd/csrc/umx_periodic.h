@@ -18,6 +18,16 @@ inline void cross3(const double* u, const double* v, double* o) {
 }
 inline double norm3(const double* u) { return std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]); }
 
+// One entry of a translation table: t = a cell[0] + b cell[1] + c cell[2] rounded to float32, and the integer triple packed in w.  The ONE
+// routine behind the table of build_periodic and the translations of a pinned graph (pin_upload_shifts), so both hold the same bits.
+inline float4 shift_entry(const double cell[9], int a, int b, int c) {
+  const unsigned code = (unsigned)(a + 8) | ((unsigned)(b + 8) << 8) | ((unsigned)(c + 8) << 16);
+  float w;
+  std::memcpy(&w, &code, sizeof(w));
+  return make_float4((float)(a * cell[0] + b * cell[3] + c * cell[6]), (float)(a * cell[1] + b * cell[4] + c * cell[7]),
+                     (float)(a * cell[2] + b * cell[5] + c * cell[8]), w);
+}
+
 // false + *why: the cell is refused
 bool build_periodic(const double cell[9], const int pbc[3], double cutoff, PeriodicHost* out, std::string* why) {
   const char ax[3] = {'a', 'b', 'c'};
@@ -86,11 +96,7 @@ bool build_periodic(const double cell[9], const int pbc[3], double cutoff, Perio
     for (int b = -N[1]; b <= N[1]; ++b)
       for (int c = -N[2]; c <= N[2]; ++c) {
         if (a == 0 && b == 0 && c == 0) per.zero = (int)out->table.size();
-        const unsigned code = (unsigned)(a + 8) | ((unsigned)(b + 8) << 8) | ((unsigned)(c + 8) << 16);
-        float w;
-        std::memcpy(&w, &code, sizeof(w));
-        out->table.push_back(make_float4((float)(a * cell[0] + b * cell[3] + c * cell[6]), (float)(a * cell[1] + b * cell[4] + c * cell[7]),
-                                         (float)(a * cell[2] + b * cell[5] + c * cell[8]), w));
+        out->table.push_back(shift_entry(cell, a, b, c));
       }
   per.n_shifts = (int)out->table.size();
   return true;
@@ -214,6 +220,10 @@ int periodic_prepare(umx_engine* eng, hipStream_t s, long K, PosPtr* d_pos) {
   if ((unsigned long long)most * (unsigned long long)eng->natoms > 0xffffffffull)
     return fail(eng, UMX_ERR_ARG, "umx_energy_forces: " + (img ? "image " + std::to_string(most_at) + ": " : std::string()) + std::to_string(most) + " lattice translations x " +
                 std::to_string(eng->natoms) + " atoms do not fit the 32-bit candidate index of the periodic graph");
+  if (eng->pin_on) {                             // pinned graph: nothing is searched; the replay shifts the positions by the stored wrap offsets itself
+    eng->last_shifts = (int)eng->pin_codes.size();
+    return UMX_OK;
+  }
   const long nt = K * eng->natoms;
   if (d_pos->d) {
     if (eng->wrap64_cap < nt) CHK(grow(eng, eng->wrap64_cap, nt, {s}, {DevBuf(eng->d_wrap64, (size_t)nt * 3)}));
@@ -281,6 +291,79 @@ void launch_graph_fill(umx_engine* eng, hipStream_t s, bool trunc, PosPtr d_pos,
                        float* evec, long lo, long hi, long img0) {
   if (d_pos.d) launch_graph_fill_of(eng, s, trunc, d_pos.d, nn, cand, row_ptr, esrc, edst, evec, lo, hi, img0);
   else launch_graph_fill_of(eng, s, trunc, d_pos.f, nn, cand, row_ptr, esrc, edst, evec, lo, hi, img0);
+}
+
+// ---- pinned graph (umx_pin_graph) ------------------------------------------------------------------------------------------------------
+// The pinning call's fill of the periodic reference image: k_graph_fill with the translation of every edge as one more output (etr: the
+// packed integer triple).  Open boundaries take the ordinary launcher: there is no translation to report.
+template <typename P>
+void launch_graph_fill_pin_of(umx_engine* eng, hipStream_t s, bool trunc, const P* d_pos, long nn, const int* cand, const int* row_ptr, int* esrc, int* edst,
+                              float* evec, int* etr) {
+  const float rc2 = eng->cutoff * eng->cutoff;
+  const dim3 grid(nblk(nn, 4)), block(256);
+  const int N = eng->natoms, mn = eng->max_neigh;
+  if (eng->n_cells > 0) {
+    const auto pi = periodic_arg<true, P>(eng, 0);
+    if (trunc) hipLaunchKernelGGL((k_graph_fill<true, true, true, P, true>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, 0L, nn, pi, etr);
+    else hipLaunchKernelGGL((k_graph_fill<false, true, true, P, true>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, 0L, nn, pi, etr);
+  } else {
+    const auto per = periodic_arg<false, P>(eng, 0);
+    if (trunc) hipLaunchKernelGGL((k_graph_fill<true, true, false, P, true>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, 0L, nn, per, etr);
+    else hipLaunchKernelGGL((k_graph_fill<false, true, false, P, true>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, 0L, nn, per, etr);
+  }
+}
+void launch_graph_fill_pin(umx_engine* eng, hipStream_t s, bool trunc, PosPtr d_pos, long nn, const int* cand, const int* row_ptr, int* esrc, int* edst,
+                           float* evec, int* etr) {
+  if (!eng->pbc_on) { launch_graph_fill(eng, s, trunc, d_pos, nn, cand, row_ptr, esrc, edst, evec, 0, nn, 0); return; }
+  if (d_pos.d) launch_graph_fill_pin_of(eng, s, trunc, d_pos.d, nn, cand, row_ptr, esrc, edst, evec, etr);
+  else launch_graph_fill_pin_of(eng, s, trunc, d_pos.f, nn, cand, row_ptr, esrc, edst, evec, etr);
+}
+// the wrap offsets of the reference image (d_pos: the caller's positions, not the wrapped copy); open boundaries: zeros
+template <typename P>
+void launch_wrap_index_of(umx_engine* eng, hipStream_t s, const P* d_pos, int* out) {
+  const long N = eng->natoms;
+  if (eng->n_cells > 0) hipLaunchKernelGGL((k_wrap_index<true, P>), dim3(nblk(N, 256)), dim3(256), 0, s, d_pos, out, N, eng->natoms, periodic_arg<true, P>(eng, 0));
+  else hipLaunchKernelGGL((k_wrap_index<false, P>), dim3(nblk(N, 256)), dim3(256), 0, s, d_pos, out, N, eng->natoms, periodic_arg<false, P>(eng, 0));
+}
+
+// The translations of the pinned edges in the cell(s) in force, [cells][distinct triples], through shift_entry -- at pinning, and again
+// when umx_set_cell / umx_set_cells bind other cells under the pin.  `into`: the buffer to fill (grown when too small).
+int pin_upload_shifts(umx_engine* eng, const std::vector<unsigned>& codes, float4** into, long* cap) {
+  const long nc = eng->n_cells > 0 ? eng->n_cells : 1, nd = (long)codes.size();
+  if (!eng->pbc_on || nd == 0) return UMX_OK;
+  std::vector<float4> tab((size_t)(nc * nd));
+  for (long k = 0; k < nc; ++k) {
+    const double* cell = eng->n_cells > 0 ? eng->cells.data() + (size_t)k * 9 : eng->cell;
+    for (long t = 0; t < nd; ++t)
+      tab[(size_t)(k * nd + t)] = shift_entry(cell, (int)(codes[t] & 255u) - 8, (int)((codes[t] >> 8) & 255u) - 8, (int)((codes[t] >> 16) & 255u) - 8);
+  }
+  if (*cap < nc * nd) {
+    if (*into) HIPCHK(eng, hipFree(*into));
+    *into = nullptr; *cap = 0;
+    HIPCHK(eng, hipMalloc(into, tab.size() * sizeof(float4)));
+    *cap = nc * nd;
+  }
+  HIPCHK(eng, hipMemcpy(*into, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice));
+  return UMX_OK;
+}
+
+// the replay of the pinned graph for the nimg images d_pos starts at: reference edges [e0, e0 + ecnt) of each (k_graph_replay)
+template <typename P>
+void launch_graph_replay_of(umx_engine* eng, hipStream_t s, const P* d_pos, long nimg, long e0, long ecnt, int* esrc, int* edst, float* evec, long img0) {
+  const long total = nimg * ecnt;
+  if (total <= 0) return;
+  const dim3 grid(nblk(total, 256)), block(256);
+  const int N = eng->natoms, nd = (int)eng->pin_codes.size();
+#define UMX_REPLAY(BC, ARG) hipLaunchKernelGGL((k_graph_replay<BC, P>), grid, block, 0, s, d_pos, N, e0, ecnt, total, eng->d_pin_src, eng->d_pin_dst, eng->d_pin_tix, \
+                                               eng->d_pin_wrap, eng->d_pin_shifts, nd, esrc, edst, evec, eng->d_flags, ARG)
+  if (eng->pbc_on && eng->n_cells > 0) UMX_REPLAY(2, (periodic_arg<true, P>(eng, img0)));
+  else if (eng->pbc_on) UMX_REPLAY(1, (periodic_arg<false, P>(eng, 0)));
+  else UMX_REPLAY(0, (periodic_arg<false, P>(eng, 0, false)));
+#undef UMX_REPLAY
+}
+void launch_graph_replay(umx_engine* eng, hipStream_t s, PosPtr d_pos, long nimg, long e0, long ecnt, int* esrc, int* edst, float* evec, long img0) {
+  if (d_pos.d) launch_graph_replay_of(eng, s, d_pos.d, nimg, e0, ecnt, esrc, edst, evec, img0);
+  else launch_graph_replay_of(eng, s, d_pos.f, nimg, e0, ecnt, esrc, edst, evec, img0);
 }
 
 }  // namespace

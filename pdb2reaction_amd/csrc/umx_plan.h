@@ -75,12 +75,16 @@ void plan_chunk(umx_engine* eng, WS& w, const PosPtr d_pos, const int* d_deg, co
   const bool rc = eng->rc_active && d_forces != nullptr;         // recompute plan: one activation slot (carve_acts), replayed layer by layer in the reverse pass
   const bool fused_rev = eng->prec.planes || !eng->dbg_on;     // k_modrot_bwd_pl produces g_xn itself (fp32 mode with debug captures: the unfused kernels, which expose xrot / g_xrot)
   const long g_lo = gp ? eng->gp_lo : 0, g_hi = gp ? eng->gp_hi : nn;
+  // pinned graph: the reference edges this chunk replays per image -- all of them, or the contiguous rows [g_lo, g_hi) of a partition
+  const bool pinned = eng->pin_on;
+  const long pin_e0 = pinned && gp ? eng->pin_row[g_lo] : 0, pin_ecnt = pinned ? (gp ? eng->pin_row[g_hi] - pin_e0 : eng->pin_edges) : 0;
   // every closure reads eng->stream when it RUNS (the executor points it at the lane's stream)
   // K1 graph, K4 + K5
   P.stream([=, &w]() -> int {
     hipStream_t s = eng->stream;
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, d_deg, nn, w.row_ptr, w.stats);
-    launch_graph_fill(eng, s, may_trunc, d_pos, nn, d_cand, w.row_ptr, w.esrc, w.edst, w.evec, g_lo, g_hi, img0);
+    if (pinned) launch_graph_replay(eng, s, d_pos, nimg, pin_e0, pin_ecnt, w.esrc, w.edst, w.evec, img0);
+    else launch_graph_fill(eng, s, may_trunc, d_pos, nn, d_cand, w.row_ptr, w.esrc, w.edst, w.evec, g_lo, g_hi, img0);
     HIPCHK(eng, hipMemsetAsync(w.out_cur, 0, (nn + 1) * sizeof(int), s));
     if (ne > 0) hipLaunchKernelGGL(k_out_count, dim3(nblk(ne, 256)), B256, 0, s, w.esrc, ne, w.out_cur);
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, w.out_cur, nn, w.out_ptr, w.stats + 2);
@@ -575,6 +579,23 @@ struct ImageEdges { std::vector<int> per_image; long emax = 0, etot = 0; };
 int degree_pass(umx_engine* eng, hipStream_t s, long K, const PosPtr d_pos, ImageEdges& ie) {
   const int N = eng->natoms;
   const long nt = K * N;
+  if (eng->pin_on) {
+    // pinned graph: every image has the reference's edges; nothing is launched and nothing read back.  (Only a call of more images
+    // than any before it extends the repeated degrees k_scan reads.)
+    if (eng->pin_deg_imgs < K) {
+      std::vector<int> rep((size_t)nt);
+      for (long k = 0; k < K; ++k) std::copy(eng->pin_deg.begin(), eng->pin_deg.end(), rep.begin() + k * N);
+      CHK(grow(eng, eng->pin_deg_imgs, K, {s, eng->stream2}, {DevBuf(eng->d_pin_deg, (size_t)nt)}));
+      HIPCHK(eng, hipMemcpy(eng->d_pin_deg, rep.data(), rep.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
+    ie.per_image.assign((size_t)K + 1, (int)eng->pin_edges);
+    ie.per_image[K] = eng->pin_maxdeg;
+    eng->last_maxdeg = eng->pin_maxdeg;
+    eng->may_truncate = false;
+    ie.emax = eng->pin_edges; ie.etot = K * eng->pin_edges;
+    eng->last_edges = ie.etot;
+    return UMX_OK;
+  }
   if (eng->deg_all_cap < nt) CHK(grow(eng, eng->deg_all_cap, nt, {s}, {DevBuf(eng->d_deg_all, nt), DevBuf(eng->d_cand_all, nt)}));
   if (eng->img_edges_cap < K + 1) CHK(grow(eng, eng->img_edges_cap, K + 1, {s}, {DevBuf(eng->d_img_edges, K + 1)}));
   HIPCHK(eng, hipMemsetAsync(eng->d_img_edges + K, 0, sizeof(int), s));
@@ -603,17 +624,31 @@ int eval_partitioned(umx_engine* eng, hipStream_t s, long img, const PosPtr d_po
   if (eng->part_cap < (long)P * N)
     CHK(grow(eng, eng->part_cap, (long)P * N, {s}, {DevBuf(eng->d_part_deg, (size_t)2 * P * N + 32), DevBuf(eng->d_part_f, (size_t)P * N * 3)}));
   int* d_cnt = eng->d_part_deg + (size_t)2 * P * N;           // [P] edge totals, [P] = max degree
-  HIPCHK(eng, hipMemsetAsync(d_cnt, 0, (P + 1) * sizeof(int), s));
   std::vector<long> lo(P), hi(P);
+  std::vector<int> cnt;
+  if (eng->pin_on) {
+    // pinned graph: partition p takes the rows [lo, hi) of the reference -- its degrees there, zero elsewhere -- and the host knows the counts
+    cnt.assign((size_t)P + 1, 0);
+    for (int p = 0; p < P; ++p) {
+      lo[p] = (long)N * p / P; hi[p] = (long)N * (p + 1) / P;
+      int* deg = eng->d_part_deg + (size_t)(2 * p) * N;
+      HIPCHK(eng, hipMemsetAsync(deg, 0, (size_t)N * sizeof(int), s));
+      if (hi[p] > lo[p]) HIPCHK(eng, hipMemcpyAsync(deg + lo[p], eng->d_pin_deg + lo[p], (size_t)(hi[p] - lo[p]) * sizeof(int), hipMemcpyDeviceToDevice, s));
+      cnt[p] = (int)(eng->pin_row[hi[p]] - eng->pin_row[lo[p]]);
+    }
+    cnt[P] = eng->pin_maxdeg;
+    eng->may_truncate = false;
+  } else {
+  HIPCHK(eng, hipMemsetAsync(d_cnt, 0, (P + 1) * sizeof(int), s));
   for (int p = 0; p < P; ++p) {
     lo[p] = (long)N * p / P; hi[p] = (long)N * (p + 1) / P;
     int* deg = eng->d_part_deg + (size_t)(2 * p) * N;
     launch_graph_count(eng, s, d_pos, (long)N, deg, deg + N, lo[p], hi[p], img);
     hipLaunchKernelGGL(k_image_edges, dim3(1), dim3(256), 0, s, deg, N, d_cnt + p, d_cnt + P);
   }
-  std::vector<int> cnt;
   CHK(read_degree_pass(eng, s, d_cnt, P, cnt, true));
   eng->may_truncate = cnt[P] >= eng->max_neigh;
+  }
   // layout: P persistent regions, then one shared region sized for the largest partition -- the transient operands and, for a recompute
   // plan, the activation slot: between two exchange points a partition replays and reverses ONE layer, then the next partition runs
   std::vector<size_t> off;
@@ -826,7 +861,8 @@ int run_chunks(umx_engine* eng, hipStream_t s, int lanes, const ImageEdges& ie, 
     for (long k = k0; k < k1; ++k) e += ie.per_image[k];
     VirialOut vir;       // the partials' slots follow the image's position in the call: the two lanes never share one
     if (eng->vir_out && d_forces) { vir.out = eng->vir_out + k0 * 9; vir.part = eng->d_vir_part + k0 * eng->vir_slabs * 9; vir.slabs = eng->vir_slabs; }
-    plan_chunk(eng, wl[lane], d_pos.atom(k0 * N), eng->d_deg_all + k0 * N, eng->d_cand_all + k0 * N, k0, k1 - k0, e, d_energy + k0,
+    // (pinned graph: every image has the reference's degrees -- the repeated copy from its start; no candidate counts)
+    plan_chunk(eng, wl[lane], d_pos.atom(k0 * N), eng->pin_on ? eng->d_pin_deg : eng->d_deg_all + k0 * N, eng->pin_on ? nullptr : eng->d_cand_all + k0 * N, k0, k1 - k0, e, d_energy + k0,
                d_forces ? d_forces + k0 * N * 3 : nullptr, P, vir);
   };
   if (lanes == 2) {          // chunks in pairs, one per lane, matrix segments alternating between the lanes (run_plans_alternating)

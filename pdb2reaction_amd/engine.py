@@ -91,6 +91,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "umx_set_cell": ([vp, dp, C.POINTER(C.c_int)], i32),
         "umx_set_cells": ([vp, C.c_int, dp, C.POINTER(C.c_int)], i32),
         "umx_last_graph_shifts": ([vp], i32),
+        "umx_pin_graph": ([vp, fp], i32),
+        "umx_pin_graph_f64": ([vp, dp], i32),
+        "umx_unpin_graph": ([vp], i32),
+        "umx_pinned_graph": ([vp, i64p, C.POINTER(C.c_int32)], i32),
         "umx_last_partitions": ([vp], i32),
         "umx_last_lanes": ([vp], i32),
         "umx_set_recompute": ([vp, i32], i32),
@@ -138,14 +142,14 @@ EXPORTED_SYMBOLS = (
     "umx_last_graph_stats", "umx_last_partitions", "umx_last_lanes", "umx_reserve_images", "umx_workspace_stats", "umx_profile_enable", "umx_profile_read", "umx_bond_changes", "umx_debug_fetch", "umx_debug_keep",
     "umx_set_expert_coefficients", "umx_expert_count", "umx_set_recompute", "umx_last_recompute", "umx_workspace_bytes",
     "umx_set_cell", "umx_set_cells", "umx_last_graph_shifts", "umx_energy_forces_virial", "umx_energy_forces_virial_dev",
-    "umx_gp_begin_virial",
+    "umx_gp_begin_virial", "umx_pin_graph", "umx_unpin_graph", "umx_pinned_graph",
 )
 # The float64-position entries, listed apart: tests/test_boundary_cpu.py holds EXPORTED_SYMBOLS to the names it reads out of the header
 # with a pattern of letters and underscores, which a name with a digit in it does not match.  load_library declares (and so demands)
 # these like every other entry; tests/test_double_positions_cpu.py holds them to the header.  build() in __graft_entry__.py and
 # test_library_exports_every_declared_symbol in tests/test_boundary_cpu.py iterate EXPORTED_SYMBOLS only, so neither sees these two: once that
 # test's pattern admits digits, fold the two lists into one.
-EXPORTED_SYMBOLS_F64 = ("umx_energy_forces_f64", "umx_energy_forces_f64_dev")
+EXPORTED_SYMBOLS_F64 = ("umx_energy_forces_f64", "umx_energy_forces_f64_dev", "umx_pin_graph_f64")
 
 
 def workspace_bytes(n_nodes: int, n_edges: int, parts: int = 0, recompute: int = 0, engine: Optional["Engine"] = None) -> int:
@@ -216,6 +220,7 @@ class Engine:
         self.dataset_list = tuple(W.DATASET_LIST)      # order of the rows of the loaded blob's dataset_embedding.weight (load_weights)
         self._cells = None              # (cells (K,3,3) float64, pbc flags (3,)) set_cells accepted last; it and _cell exclude each other
         self._cell = None               # (cell (3,3) float64, pbc flags (3,)) the engine accepted last (set_cell), None for open boundaries
+        self._pin = None                # (reference positions (N,3), double_positions, pbc flags | None) of the graph pinned now, else None
         if precision is not None:
             self._chk(self.lib.umx_set_precision(self._h, precision.encode()), "umx_set_precision")
         if recompute is not None:
@@ -291,6 +296,7 @@ class Engine:
                   "umx_set_system")
         self.natoms = len(z)
         self._system = (z.copy(), int(charge), int(spin), task, radius, max_neigh)
+        self._pin = None                # umx_set_system unpins
 
     def set_cell(self, cell=None, pbc=None):
         """Periodic boundary conditions (``umx_set_cell``): ``cell`` (3,3) lattice vectors as rows in Angstrom, ``pbc`` one flag per axis
@@ -302,11 +308,13 @@ class Engine:
         if cell is None or flags is None or not flags.any():
             self._chk(self.lib.umx_set_cell(self._h, None, None), "umx_set_cell")
             self._cell = self._cells = None
+            self._pin_follow()
             return
         c = np.ascontiguousarray(np.asarray(cell, dtype=np.float64).reshape(3, 3))
         f = np.ascontiguousarray(flags, dtype=np.intc)
         self._chk(self.lib.umx_set_cell(self._h, c.ctypes.data_as(C.POINTER(C.c_double)), f.ctypes.data_as(C.POINTER(C.c_int))), "umx_set_cell")
         self._cell, self._cells = (c.copy(), tuple(bool(x) for x in flags)), None
+        self._pin_follow()
 
     def set_cells(self, cells=None, pbc=None):
         """Per-image cells (``umx_set_cells``): ``cells`` (K,3,3), cell k for image k of the evaluations that follow, ``pbc`` as for
@@ -319,6 +327,7 @@ class Engine:
         if cells is None or flags is None or not flags.any():
             self._chk(self.lib.umx_set_cells(self._h, 0, None, None), "umx_set_cells")
             self._cell = self._cells = None
+            self._pin_follow()
             return
         c = np.ascontiguousarray(np.asarray(cells, dtype=np.float64))
         if c.ndim != 3 or c.shape[1:] != (3, 3) or c.shape[0] == 0:
@@ -327,10 +336,56 @@ class Engine:
         self._chk(self.lib.umx_set_cells(self._h, c.shape[0], c.ctypes.data_as(C.POINTER(C.c_double)), f.ctypes.data_as(C.POINTER(C.c_int))),
                   "umx_set_cells")
         self._cell, self._cells = None, (c.copy(), tuple(bool(x) for x in flags))
+        self._pin_follow()
 
     def last_graph_shifts(self) -> int:
         """Lattice translations the most recent evaluation searched (``umx_last_graph_shifts``); 0 = open boundaries."""
         return int(self.lib.umx_last_graph_shifts(self._h))
+
+    # ---- pinned neighbour graph ------------------------------------------------------------------
+    def pin_graph(self, pos_ang, double_positions: bool = False):
+        """Pin the neighbour graph of ONE reference image (``umx_pin_graph`` / ``umx_pin_graph_f64``): ``pos_ang`` (N,3) or (1,N,3)
+        Angstrom, rounded to float32 unless ``double_positions``.  The graph is built with the radius, ``max_neigh``, cell and pbc flags
+        in force, exactly as an evaluation of that image builds it; from then on every image of every evaluation uses that edge set --
+        only the edge vectors follow the positions (and the cell in force) -- until ``unpin_graph``.  For whatever differences
+        evaluations of nearby geometries: without the pin an edge that enters or leaves through the ``max_neigh`` cap makes the energy
+        jump.  ``set_system`` unpins; ``set_cell`` / ``set_cells`` keep the pin while the pbc flags stay those of pin time.  A refused
+        pin (``UmxError``) leaves the previous state."""
+        p = self._positions(pos_ang, double_positions)
+        if p.shape[0] != 1:
+            raise ValueError(f"pin_graph takes one reference image, got {p.shape[0]}")
+        if double_positions:
+            self._chk(self.lib.umx_pin_graph_f64(self._h, p.ctypes.data_as(C.POINTER(C.c_double))), "umx_pin_graph_f64")
+        else:
+            self._chk(self.lib.umx_pin_graph(self._h, p.ctypes.data_as(C.POINTER(C.c_float))), "umx_pin_graph")
+        self._pin = (p[0].copy(), bool(double_positions), self._pbc_flags())
+
+    def unpin_graph(self):
+        """Back to a graph rebuilt from the positions of every evaluation (``umx_unpin_graph``), bit for bit what it was."""
+        self._chk(self.lib.umx_unpin_graph(self._h), "umx_unpin_graph")
+        self._pin = None
+
+    def pinned_graph(self) -> Optional[Tuple[int, int]]:
+        """(directed edges, largest in-degree) of the pinned graph (``umx_pinned_graph``), or None when nothing is pinned."""
+        if getattr(self, "_pin", None) is None:
+            return None
+        ne, md = C.c_int64(), C.c_int32()
+        self._chk(self.lib.umx_pinned_graph(self._h, C.byref(ne), C.byref(md)), "umx_pinned_graph")
+        return int(ne.value), int(md.value)
+
+    def pinned(self, pos_ang, double_positions: bool = False):
+        """``with engine.pinned(x_ref): ...`` -- ``pin_graph(x_ref)`` for the block, ``unpin_graph()`` on the way out, also on an exception."""
+        return _Pinned(self, pos_ang, dp_kw(double_positions))
+
+    def _pin_follow(self):
+        """After ``set_cell`` / ``set_cells``: the engine dropped the pin when the pbc flags are no longer those of pin time."""
+        if getattr(self, "_pin", None) is not None and self._pbc_flags() != self._pin[2]:
+            self._pin = None
+
+    def _pbc_flags(self):
+        """The pbc flags in force (a tuple of three bools), None for open boundaries."""
+        bound = getattr(self, "_cell", None) or getattr(self, "_cells", None)
+        return None if bound is None else tuple(bound[1])
 
     def set_workspace_limit(self, nbytes: int):
         self._chk(self.lib.umx_set_workspace_limit(self._h, int(nbytes)), "umx_set_workspace_limit")
@@ -452,7 +507,10 @@ class Engine:
         self.precision, self.widened = wider, True
         self.load_weights(self._blob)
         z, charge, spin, task, radius, max_neigh = self._system
+        pin = getattr(self, "_pin", None)
         self.set_system(z, charge, spin, task, radius, max_neigh)
+        if pin is not None:             # set_system unpinned: the same graph again (the graph does not depend on the arithmetic)
+            self.pin_graph(pin[0], double_positions=pin[1])
         return True
 
     def energy_forces_dev(self, n_images: int, d_pos: int, d_energy: int, d_forces: Optional[int], stream: int = 0, double_positions: bool = False):
@@ -571,3 +629,18 @@ class Engine:
         self._chk(self.lib.umx_debug_fetch(self._h, name.encode(), out.ctypes.data_as(C.c_void_p), out.nbytes, None),
                   "umx_debug_fetch")
         return out
+
+
+class _Pinned:
+    """Context manager behind ``Engine.pinned`` / ``LocalEnginePool.pinned`` / ``UMXCalculator.pinned``: pin on entry, unpin on exit."""
+
+    def __init__(self, target, pos_ang, kw: dict):
+        self.target, self.pos, self.kw = target, pos_ang, kw
+
+    def __enter__(self):
+        self.target.pin_graph(self.pos, **self.kw)
+        return self.target
+
+    def __exit__(self, *exc):
+        self.target.unpin_graph()
+        return False

@@ -464,6 +464,7 @@ class LocalEnginePool:
         self._cells = None                      # per-image cells (``set_cells``): (cells (K,3,3) float64, pbc flags (3,)), else None
         self._cells_on = [None] * len(self.engines)   # what engine r has bound of them: its block (lo, hi), or "single" for cells[0] alone
         self.recompute = None                   # what ``create`` / ``set_recompute`` gave every engine (None: the engines' own setting)
+        self._pinned = False                    # a graph is pinned on every engine (``pin_graph``): a single geometry goes to engine 0 alone
         if len(set(self.devices)) < len(self.devices):
             free = free_bytes or (lambda d: torch.cuda.mem_get_info(d)[0])
             for eng, lim in zip(self.engines, shared_workspace_limits(self.devices, free)):
@@ -516,6 +517,48 @@ class LocalEnginePool:
             eng.set_system(atomic_numbers, **kw)
         self.natoms = len(atomic_numbers)
         self._gp_buf = self._gp_wbuf = None
+        self._pinned = False                    # (umx_set_system unpins)
+
+    # ---- pinned neighbour graph ----------------------------------------------------------------------------------------------------
+    def pin_graph(self, pos_ang, double_positions: bool = False) -> None:
+        """``Engine.pin_graph`` on EVERY engine, with the cell each has in force: a batch dealt over the pool then sees one edge set, as on
+        one engine.  While pinned, a single geometry is evaluated on engine 0 alone (``last_route == "single"``): the graph-parallel
+        entries build their own graph and refuse a pinned engine.  If an engine refuses, the ones pinned before it are unpinned again."""
+        from .engine import dp_kw
+
+        done = []
+        try:
+            for eng in self.engines:
+                eng.pin_graph(pos_ang, **dp_kw(double_positions))
+                done.append(eng)
+        except Exception:
+            for eng in done:
+                eng.unpin_graph()
+            self._pinned = False
+            raise
+        self._pinned = True
+
+    def unpin_graph(self) -> None:
+        """``Engine.unpin_graph`` on every engine (all are tried; the first error is raised afterwards)."""
+        first = None
+        for eng in self.engines:
+            try:
+                eng.unpin_graph()
+            except Exception as exc:      # noqa: BLE001
+                first = first or exc
+        self._pinned = False
+        if first is not None:
+            raise first
+
+    def pinned_graph(self):
+        """Engine 0's ``pinned_graph()``: (edges, max_degree), or None when nothing is pinned."""
+        return self.engines[0].pinned_graph() if self._pinned else None
+
+    def pinned(self, pos_ang, double_positions: bool = False):
+        """``with pool.pinned(x_ref): ...`` -- pinned on every engine for the block, unpinned on the way out, also on an exception."""
+        from .engine import _Pinned, dp_kw
+
+        return _Pinned(self, pos_ang, dp_kw(double_positions))
 
     def set_cell(self, cell=None, pbc=None) -> None:
         """``Engine.set_cell`` on every engine: batches dealt over the pool and the graph-parallel single image see the same cell."""
@@ -649,7 +692,7 @@ class LocalEnginePool:
         kw = dp_kw(double_positions)
         if p.shape[0] == 1:
             self._bind_cells(1, None)
-            if self.gp and len(self.engines) > 1 and self.recompute != 2 and not double_positions:
+            if self.gp and len(self.engines) > 1 and self.recompute != 2 and not double_positions and not self._pinned:
                 return self._graph_parallel(p[0], forces)
             self.last_route, self.last_blocks = "single", [(0, 1)]
             return self.engines[0].energy_forces(p, forces=forces, **kw)
@@ -673,6 +716,8 @@ class LocalEnginePool:
 
         if graph_parallel and double_positions:
             raise ValueError(GP_FLOAT32_ONLY)
+        if graph_parallel and self._pinned:
+            raise ValueError("graph_parallel=True: a graph is pinned (pin_graph) and the graph-parallel entries build their own -- unpin, or leave graph_parallel off")
         p = self._images(pos_ang, double_positions)
         kw = dp_kw(double_positions)
         if p.shape[0] == 1:

@@ -63,6 +63,9 @@ CALC_KW: Dict[str, Any] = {
     "hessian_double": True,
 }
 
+PIN_NOT_GP = ("hessian_pin_graph=True cannot be combined with the graph-parallel mode (workers == world size / enable_graph_parallel): its "
+              "entries (umx_gp_begin) build their own graph and refuse a pinned engine")
+
 # number of displaced geometries evaluated per engine call while building an FD Hessian
 FD_BATCH = int(os.environ.get("UMX_FD_BATCH", "64"))
 
@@ -391,6 +394,11 @@ class uma_pysis(Calculator):
         # through get_energy / get_forces / get_forces_batch / get_hessian to the engine (edge vectors from float64 differences, FD
         # displacements realised in float64).  Not with the graph-parallel mode.
         self.double_positions = bool(kwargs.pop("double_positions", False))
+        # likewise: True makes get_hessian pin the neighbour graph of the geometry it was given (Engine.pin_graph) for the displaced images
+        # of the finite-difference Hessian, so that no column differences across a change of the edge set (an edge entering or leaving
+        # through max_neigh) -- the graph held fixed is what the reference's "Analytical" mode differentiates (:394-417).  Not with the
+        # graph-parallel mode, whose entries build their own graph.
+        self.hessian_pin_graph = bool(kwargs.pop("hessian_pin_graph", False))
         super().__init__(charge=charge, mult=spin, **kwargs)
         self._core: Optional[UMAcore] = None
         self._core_kw = dict(
@@ -449,6 +457,8 @@ class uma_pysis(Calculator):
         (see ``UMAcore.enable_graph_parallel``).  Every later ``get_energy / get_forces / get_hessian`` call is then a collective."""
         if on and self._hess_shard:
             raise RuntimeError("enable_graph_parallel: FD-Hessian column sharding is on (enable_hessian_sharding); the two cannot be combined")
+        if on and getattr(self, "hessian_pin_graph", False):
+            raise ValueError(PIN_NOT_GP)
         self._ensure_core(elem).enable_graph_parallel(on, group)
 
     def enable_hessian_sharding(self, on: bool = True, group=None) -> None:
@@ -471,6 +481,9 @@ class uma_pysis(Calculator):
             # structure fits); the columns are computed by all ranks together, un-sharded.
             raise RuntimeError("FD Hessian: column sharding (enable_hessian_sharding) and the graph-parallel mode (workers == world size / "
                                "enable_graph_parallel) cannot be combined: in graph-parallel mode every force call is a collective on one geometry")
+        pin = getattr(self, "hessian_pin_graph", False)
+        if pin and getattr(core, "_gp", None) is not None:
+            raise ValueError(PIN_NOT_GP)
         base = core.compute(coord_ang, forces=True, hessian=False)
         # the displaced geometries and their forces stay on the GPU when the core runs on the HIP engine (round 6); the graph-parallel mode and
         # stand-in cores keep the host form
@@ -478,10 +491,19 @@ class uma_pysis(Calculator):
         dev_fn = core.compute_batch_dev if (getattr(core, "_gp", None) is None and getattr(core, "_pool", None) is None and hasattr(core, "compute_batch_dev")
                                             and hasattr(getattr(core, "engine", None), "energy_forces_dev")
                                             and getattr(core.device, "type", "cpu") == "cuda") else None
-        hess = H.fd_hessian(lambda c: core.compute_batch(c, forces=True)["forces"], coord_ang, self.freeze_atoms, device=core.device,
-                            double=self.hessian_double, partial=self.return_partial_hessian, batch=FD_BATCH,
-                            shard=self._hess_shard, group=self._hess_group, engine=getattr(core, "engine", None), batch_forces_dev=dev_fn,
-                            **({"double_positions": True} if self.double_positions else {}))
+        # hessian_pin_graph: the displaced images on the edge set of the geometry at hand -- pinned on the engine (every engine of a pool)
+        # around fd_hessian, which runs exactly as without it, and unpinned whatever happens in there
+        pinner = (getattr(core, "_pool", None) or core.engine) if pin else None
+        if pinner is not None:
+            pinner.pin_graph(coord_ang, **({"double_positions": True} if self.double_positions else {}))
+        try:
+            hess = H.fd_hessian(lambda c: core.compute_batch(c, forces=True)["forces"], coord_ang, self.freeze_atoms, device=core.device,
+                                double=self.hessian_double, partial=self.return_partial_hessian, batch=FD_BATCH,
+                                shard=self._hess_shard, group=self._hess_group, engine=getattr(core, "engine", None), batch_forces_dev=dev_fn,
+                                **({"double_positions": True} if self.double_positions else {}))
+        finally:
+            if pinner is not None:
+                pinner.unpin_graph()
         # (a pool that widens in the middle of this Hessian widens ALL its engines, engine 0 -- `engine` above -- included, so fd_hessian's
         # "compute every column again" rule sees it)
         return {"energy": base["energy"], "forces": base["forces"], "hessian": hess}
