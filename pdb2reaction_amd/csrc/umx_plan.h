@@ -915,7 +915,12 @@ int evaluate_planned(umx_engine* eng, hipStream_t s, long K, const PosPtr d_pos,
   if (env_cap > 0) max_chunk = std::min(max_chunk, env_cap);
   Chunks chunks;
   const int pst = eng->force_parts >= 2 ? UMX_ERR_CAPACITY : plan_chunks(eng, K, ie, max_chunk, budget, chunks);
-  if (pst == UMX_ERR_CAPACITY && !eng->gp && !eng->dbg_on) return eval_images_partitioned(eng, s, K, d_pos, d_energy, d_forces, budget * lanes, eng->err);
+  // (debug captures name ONE chunk's buffers: an image too large for one piece is not partitioned behind their back.  Partitions that were
+  // ASKED for, UMX_FORCE_PARTS, run with captures on -- every partition captures under the same names, the last one's stay)
+  if (pst == UMX_ERR_CAPACITY && !eng->gp && (!eng->dbg_on || eng->force_parts >= 2)) {
+    if (eng->dbg_on) eng->dbg.clear();
+    return eval_images_partitioned(eng, s, K, d_pos, d_energy, d_forces, budget * lanes, eng->err);
+  }
   if (pst != UMX_OK) return pst;
   eng->last_parts = 0;
   if (lanes == 2 && chunks.img.size() > 1) {
