@@ -53,6 +53,8 @@ __global__ void k_split_q_f16(const float* __restrict__ src, long rows, long ld,
 
 // fp32 -> the two 8-bit planes of the X8 form (umx_gemm_q.h, O8 layout).  WEIGHT = 0 (activations): x1' = bf8(2^10 lo), x2' = bf8(2^20 (x - hi - lo));
 // WEIGHT = 1: w0' = bf8(w), w1' = bf8(2^10 lo)
+constexpr int Q8_SHIFT = 20;      // x2' = bf8(2^Q8_SHIFT x (residual of the two half planes)),
+constexpr int Q8_SHIFT1 = 10;     // x1' = bf8(2^Q8_SHIFT1 x (the low half plane))
 template <int WEIGHT>
 __global__ void k_split_o8(const float* __restrict__ src, long rows, long ld, int K, unsigned char* __restrict__ dst) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

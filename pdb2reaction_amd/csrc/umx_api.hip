@@ -426,18 +426,13 @@ int umx_gp_step(umx_engine* eng, float** d_buf, size_t* count, int* done) {
   if (!eng || !d_buf || !count || !done) return UMX_ERR_ARG;
   if (!eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_gp_step: no graph-parallel evaluation in progress (umx_gp_begin)");
   HIPCHK(eng, hipSetDevice(eng->dev));
-  Plan* P = eng->gp_plan.get();
   hipStream_t own = eng->stream;
   eng->stream = eng->gp_stream;
-  int st = UMX_OK;
   *d_buf = nullptr; *count = 0; *done = 0;
-  while (eng->gp_at < P->segs.size()) {
-    Seg& sg = P->segs[eng->gp_at++];
-    if (sg.sync_buf) { *d_buf = sg.sync_buf; *count = sg.sync_count; eng->stream = own; return UMX_OK; }
-    st = sg.fn();
-    if (st != UMX_OK) break;
-  }
+  const Seg* stop = nullptr;
+  int st = eng->gp_plan->run_to_sync(eng->gp_at, &stop);
   eng->stream = own;
+  if (stop) { *d_buf = stop->sync_buf; *count = stop->sync_count; return UMX_OK; }     // an exchange point: the caller sums, then steps again
   if (st == UMX_OK) {
     *done = 1;
     eng->ran_on_caller = true;

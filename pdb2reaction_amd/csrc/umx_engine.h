@@ -1,5 +1,5 @@
 // umx_engine.h -- host side, part 1 of 5: the engine's state (struct umx_engine) and the small types it is made of: the precision
-// descriptor, the weight views, the workspace view (WS), the launch plan (Seg / Plan), and the error / buffer helpers every other
+// descriptor, the weight views, the workspace view (WS), the launch plan (Seg / Plan and its one-lane executor), and the error / buffer helpers every other
 // host header uses.  Host headers are included by umx_api.hip only, in this order: umx_engine.h, umx_launch.h, umx_workspace.h,
 // umx_plan.h, umx_weights.h (one translation unit: every kernel template is instantiated once; they do not include one another).
 #pragma once
@@ -170,6 +170,18 @@ struct Plan {
   // graph-parallel single-image mode: an exchange point -- the buffer holds this rank's partial sums over ITS edges and must be
   // summed over the ranks (all-reduce, done by the caller between two umx_gp_step calls) before the next segment runs
   void sync(float* buf, size_t count) { Seg sg{false, nullptr}; sg.sync_buf = buf; sg.sync_count = count; segs.push_back(std::move(sg)); }
+  // The one-lane executor: issue the segments from `at` on, on the stream eng->stream points at, up to the next exchange point or the
+  // end.  *stop = the exchange point reached (`at` is behind it), nullptr at the end of the plan; a failing segment returns its status.
+  int run_to_sync(size_t& at, const Seg** stop) {
+    *stop = nullptr;
+    while (at < segs.size()) {
+      Seg& sg = segs[at++];
+      if (sg.sync_buf) { *stop = &sg; return UMX_OK; }
+      const int st = sg.fn();
+      if (st != UMX_OK) return st;
+    }
+    return UMX_OK;
+  }
 };
 
 }  // namespace
@@ -375,6 +387,8 @@ int grow(umx_engine* eng, Cap& cap, Cap new_cap, std::initializer_list<hipStream
   cap = new_cap;
   return UMX_OK;
 }
+// edges a growing workspace is sized for when a chunk needs e: 2 % + 1024 on top, so that a slightly denser batch does not re-allocate
+inline long grown_edges(long e) { return e + e / 50 + 1024; }
 // the workspace arena: the second lane may still be running in it
 int grow_arena(umx_engine* eng, hipStream_t s, size_t bytes) {
   CHK(grow(eng, eng->arena_bytes, bytes, {s, eng->stream2}, {DevBuf(eng->arena, bytes)}));

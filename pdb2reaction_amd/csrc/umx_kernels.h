@@ -657,14 +657,7 @@ __global__ void k_edge_geom(const float* __restrict__ evec, long ne, float cutof
 // sysemb is DOUBLE (round 3): the system embedding is added to every atom, here and in every layer's norm -- held in float32 its
 // representation error (the same few 1e-8 for every atom) is a systematic energy error proportional to N; added in double and
 // rounded once, what is left is the rounding of each atom's own sum.
-__global__ void k_node_init(const int* __restrict__ znode, int natoms, long nt, const float* __restrict__ emb,
-                            const double* __restrict__ sysemb, float* __restrict__ x) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nt * ROW) return;
-  const long node = i / ROW;
-  const int r = (int)(i % ROW);
-  x[i] = (r < C) ? (float)((double)emb[znode[node % natoms] * C + r] + sysemb[r]) : 0.f;
-}
+// (The node init x0 = element embedding + system embedding has no kernel of its own: k_rotate_back_reduce<3> adds it as its base.)
 // graph-parallel mode: x0 = node init + the all-reduced edge-degree aggregate, the l = 0 row in the SAME expression as the fused
 // k_rotate_back_reduce<3> of the ordinary path (with all edges on one rank the two paths stay bitwise equal)
 __global__ void k_node_init_add(const int* __restrict__ znode, int natoms, long nt, const float* __restrict__ emb,

@@ -473,70 +473,7 @@ __global__ __launch_bounds__(256) void k_gate_edge_bwd_q3(const float* __restric
   }
 }
 
-// backward of the radial modulation with the rotated message RE-DERIVED in place (gather + rotate, no HBM round trip):
-// gy1 (9x256 fp32, in/out -> gxrot = gy1 .* rad), g_rad (1536) as PL planes, tau += <gxrot, L xrot>
-template <int P>
-__global__ __launch_bounds__(256) void k_modulate_bwd_pl(float* __restrict__ gy1, const float* __restrict__ xn,
-                                                         const int* __restrict__ esrc, const int* __restrict__ edst,
-                                                         const float* __restrict__ frame, const float* __restrict__ rad,
-                                                         unsigned short* __restrict__ grad, float* __restrict__ tau, long ne, float odd_sign) {
-  UMX_WAVE_ITEM_PL(e, ne)
-  const int c0 = lane * 4;                     // column of the 256-wide [src | dst] row; lanes 0-31 own the source half
-  const float* f = frame + e * FRAME;
-  const long node = (lane < 32) ? esrc[e] : edst[e];
-  const int cn = c0 & (C - 1);
-  float4 xv[9];
-  {
-    float4 raw[9];
-#pragma unroll
-    for (int r = 0; r < 9; ++r) raw[r] = *reinterpret_cast<const float4*>(xn + node * ROW + r * C + cn);
-    float in[9], out[9];
-#pragma unroll
-    for (int comp = 0; comp < 4; ++comp) {
-#pragma unroll
-      for (int r = 0; r < 9; ++r) in[r] = comp == 0 ? raw[r].x : comp == 1 ? raw[r].y : comp == 2 ? raw[r].z : raw[r].w;
-      rot_fwd(f, in, out);
-#pragma unroll
-      for (int r = 0; r < 9; ++r) {
-        if (comp == 0) xv[r].x = out[r]; else if (comp == 1) xv[r].y = out[r]; else if (comp == 2) xv[r].z = out[r]; else xv[r].w = out[r];
-      }
-    }
-  }
-  float* g = gy1 + e * XROT + c0;
-  const float* rd = rad + e * RAD + c0;
-  float4 gv[9], rv[6], gacc[6];
-#pragma unroll
-  for (int r = 0; r < 9; ++r) gv[r] = *reinterpret_cast<const float4*>(g + r * 2 * C);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) { rv[k] = *reinterpret_cast<const float4*>(rd + k * 2 * C); gacc[k] = make_float4(0.f, 0.f, 0.f, 0.f); }
-  const int ridx[9] = {0, 1, 2, 3, 4, 3, 4, 5, 5};
-#pragma unroll
-  for (int r = 0; r < 9; ++r) {
-    const int k = ridx[r];
-    gacc[k].x += gv[r].x * xv[r].x; gacc[k].y += gv[r].y * xv[r].y; gacc[k].z += gv[r].z * xv[r].z; gacc[k].w += gv[r].w * xv[r].w;
-    gv[r].x *= rv[k].x; gv[r].y *= rv[k].y; gv[r].z *= rv[k].z; gv[r].w *= rv[k].w;
-    *reinterpret_cast<float4*>(g + r * 2 * C) = gv[r];
-  }
-  unsigned short* gr = grad + e * (long)(RAD * P);
-  const float sg = row_sign(e, odd_sign);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) pl_store4<P>(gr, k * 2 * C + c0, make_float4(sg * gacc[k].x, sg * gacc[k].y, sg * gacc[k].z, sg * gacc[k].w));
-  float tx = 0.f, ty = 0.f, tz = 0.f;
-  float ga[9], xa[9];
-#pragma unroll
-  for (int comp = 0; comp < 4; ++comp) {
-#pragma unroll
-    for (int r = 0; r < 9; ++r) {
-      ga[r] = comp == 0 ? gv[r].x : comp == 1 ? gv[r].y : comp == 2 ? gv[r].z : gv[r].w;
-      xa[r] = comp == 0 ? xv[r].x : comp == 1 ? xv[r].y : comp == 2 ? xv[r].z : xv[r].w;
-    }
-    torque_acc(ga, xa, 1.0f, tx, ty, tz);
-  }
-  tx = wave_sum(tx); ty = wave_sum(ty); tz = wave_sum(tz);
-  if (lane == 0) { tau[e * 4 + 0] += tx; tau[e * 4 + 1] += ty; tau[e * 4 + 2] += tz; }
-}
-
-// Reverse pass of K7a in ONE node-centric kernel (replaces k_modulate_bwd_pl + k_gather_rotate_bwd): for every node n the wave
+// Reverse pass of K7a in ONE node-centric kernel (in place of an edge-wise modulation backward + k_gather_rotate_bwd): for every node n the wave
 // walks its incoming edges (n is the target: columns C..2C of the 256-wide [src | dst] rows) and its outgoing edges (n is the
 // source: columns 0..C).  In both walks the un-rotated feature is the node's OWN xn[n], so the rotated message is re-derived
 // in registers, and

@@ -1,5 +1,6 @@
 // umx_launch.h -- host side, part 2 of 5: the profiling bracket and the GEMM launchers (fp32 MFMA / float64-accumulating node kernel:
-// launch_gemm; split-precision plane GEMMs: gemm_pl = choose_pl + the table of instantiations + one launch site).
+// launch_gemm; split-precision plane GEMMs: gemm_pl = choose_pl + the table of instantiations + one launch site), and the SO(2)
+// convolutions: their column layouts stated once (So2Layout) and the one function that issues a convolution's three products (so2_conv).
 #pragma once
 
 namespace {
@@ -25,6 +26,11 @@ int prof_close(umx_engine* eng, ProfRec* pr) {
 // grid of a grid-stride ("virtual block") kernel: all blocks normally, capped in throttled two-lane mode
 inline unsigned vgrid(const umx_engine* eng, unsigned blocks) {
   return (eng->throttle && eng->stream_cap > 0 && blocks > (unsigned)eng->stream_cap) ? (unsigned)eng->stream_cap : blocks;
+}
+
+// k_scan is a single block of 1024 threads (umx_kernels.h)
+inline void launch_scan(hipStream_t s, const int* deg, long n, int* row_ptr, int* stats) {
+  hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, deg, n, row_ptr, stats);
 }
 
 // ---- fp32 GEMM launcher ------------------------------------------------------------------------
@@ -240,6 +246,38 @@ int gemm_pl(umx_engine* eng, int cplx, Pass pass, const unsigned short* Apl, int
   hipLaunchKernelGGL(k->fn, dim3(c.blocks), dim3(k->half ? 256 : 512), 0, eng->stream, q);
   HIPCHK(eng, hipGetLastError());
   return prof_close(eng, pr);
+}
+
+// ---- the SO(2) convolutions ----------------------------------------------------------------------
+// The m-primary column layout of an edge row that an SO(2) convolution reads or writes: the m = 0 block first, then re | im of m = 1 and
+// of m = 2.  ld = the row's columns, m0 = the width of the m = 0 block, re / im / w = the column offsets and the width of one half.
+struct So2Layout { int ld, m0, m1re, m1im, m1w, m2re, m2im, m2w; };
+constexpr So2Layout SO2_Y1 = {XROT, 768, 768, 1280, 512, 1792, 2048, 256};    // y1 / g_y1 (and xrot): the rotated [src | dst] message
+constexpr So2Layout SO2_HG = {HG, 640, 640, 896, 256, 1152, 1280, 128};       // hg / g_hg: [gate scalars | hidden m = 0], hidden m = 1, m = 2
+constexpr So2Layout SO2_MSG = {ROW, 384, 384, 640, 256, 896, 1024, 128};      // hid / msg / g_msg
+// the radial weights (RAD columns) that modulate the three blocks of an fp32 conv-1's A operand: one column per (re, im) pair
+constexpr int SO2_RAD_M1 = 768, SO2_RAD_M2 = 1280;
+
+// One SO(2) convolution C = conv(A): the plain m = 0 product and the complex m = 1 and m = 2 products, in this order.  N and K of every
+// product are the block widths of C's and A's layout; every weight is (N x K) row-major per half, so ldb == K and bHalf == N.  A
+// transposed convolution is the same call with the layouts of A and C swapped, the transposed weights, pass REV and conj = -1.
+// Split-precision modes: A = the pre-split operand planes (gemm_pl).  fp32 mode: A = float32 rows; R != nullptr (conv 1 forward): the
+// A operand is modulated by the radial rows R while it is staged.
+int so2_conv(umx_engine* eng, Pass pass, const void* A, const So2Layout& la, float* Cp, const So2Layout& lc, const float* Wm0, const float* Wm1,
+             const float* Wm2, const float* bias, long ne, float conj, const float* R = nullptr) {
+  if (eng->prec.planes) {
+    const unsigned short* Apl = static_cast<const unsigned short*>(A);
+    CHK(gemm_pl(eng, 0, pass, Apl, la.ld, 0, 0, Wm0, 0, bias, Cp, lc.ld, 0, 0, ne, lc.m0, la.m0, 1.0f));
+    CHK(gemm_pl(eng, 1, pass, Apl, la.ld, la.m1re, la.m1im, Wm1, lc.m1w, nullptr, Cp, lc.ld, lc.m1re, lc.m1im, ne, lc.m1w, la.m1w, conj));
+    return gemm_pl(eng, 1, pass, Apl, la.ld, la.m2re, la.m2im, Wm2, lc.m2w, nullptr, Cp, lc.ld, lc.m2re, lc.m2im, ne, lc.m2w, la.m2w, conj);
+  }
+  const float* Af = static_cast<const float*>(A);
+  GemmP p = gp_zero();
+  p.A = Af; p.lda = la.ld; p.R = R; p.ldr = R ? RAD : 0; p.B = Wm0; p.ldb = la.m0; p.bias = bias;
+  p.Cp = Cp; p.ldc = lc.ld; p.M = (int)ne; p.N = lc.m0; p.K = la.m0;
+  CHK(launch_gemm(eng, p, R ? A_MODUL : A_PLAIN, 0, E_BIAS));
+  CHK(gemm_cplx(eng, Af, la.ld, la.m1re, la.m1im, R, R ? RAD : 0, R ? SO2_RAD_M1 : 0, Wm1, la.m1w, lc.m1w, Cp, lc.ld, lc.m1re, lc.m1im, ne, lc.m1w, la.m1w, conj));
+  return gemm_cplx(eng, Af, la.ld, la.m2re, la.m2im, R, R ? RAD : 0, R ? SO2_RAD_M2 : 0, Wm2, la.m2w, lc.m2w, Cp, lc.ld, lc.m2re, lc.m2im, ne, lc.m2w, la.m2w, conj);
 }
 
 }  // namespace

@@ -1,40 +1,119 @@
-// umx_plan.h -- host side, part 4 of 5: the launch plan of one chunk (plan_chunk: forward, readout, analytic reverse pass), the
-// executors that issue plans on one stream or on two lanes, and one evaluation (energy_forces_on) as its phases -- degree pass, workspace
-// budget, lane choice, amortised workspace size, chunk planning, the partitioned fallback for an oversized image, the arena, execution.
-// Seg / Plan themselves are in umx_engine.h.
+// umx_plan.h -- host side, part 4 of 5:
+//   the edge links between the GEMMs, one launcher each (link_*: instantiation by precision mode, grid, launch, operand capture);
+//   the launch plan of one chunk, stage by stage (plan_chunk = plan_graph, plan_layer_fwd per layer, readout + reverse head, and per
+//   layer in reverse the optional replay of plan_edge_fwd, plan_atomwise_bwd, plan_edge_bwd, plan_norm1_bwd, then force_assembly);
+//   the executors (run_plan: Plan::run_to_sync of umx_engine.h on one stream; run_plans_alternating: two lanes and the matrix token);
+//   one evaluation (energy_forces_on) as its phases -- degree pass, workspace budget, lane choice, amortised workspace size, chunk
+//   planning, the partitioned fallback for an oversized image, the arena, execution.
+// Functions named plan_* append segments to a Plan when the plan is made; the others issue launches when a segment runs.
 #pragma once
 
 namespace {
 
-// ---- radial MLP forward / backward -------------------------------------------------------------
-// Each is split into its small layers (fp32 GEMMs + LayerNorm/SiLU kernels: "streaming" work) and the one large fc3 GEMM, so that
-// the two-lane executor can treat the large GEMM as a matrix-pipe segment (Plan, umx_engine.h).
-int radial_fwd_head(umx_engine* eng, const WS& w, const RadialW& r, int slot, long ne) {
-  // one persistent kernel: gaussians -> fc1 -> LN+SiLU -> fc2 -> LN+SiLU -> the fc3 operand (fp16 planes / float32 quad-row blocks of the
-  // split modes, or fp32 rows in w.ra); the intermediate rows never reach HBM
+// ---- debug captures of the edge links' GEMM operands ---------------------------------------------
+// (debug) An operand is captured as the GEMM reads it, directly behind the kernel that writes it, under the name of its format --
+// tests/test_gpu_mfma_model.py holds the GEMMs' outputs against the bit-exact model of the matrix core on exactly these bits,
+// tests/test_gpu_forward_links.py and test_gpu_edge_links.py the producers.  Odd rows are negated in every split-mode format.
+enum OpFmt {
+  OP_QUAD,      // <base>q:  float32 quad-row blocks, rows padded to 4 (bf16x3; the forward operands of split-bf16)
+  OP_HALVES,    // <base>h:  the raw halves of the two-plane fp16 "Q2H" blocks (umx_kernels_pl.h): 4-row-padded rows x columns x 2 (split-f16 forward)
+  OP_PLANES,    // <base>pl: PL bf16 planes of the rows themselves (the 16-bit reverse operands; the edge-degree fc3^T operand of every split mode)
+  OP_ROWS       // <base>:   plain float32 rows (fp32 mode; g_rad of the bf16x3 reverse pass, which the fc3^T GEMM splits in registers)
+};
+OpFmt fwd_operand(const Precision& p) { return !p.planes ? OP_ROWS : p.fwd_fmt == 1 ? OP_HALVES : OP_QUAD; }
+OpFmt rev_operand(const Precision& p) { return p.rev_quad() ? OP_QUAD : OP_PLANES; }
+std::string link_tag(int slot) { return slot == NL ? ".deg" : "." + std::to_string(slot); }     // slot NL: the edge-degree embedding
+int dbg_operand(umx_engine* eng, const char* base, int slot, OpFmt fmt, const void* ptr, long ne, long cols, int planes = 2) {
+  if (!eng->dbg_on) return UMX_OK;
+  const long rows = (fmt == OP_QUAD || fmt == OP_HALVES) ? (ne + 3) / 4 * 4 : ne;
+  const size_t elem = fmt == OP_PLANES ? 2 * (size_t)planes : 4;
+  return dbg_capture(eng, std::string(base) + (fmt == OP_QUAD ? "q" : fmt == OP_HALVES ? "h" : fmt == OP_PLANES ? "pl" : "") + link_tag(slot), ptr, (size_t)rows * cols * elem);
+}
+
+// ---- the edge links between the GEMMs ------------------------------------------------------------
+// One launcher per link: it picks the instantiation the precision mode runs, computes the grid, launches on eng->stream and captures the
+// operand it wrote.  (The fp32 mode's own kernels -- k_gather_rotate, k_gate_edge_fwd / _bwd, k_rotate_back_bwd<9> -- are launched by the
+// one-segment fp32 branches of plan_edge_fwd / plan_edge_bwd.)
+#define UMX_LAUNCH(kernel, grid, ...) hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, eng->stream, __VA_ARGS__)
+
+// The radial MLP is split into its small layers (one fused kernel: "streaming" work) and the one large fc3 GEMM, so that the two-lane
+// executor can treat the large GEMM as a matrix-pipe segment (Plan, umx_engine.h).
+// Radial head, one persistent kernel: gaussians -> fc1 -> LN+SiLU -> fc2 -> LN+SiLU -> the fc3 operand (fp16 planes / float32 quad-row
+// blocks of the split modes, or fp32 rows in w.ra); the intermediate rows never reach HBM
+int link_radial_head(umx_engine* eng, const WS& w, const RadialW& r, int slot, long ne) {
   const bool planes = eng->prec.planes && eng->planes.count(r.w3);
   const unsigned tiles = nblk(ne, 64);                      // two 32-row MFMA tiles per workgroup tile, two workgroups per CU
-  const dim3 grid(vgrid(eng, tiles < 512u ? tiles : 512u));
+  auto k = !planes ? k_radial_head<0> : eng->prec.fwd_fmt == 1 ? k_radial_head<2> : k_radial_head<4>;
   ProfRec* pr;
   CHK(prof_open(eng, &pr, 2.0 * ne * ((double)NG * RH + (double)RH * RH), -1, ne, RH, NG + RH));
-#define UMX_RH_LAUNCH(Q, OUT) hipLaunchKernelGGL((k_radial_head<Q>), grid, dim3(256), 0, eng->stream, w.evec, w.ez, eng->gcoef, eng->d_gmu, r.w1g, r.tsd, r.ttd, r.ln1w, \
-                                                 r.ln1b, r.w2, r.b2, r.ln2w, r.ln2b, w.h1pre[slot], w.h2pre[slot], (void*)(OUT), ne, eng->odd_sign)
-  if (planes && eng->prec.fwd_fmt == 1) UMX_RH_LAUNCH(2, w.a2pl); else if (planes) UMX_RH_LAUNCH(4, w.a2pl); else UMX_RH_LAUNCH(0, w.ra);
-#undef UMX_RH_LAUNCH
+  UMX_LAUNCH(k, vgrid(eng, tiles < 512u ? tiles : 512u), w.evec, w.ez, eng->gcoef, eng->d_gmu, r.w1g, r.tsd, r.ttd, r.ln1w, r.ln1b, r.w2, r.b2, r.ln2w, r.ln2b,
+             w.h1pre[slot], w.h2pre[slot], planes ? (void*)w.a2pl : (void*)w.ra, ne, eng->odd_sign);
   CHK(prof_close(eng, pr));
   HIPCHK(eng, hipGetLastError());
-  return UMX_OK;
+  return dbg_operand(eng, "a2", slot, fwd_operand(eng->prec), eng->prec.planes ? (const void*)w.a2pl : (const void*)w.ra, ne, RH);
 }
+// K7a gather + rotate + radial modulation -> y1, conv 1's A operand
+int link_gather_rotate_mod(umx_engine* eng, const WS& w, int i, long ne) {
+  auto k = eng->prec.fwd_fmt == 1 ? k_gather_rotate_mod_q3<1> : k_gather_rotate_mod_q3<3>;
+  UMX_LAUNCH(k, vgrid(eng, (nblk(ne, 4) + 7) / 8 * 8), w.xn[i], w.esrc, w.edst, w.frame, w.rad[i], w.y1pl, ne, eng->odd_sign);
+  HIPCHK(eng, hipGetLastError());
+  return dbg_operand(eng, "y1", i, fwd_operand(eng->prec), w.y1pl, ne, XROT);
+}
+// gate forward: hg = [gate | hpre] -> hid, conv 2's A operand
+int link_gate_fwd(umx_engine* eng, const WS& w, int i, long ne) {
+  auto k = eng->prec.fwd_fmt == 1 ? k_gate_edge_fwd_q3<1> : k_gate_edge_fwd_q3<3>;
+  UMX_LAUNCH(k, vgrid(eng, nblk(ne, 8)), w.hg[i], w.hidpl, ne, eng->odd_sign);
+  HIPCHK(eng, hipGetLastError());
+  return dbg_operand(eng, "hid", i, fwd_operand(eng->prec), w.hidpl, ne, ROW);
+}
+// rotate-back backward of a layer: g_xmid (G2) -> g_msg, conv 2^T's A operand (+ dE/dd and the torque of the rotation)
+int link_rotate_back_bwd(umx_engine* eng, const WS& w, int i, long ne) {
+  auto k = eng->prec.rev_quad() ? k_rotate_back_bwd_q3<3> : k_rotate_back_bwd_pl<2>;
+  UMX_LAUNCH(k, vgrid(eng, (nblk(ne, 4) + 7) / 8 * 8), w.G2, w.msg[i], w.frame, w.edst, w.gmsgpl, w.dedd, w.tau, ne, eng->odd_sign);
+  HIPCHK(eng, hipGetLastError());
+  return dbg_operand(eng, "gmsg", i, rev_operand(eng->prec), w.gmsgpl, ne, ROW);
+}
+// ... and of the edge-degree embedding: g_x0 (G0) -> the gradient of the edge-degree radial output, the fc3^T operand.  Split modes: straight
+// into the PL planes of the fc3^T GEMM (gmsgpl is free here), three planes in the bf16x3 mode; else float32 rows in gmsg.
+bool deg_rev_planes(const umx_engine* eng) { return eng->prec.planes && eng->planes.count(eng->rdeg.w3T) != 0; }
+int link_rotate_back_bwd_deg(umx_engine* eng, const WS& w, long ne) {
+  const bool dpl = deg_rev_planes(eng);
+  auto k = !dpl ? k_rotate_back_bwd<3, 0> : eng->prec.rev_planes == 3 ? k_rotate_back_bwd<3, 3> : k_rotate_back_bwd<3, 2>;
+  UMX_LAUNCH(k, nblk(ne, 4), w.G0, w.rad_deg, w.frame, w.edst, dpl ? reinterpret_cast<float*>(w.gmsgpl) : w.gmsg, w.dedd, w.tau, ne, DEG_RESCALE,
+             dpl ? eng->odd_sign : 1.0f);
+  return dpl ? dbg_operand(eng, "grad", NL, OP_PLANES, w.gmsgpl, ne, 3 * C, eng->prec.rev_planes) : UMX_OK;
+}
+// gate backward: g_hid -> g_hg, conv 1^T's A operand
+int link_gate_bwd(umx_engine* eng, const WS& w, int i, long ne) {
+  const bool quad = eng->prec.rev_quad();
+  auto k = quad ? k_gate_edge_bwd_q3<3> : k_gate_edge_bwd_pl<2>;
+  UMX_LAUNCH(k, vgrid(eng, quad ? nblk(ne, 8) : nblk(ne * (H / 4), 256)), w.hid, w.hg[i], w.ghgpl, ne, eng->odd_sign);
+  HIPCHK(eng, hipGetLastError());
+  return dbg_operand(eng, "ghg", i, rev_operand(eng->prec), w.ghgpl, ne, HG);
+}
+// One node-centric kernel: modulation backward + rotate-back + segmented sum -> g_xn in G1 (g_xrot stays in registers); g_rad, the fc3^T
+// operand, as float32 rows (sign-alternating; split by the fc3^T GEMM in registers) in the bf16x3 mode, as two PL bf16 planes in the
+// 16-bit-reverse modes.  Round 4: the fp32 mode takes it too (P = 0, rows in w.grad, no alternating sign) instead of k_gather_rotate +
+// k_modulate_bwd + k_gather_rotate_bwd -- the rotated message and g_xrot never touch HBM (-27 KB per edge and layer).
+int link_modrot_bwd(umx_engine* eng, const WS& w, int i, long nn, long ne) {
+  const bool pl = eng->prec.planes, rows = !pl || eng->prec.rev_quad();
+  auto k = rows ? k_modrot_bwd_pl<0> : k_modrot_bwd_pl<2>;
+  UMX_LAUNCH(k, (unsigned)nn, w.gy1, w.xn[i], w.frame, w.rad[i], w.row_ptr, w.out_ptr, w.out_edge, pl ? w.gradpl : reinterpret_cast<unsigned short*>(w.grad),
+             w.tau, w.tau2, w.G1, nn, pl ? eng->odd_sign : 1.0f);
+  HIPCHK(eng, hipGetLastError());
+  if (!pl) return UMX_OK;                      // (fp32: with captures on the unfused kernels run, see plan_edge_bwd)
+  return rows ? dbg_operand(eng, "gradq", i, OP_ROWS, w.gradpl, ne, RAD) : dbg_operand(eng, "grad", i, OP_PLANES, w.gradpl, ne, RAD);
+}
+
+// ---- radial MLP: the fc3 GEMM and the reverse pass -------------------------------------------------
 int radial_fwd_fc3(umx_engine* eng, const WS& w, const RadialW& r, long ne, float* rad_out) {
   if (eng->prec.planes && eng->planes.count(r.w3)) return gemm_pl(eng, 0, FWD, w.a2pl, RH, 0, 0, r.w3, 0, r.b3, rad_out, r.out, 0, 0, ne, r.out, RH, 1.0f);
   return gemm_plain(eng, w.ra, RH, 0, r.w3, RH, r.b3, rad_out, r.out, 0, ne, r.out, RH);
 }
 int radial_fwd(umx_engine* eng, const WS& w, const RadialW& r, int slot, long ne, float* rad_out) {
-  CHK(radial_fwd_head(eng, w, r, slot, ne));
-  if (eng->dbg_on && !eng->prec.planes) DBG("a2." + std::to_string(slot), w.ra, ne * RH);       // (debug) fp32 mode: the fc3 operand rows behind the head
+  CHK(link_radial_head(eng, w, r, slot, ne));
   return radial_fwd_fc3(eng, w, r, ne, rad_out);
 }
-
 int radial_bwd_fc3(umx_engine* eng, const WS& w, const RadialW& r, long ne, const float* grad, const unsigned short* gradpl, bool f32rows = false) {
   if (gradpl) return gemm_pl(eng, 0, REV, gradpl, r.out, 0, 0, r.w3T, 0, nullptr, w.e128a, RH, 0, 0, ne, RH, r.out, 1.0f, f32rows);
   return gemm_plain(eng, grad, r.out, 0, r.w3T, r.out, nullptr, w.e128a, RH, 0, ne, RH, r.out);
@@ -42,13 +121,12 @@ int radial_bwd_fc3(umx_engine* eng, const WS& w, const RadialW& r, long ne, cons
 int radial_bwd_tail(umx_engine* eng, const WS& w, const RadialW& r, int slot, long ne) {
   // one persistent kernel: LN+SiLU bwd -> fc2^T -> LN+SiLU bwd -> fc1^T -> dE/dd through the gaussians (accumulated into dedd_rad)
   const unsigned tiles = nblk(ne, 64);
-  const dim3 grid(vgrid(eng, tiles < 512u ? tiles : 512u));
   ProfRec* pr;
   CHK(prof_open(eng, &pr, 2.0 * ne * ((double)NG * RH + (double)RH * RH), -1, ne, RH, NG + RH));
-  const std::string t = slot == NL ? ".deg" : "." + std::to_string(slot);
+  const std::string t = link_tag(slot);
   DBG("g_a2" + t, w.e128a, ne * RH);           // (debug) the output of fc3^T, the tail's input
-  hipLaunchKernelGGL(k_radial_tail, grid, dim3(256), 0, eng->stream, w.e128a, w.h2pre[slot], w.h1pre[slot], w.evec, eng->gcoef, eng->d_gmu, r.ln2w, r.ln2b, r.ln1w, r.ln1b,
-                     r.w2T, r.w1gT, w.dedd_rad, ne);
+  UMX_LAUNCH(k_radial_tail, vgrid(eng, tiles < 512u ? tiles : 512u), w.e128a, w.h2pre[slot], w.h1pre[slot], w.evec, eng->gcoef, eng->d_gmu, r.ln2w, r.ln2b, r.ln1w, r.ln1b,
+             r.w2T, r.w1gT, w.dedd_rad, ne);
   CHK(prof_close(eng, pr));
   HIPCHK(eng, hipGetLastError());
   DBG("dedd_rad" + t, w.dedd_rad, ne);         // (debug) accumulated over the layers (NL - 1 first, then the edge-degree MLP)
@@ -60,423 +138,417 @@ int radial_bwd(umx_engine* eng, const WS& w, const RadialW& r, int slot, long ne
 }
 
 // ---- one chunk: nn nodes (= images * natoms), edges counted on the fly --------------------------
-// vir.out != nullptr: the chunk's final segment also takes the virial of its images (umx_virial.h)
-// img0: the index within the call of the chunk's first image (d_pos, d_deg, d_cand and the outputs start there; per-image cells are
-// indexed by it)
-void plan_chunk(umx_engine* eng, WS& w, const PosPtr d_pos, const int* d_deg, const int* d_cand, long img0, long nimg, long ne, double* d_energy,
-                float* d_forces, Plan& P, const VirialOut vir = VirialOut()) {
-  const int N = eng->natoms;
-  const long nn = nimg * N;
-  const float rc2 = eng->cutoff * eng->cutoff;
-  const dim3 B256(256);
-  const bool pl = eng->prec.planes;
-  const bool gp = eng->gp;                                       // graph-parallel: partial sums over this rank's edges + exchange points
-  const bool may_trunc = eng->may_truncate;                      // some node of this call has more candidates than max_neigh (known on the host)
-  const bool rc = eng->rc_active && d_forces != nullptr;         // recompute plan: one activation slot (carve_acts), replayed layer by layer in the reverse pass
-  const bool fused_rev = eng->prec.planes || !eng->dbg_on;     // k_modrot_bwd_pl produces g_xn itself (fp32 mode with debug captures: the unfused kernels, which expose xrot / g_xrot)
-  const long g_lo = gp ? eng->gp_lo : 0, g_hi = gp ? eng->gp_hi : nn;
-  // pinned graph: the reference edges this chunk replays per image -- all of them, or the contiguous rows [g_lo, g_hi) of a partition
-  const bool pinned = eng->pin_on;
-  const long pin_e0 = pinned && gp ? eng->pin_row[g_lo] : 0, pin_ecnt = pinned ? (gp ? eng->pin_row[g_hi] - pin_e0 : eng->pin_edges) : 0;
-  // every closure reads eng->stream when it RUNS (the executor points it at the lane's stream)
-  // K1 graph, K4 + K5
+// What the stages of a chunk's plan share, computed once by plan_chunk.  A Plan outlives plan_chunk (run_chunks and eval_partitioned run
+// it after planning has returned, umx_gp_step in later calls), so every closure holds its OWN COPY of the context: it is captured by
+// value, never by reference.  The one reference a closure holds is the workspace view `w`, whose owner (the lanes' views of
+// evaluate_planned, the partitions' of eval_partitioned, eng->gp_ws) outlives the plan.
+//   eng->stream is read when a closure RUNS (the executor points it at the lane's stream);
+//   eng->gp, gp_lo / gp_hi and the pinned ranges are read when the plan is MADE (eval_partitioned changes them around every plan_chunk).
+struct ChunkCtx {
+  umx_engine* eng;
+  long nn, ne, nimg;
+  long img0;                     // the index within the call of the chunk's first image (d_pos, d_deg, d_cand and the outputs start there; per-image cells are indexed by it)
+  bool gp;                       // graph-parallel: partial sums over this rank's edges + exchange points
+  long g_lo, g_hi;               // ... of the targets [g_lo, g_hi)
+  bool pinned;                   // pinned graph: the reference edges this chunk replays per image -- all of them, or the contiguous rows
+  long pin_e0, pin_ecnt;         // [g_lo, g_hi) of a partition
+  bool may_trunc;                // some node of this call has more candidates than max_neigh (known on the host)
+  bool rc;                       // recompute plan: one activation slot (carve_acts), replayed layer by layer in the reverse pass
+  bool fused_rev;                // k_modrot_bwd_pl produces g_xn itself (fp32 mode with debug captures: the unfused kernels, which expose xrot / g_xrot)
+  PosPtr d_pos; const int *d_deg, *d_cand;
+  double* d_energy; float* d_forces;
+  VirialOut vir;                 // vir.out != nullptr: the chunk's final segment also takes the virial of its images (umx_virial.h)
+};
+#define UMX_STAGE(c) umx_engine* const eng = (c).eng; const hipStream_t s = eng->stream; const long nn = (c).nn, ne = (c).ne; (void)s; (void)nn; (void)ne
+
+// K1 graph: row pointers, edge list, out-lists, frames, element pairs
+int graph_build(const ChunkCtx& c, const WS& w) {
+  UMX_STAGE(c);
+  launch_scan(s, c.d_deg, nn, w.row_ptr, w.stats);
+  if (c.pinned) launch_graph_replay(eng, s, c.d_pos, c.nimg, c.pin_e0, c.pin_ecnt, w.esrc, w.edst, w.evec, c.img0);
+  else launch_graph_fill(eng, s, c.may_trunc, c.d_pos, nn, c.d_cand, w.row_ptr, w.esrc, w.edst, w.evec, c.g_lo, c.g_hi, c.img0);
+  HIPCHK(eng, hipMemsetAsync(w.out_cur, 0, (nn + 1) * sizeof(int), s));
+  if (ne > 0) UMX_LAUNCH(k_out_count, nblk(ne, 256), w.esrc, ne, w.out_cur);
+  launch_scan(s, w.out_cur, nn, w.out_ptr, w.stats + 2);
+  HIPCHK(eng, hipMemsetAsync(w.out_cur, 0, (nn + 1) * sizeof(int), s));
+  if (ne > 0) {
+    UMX_LAUNCH(k_out_fill, nblk(ne, 256), w.esrc, ne, w.out_ptr, w.out_cur, w.out_edge);
+    UMX_LAUNCH(k_out_sort, nblk(nn, 4), w.out_ptr, nn, w.out_edge);
+    UMX_LAUNCH(k_edge_geom, nblk(ne, 256), w.evec, ne, eng->cutoff, w.frame);
+    UMX_LAUNCH(k_edge_z, nblk(ne, 256), w.esrc, w.edst, eng->d_z, eng->natoms, w.ez, ne);
+  }
+  HIPCHK(eng, hipGetLastError());
+  DBG("row_ptr", w.row_ptr, nn + 1); DBG("src", w.esrc, ne); DBG("dst", w.edst, ne); DBG("out_ptr", w.out_ptr, nn + 1); DBG("out_edge", w.out_edge, ne);
+  DBG("evec", w.evec, ne * 4); DBG("frame", w.frame, ne * FRAME);
+  return UMX_OK;
+}
+
+// K4 + K5 edge-degree embedding: x0 = node init + sum over incoming edges (one kernel, the base added in double); graph-parallel: the bare
+// partial sum goes to G1 and is all-reduced first, the base is added by k_node_init_add behind the exchange point
+int edge_degree_embed(const ChunkCtx& c, const WS& w) {
+  UMX_STAGE(c);
+  if (ne > 0) {
+    CHK(link_radial_head(eng, w, eng->rdeg, NL, ne));
+    CHK(radial_fwd_fc3(eng, w, eng->rdeg, ne, w.rad_deg));
+  }
+  if (c.gp) UMX_LAUNCH(k_rotate_back_reduce<3>, nblk(nn, 4), w.rad_deg, w.frame, w.row_ptr, (const float*)nullptr, w.G1, nn, DEG_RESCALE,
+                       (const int*)nullptr, 0, (const float*)nullptr, (const double*)nullptr);
+  else UMX_LAUNCH(k_rotate_back_reduce<3>, nblk(nn, 4), w.rad_deg, w.frame, w.row_ptr, (const float*)nullptr, w.xs[0], nn, DEG_RESCALE,
+                  (const int*)eng->d_z, eng->natoms, eng->emb_sphere, (const double*)eng->d_sysemb);
+  HIPCHK(eng, hipGetLastError());
+  if (!c.gp) { DBG("rad.deg", w.rad_deg, ne * 3 * C); DBG("x0", w.xs[0], nn * ROW); DBG("h1pre.deg", w.h1pre[NL], ne * RH); DBG("h2pre.deg", w.h2pre[NL], ne * RH); }
+  return UMX_OK;
+}
+
+void plan_graph(Plan& P, WS& w, const ChunkCtx& c) {
+  P.stream([c, &w]() -> int { CHK(graph_build(c, w)); return edge_degree_embed(c, w); });
+  if (!c.gp) return;
+  P.sync(w.G1, (size_t)c.nn * ROW);
+  P.stream([c, &w]() -> int {
+    UMX_STAGE(c);
+    UMX_LAUNCH(k_node_init_add, nblk(nn * ROW, 256), eng->d_z, eng->natoms, nn, eng->emb_sphere, eng->d_sysemb, w.G1, w.xs[0]);
+    HIPCHK(eng, hipGetLastError());
+    return UMX_OK;
+  });
+}
+
+// The edge pipeline of layer i's forward pass (radial MLP, gather / rotate / modulate, conv 1, gate, conv 2 -> rad, hg, msg, h1pre,
+// h2pre of the layer), led by the layer's first norm.  replay (recompute plans, reverse pass): the same segments from the STORED node
+// input xn[i] -- the norm, like everything node-level, is not issued again; no kernel of the pipeline writes node state.
+void norm1_fwd(const ChunkCtx& c, const WS& w, int i) {       // xn[i] = norm 1 of the layer's input (+ the system embedding)
+  UMX_STAGE(c);
+  UMX_LAUNCH(k_norm_fwd, nblk(nn, 4), w.xs[2 * i], eng->lw[i].n1w, eng->lw[i].n1b, eng->d_sysemb, w.xn[i], nn);
+}
+void plan_edge_fwd(Plan& P, WS& w, const ChunkCtx& c, int i, bool replay) {
+  const LayerW* L = &c.eng->lw[i];
+  if (c.ne > 0 && c.eng->prec.planes) {
+    P.stream([=, &w]() -> int {
+      if (!replay) norm1_fwd(c, w, i);
+      return link_radial_head(c.eng, w, L->rad, i, c.ne);
+    });
+    P.matrix([=, &w]() -> int { return radial_fwd_fc3(c.eng, w, L->rad, c.ne, w.rad[i]); });
+    P.stream([=, &w]() -> int { return link_gather_rotate_mod(c.eng, w, i, c.ne); });
+    // SO(2) conv 1 on the pre-modulated planes -> hg = [gate | hpre]
+    P.matrix([=, &w]() -> int { return so2_conv(c.eng, FWD, w.y1pl, SO2_Y1, w.hg[i], SO2_HG, L->c1m0, L->c1m1, L->c1m2, L->c1m0b, c.ne, 1.0f); });
+    P.stream([=, &w]() -> int { return link_gate_fwd(c.eng, w, i, c.ne); });
+    // SO(2) conv 2 -> msg
+    P.matrix([=, &w]() -> int { return so2_conv(c.eng, FWD, w.hidpl, SO2_MSG, w.msg[i], SO2_MSG, L->c2m0, L->c2m1, L->c2m2, L->c2m0b, c.ne, 1.0f); });
+    return;
+  }
+  // fp32 mode (or no edges): one stream segment
   P.stream([=, &w]() -> int {
-    hipStream_t s = eng->stream;
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, d_deg, nn, w.row_ptr, w.stats);
-    if (pinned) launch_graph_replay(eng, s, d_pos, nimg, pin_e0, pin_ecnt, w.esrc, w.edst, w.evec, img0);
-    else launch_graph_fill(eng, s, may_trunc, d_pos, nn, d_cand, w.row_ptr, w.esrc, w.edst, w.evec, g_lo, g_hi, img0);
-    HIPCHK(eng, hipMemsetAsync(w.out_cur, 0, (nn + 1) * sizeof(int), s));
-    if (ne > 0) hipLaunchKernelGGL(k_out_count, dim3(nblk(ne, 256)), B256, 0, s, w.esrc, ne, w.out_cur);
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, w.out_cur, nn, w.out_ptr, w.stats + 2);
-    HIPCHK(eng, hipMemsetAsync(w.out_cur, 0, (nn + 1) * sizeof(int), s));
+    UMX_STAGE(c);
+    if (!replay) norm1_fwd(c, w, i);
     if (ne > 0) {
-      hipLaunchKernelGGL(k_out_fill, dim3(nblk(ne, 256)), B256, 0, s, w.esrc, ne, w.out_ptr, w.out_cur, w.out_edge);
-      hipLaunchKernelGGL(k_out_sort, dim3(nblk(nn, 4)), B256, 0, s, w.out_ptr, nn, w.out_edge);
-      hipLaunchKernelGGL(k_edge_geom, dim3(nblk(ne, 256)), B256, 0, s, w.evec, ne, eng->cutoff, w.frame);
-      hipLaunchKernelGGL(k_edge_z, dim3(nblk(ne, 256)), B256, 0, s, w.esrc, w.edst, eng->d_z, N, w.ez, ne);
+      UMX_LAUNCH(k_gather_rotate, nblk(ne, 4), w.xn[i], w.esrc, w.edst, w.frame, w.xrot, ne);
+      CHK(radial_fwd(eng, w, L->rad, i, ne, w.rad[i]));
+      // SO(2) conv 1 (radially modulated) -> hg = [gate | hpre]
+      CHK(so2_conv(eng, FWD, w.xrot, SO2_Y1, w.hg[i], SO2_HG, L->c1m0, L->c1m1, L->c1m2, L->c1m0b, ne, 1.0f, w.rad[i]));
+      UMX_LAUNCH(k_gate_edge_fwd, nblk(ne * (H / 4), 256), w.hg[i], w.hid, ne);
+      // SO(2) conv 2 -> msg
+      CHK(so2_conv(eng, FWD, w.hid, SO2_MSG, w.msg[i], SO2_MSG, L->c2m0, L->c2m1, L->c2m2, L->c2m0b, ne, 1.0f));
     }
     HIPCHK(eng, hipGetLastError());
-    DBG("row_ptr", w.row_ptr, nn + 1); DBG("src", w.esrc, ne); DBG("dst", w.edst, ne); DBG("out_ptr", w.out_ptr, nn + 1); DBG("out_edge", w.out_edge, ne);
-    DBG("evec", w.evec, ne * 4); DBG("frame", w.frame, ne * FRAME);
-    if (ne > 0) {
-      CHK(radial_fwd_head(eng, w, eng->rdeg, NL, ne));
-      // (debug) the fc3 A operand exactly as the GEMM reads it: float32 quad-row blocks, odd rows negated -- tests/test_gpu_mfma_model.py holds the
-      // GEMM's output against the bit-exact model of the matrix core on exactly these bits
-      if (eng->prec.planes && eng->prec.fwd_fmt == 3) DBG("a2q.deg", reinterpret_cast<const float*>(w.a2pl), (ne + 3) / 4 * 4 * RH);
-      // (debug) the fast mode's operand: the raw halves of the two-plane "Q2H" blocks (umx_kernels_pl.h), 4-row-padded rows x columns x 2;
-      // fp32 mode: the float32 rows of the fc3 operand -- tests/test_gpu_forward_links.py
-      if (eng->prec.planes && eng->prec.fwd_fmt == 1) DBG("a2h.deg", w.a2pl, (ne + 3) / 4 * 4 * RH * 2);
-      if (!eng->prec.planes) DBG("a2.deg", w.ra, ne * RH);
+    return UMX_OK;
+  });
+}
+
+// K7b aggregate: xmid = xin + the sum of the incoming messages.  Graph-parallel: the partial sum of this rank's edges has been all-reduced
+// in xn2 (plan_layer_fwd).  Then the layer's forward captures, every buffer still holding this layer.
+int aggregate_fwd(const ChunkCtx& c, const WS& w, int i) {
+  UMX_STAGE(c);
+  float *xin = w.xs[2 * i], *xmid = w.xs[2 * i + 1];
+  const std::string t = "." + std::to_string(i);
+  if (c.gp) UMX_LAUNCH(k_add_rows, nblk(nn * ROW / 4, 256), xmid, xin, w.xn2, nn * ROW / 4);
+  else UMX_LAUNCH(k_rotate_back_reduce<9>, vgrid(eng, nblk(nn, 4)), w.msg[i], w.frame, w.row_ptr, xin, xmid, nn, 1.0f,
+                  (const int*)nullptr, 0, (const float*)nullptr, (const double*)nullptr);
+  HIPCHK(eng, hipGetLastError());
+  DBG("xn" + t, w.xn[i], nn * ROW); DBG("rad" + t, w.rad[i], ne * RAD); DBG("h1pre" + t, w.h1pre[i], ne * RH); DBG("h2pre" + t, w.h2pre[i], ne * RH);
+  if (!eng->prec.planes) { DBG("xrot" + t, w.xrot, ne * XROT); DBG("hid" + t, w.hid, ne * ROW); }
+  DBG("hg" + t, w.hg[i], ne * HG); DBG("msg" + t, w.msg[i], ne * ROW); DBG("xmid" + t, xmid, nn * ROW);
+  return UMX_OK;
+}
+
+// K8 atom-wise block, spectral form: xout = xmid + SO(3) linear 2 (gate (SO(3) linear 1 (xn2), scalar MLP (xn2)))
+int atomwise_fwd_spectral(const ChunkCtx& c, const WS& w, int i) {
+  UMX_STAGE(c);
+  const LayerW& L = eng->lw[i];
+  float *xmid = w.xs[2 * i + 1], *xout = w.xs[2 * i + 2];
+  const std::string t = "." + std::to_string(i);
+  CHK(gemm_node(eng, w.xn2, ROW, 0, L.smlp, C, L.smlpb, w.gspre[i], 2 * H, 0, nn, 2 * H, C));
+  CHK(so3_linear(eng, w.xn2, L.l1w, L.l1b, w.ffh[i], nn, nullptr));
+  UMX_LAUNCH(k_gate_node_fwd, nblk(nn * H, 256), w.ffh[i], w.gspre[i], w.ffhg, nn);
+  CHK(so3_linear(eng, w.ffhg, L.l2w, L.l2b, xout, nn, xmid));
+  HIPCHK(eng, hipGetLastError());
+  DBG("xn2" + t, w.xn2, nn * ROW); DBG("gspre" + t, w.gspre[i], nn * 2 * H); DBG("ffh" + t, w.ffh[i], nn * ROW); DBG("x" + t, xout, nn * ROW);
+  if (eng->dbg_on) DBG("ffhg" + t, w.ffhg, nn * ROW);         // (debug) the gated hidden rows: one buffer for all layers
+  return UMX_OK;
+}
+// ... grid form (GridAtomwise): to-grid -> Linear, SiLU, Linear, SiLU, Linear over the channels of every grid point -> from-grid (+ residual).
+// The hidden pre-activations stay resident for the reverse pass; the SiLUs are applied while the next GEMM stages its A operand.
+int atomwise_fwd_grid(const ChunkCtx& c, const WS& w, int i) {
+  UMX_STAGE(c);
+  const LayerW& L = eng->lw[i];
+  float *xmid = w.xs[2 * i + 1], *xout = w.xs[2 * i + 2];
+  const std::string t = "." + std::to_string(i);
+  const int G = eng->grid_G;
+  const long ng = nn * G;
+  UMX_LAUNCH(k_grid_expand, nblk(nn, 4), w.xn2, eng->to_grid, G, w.gridA, nn);
+  if (eng->dbg_on) DBG("gridin" + t, w.gridA, ng * C);      // (debug) the to-grid projection: gridA is overwritten by the third GEMM
+  CHK(gemm_grid(eng, w.gridA, C, 0, L.g1w, C, L.g1b, w.ffg1[i], H, 0, ng, H, C));
+  CHK(gemm_grid(eng, w.ffg1[i], H, 0, L.g2w, H, L.g2b, w.ffg2[i], H, 0, ng, H, H, A_SILU));
+  CHK(gemm_grid(eng, w.ffg2[i], H, 0, L.g3w, H, L.g3b, w.gridA, C, 0, ng, C, H, A_SILU));
+  UMX_LAUNCH(k_grid_contract, nblk(nn, 4), w.gridA, eng->from_grid, G, xmid, xout, nn);
+  HIPCHK(eng, hipGetLastError());
+  if (eng->dbg_on) DBG("gridout" + t, w.gridA, ng * C);     // (debug) the grid MLP's output, from-grid's input
+  DBG("xn2" + t, w.xn2, nn * ROW); DBG("ffg1" + t, w.ffg1[i], ng * H); DBG("ffg2" + t, w.ffg2[i], ng * H); DBG("x" + t, xout, nn * ROW);
+  return UMX_OK;
+}
+
+// layer i forward: edge pipeline, aggregate, atom-wise block
+void plan_layer_fwd(Plan& P, WS& w, const ChunkCtx& c, int i) {
+  plan_edge_fwd(P, w, c, i, false);
+  if (c.gp) {      // partial aggregate of this rank's edges -> xn2 (free until the norm below), all-reduce, xmid = xin + sum
+    P.stream([c, &w, i]() -> int {
+      UMX_STAGE(c);
+      UMX_LAUNCH(k_rotate_back_reduce<9>, nblk(nn, 4), w.msg[i], w.frame, w.row_ptr, (const float*)nullptr, w.xn2, nn, 1.0f,
+                 (const int*)nullptr, 0, (const float*)nullptr, (const double*)nullptr);
+      HIPCHK(eng, hipGetLastError());
+      return UMX_OK;
+    });
+    P.sync(w.xn2, (size_t)c.nn * ROW);
+  }
+  P.stream([c, &w, i]() -> int {
+    UMX_STAGE(c);
+    const LayerW& L = eng->lw[i];
+    CHK(aggregate_fwd(c, w, i));
+    UMX_LAUNCH(k_norm_fwd, nblk(nn, 4), w.xs[2 * i + 1], L.n2w, L.n2b, (const double*)nullptr, w.xn2, nn);
+    return eng->ff_grid ? atomwise_fwd_grid(c, w, i) : atomwise_fwd_spectral(c, w, i);
+  });
+}
+
+// K9 readout: final norm, the energy MLP on the l = 0 channels, per-image sums
+int readout(const ChunkCtx& c, const WS& w) {
+  UMX_STAGE(c);
+  UMX_LAUNCH(k_norm_fwd, nblk(nn, 4), w.xs[2 * NL], eng->normw, eng->normb, (const double*)nullptr, w.xf, nn);
+  CHK(gemm_node(eng, w.xf, ROW, 0, eng->e0, C, eng->e0b, w.pre1, H, 0, nn, H, C));
+  CHK(gemm_node(eng, w.pre1, H, 0, eng->e2, H, eng->e2b, w.pre2, H, 0, nn, H, H, A_SILU));
+  UMX_LAUNCH(k_energy_node, nblk(nn, 4), w.pre2, eng->e4, eng->e4b, w.enode, nn);
+  UMX_LAUNCH(k_energy, (unsigned)c.nimg, w.enode, eng->natoms, eng->rmsd, eng->refsum, c.d_energy, eng->d_flags);
+  HIPCHK(eng, hipGetLastError());
+  DBG("e_node", w.enode, nn); DBG("pre1", w.pre1, nn * H); DBG("pre2", w.pre2, nn * H);
+  if (eng->dbg_on) DBG("xf", w.xf, nn * ROW);
+  return UMX_OK;
+}
+
+// K10, the analytic reverse pass: its node-level head, dE/d(energy MLP) back to G0 = dE/dx of the last layer's output.
+// (debug) every capture of the reverse node links sits directly behind the launch that writes its buffer: n128a / n128b, G0 / G1 / G2,
+// ggs and gridA / gridB are reused from link to link
+int reverse_head(const ChunkCtx& c, const WS& w) {
+  UMX_STAGE(c);
+  if (ne > 0) {
+    HIPCHK(eng, hipMemsetAsync(w.dedd, 0, ne * sizeof(float), s));
+    HIPCHK(eng, hipMemsetAsync(w.dedd_rad, 0, ne * sizeof(float), s));
+    HIPCHK(eng, hipMemsetAsync(w.tau, 0, ne * 4 * sizeof(float), s));
+    HIPCHK(eng, hipMemsetAsync(w.tau2, 0, ne * 4 * sizeof(float), s));
+  }
+  UMX_LAUNCH(k_silu_bwd, nblk(nn * H, 256), eng->e4, 0L, w.pre2, w.n128a, nn, H);
+  if (eng->dbg_on) DBG("g_pre2", w.n128a, nn * H);
+  CHK(gemm_node(eng, w.n128a, H, 0, eng->e2T, H, nullptr, w.n128b, H, 0, nn, H, H));
+  if (eng->dbg_on) DBG("g_sil1", w.n128b, nn * H);              // dE / d silu(pre1)
+  UMX_LAUNCH(k_silu_bwd, nblk(nn * H, 256), w.n128b, (long)H, w.pre1, w.n128a, nn, H);
+  if (eng->dbg_on) DBG("g_pre1", w.n128a, nn * H);
+  HIPCHK(eng, hipMemsetAsync(w.G1, 0, nn * ROW * sizeof(float), s));
+  CHK(gemm_node(eng, w.n128a, H, 0, eng->e0T, H, nullptr, w.G1, ROW, 0, nn, C, H));
+  if (eng->dbg_on) DBG("g_xf", w.G1, nn * ROW);                 // the whole row: the columns of l > 0 must still be zero
+  UMX_LAUNCH(k_norm_bwd, nblk(nn, 4), w.G1, w.xs[2 * NL], eng->normw, (const float*)nullptr, w.G0, nn);
+  HIPCHK(eng, hipGetLastError());
+  DBG("g_xfinal", w.G0, nn * ROW);
+  return UMX_OK;
+}
+
+// atom-wise backward, spectral form: G0 = dE/dx_out -> G1 = g_xn2
+int atomwise_bwd_spectral(const ChunkCtx& c, const WS& w, int i) {
+  UMX_STAGE(c);
+  const LayerW& L = eng->lw[i];
+  const std::string t = "." + std::to_string(i);
+  CHK(so3_linear(eng, w.G0, L.l2T, nullptr, w.G1, nn, nullptr));                         // G1 = g_ffhg
+  if (eng->dbg_on) DBG("g_ffhg" + t, w.G1, nn * ROW);
+  UMX_LAUNCH(k_gate_node_bwd, nblk(nn * H, 256), w.G1, w.ffh[i], w.gspre[i], w.G2, w.ggs, nn);
+  if (eng->dbg_on) { DBG("g_ffh" + t, w.G2, nn * ROW); DBG("g_gs" + t, w.ggs, nn * 2 * H); }
+  CHK(so3_linear(eng, w.G2, L.l1T, nullptr, w.G1, nn, nullptr));                         // G1 = g_xn2
+  if (eng->dbg_on) DBG("g_xn2a" + t, w.G1, nn * ROW);         // before the scalar MLP's share lands in the l = 0 columns
+  CHK(gemm_node(eng, w.ggs, 2 * H, 0, L.smlpT, 2 * H, nullptr, w.G1, ROW, 0, nn, C, 2 * H, A_PLAIN, 1, 0, 0, w.G1, ROW, 0, 0));
+  if (eng->dbg_on) DBG("g_xn2" + t, w.G1, nn * ROW);
+  return UMX_OK;
+}
+// ... grid form, the reverse of GridAtomwise: from-grid^T -> W3^T, SiLU', W2^T, SiLU', W1^T -> to-grid^T
+int atomwise_bwd_grid(const ChunkCtx& c, const WS& w, int i) {
+  UMX_STAGE(c);
+  const LayerW& L = eng->lw[i];
+  const std::string t = "." + std::to_string(i);
+  const int G = eng->grid_G;
+  const long ng = nn * G;
+  UMX_LAUNCH(k_grid_expand, nblk(nn, 4), w.G0, eng->from_grid, G, w.gridA, nn);
+  if (eng->dbg_on) DBG("g_gridout" + t, w.gridA, ng * C);
+  CHK(gemm_grid(eng, w.gridA, C, 0, L.g3T, C, nullptr, w.gridB, H, 0, ng, H, C));
+  if (eng->dbg_on) DBG("g_gsil2" + t, w.gridB, ng * H);       // dE / d silu(ffg2)
+  UMX_LAUNCH(k_silu_bwd, nblk(ng * H, 256), w.gridB, (long)H, w.ffg2[i], w.gridA, ng, H);
+  if (eng->dbg_on) DBG("g_ffg2" + t, w.gridA, ng * H);
+  CHK(gemm_grid(eng, w.gridA, H, 0, L.g2T, H, nullptr, w.gridB, H, 0, ng, H, H));
+  if (eng->dbg_on) DBG("g_gsil1" + t, w.gridB, ng * H);       // dE / d silu(ffg1)
+  UMX_LAUNCH(k_silu_bwd, nblk(ng * H, 256), w.gridB, (long)H, w.ffg1[i], w.gridA, ng, H);
+  if (eng->dbg_on) DBG("g_ffg1" + t, w.gridA, ng * H);
+  CHK(gemm_grid(eng, w.gridA, H, 0, L.g1T, H, nullptr, w.gridB, C, 0, ng, C, H));
+  if (eng->dbg_on) DBG("g_gridin" + t, w.gridB, ng * C);
+  UMX_LAUNCH(k_grid_contract, nblk(nn, 4), w.gridB, eng->to_grid, G, (const float*)nullptr, w.G1, nn);     // G1 = g_xn2
+  if (eng->dbg_on) DBG("g_xn2" + t, w.G1, nn * ROW);
+  return UMX_OK;
+}
+
+// layer i's atom-wise backward (G0 = dE/dx_out -> G2 = g_xmid) + the first edge kernel of the layer (split modes)
+void plan_atomwise_bwd(Plan& P, WS& w, const ChunkCtx& c, int i) {
+  P.stream([c, &w, i]() -> int {
+    UMX_STAGE(c);
+    CHK(eng->ff_grid ? atomwise_bwd_grid(c, w, i) : atomwise_bwd_spectral(c, w, i));
+    UMX_LAUNCH(k_norm_bwd, nblk(nn, 4), w.G1, w.xs[2 * i + 1], eng->lw[i].n2w, w.G0, w.G2, nn);   // G2 = g_xmid
+    HIPCHK(eng, hipGetLastError());
+    DBG("g_xmid." + std::to_string(i), w.G2, nn * ROW);
+    if (ne > 0 && eng->prec.planes) CHK(link_rotate_back_bwd(eng, w, i, ne));
+    return UMX_OK;
+  });
+}
+
+// The edge pipeline of layer i's reverse pass: g_xmid (G2) -> conv 2^T, gate backward, conv 1^T, modulation + rotation backward (g_xn
+// in G1 when fused), the radial MLP backward (dE/dd)
+void plan_edge_bwd(Plan& P, WS& w, const ChunkCtx& c, int i) {
+  if (c.ne <= 0) return;
+  const LayerW* L = &c.eng->lw[i];
+  if (c.eng->prec.planes) {
+    P.matrix([=, &w]() -> int { return so2_conv(c.eng, REV, w.gmsgpl, SO2_MSG, w.hid, SO2_MSG, L->c2m0T, L->c2m1T, L->c2m2T, nullptr, c.ne, -1.0f); });
+    P.stream([=, &w]() -> int {
+      UMX_STAGE(c);
+      DBG("g_hid." + std::to_string(i), w.hid, ne * ROW);
+      return link_gate_bwd(eng, w, i, ne);
+    });
+    P.matrix([=, &w]() -> int { return so2_conv(c.eng, REV, w.ghgpl, SO2_HG, w.gy1, SO2_Y1, L->c1m0T, L->c1m1T, L->c1m2T, nullptr, c.ne, -1.0f); });
+    // (a matrix-token segment although it is HBM-bound: at 240 VGPRs its waves cannot share a SIMD with a GEMM wave, so beside
+    //  the other lane's GEMM it would only take CUs away from it; the other lane's throttled stream kernels do fit beside it)
+    P.matrix([=, &w]() -> int {
+      UMX_STAGE(c);
+      DBG("g_y1." + std::to_string(i), w.gy1, ne * XROT);        // (debug) conv-1^T's output
+      return link_modrot_bwd(eng, w, i, nn, ne);
+    });
+    P.matrix([=, &w]() -> int { return radial_bwd_fc3(c.eng, w, L->rad, c.ne, nullptr, w.gradpl, c.eng->prec.rev_quad()); });
+    P.stream([=, &w]() -> int { return radial_bwd_tail(c.eng, w, L->rad, i, c.ne); });     // feeds only the scalar dE/dd (own accumulator dedd_rad)
+    return;
+  }
+  // fp32 mode: one stream segment
+  P.stream([=, &w]() -> int {
+    UMX_STAGE(c);
+    const std::string t = "." + std::to_string(i);
+    UMX_LAUNCH(k_rotate_back_bwd<9>, nblk(ne, 4), w.G2, w.msg[i], w.frame, w.edst, w.gmsg, w.dedd, w.tau, ne, 1.0f);
+    CHK(so2_conv(eng, REV, w.gmsg, SO2_MSG, w.hid, SO2_MSG, L->c2m0T, L->c2m1T, L->c2m2T, nullptr, ne, -1.0f));
+    DBG("g_msg" + t, w.gmsg, ne * ROW); DBG("g_hid" + t, w.hid, ne * ROW);
+    UMX_LAUNCH(k_gate_edge_bwd, nblk(ne * H, 256), w.hid, w.hg[i], w.ghg, ne);
+    CHK(so2_conv(eng, REV, w.ghg, SO2_HG, w.gy1, SO2_Y1, L->c1m0T, L->c1m1T, L->c1m2T, nullptr, ne, -1.0f));
+    DBG("g_hg" + t, w.ghg, ne * HG); DBG("g_y1" + t, w.gy1, ne * XROT);      // (k_modulate_bwd below turns g_y1 into g_xrot in place)
+    if (c.fused_rev) CHK(link_modrot_bwd(eng, w, i, nn, ne));
+    else {       // with debug captures on the unfused kernels run: they expose xrot / g_xrot to the stage-by-stage test
+      UMX_LAUNCH(k_gather_rotate, nblk(ne, 4), w.xn[i], w.esrc, w.edst, w.frame, w.xrot, ne);
+      UMX_LAUNCH(k_modulate_bwd, nblk(ne, 4), w.gy1, w.xrot, w.rad[i], w.grad, w.tau, ne);
+      DBG("g_xrot" + t, w.gy1, ne * XROT); DBG("g_rad" + t, w.grad, ne * RAD);
+    }
+    return radial_bwd(eng, w, L->rad, i, ne, w.grad);
+  });
+}
+
+// g_xn of layer i (G1) and the layer's first norm backward: G0 = g_xin, the next layer's dE/dx_out
+void plan_norm1_bwd(Plan& P, WS& w, const ChunkCtx& c, int i) {
+  const bool have_gxn = c.ne > 0 && c.fused_rev;         // k_modrot_bwd_pl has left g_xn in G1
+  auto gather_rotate_bwd = [c, &w]() -> int {            // unfused reverse (or no edges): G1 = g_xn from g_xrot (in gy1)
+    UMX_STAGE(c);
+    UMX_LAUNCH(k_gather_rotate_bwd, nblk(nn, 4), w.gy1, w.frame, w.row_ptr, w.out_ptr, w.out_edge, w.G1, nn);
+    HIPCHK(eng, hipGetLastError());
+    return UMX_OK;
+  };
+  if (c.gp) {
+    // g_xn: every rank holds the contributions of its own edges only.  A rank WITHOUT edges (fewer atoms than ranks, or only isolated
+    // targets) has run no edge kernel: G1 still holds g_xn2 of the atom-wise backward and must not enter the sum
+    if (c.ne == 0) P.stream([c, &w]() -> int { HIPCHK(c.eng, hipMemsetAsync(w.G1, 0, (size_t)c.nn * ROW * sizeof(float), c.eng->stream)); return UMX_OK; });
+    else if (!c.fused_rev) P.stream(gather_rotate_bwd);       // unfused reverse: the partial g_xn of this rank's edges has to exist BEFORE the exchange
+    P.sync(w.G1, (size_t)c.nn * ROW);
+  }
+  P.stream([=, &w]() -> int {
+    UMX_STAGE(c);
+    if (!have_gxn && !c.gp) CHK(gather_rotate_bwd());
+    UMX_LAUNCH(k_norm_bwd, nblk(nn, 4), w.G1, w.xs[2 * i], eng->lw[i].n1w, w.G2, w.G0, nn);                      // G0 = g_xin
+    HIPCHK(eng, hipGetLastError());
+    const std::string t = "." + std::to_string(i);
+    DBG("g_xn" + t, w.G1, nn * ROW); DBG("g_xin" + t, w.G0, nn * ROW);
+    return UMX_OK;
+  });
+}
+
+// the edge-degree embedding's reverse links, the per-edge force and its sum over the nodes (+ the virial of the chunk's images)
+int force_assembly(const ChunkCtx& c, const WS& w) {
+  UMX_STAGE(c);
+  if (ne > 0) {
+    if (c.rc) {      // recompute plan: the edge-degree link's radial MLP again (h1pre / h2pre / rad_deg of the slot), not its node sum
+      CHK(link_radial_head(eng, w, eng->rdeg, NL, ne));
       CHK(radial_fwd_fc3(eng, w, eng->rdeg, ne, w.rad_deg));
     }
-    // x0 = node init + sum over incoming edges (one kernel, the base added in double); graph-parallel: the bare partial sum goes to G1 and is
-    // all-reduced first, the base is added by k_node_init_add behind the exchange point
-    if (gp) hipLaunchKernelGGL(k_rotate_back_reduce<3>, dim3(nblk(nn, 4)), B256, 0, s, w.rad_deg, w.frame, w.row_ptr, (const float*)nullptr, w.G1, nn, DEG_RESCALE,
-                               (const int*)nullptr, 0, (const float*)nullptr, (const double*)nullptr);
-    else hipLaunchKernelGGL(k_rotate_back_reduce<3>, dim3(nblk(nn, 4)), B256, 0, s, w.rad_deg, w.frame, w.row_ptr, (const float*)nullptr, w.xs[0], nn, DEG_RESCALE,
-                            (const int*)eng->d_z, N, eng->emb_sphere, (const double*)eng->d_sysemb);
-    HIPCHK(eng, hipGetLastError());
-    if (!gp) { DBG("rad.deg", w.rad_deg, ne * 3 * C); DBG("x0", w.xs[0], nn * ROW); DBG("h1pre.deg", w.h1pre[NL], ne * RH); DBG("h2pre.deg", w.h2pre[NL], ne * RH); }
-    return UMX_OK;
-  });
-  if (gp) {
-    P.sync(w.G1, (size_t)nn * ROW);
-    P.stream([=, &w]() -> int {
-      hipLaunchKernelGGL(k_node_init_add, dim3(nblk(nn * ROW, 256)), B256, 0, eng->stream, eng->d_z, N, nn, eng->emb_sphere, eng->d_sysemb, w.G1, w.xs[0]);
-      HIPCHK(eng, hipGetLastError());
-      return UMX_OK;
-    });
+    CHK(link_rotate_back_bwd_deg(eng, w, ne));
+    CHK(radial_bwd(eng, w, eng->rdeg, NL, ne, w.gmsg, deg_rev_planes(eng) ? w.gmsgpl : nullptr));
+    if (c.fused_rev) UMX_LAUNCH(k_add4, nblk(ne, 256), w.tau, w.tau2, ne);
+    UMX_LAUNCH(k_force_edge, nblk(ne, 256), w.dedd, w.dedd_rad, w.tau, w.frame, w.evec, w.gvec, ne);
   }
+  UMX_LAUNCH(k_force_node, nblk(nn, 4), w.gvec, w.row_ptr, w.out_ptr, w.out_edge, (float)eng->rmsd, c.d_forces, nn);
+  HIPCHK(eng, hipGetLastError());
+  if (c.vir.out) CHK(virial_launch(eng, w, c.vir, c.nimg, ne));       // (a partition: before the next one overwrites the shared gvec)
+  DBG("dedd", w.dedd, ne); DBG("tau", w.tau, ne * 4); DBG("gvec", w.gvec, ne * 4);
+  return UMX_OK;
+}
 
-  // The edge pipeline of layer i's forward pass (radial MLP, gather / rotate / modulate, conv 1, gate, conv 2 -> rad, hg, msg, h1pre,
-  // h2pre of the layer), led by the layer's first norm.  replay (recompute plans, reverse pass): the same segments from the STORED node
-  // input xn[i] -- the norm, like everything node-level, is not issued again; no kernel of the pipeline writes node state.
-  auto edge_fwd = [&](int i, bool replay) {
-    const LayerW* Lp = &eng->lw[i];
-    float* xin = w.xs[2 * i];
-    if (ne > 0 && pl) {
-      P.stream([=, &w]() -> int {
-        hipStream_t s = eng->stream;
-        if (!replay) hipLaunchKernelGGL(k_norm_fwd, dim3(nblk(nn, 4)), B256, 0, s, xin, Lp->n1w, Lp->n1b, eng->d_sysemb, w.xn[i], nn);
-        return radial_fwd_head(eng, w, Lp->rad, i, ne);
-      });
-      P.matrix([=, &w]() -> int {
-        if (eng->prec.fwd_fmt == 3) DBG("a2q." + std::to_string(i), reinterpret_cast<const float*>(w.a2pl), (ne + 3) / 4 * 4 * RH);
-        if (eng->prec.fwd_fmt == 1) DBG("a2h." + std::to_string(i), w.a2pl, (ne + 3) / 4 * 4 * RH * 2);
-        return radial_fwd_fc3(eng, w, Lp->rad, ne, w.rad[i]);
-      });
-      P.stream([=, &w]() -> int {
-        hipStream_t s = eng->stream;
-        if (eng->prec.fwd_fmt == 1) hipLaunchKernelGGL(k_gather_rotate_mod_q3<1>, dim3(vgrid(eng, (nblk(ne, 4) + 7) / 8 * 8)), B256, 0, s, w.xn[i], w.esrc, w.edst, w.frame, w.rad[i], w.y1pl, ne, eng->odd_sign);
-        else hipLaunchKernelGGL(k_gather_rotate_mod_q3<3>, dim3(vgrid(eng, (nblk(ne, 4) + 7) / 8 * 8)), B256, 0, s, w.xn[i], w.esrc, w.edst, w.frame, w.rad[i], w.y1pl, ne, eng->odd_sign);
-        HIPCHK(eng, hipGetLastError());
-        return UMX_OK;
-      });
-      // SO(2) conv 1 on the pre-modulated planes -> hg = [gate | hpre]
-      P.matrix([=, &w]() -> int {
-        if (eng->prec.fwd_fmt == 3) DBG("y1q." + std::to_string(i), reinterpret_cast<const float*>(w.y1pl), (ne + 3) / 4 * 4 * XROT);     // (debug) conv-1's A operand as the GEMMs read it
-        if (eng->prec.fwd_fmt == 1) DBG("y1h." + std::to_string(i), w.y1pl, (ne + 3) / 4 * 4 * XROT * 2);
-        CHK(gemm_pl(eng, 0, FWD, w.y1pl, XROT, 0, 0, Lp->c1m0, 0, Lp->c1m0b, w.hg[i], HG, 0, 0, ne, 640, 768, 1.0f));
-        CHK(gemm_pl(eng, 1, FWD, w.y1pl, XROT, 768, 1280, Lp->c1m1, 256, nullptr, w.hg[i], HG, 640, 896, ne, 256, 512, 1.0f));
-        return gemm_pl(eng, 1, FWD, w.y1pl, XROT, 1792, 2048, Lp->c1m2, 128, nullptr, w.hg[i], HG, 1152, 1280, ne, 128, 256, 1.0f);
-      });
-      P.stream([=, &w]() -> int {
-        hipStream_t s = eng->stream;
-        if (eng->prec.fwd_fmt == 1) hipLaunchKernelGGL(k_gate_edge_fwd_q3<1>, dim3(vgrid(eng, nblk(ne, 8))), B256, 0, s, w.hg[i], w.hidpl, ne, eng->odd_sign);
-        else hipLaunchKernelGGL(k_gate_edge_fwd_q3<3>, dim3(vgrid(eng, nblk(ne, 8))), B256, 0, s, w.hg[i], w.hidpl, ne, eng->odd_sign);
-        HIPCHK(eng, hipGetLastError());
-        return UMX_OK;
-      });
-      P.matrix([=, &w]() -> int {
-        if (eng->prec.fwd_fmt == 3) DBG("hidq." + std::to_string(i), reinterpret_cast<const float*>(w.hidpl), (ne + 3) / 4 * 4 * ROW);      // (debug) conv-2's A operand
-        if (eng->prec.fwd_fmt == 1) DBG("hidh." + std::to_string(i), w.hidpl, (ne + 3) / 4 * 4 * ROW * 2);
-        CHK(gemm_pl(eng, 0, FWD, w.hidpl, ROW, 0, 0, Lp->c2m0, 0, Lp->c2m0b, w.msg[i], ROW, 0, 0, ne, 384, 384, 1.0f));
-        CHK(gemm_pl(eng, 1, FWD, w.hidpl, ROW, 384, 640, Lp->c2m1, 256, nullptr, w.msg[i], ROW, 384, 640, ne, 256, 256, 1.0f));
-        return gemm_pl(eng, 1, FWD, w.hidpl, ROW, 896, 1024, Lp->c2m2, 128, nullptr, w.msg[i], ROW, 896, 1024, ne, 128, 128, 1.0f);
-      });
-    } else {
-      P.stream([=, &w]() -> int {
-        hipStream_t s = eng->stream;
-        const LayerW& L = *Lp;
-        if (!replay) hipLaunchKernelGGL(k_norm_fwd, dim3(nblk(nn, 4)), B256, 0, s, xin, L.n1w, L.n1b, eng->d_sysemb, w.xn[i], nn);
-        if (ne > 0) {
-          hipLaunchKernelGGL(k_gather_rotate, dim3(nblk(ne, 4)), B256, 0, s, w.xn[i], w.esrc, w.edst, w.frame, w.xrot, ne);
-          CHK(radial_fwd(eng, w, L.rad, i, ne, w.rad[i]));
-          // SO(2) conv 1 (radially modulated) -> hg = [gate | hpre]
-          {
-            GemmP p = gp_zero();
-            p.A = w.xrot; p.lda = XROT; p.R = w.rad[i]; p.ldr = RAD; p.B = L.c1m0; p.ldb = 3 * 2 * C; p.bias = L.c1m0b;
-            p.Cp = w.hg[i]; p.ldc = HG; p.M = (int)ne; p.N = 2 * H + 3 * H; p.K = 3 * 2 * C;
-            CHK(launch_gemm(eng, p, A_MODUL, 0, E_BIAS));
-          }
-          CHK(gemm_cplx(eng, w.xrot, XROT, 768, 1280, w.rad[i], RAD, 768, L.c1m1, 512, 256, w.hg[i], HG, 640, 896, ne, 256, 512, 1.0f));
-          CHK(gemm_cplx(eng, w.xrot, XROT, 1792, 2048, w.rad[i], RAD, 1280, L.c1m2, 256, 128, w.hg[i], HG, 1152, 1280, ne, 128, 256, 1.0f));
-          hipLaunchKernelGGL(k_gate_edge_fwd, dim3(nblk(ne * (H / 4), 256)), B256, 0, s, w.hg[i], w.hid, ne);
-          // SO(2) conv 2 -> msg
-          CHK(gemm_plain(eng, w.hid, ROW, 0, L.c2m0, 3 * H, L.c2m0b, w.msg[i], ROW, 0, ne, 3 * C, 3 * H));
-          CHK(gemm_cplx(eng, w.hid, ROW, 384, 640, nullptr, 0, 0, L.c2m1, 256, 256, w.msg[i], ROW, 384, 640, ne, 256, 256, 1.0f));
-          CHK(gemm_cplx(eng, w.hid, ROW, 896, 1024, nullptr, 0, 0, L.c2m2, 128, 128, w.msg[i], ROW, 896, 1024, ne, 128, 128, 1.0f));
-        }
-        HIPCHK(eng, hipGetLastError());
-        return UMX_OK;
-      });
-    }
-  };
-  for (int i = 0; i < NL; ++i) {
-    const LayerW* Lp = &eng->lw[i];
-    float* xin = w.xs[2 * i];
-    float* xmid = w.xs[2 * i + 1];
-    float* xout = w.xs[2 * i + 2];
-    edge_fwd(i, false);
-    if (gp) {      // partial aggregate of this rank's edges -> xn2 (free until the norm below), all-reduce, xmid = xin + sum
-      P.stream([=, &w]() -> int {
-        hipLaunchKernelGGL(k_rotate_back_reduce<9>, dim3(nblk(nn, 4)), B256, 0, eng->stream, w.msg[i], w.frame, w.row_ptr, (const float*)nullptr, w.xn2, nn, 1.0f,
-                           (const int*)nullptr, 0, (const float*)nullptr, (const double*)nullptr);
-        HIPCHK(eng, hipGetLastError());
-        return UMX_OK;
-      });
-      P.sync(w.xn2, (size_t)nn * ROW);
-    }
-    P.stream([=, &w]() -> int {
-      hipStream_t s = eng->stream;
-      const LayerW& L = *Lp;
-      const std::string t = "." + std::to_string(i);
-      if (gp) hipLaunchKernelGGL(k_add_rows, dim3(nblk(nn * ROW / 4, 256)), B256, 0, s, xmid, xin, w.xn2, nn * ROW / 4);
-      else hipLaunchKernelGGL(k_rotate_back_reduce<9>, dim3(vgrid(eng, nblk(nn, 4))), B256, 0, s, w.msg[i], w.frame, w.row_ptr, xin, xmid, nn, 1.0f,
-                              (const int*)nullptr, 0, (const float*)nullptr, (const double*)nullptr);
-      HIPCHK(eng, hipGetLastError());
-      DBG("xn" + t, w.xn[i], nn * ROW); DBG("rad" + t, w.rad[i], ne * RAD); DBG("h1pre" + t, w.h1pre[i], ne * RH); DBG("h2pre" + t, w.h2pre[i], ne * RH);
-      if (!eng->prec.planes) { DBG("xrot" + t, w.xrot, ne * XROT); DBG("hid" + t, w.hid, ne * ROW); }
-      DBG("hg" + t, w.hg[i], ne * HG); DBG("msg" + t, w.msg[i], ne * ROW); DBG("xmid" + t, xmid, nn * ROW);
-      // K8 atom-wise
-      hipLaunchKernelGGL(k_norm_fwd, dim3(nblk(nn, 4)), B256, 0, s, xmid, L.n2w, L.n2b, (const double*)nullptr, w.xn2, nn);
-      if (eng->ff_grid) {
-        // GridAtomwise: to-grid -> Linear, SiLU, Linear, SiLU, Linear over the channels of every grid point -> from-grid (+ residual).
-        // The hidden pre-activations stay resident for the reverse pass; the SiLUs are applied while the next GEMM stages its A operand.
-        const int G = eng->grid_G;
-        const long ng = nn * G;
-        hipLaunchKernelGGL(k_grid_expand, dim3(nblk(nn, 4)), B256, 0, s, w.xn2, eng->to_grid, G, w.gridA, nn);
-        if (eng->dbg_on) DBG("gridin" + t, w.gridA, ng * C);      // (debug) the to-grid projection: gridA is overwritten by the third GEMM
-        CHK(gemm_grid(eng, w.gridA, C, 0, L.g1w, C, L.g1b, w.ffg1[i], H, 0, ng, H, C));
-        CHK(gemm_grid(eng, w.ffg1[i], H, 0, L.g2w, H, L.g2b, w.ffg2[i], H, 0, ng, H, H, A_SILU));
-        CHK(gemm_grid(eng, w.ffg2[i], H, 0, L.g3w, H, L.g3b, w.gridA, C, 0, ng, C, H, A_SILU));
-        hipLaunchKernelGGL(k_grid_contract, dim3(nblk(nn, 4)), B256, 0, s, w.gridA, eng->from_grid, G, xmid, xout, nn);
-        HIPCHK(eng, hipGetLastError());
-        if (eng->dbg_on) DBG("gridout" + t, w.gridA, ng * C);     // (debug) the grid MLP's output, from-grid's input
-        DBG("xn2" + t, w.xn2, nn * ROW); DBG("ffg1" + t, w.ffg1[i], ng * H); DBG("ffg2" + t, w.ffg2[i], ng * H); DBG("x" + t, xout, nn * ROW);
-        return UMX_OK;
-      }
-      CHK(gemm_node(eng, w.xn2, ROW, 0, L.smlp, C, L.smlpb, w.gspre[i], 2 * H, 0, nn, 2 * H, C));
-      CHK(so3_linear(eng, w.xn2, L.l1w, L.l1b, w.ffh[i], nn, nullptr));
-      hipLaunchKernelGGL(k_gate_node_fwd, dim3(nblk(nn * H, 256)), B256, 0, s, w.ffh[i], w.gspre[i], w.ffhg, nn);
-      CHK(so3_linear(eng, w.ffhg, L.l2w, L.l2b, xout, nn, xmid));
-      HIPCHK(eng, hipGetLastError());
-      DBG("xn2" + t, w.xn2, nn * ROW); DBG("gspre" + t, w.gspre[i], nn * 2 * H); DBG("ffh" + t, w.ffh[i], nn * ROW); DBG("x" + t, xout, nn * ROW);
-      if (eng->dbg_on) DBG("ffhg" + t, w.ffhg, nn * ROW);         // (debug) the gated hidden rows: one buffer for all layers
-      return UMX_OK;
-    });
-  }
+// The launch sequence of one chunk, stage by stage: graph and edge-degree embedding; NL layers forward; readout; with forces, the analytic
+// reverse pass layer by layer and the force assembly.  d_pos, d_deg, d_cand and the outputs are the chunk's own (they start at image img0
+// of the call).
+void plan_chunk(umx_engine* eng, WS& w, const PosPtr d_pos, const int* d_deg, const int* d_cand, long img0, long nimg, long ne, double* d_energy,
+                float* d_forces, Plan& P, const VirialOut vir = VirialOut()) {
+  const bool gp = eng->gp, pinned = eng->pin_on;
+  const long nn = nimg * eng->natoms, g_lo = gp ? eng->gp_lo : 0, g_hi = gp ? eng->gp_hi : nn;
+  const long pin_e0 = pinned && gp ? eng->pin_row[g_lo] : 0, pin_ecnt = pinned ? (gp ? eng->pin_row[g_hi] - pin_e0 : eng->pin_edges) : 0;
+  const ChunkCtx c{eng, nn, ne, nimg, img0, gp, g_lo, g_hi, pinned, pin_e0, pin_ecnt, eng->may_truncate, eng->rc_active && d_forces != nullptr,
+                   eng->prec.planes || !eng->dbg_on, d_pos, d_deg, d_cand, d_energy, d_forces, vir};
+  plan_graph(P, w, c);
+  for (int i = 0; i < NL; ++i) plan_layer_fwd(P, w, c, i);
   // K9 readout (+ the node-level head of the reverse pass)
-  float* xlast = w.xs[2 * NL];
-  P.stream([=, &w]() -> int {
-    hipStream_t s = eng->stream;
-    hipLaunchKernelGGL(k_norm_fwd, dim3(nblk(nn, 4)), B256, 0, s, xlast, eng->normw, eng->normb, (const double*)nullptr, w.xf, nn);
-    CHK(gemm_node(eng, w.xf, ROW, 0, eng->e0, C, eng->e0b, w.pre1, H, 0, nn, H, C));
-    CHK(gemm_node(eng, w.pre1, H, 0, eng->e2, H, eng->e2b, w.pre2, H, 0, nn, H, H, A_SILU));
-    hipLaunchKernelGGL(k_energy_node, dim3(nblk(nn, 4)), B256, 0, s, w.pre2, eng->e4, eng->e4b, w.enode, nn);
-    hipLaunchKernelGGL(k_energy, dim3((unsigned)nimg), B256, 0, s, w.enode, N, eng->rmsd, eng->refsum, d_energy, eng->d_flags);
-    HIPCHK(eng, hipGetLastError());
-    DBG("e_node", w.enode, nn); DBG("pre1", w.pre1, nn * H); DBG("pre2", w.pre2, nn * H);
-    if (eng->dbg_on) DBG("xf", w.xf, nn * ROW);
-    if (!d_forces) return UMX_OK;
-    // ---------------- K10: analytic reverse pass ----------------
-    if (ne > 0) {
-      HIPCHK(eng, hipMemsetAsync(w.dedd, 0, ne * sizeof(float), s));
-      HIPCHK(eng, hipMemsetAsync(w.dedd_rad, 0, ne * sizeof(float), s));
-      HIPCHK(eng, hipMemsetAsync(w.tau, 0, ne * 4 * sizeof(float), s));
-      HIPCHK(eng, hipMemsetAsync(w.tau2, 0, ne * 4 * sizeof(float), s));
-    }
-    // (debug) every capture of the reverse node links sits directly behind the launch that writes its buffer: n128a / n128b, G0 / G1 / G2,
-    // ggs and gridA / gridB are reused from link to link
-    hipLaunchKernelGGL(k_silu_bwd, dim3(nblk(nn * H, 256)), B256, 0, s, eng->e4, 0L, w.pre2, w.n128a, nn, H);
-    if (eng->dbg_on) DBG("g_pre2", w.n128a, nn * H);
-    CHK(gemm_node(eng, w.n128a, H, 0, eng->e2T, H, nullptr, w.n128b, H, 0, nn, H, H));
-    if (eng->dbg_on) DBG("g_sil1", w.n128b, nn * H);              // dE / d silu(pre1)
-    hipLaunchKernelGGL(k_silu_bwd, dim3(nblk(nn * H, 256)), B256, 0, s, w.n128b, (long)H, w.pre1, w.n128a, nn, H);
-    if (eng->dbg_on) DBG("g_pre1", w.n128a, nn * H);
-    HIPCHK(eng, hipMemsetAsync(w.G1, 0, nn * ROW * sizeof(float), s));
-    CHK(gemm_node(eng, w.n128a, H, 0, eng->e0T, H, nullptr, w.G1, ROW, 0, nn, C, H));
-    if (eng->dbg_on) DBG("g_xf", w.G1, nn * ROW);                 // the whole row: the columns of l > 0 must still be zero
-    hipLaunchKernelGGL(k_norm_bwd, dim3(nblk(nn, 4)), B256, 0, s, w.G1, xlast, eng->normw, (const float*)nullptr, w.G0, nn);
-    HIPCHK(eng, hipGetLastError());
-    DBG("g_xfinal", w.G0, nn * ROW);
-    return UMX_OK;
+  P.stream([c, &w]() -> int {
+    CHK(readout(c, w));
+    return c.d_forces ? reverse_head(c, w) : UMX_OK;
   });
   if (!d_forces) return;
-
   for (int i = NL - 1; i >= 0; --i) {
-    const LayerW* Lp = &eng->lw[i];
-    float* xin = w.xs[2 * i];
-    float* xmid = w.xs[2 * i + 1];
     // recompute plan: the activation slot holds another layer (or, between exchange points, another partition): replay this layer's
     // forward edge pipeline into it first.  Every transient operand is free here: the reverse segments of layer i + 1 are complete.
     // (One piece: the slot still holds layer NL - 1 when the reverse pass starts.)
-    if (rc && ne > 0 && (gp || i != NL - 1)) edge_fwd(i, true);
-    // atom-wise backward: G0 = dE/dx_out  (+ the first edge kernel of the layer)
-    P.stream([=, &w]() -> int {
-      hipStream_t s = eng->stream;
-      const LayerW& L = *Lp;
-      const std::string t = "." + std::to_string(i);
-      if (eng->ff_grid) {
-        // reverse of GridAtomwise: from-grid^T -> W3^T, SiLU', W2^T, SiLU', W1^T -> to-grid^T
-        const int G = eng->grid_G;
-        const long ng = nn * G;
-        hipLaunchKernelGGL(k_grid_expand, dim3(nblk(nn, 4)), B256, 0, s, w.G0, eng->from_grid, G, w.gridA, nn);
-        if (eng->dbg_on) DBG("g_gridout" + t, w.gridA, ng * C);
-        CHK(gemm_grid(eng, w.gridA, C, 0, L.g3T, C, nullptr, w.gridB, H, 0, ng, H, C));
-        if (eng->dbg_on) DBG("g_gsil2" + t, w.gridB, ng * H);       // dE / d silu(ffg2)
-        hipLaunchKernelGGL(k_silu_bwd, dim3(nblk(ng * H, 256)), B256, 0, s, w.gridB, (long)H, w.ffg2[i], w.gridA, ng, H);
-        if (eng->dbg_on) DBG("g_ffg2" + t, w.gridA, ng * H);
-        CHK(gemm_grid(eng, w.gridA, H, 0, L.g2T, H, nullptr, w.gridB, H, 0, ng, H, H));
-        if (eng->dbg_on) DBG("g_gsil1" + t, w.gridB, ng * H);       // dE / d silu(ffg1)
-        hipLaunchKernelGGL(k_silu_bwd, dim3(nblk(ng * H, 256)), B256, 0, s, w.gridB, (long)H, w.ffg1[i], w.gridA, ng, H);
-        if (eng->dbg_on) DBG("g_ffg1" + t, w.gridA, ng * H);
-        CHK(gemm_grid(eng, w.gridA, H, 0, L.g1T, H, nullptr, w.gridB, C, 0, ng, C, H));
-        if (eng->dbg_on) DBG("g_gridin" + t, w.gridB, ng * C);
-        hipLaunchKernelGGL(k_grid_contract, dim3(nblk(nn, 4)), B256, 0, s, w.gridB, eng->to_grid, G, (const float*)nullptr, w.G1, nn);     // G1 = g_xn2
-        if (eng->dbg_on) DBG("g_xn2" + t, w.G1, nn * ROW);
-      } else {
-      CHK(so3_linear(eng, w.G0, L.l2T, nullptr, w.G1, nn, nullptr));                         // G1 = g_ffhg
-      if (eng->dbg_on) DBG("g_ffhg" + t, w.G1, nn * ROW);
-      hipLaunchKernelGGL(k_gate_node_bwd, dim3(nblk(nn * H, 256)), B256, 0, s, w.G1, w.ffh[i], w.gspre[i], w.G2, w.ggs, nn);
-      if (eng->dbg_on) { DBG("g_ffh" + t, w.G2, nn * ROW); DBG("g_gs" + t, w.ggs, nn * 2 * H); }
-      CHK(so3_linear(eng, w.G2, L.l1T, nullptr, w.G1, nn, nullptr));                         // G1 = g_xn2
-      if (eng->dbg_on) DBG("g_xn2a" + t, w.G1, nn * ROW);         // before the scalar MLP's share lands in the l = 0 columns
-      CHK(gemm_node(eng, w.ggs, 2 * H, 0, L.smlpT, 2 * H, nullptr, w.G1, ROW, 0, nn, C, 2 * H, A_PLAIN, 1, 0, 0, w.G1, ROW, 0, 0));
-      if (eng->dbg_on) DBG("g_xn2" + t, w.G1, nn * ROW);
-      }
-      hipLaunchKernelGGL(k_norm_bwd, dim3(nblk(nn, 4)), B256, 0, s, w.G1, xmid, L.n2w, w.G0, w.G2, nn);   // G2 = g_xmid
-      HIPCHK(eng, hipGetLastError());
-      DBG("g_xmid" + t, w.G2, nn * ROW);
-      if (ne > 0 && eng->prec.planes)
-      {
-        if (eng->prec.rev_quad()) hipLaunchKernelGGL(k_rotate_back_bwd_q3<3>, dim3(vgrid(eng, (nblk(ne, 4) + 7) / 8 * 8)), B256, 0, s, w.G2, w.msg[i], w.frame, w.edst, w.gmsgpl, w.dedd, w.tau, ne, eng->odd_sign);
-        else hipLaunchKernelGGL(k_rotate_back_bwd_pl<2>, dim3(vgrid(eng, (nblk(ne, 4) + 7) / 8 * 8)), B256, 0, s, w.G2, w.msg[i], w.frame, w.edst, w.gmsgpl, w.dedd, w.tau, ne, eng->odd_sign);
-        // (debug) conv-2^T's A operand as the GEMMs read it: float32 quad-row blocks (bf16x3) or two PL planes (split-bf16); odd rows negated
-        if (eng->prec.rev_quad()) DBG("gmsgq" + t, reinterpret_cast<const float*>(w.gmsgpl), (ne + 3) / 4 * 4 * ROW);
-        else DBG("gmsgpl" + t, w.gmsgpl, ne * ROW * 2);
-      }
-      HIPCHK(eng, hipGetLastError());
-      return UMX_OK;
-    });
-    if (ne > 0 && pl) {
-      P.matrix([=, &w]() -> int {
-        CHK(gemm_pl(eng, 0, REV, w.gmsgpl, ROW, 0, 0, Lp->c2m0T, 0, nullptr, w.hid, ROW, 0, 0, ne, 384, 384, 1.0f));
-        CHK(gemm_pl(eng, 1, REV, w.gmsgpl, ROW, 384, 640, Lp->c2m1T, 256, nullptr, w.hid, ROW, 384, 640, ne, 256, 256, -1.0f));
-        return gemm_pl(eng, 1, REV, w.gmsgpl, ROW, 896, 1024, Lp->c2m2T, 128, nullptr, w.hid, ROW, 896, 1024, ne, 128, 128, -1.0f);
-      });
-      P.stream([=, &w]() -> int {
-        hipStream_t s = eng->stream;
-        DBG("g_hid." + std::to_string(i), w.hid, ne * ROW);
-        if (eng->prec.rev_quad()) hipLaunchKernelGGL(k_gate_edge_bwd_q3<3>, dim3(vgrid(eng, nblk(ne, 8))), B256, 0, s, w.hid, w.hg[i], w.ghgpl, ne, eng->odd_sign);
-        else hipLaunchKernelGGL(k_gate_edge_bwd_pl<2>, dim3(vgrid(eng, nblk(ne * (H / 4), 256))), B256, 0, s, w.hid, w.hg[i], w.ghgpl, ne, eng->odd_sign);
-        HIPCHK(eng, hipGetLastError());
-        // (debug) conv-1^T's A operand, in the format of gmsgq / gmsgpl
-        if (eng->prec.rev_quad()) DBG("ghgq." + std::to_string(i), reinterpret_cast<const float*>(w.ghgpl), (ne + 3) / 4 * 4 * HG);
-        else DBG("ghgpl." + std::to_string(i), w.ghgpl, ne * HG * 2);
-        return UMX_OK;
-      });
-      P.matrix([=, &w]() -> int {
-        CHK(gemm_pl(eng, 0, REV, w.ghgpl, HG, 0, 0, Lp->c1m0T, 0, nullptr, w.gy1, XROT, 0, 0, ne, 768, 640, 1.0f));
-        CHK(gemm_pl(eng, 1, REV, w.ghgpl, HG, 640, 896, Lp->c1m1T, 512, nullptr, w.gy1, XROT, 768, 1280, ne, 512, 256, -1.0f));
-        return gemm_pl(eng, 1, REV, w.ghgpl, HG, 1152, 1280, Lp->c1m2T, 256, nullptr, w.gy1, XROT, 1792, 2048, ne, 256, 128, -1.0f);
-      });
-      // (a matrix-token segment although it is HBM-bound: at 240 VGPRs its waves cannot share a SIMD with a GEMM wave, so beside
-      //  the other lane's GEMM it would only take CUs away from it; the other lane's throttled stream kernels do fit beside it)
-      P.matrix([=, &w]() -> int {
-        hipStream_t s = eng->stream;
-        const std::string t = "." + std::to_string(i);
-        DBG("g_y1" + t, w.gy1, ne * XROT);        // (debug) conv-1^T's output
-        // one node-centric kernel: modulation backward + rotate-back + segmented sum (g_xrot stays in registers); g_rad as float32 rows
-        // (sign-alternating; split by the fc3^T GEMM in registers) in the bf16x3 mode, as two PL bf16 planes in the 16-bit-reverse modes
-        if (eng->prec.rev_quad()) hipLaunchKernelGGL(k_modrot_bwd_pl<0>, dim3((unsigned)nn), B256, 0, s, w.gy1, w.xn[i], w.frame, w.rad[i], w.row_ptr, w.out_ptr, w.out_edge,
-                                            w.gradpl, w.tau, w.tau2, w.G1, nn, eng->odd_sign);
-        else hipLaunchKernelGGL(k_modrot_bwd_pl<2>, dim3((unsigned)nn), B256, 0, s, w.gy1, w.xn[i], w.frame, w.rad[i], w.row_ptr, w.out_ptr, w.out_edge,
-                                w.gradpl, w.tau, w.tau2, w.G1, nn, eng->odd_sign);
-        HIPCHK(eng, hipGetLastError());
-        // (debug) fc3^T's A operand: float32 rows (bf16x3) or two PL planes (split-bf16); odd rows negated
-        if (eng->prec.rev_quad()) DBG("gradq" + t, reinterpret_cast<const float*>(w.gradpl), ne * RAD);
-        else DBG("gradpl" + t, w.gradpl, ne * RAD * 2);
-        return UMX_OK;
-      });
-      P.matrix([=, &w]() -> int { return radial_bwd_fc3(eng, w, Lp->rad, ne, nullptr, w.gradpl, eng->prec.rev_quad()); });
-      P.stream([=, &w]() -> int { return radial_bwd_tail(eng, w, Lp->rad, i, ne); });     // feeds only the scalar dE/dd (own accumulator dedd_rad)
-    } else if (ne > 0) {
-      P.stream([=, &w]() -> int {
-        hipStream_t s = eng->stream;
-        const LayerW& L = *Lp;
-        const std::string t = "." + std::to_string(i);
-        hipLaunchKernelGGL(k_rotate_back_bwd<9>, dim3(nblk(ne, 4)), B256, 0, s, w.G2, w.msg[i], w.frame, w.edst, w.gmsg, w.dedd, w.tau, ne, 1.0f);
-        CHK(gemm_plain(eng, w.gmsg, ROW, 0, L.c2m0T, 3 * C, nullptr, w.hid, ROW, 0, ne, 3 * H, 3 * C));
-        CHK(gemm_cplx(eng, w.gmsg, ROW, 384, 640, nullptr, 0, 0, L.c2m1T, 256, 256, w.hid, ROW, 384, 640, ne, 256, 256, -1.0f));
-        CHK(gemm_cplx(eng, w.gmsg, ROW, 896, 1024, nullptr, 0, 0, L.c2m2T, 128, 128, w.hid, ROW, 896, 1024, ne, 128, 128, -1.0f));
-        DBG("g_msg" + t, w.gmsg, ne * ROW); DBG("g_hid" + t, w.hid, ne * ROW);
-        hipLaunchKernelGGL(k_gate_edge_bwd, dim3(nblk(ne * H, 256)), B256, 0, s, w.hid, w.hg[i], w.ghg, ne);
-        CHK(gemm_plain(eng, w.ghg, HG, 0, L.c1m0T, 640, nullptr, w.gy1, XROT, 0, ne, 768, 640));
-        CHK(gemm_cplx(eng, w.ghg, HG, 640, 896, nullptr, 0, 0, L.c1m1T, 256, 512, w.gy1, XROT, 768, 1280, ne, 512, 256, -1.0f));
-        CHK(gemm_cplx(eng, w.ghg, HG, 1152, 1280, nullptr, 0, 0, L.c1m2T, 128, 256, w.gy1, XROT, 1792, 2048, ne, 256, 128, -1.0f));
-        DBG("g_hg" + t, w.ghg, ne * HG); DBG("g_y1" + t, w.gy1, ne * XROT);      // (k_modulate_bwd below turns g_y1 into g_xrot in place)
-        if (!eng->dbg_on) {
-          // round 4: the fp32 mode takes the node-centric fused kernel of the split path too (P = 0: g_rad as float32 rows) instead of
-          // k_gather_rotate + k_modulate_bwd + k_gather_rotate_bwd -- the rotated message and g_xrot never touch HBM (-27 KB per edge and
-          // layer).  With debug captures on the unfused kernels run: they expose xrot / g_xrot to the stage-by-stage test.
-          hipLaunchKernelGGL(k_modrot_bwd_pl<0>, dim3((unsigned)nn), B256, 0, s, w.gy1, w.xn[i], w.frame, w.rad[i], w.row_ptr, w.out_ptr, w.out_edge,
-                             reinterpret_cast<unsigned short*>(w.grad), w.tau, w.tau2, w.G1, nn, 1.0f);
-          HIPCHK(eng, hipGetLastError());
-        } else {
-          hipLaunchKernelGGL(k_gather_rotate, dim3(nblk(ne, 4)), B256, 0, s, w.xn[i], w.esrc, w.edst, w.frame, w.xrot, ne);
-          hipLaunchKernelGGL(k_modulate_bwd, dim3(nblk(ne, 4)), B256, 0, s, w.gy1, w.xrot, w.rad[i], w.grad, w.tau, ne);
-          DBG("g_xrot" + t, w.gy1, ne * XROT); DBG("g_rad" + t, w.grad, ne * RAD);
-        }
-        return radial_bwd(eng, w, L.rad, i, ne, w.grad);
-      });
-    }
-    if (gp) {
-      // g_xn: every rank holds the contributions of its own edges only.  A rank WITHOUT edges (fewer atoms than ranks, or only isolated
-      // targets) has run no edge kernel: G1 still holds g_xn2 of the atom-wise backward and must not enter the sum
-      if (ne == 0) P.stream([=, &w]() -> int { HIPCHK(eng, hipMemsetAsync(w.G1, 0, (size_t)nn * ROW * sizeof(float), eng->stream)); return UMX_OK; });
-      else if (!fused_rev)                     // unfused reverse: the partial g_xn of this rank's edges has to exist BEFORE the exchange
-        P.stream([=, &w]() -> int {
-          hipLaunchKernelGGL(k_gather_rotate_bwd, dim3(nblk(nn, 4)), B256, 0, eng->stream, w.gy1, w.frame, w.row_ptr, w.out_ptr, w.out_edge, w.G1, nn);
-          HIPCHK(eng, hipGetLastError());
-          return UMX_OK;
-        });
-      P.sync(w.G1, (size_t)nn * ROW);
-    }
-    P.stream([=, &w]() -> int {
-      hipStream_t s = eng->stream;
-      const std::string t = "." + std::to_string(i);
-      if (!(ne > 0 && fused_rev) && !gp)
-        hipLaunchKernelGGL(k_gather_rotate_bwd, dim3(nblk(nn, 4)), B256, 0, s, w.gy1, w.frame, w.row_ptr, w.out_ptr, w.out_edge, w.G1, nn);   // G1 = g_xn
-      hipLaunchKernelGGL(k_norm_bwd, dim3(nblk(nn, 4)), B256, 0, s, w.G1, xin, Lp->n1w, w.G2, w.G0, nn);                      // G0 = g_xin
-      HIPCHK(eng, hipGetLastError());
-      DBG("g_xn" + t, w.G1, nn * ROW); DBG("g_xin" + t, w.G0, nn * ROW);
-      return UMX_OK;
-    });
+    if (c.rc && ne > 0 && (gp || i != NL - 1)) plan_edge_fwd(P, w, c, i, true);
+    plan_atomwise_bwd(P, w, c, i);
+    plan_edge_bwd(P, w, c, i);
+    plan_norm1_bwd(P, w, c, i);
   }
-  P.stream([=, &w]() -> int {
-    hipStream_t s = eng->stream;
-    if (ne > 0) {
-      if (rc) {      // recompute plan: the edge-degree link's radial MLP again (h1pre / h2pre / rad_deg of the slot), not its node sum
-        CHK(radial_fwd_head(eng, w, eng->rdeg, NL, ne));
-        CHK(radial_fwd_fc3(eng, w, eng->rdeg, ne, w.rad_deg));
-      }
-      // split path: the gradient of the edge-degree radial output goes straight into the PL planes of the fc3^T GEMM (gmsgpl is free here)
-      const bool dpl = eng->prec.planes && eng->planes.count(eng->rdeg.w3T) != 0;
-      if (dpl && eng->prec.rev_planes == 3) hipLaunchKernelGGL((k_rotate_back_bwd<3, 3>), dim3(nblk(ne, 4)), B256, 0, s, w.G0, w.rad_deg, w.frame, w.edst,
-                                                          reinterpret_cast<float*>(w.gmsgpl), w.dedd, w.tau, ne, DEG_RESCALE, eng->odd_sign);
-      else if (dpl) hipLaunchKernelGGL((k_rotate_back_bwd<3, 2>), dim3(nblk(ne, 4)), B256, 0, s, w.G0, w.rad_deg, w.frame, w.edst,
-                                       reinterpret_cast<float*>(w.gmsgpl), w.dedd, w.tau, ne, DEG_RESCALE, eng->odd_sign);
-      if (dpl) DBG("gradpl.deg", w.gmsgpl, ne * 3 * C * eng->prec.rev_planes);      // (debug) the PL planes of the edge-degree fc3^T operand
-      else hipLaunchKernelGGL(k_rotate_back_bwd<3>, dim3(nblk(ne, 4)), B256, 0, s, w.G0, w.rad_deg, w.frame, w.edst, w.gmsg, w.dedd, w.tau, ne,
-                              DEG_RESCALE);
-      CHK(radial_bwd(eng, w, eng->rdeg, NL, ne, w.gmsg, dpl ? w.gmsgpl : nullptr));
-      if (fused_rev) hipLaunchKernelGGL(k_add4, dim3(nblk(ne, 256)), B256, 0, s, w.tau, w.tau2, ne);
-      hipLaunchKernelGGL(k_force_edge, dim3(nblk(ne, 256)), B256, 0, s, w.dedd, w.dedd_rad, w.tau, w.frame, w.evec, w.gvec, ne);
-    }
-    hipLaunchKernelGGL(k_force_node, dim3(nblk(nn, 4)), B256, 0, s, w.gvec, w.row_ptr, w.out_ptr, w.out_edge, (float)eng->rmsd, d_forces, nn);
-    HIPCHK(eng, hipGetLastError());
-    if (vir.out) CHK(virial_launch(eng, w, vir, nimg, ne));       // (a partition: before the next one overwrites the shared gvec)
-    DBG("dedd", w.dedd, ne); DBG("tau", w.tau, ne * 4); DBG("gvec", w.gvec, ne * 4);
-    return UMX_OK;
-  });
+  P.stream([c, &w]() -> int { return force_assembly(c, w); });
   if (gp) P.sync(d_forces, (size_t)nn * 3);           // forces: sum of the ranks' edge contributions
 }
+#undef UMX_STAGE
+#undef UMX_LAUNCH
 
-// Issue one plan on the stream eng->stream points at.
+// Issue one plan without exchange points on the stream eng->stream points at.
 int run_plan(umx_engine* eng, Plan& P) {
-  for (auto& sg : P.segs) CHK(sg.fn());
-  return UMX_OK;
+  size_t at = 0;
+  const Seg* stop = nullptr;
+  CHK(P.run_to_sync(at, &stop));
+  return stop ? fail(eng, UMX_ERR_ARG, "run_plan: a plan with exchange points is issued step by step (umx_gp_step, eval_partitioned)") : UMX_OK;
 }
 
 // Issue two plans on two streams, alternating between the lanes after every matrix segment and passing the matrix token:
@@ -678,13 +750,10 @@ int eval_partitioned(umx_engine* eng, hipStream_t s, long img, const PosPtr d_po
     PartPtrs pp; pp.n = P;
     size_t count = 0; int waiting = 0;
     for (int p = 0; p < P && st == UMX_OK; ++p) {
-      pp.p[p] = nullptr;
-      while (at[p] < plans[p].segs.size()) {
-        Seg& sg = plans[p].segs[at[p]++];
-        if (sg.sync_buf) { pp.p[p] = sg.sync_buf; count = sg.sync_count; ++waiting; break; }
-        st = sg.fn();
-        if (st != UMX_OK) break;
-      }
+      const Seg* stop = nullptr;
+      st = plans[p].run_to_sync(at[p], &stop);
+      pp.p[p] = stop ? stop->sync_buf : nullptr;
+      if (stop) { count = stop->sync_count; ++waiting; }
     }
     if (st != UMX_OK || waiting == 0) break;
     if (waiting != P) { st = fail(eng, UMX_ERR_ARG, "eval_partitioned: the partitions' plans disagree on their exchange points"); break; }
@@ -769,8 +838,8 @@ size_t amortised_budget(umx_engine* eng, long K, const ImageEdges& ie, size_t bu
   const size_t want = ws_bytes(eng, per * N, per * (emax + emax / 20 + 64));
   const size_t cur = eng->cap_nodes > 0 ? ws_bytes(eng, eng->cap_nodes, eng->cap_edges) : 0;
   const size_t soft = std::min(budget, std::max(want, cur));
-  const size_t full = std::min(budget, ws_bytes(eng, K * N, ie.etot + ie.etot / 50 + 1024));
-  return (full > soft && (now - eng->t_first_eval) >= 8.0 * 0.045 * (double)(full >> 20) / 1024.0) ? full : soft;
+  const size_t full = std::min(budget, ws_bytes(eng, K * N, grown_edges(ie.etot)));
+  return (full > soft && (now - eng->t_first_eval) >= 8.0 * 0.045 * (double)(full >> 20) / (double)(1 << 10)) ? full : soft;
 }
 
 // ---- chunk planning --------------------------------------------------------------------------------
@@ -823,10 +892,10 @@ int prepare_arena(umx_engine* eng, hipStream_t s, const ImageEdges& ie, const Ch
   const bool hint_now = eng->hint_applied != eng->hint_images && (hint_nodes > eng->cap_nodes || hint_edges > eng->cap_edges);
   if (eng->hint_images > 0 && (hint_nodes || hint_edges || eng->cap_nodes >= (long)eng->hint_images * N)) eng->hint_applied = eng->hint_images;
   if (need_nodes > eng->cap_nodes || need_edges > eng->cap_edges || hint_now) {
-    long cn = std::max(std::max(need_nodes, hint_nodes), eng->cap_nodes), ce = std::max(std::max(need_edges + need_edges / 50 + 1024, hint_edges), eng->cap_edges);
+    long cn = std::max(std::max(need_nodes, hint_nodes), eng->cap_nodes), ce = std::max(std::max(grown_edges(need_edges), hint_edges), eng->cap_edges);
     size_t bytes = ws_bytes(eng, cn, ce);
     if (bytes > budget && (hint_nodes || hint_edges)) {      // hint and need combined overshoot: size for the need alone
-      cn = std::max(need_nodes, eng->cap_nodes); ce = std::max(need_edges + need_edges / 50 + 1024, eng->cap_edges);
+      cn = std::max(need_nodes, eng->cap_nodes); ce = std::max(grown_edges(need_edges), eng->cap_edges);
       bytes = ws_bytes(eng, cn, ce);
     }
     if (bytes > budget) { ce = std::max(need_edges, 1L); bytes = ws_bytes(eng, cn, ce); }
@@ -840,7 +909,7 @@ int prepare_arena(umx_engine* eng, hipStream_t s, const ImageEdges& ie, const Ch
   if (lanes == 2 && eng->arena_bytes < 2 * ws_bytes(eng, use_nodes, use_edges)) {
     // the arena was sized for ONE lane of larger chunks (an engine that has seen smaller batches, or one lane, before): two lanes of THIS
     // call's chunks may still fit it -- else one lane
-    const long ce = need_edges + need_edges / 50 + 1024;
+    const long ce = grown_edges(need_edges);
     if (2 * ws_bytes(eng, need_nodes, ce) <= eng->arena_bytes) { use_nodes = need_nodes; use_edges = ce; }
     else lanes = 1;
   }
