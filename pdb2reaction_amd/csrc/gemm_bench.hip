@@ -164,18 +164,17 @@ __global__ __launch_bounds__(512, 1) void gemm_qf_kernel(const GemmPL p) {
     for (int q = 0; q < PB; ++q) b_ad[t][q] = A_BYTES + q_row_off<PB>(row) + ((q * 2 + h) ^ q_swz<PB>(row >> 2)) * 16;
   }
   const int nk = p.K / 16;
-  constexpr int TAG = 77000 + S * 10 + WIDE;
   constexpr int GI = JA + JBF;
 #pragma unroll
   for (int t = 0; t < S - 1; ++t)
-    if (t < nk) q3_issue<JA, JBF, BHR, A_BYTES, TAG>(Ab, Bb, ring + t * STAGE, a_off, b_off, (long)t * 256, (long)t * BLKB, piece, b_tail);
+    if (t < nk) q3_issue<JA, JBF, BHR, A_BYTES, kernel_tag<7, S, WIDE>()>(Ab, Bb, ring + t * STAGE, a_off, b_off, (long)t * 256, (long)t * BLKB, piece, b_tail);
   int st_cur = 0, st_nxt = S - 1;
   for (int kt = 0; kt < nk; ++kt) {
     if (S == 2 || kt + S - 2 >= nk) wait_vmcnt<0>();
     else if (BHR != 0 && b_tail) wait_vmcnt<(S - 2) * (GI + 1)>();
     else wait_vmcnt<(S - 2) * GI>();
     __builtin_amdgcn_s_barrier();
-    if (kt + S - 1 < nk) q3_issue<JA, JBF, BHR, A_BYTES, TAG>(Ab, Bb, ring + st_nxt * STAGE, a_off, b_off, (long)(kt + S - 1) * 256, (long)(kt + S - 1) * BLKB, piece, b_tail);
+    if (kt + S - 1 < nk) q3_issue<JA, JBF, BHR, A_BYTES, kernel_tag<7, S, WIDE>()>(Ab, Bb, ring + st_nxt * STAGE, a_off, b_off, (long)(kt + S - 1) * 256, (long)(kt + S - 1) * BLKB, piece, b_tail);
     const unsigned char* sb = ring + st_cur * STAGE;
     st_cur = st_cur + 1 == S ? 0 : st_cur + 1;
     st_nxt = st_nxt + 1 == S ? 0 : st_nxt + 1;
@@ -275,7 +274,7 @@ static int f16_mode(long M, int N, int K) {
       fflush(stdout);
     };
     CK(hipMemset(C, 0, M * (long)N * 4));
-    report("fp32 MFMA", timeit([&] { hipLaunchKernelGGL((umx_gemm_kernel<A_PLAIN, 0, E_BIAS>), gf, dim3(256), 0, 0, pf); }));
+    report("fp32 MFMA", timeit([&] { hipLaunchKernelGGL((umx_gemm_kernel<A_PLAIN, 0>), gf, dim3(256), 0, 0, pf); }));
     CK(hipMemset(C, 0, M * (long)N * 4));
     report("Q3 bf16 x3 planes, 6 products", timeit([&] { hipLaunchKernelGGL((umx_gemm_q_kernel<0, 1>), gw, dim3(512), 0, 0, g3); }));
     {
@@ -396,7 +395,7 @@ int main(int argc, char** argv) {
   CK(hipDeviceSynchronize());
   // the register-staged kernels take separate planes for B: give them fp32-derived planes via a second split (not timed for accuracy)
   GemmP p; std::memset(&p, 0, sizeof(p)); p.conj = 1.f;
-  p.A = A; p.lda = lda; p.B = B; p.ldb = K; p.Bpl = Bp; p.bplane = (long)N * K; p.Cp = C; p.ldc = N; p.M = (int)M; p.N = N; p.K = K;
+  p.A = A; p.lda = lda; p.B = B; p.ldb = K; p.Cp = C; p.ldc = N; p.M = (int)M; p.N = N; p.K = K;
   GemmPL q; std::memset(&q, 0, sizeof(q)); q.conj = 1.f;
   q.Apl = Ap; q.lda = 3L * K; q.Bpl = Bp; q.ldb = 3L * K; q.Cp = C2; q.ldc = N; q.M = (int)M; q.N = N; q.K = K;
   GemmPL q2 = q; q2.Apl = Ap2; q2.lda = 2L * K; q2.Bpl = Bp2; q2.ldb = 2L * K;
@@ -414,28 +413,28 @@ int main(int argc, char** argv) {
     printf("   check %-30s max|diff| %.3e (max|ref| %.3e)\n", name, md, mr);
     if (getenv("DBG")) { for (int r : {0, 1, 33, 130}) { printf("     row %d ref:", r); for (int c : {0, 1, 31, 32, 64, 100}) printf(" %9.4f", c1[(size_t)r * N + c]); printf("\n     row %d got:", r); for (int c : {0, 1, 31, 32, 64, 100}) printf(" %9.4f", c2[(size_t)r * N + c]); printf("\n"); } }
   };
-  rep("fp32 PLAIN", timeit([&] { hipLaunchKernelGGL((umx_gemm_kernel<A_PLAIN, 0, E_BIAS>), grid, block, 0, 0, p); }));
+  rep("fp32 PLAIN", timeit([&] { hipLaunchKernelGGL((umx_gemm_kernel<A_PLAIN, 0>), grid, block, 0, 0, p); }));
   auto launch_pl = [&](void (*k)(const GemmPL), dim3 g, const GemmPL& a, int nthr = 256) { hipLaunchKernelGGL(k, g, dim3(nthr), 0, 0, a); };
   auto gridpl = [&](int bn) { const long nm = (M + 255) / 256, nn = (N + bn - 1) / bn; return dim3((unsigned)(((nm + 7) / 8) * 8 * nn)); };
   CK(hipMemset(C2, 0, M * (long)N * 4));
-  rep("PL 8w 256x128 P=3 S=2", timeit([&] { launch_pl(&umx_gemm_pl_kernel<0, 3, 2, 4, 2, 2, 2>, gridpl(128), q, 512); }));
+  rep("PL 8w 256x128 P=3 S=2", timeit([&] { launch_pl(&umx_gemm_pl_kernel<32, 0, 3, 2, 4, 2, 2, 2>, gridpl(128), q, 512); }));
   check("PL 8w 256x128 P=3 S=2 vs fp32");
   CK(hipMemset(C2, 0, M * (long)N * 4));
-  rep("PL 8w 256x128 P=2 S=3", timeit([&] { launch_pl(&umx_gemm_pl_kernel<0, 2, 3, 4, 2, 2, 2>, gridpl(128), q2, 512); }));
+  rep("PL 8w 256x128 P=2 S=3", timeit([&] { launch_pl(&umx_gemm_pl_kernel<32, 0, 2, 3, 4, 2, 2, 2>, gridpl(128), q2, 512); }));
   check("PL 8w 256x128 P=2 S=3 vs fp32");
   CK(hipMemset(C2, 0, M * (long)N * 4));
-  rep("PL16 8w 256x128 P=3 S=2 (16x16x32)", timeit([&] { launch_pl(&umx_gemm_pl16_kernel<0, 3, 2, 4, 2, 2, 2>, gridpl(128), q, 512); }));
+  rep("PL16 8w 256x128 P=3 S=2 (16x16x32)", timeit([&] { launch_pl(&umx_gemm_pl_kernel<16, 0, 3, 2, 4, 2, 2, 2>, gridpl(128), q, 512); }));
   check("PL16 P=3 vs fp32");
   CK(hipMemset(C2, 0, M * (long)N * 4));
-  rep("PL16 8w 256x128 P=2 S=3 (16x16x32)", timeit([&] { launch_pl(&umx_gemm_pl16_kernel<0, 2, 3, 4, 2, 2, 2>, gridpl(128), q2, 512); }));
+  rep("PL16 8w 256x128 P=2 S=3 (16x16x32)", timeit([&] { launch_pl(&umx_gemm_pl_kernel<16, 0, 2, 3, 4, 2, 2, 2>, gridpl(128), q2, 512); }));
   check("PL16 P=2 vs fp32");
   {
     auto grid128 = [&](int bn) { const long nm = (M + 127) / 128, nn = (N + bn - 1) / bn; return dim3((unsigned)(((nm + 7) / 8) * 8 * nn)); };
     CK(hipMemset(C2, 0, M * (long)N * 4));
-    rep("PL16 4w 128x128 P=2 S=2 (2 blocks/CU)", timeit([&] { launch_pl(&umx_gemm_pl16_kernel<0, 2, 2, 2, 2, 2, 2>, grid128(128), q2, 256); }));
+    rep("PL16 4w 128x128 P=2 S=2 (2 blocks/CU)", timeit([&] { launch_pl(&umx_gemm_pl_kernel<16, 0, 2, 2, 2, 2, 2, 2>, grid128(128), q2, 256); }));
     check("PL16 4w 128x128 P=2 vs fp32");
     CK(hipMemset(C2, 0, M * (long)N * 4));
-    rep("PL32 4w 128x128 P=2 S=2 (2 blocks/CU)", timeit([&] { launch_pl(&umx_gemm_pl_kernel<0, 2, 2, 2, 2, 2, 2>, grid128(128), q2, 256); }));
+    rep("PL32 4w 128x128 P=2 S=2 (2 blocks/CU)", timeit([&] { launch_pl(&umx_gemm_pl_kernel<32, 0, 2, 2, 2, 2, 2, 2>, grid128(128), q2, 256); }));
     check("PL32 4w 128x128 P=2 vs fp32");
   }
   if (N % 256 == 0) {      // Q2: two-plane quad-row layout (experiment)
@@ -478,20 +477,16 @@ int main(int argc, char** argv) {
   }
   if (N % 256 == 0) {
     CK(hipMemset(C2, 0, M * (long)N * 4));
-    rep("PL32 8w 256x256 P=2 S=2 (wave 128x64)", timeit([&] { launch_pl(&umx_gemm_pl_kernel<0, 2, 2, 2, 4, 4, 2>, gridpl(256), q2, 512); }));
+    rep("PL32 8w 256x256 P=2 S=2 (wave 128x64)", timeit([&] { launch_pl(&umx_gemm_pl_kernel<32, 0, 2, 2, 2, 4, 4, 2>, gridpl(256), q2, 512); }));
     check("PL32 256x256 P=2 vs fp32");
     CK(hipMemset(C2, 0, M * (long)N * 4));
-    rep("PL16 8w 256x256 P=2 S=2 (wave 128x64)", timeit([&] { launch_pl(&umx_gemm_pl16_kernel<0, 2, 2, 2, 4, 4, 2>, gridpl(256), q2, 512); }));
+    rep("PL16 8w 256x256 P=2 S=2 (wave 128x64)", timeit([&] { launch_pl(&umx_gemm_pl_kernel<16, 0, 2, 2, 2, 4, 4, 2>, gridpl(256), q2, 512); }));
     check("PL16 256x256 P=2 vs fp32");
     CK(hipMemset(C2, 0, M * (long)N * 4));
-    rep("PL16 8w 256x256 P=2 S=2 (wave 64x128)", timeit([&] { launch_pl(&umx_gemm_pl16_kernel<0, 2, 2, 4, 2, 2, 4>, gridpl(256), q2, 512); }));
+    rep("PL16 8w 256x256 P=2 S=2 (wave 64x128)", timeit([&] { launch_pl(&umx_gemm_pl_kernel<16, 0, 2, 2, 4, 2, 2, 4>, gridpl(256), q2, 512); }));
     check("PL16 256x256 b P=2 vs fp32");
   }
-  if (getenv("ABLATE")) {
-#define ABL3(flag) rep("  P=3 S=2 8w ABL=" #flag, timeit([&] { launch_pl(&umx_gemm_pl_kernel<0, 3, 2, 4, 2, 2, 2, flag>, gridpl(128), q, 512); }))
-#define ABL2(flag) rep("  P=2 S=3 8w ABL=" #flag, timeit([&] { launch_pl(&umx_gemm_pl_kernel<0, 2, 3, 4, 2, 2, 2, flag>, gridpl(128), q2, 512); }))
-    ABL3(1); ABL3(4); ABL3(8); ABL3(5); ABL3(9); ABL3(12); ABL3(13); ABL3(2); ABL3(6);
-    ABL2(1); ABL2(4); ABL2(8); ABL2(5); ABL2(9); ABL2(12); ABL2(13); ABL2(2); ABL2(6);
-  }
+  // (the round-2 timing ablations of the PL kernel -- no DMA / no MFMA / no stores / no fragment reads -- are in NOTES.md section 5,
+  //  "PL GEMM design" item 6)
   return 0;
 }

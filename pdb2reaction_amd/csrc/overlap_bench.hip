@@ -73,7 +73,7 @@ static int pmc_mode(int reps, bool x3 = false) {
       hipLaunchKernelGGL((umx_gemm_q_kernel<0, 1, 3, 2, 0, 6, 3, 1>), grid(0, 1, 768), dim3(512), 0, 0, mk(3, 1408, 0, 0, 0, 2304, 0, 0, 768, 640));
       hipLaunchKernelGGL((umx_gemm_q_kernel<1, 1, 3, 2, 0, 6, 3, 1>), grid(1, 1, 512), dim3(512), 0, 0, mk(3, 1408, 640, 896, 512, 2304, 768, 1280, 512, 256));
       hipLaunchKernelGGL((umx_gemm_q_kernel<1, 1, 3, 2, 0, 6, 3, 1>), grid(1, 1, 256), dim3(512), 0, 0, mk(3, 1408, 1152, 1280, 256, 2304, 1792, 2048, 256, 128));
-      { GemmPL qg = mk(3, 1536, 0, 0, 0, 128, 0, 0, 128, 1536); qg.lda = 2L * 1536; hipLaunchKernelGGL((umx_gemm_pl16_kernel<0, 3, 2, 4, 2, 2, 2, 0, 1>), grid(0, 0, 128), dim3(512), 0, 0, qg); }   // g_rad as float32 rows
+      { GemmPL qg = mk(3, 1536, 0, 0, 0, 128, 0, 0, 128, 1536); qg.lda = 2L * 1536; hipLaunchKernelGGL((umx_gemm_pl_kernel<16, 0, 3, 2, 4, 2, 2, 2, 1>), grid(0, 0, 128), dim3(512), 0, 0, qg); }   // g_rad as float32 rows
     }
     CK(hipDeviceSynchronize());
     printf("pmc3 mode: %d x 14 GEMM launches done\n", reps);
@@ -89,13 +89,13 @@ static int pmc_mode(int reps, bool x3 = false) {
     hipLaunchKernelGGL((umx_gemm_q_kernel<1, 1, 2, 2, 1, 4, 3>), grid(1, 1, 128), dim3(512), 0, 0, mk(2, 1152, 896, 1024, 128, 1152, 896, 1024, 128, 128));
     hipLaunchKernelGGL((umx_gemm_q_kernel<0, 1, 2, 2, 1, 4, 3>), grid(0, 1, 1536), dim3(512), 0, 0, mk(2, 128, 0, 0, 0, 1536, 0, 0, 1536, 128));
     // reverse (PL, P=2): conv-2^T m0 / m1 / m2, conv-1^T m0 / m1 / m2, fc3^T
-    hipLaunchKernelGGL((umx_gemm_pl16_kernel<0, 2, 3, 4, 2, 2, 2>), grid(0, 0, 384), dim3(512), 0, 0, mk(2, 1152, 0, 0, 0, 1152, 0, 0, 384, 384));
-    hipLaunchKernelGGL((umx_gemm_pl16_kernel<1, 2, 2, 4, 2, 2, 4>), grid(1, 1, 256), dim3(512), 0, 0, mk(2, 1152, 384, 640, 256, 1152, 384, 640, 256, 256));
-    hipLaunchKernelGGL((umx_gemm_pl16_kernel<1, 2, 2, 4, 2, 2, 4>), grid(1, 1, 128), dim3(512), 0, 0, mk(2, 1152, 896, 1024, 128, 1152, 896, 1024, 128, 128));
-    hipLaunchKernelGGL((umx_gemm_pl16_kernel<0, 2, 2, 4, 2, 2, 4>), grid(0, 1, 768), dim3(512), 0, 0, mk(2, 1408, 0, 0, 0, 2304, 0, 0, 768, 640));
-    hipLaunchKernelGGL((umx_gemm_pl16_kernel<1, 2, 2, 4, 2, 2, 4>), grid(1, 1, 512), dim3(512), 0, 0, mk(2, 1408, 640, 896, 512, 2304, 768, 1280, 512, 256));
-    hipLaunchKernelGGL((umx_gemm_pl16_kernel<1, 2, 2, 4, 2, 2, 4>), grid(1, 1, 256), dim3(512), 0, 0, mk(2, 1408, 1152, 1280, 256, 2304, 1792, 2048, 256, 128));
-    hipLaunchKernelGGL((umx_gemm_pl_kernel<0, 2, 3, 4, 2, 2, 2>), grid(0, 0, 128), dim3(512), 0, 0, mk(2, 1536, 0, 0, 0, 128, 0, 0, 128, 1536));
+    hipLaunchKernelGGL((umx_gemm_pl_kernel<16, 0, 2, 3, 4, 2, 2, 2>), grid(0, 0, 384), dim3(512), 0, 0, mk(2, 1152, 0, 0, 0, 1152, 0, 0, 384, 384));
+    hipLaunchKernelGGL((umx_gemm_pl_kernel<16, 1, 2, 2, 4, 2, 2, 4>), grid(1, 1, 256), dim3(512), 0, 0, mk(2, 1152, 384, 640, 256, 1152, 384, 640, 256, 256));
+    hipLaunchKernelGGL((umx_gemm_pl_kernel<16, 1, 2, 2, 4, 2, 2, 4>), grid(1, 1, 128), dim3(512), 0, 0, mk(2, 1152, 896, 1024, 128, 1152, 896, 1024, 128, 128));
+    hipLaunchKernelGGL((umx_gemm_pl_kernel<16, 0, 2, 2, 4, 2, 2, 4>), grid(0, 1, 768), dim3(512), 0, 0, mk(2, 1408, 0, 0, 0, 2304, 0, 0, 768, 640));
+    hipLaunchKernelGGL((umx_gemm_pl_kernel<16, 1, 2, 2, 4, 2, 2, 4>), grid(1, 1, 512), dim3(512), 0, 0, mk(2, 1408, 640, 896, 512, 2304, 768, 1280, 512, 256));
+    hipLaunchKernelGGL((umx_gemm_pl_kernel<16, 1, 2, 2, 4, 2, 2, 4>), grid(1, 1, 256), dim3(512), 0, 0, mk(2, 1408, 1152, 1280, 256, 2304, 1792, 2048, 256, 128));
+    hipLaunchKernelGGL((umx_gemm_pl_kernel<32, 0, 2, 3, 4, 2, 2, 2>), grid(0, 0, 128), dim3(512), 0, 0, mk(2, 1536, 0, 0, 0, 128, 0, 0, 128, 1536));
   }
   CK(hipDeviceSynchronize());
   printf("pmc mode: %d x 14 GEMM launches done\n", reps);
@@ -140,11 +140,11 @@ static int verify_mode(long M, int iters) {
   ls.push_back({"fwd conv1 m0  q<0,0>", [&] { hipLaunchKernelGGL((umx_gemm_q_kernel<0, 0, 2, 2, 1, 4, 3>), grid(0, 0, 640), dim3(512), 0, sa, mk(2, 2304, 0, 0, 0, 1408, 0, 0, 640, 768)); }});
   ls.push_back({"fwd conv1 m1  q<1,1>", [&] { hipLaunchKernelGGL((umx_gemm_q_kernel<1, 1, 2, 2, 1, 4, 3>), grid(1, 1, 256), dim3(512), 0, sa, mk(2, 2304, 768, 1280, 256, 1408, 640, 896, 256, 512)); }});
   ls.push_back({"fwd fc3       q<0,1>", [&] { hipLaunchKernelGGL((umx_gemm_q_kernel<0, 1, 2, 2, 1, 4, 3>), grid(0, 1, 1536), dim3(512), 0, sa, mk(2, 128, 0, 0, 0, 1536, 0, 0, 1536, 128)); }});
-  ls.push_back({"rev conv2T m0 pl16<0,2,3,4,2,2,2>", [&] { hipLaunchKernelGGL((umx_gemm_pl16_kernel<0, 2, 3, 4, 2, 2, 2>), grid(0, 0, 384), dim3(512), 0, sa, mk(2, 1152, 0, 0, 0, 1152, 0, 0, 384, 384)); }});
-  ls.push_back({"rev conv2T m1 pl16<1,2,2,4,2,2,4>", [&] { hipLaunchKernelGGL((umx_gemm_pl16_kernel<1, 2, 2, 4, 2, 2, 4>), grid(1, 1, 256), dim3(512), 0, sa, mk(2, 1152, 384, 640, 256, 1152, 384, 640, 256, 256)); }});
-  ls.push_back({"rev conv1T m0 pl16<0,2,2,4,2,2,4>", [&] { hipLaunchKernelGGL((umx_gemm_pl16_kernel<0, 2, 2, 4, 2, 2, 4>), grid(0, 1, 768), dim3(512), 0, sa, mk(2, 1408, 0, 0, 0, 2304, 0, 0, 768, 640)); }});
-  ls.push_back({"rev conv1T m1 pl16<1,2,2,4,2,2,4>", [&] { hipLaunchKernelGGL((umx_gemm_pl16_kernel<1, 2, 2, 4, 2, 2, 4>), grid(1, 1, 512), dim3(512), 0, sa, mk(2, 1408, 640, 896, 512, 2304, 768, 1280, 512, 256)); }});
-  ls.push_back({"rev fc3T      pl<0,2,3,4,2,2,2>", [&] { hipLaunchKernelGGL((umx_gemm_pl_kernel<0, 2, 3, 4, 2, 2, 2>), grid(0, 0, 128), dim3(512), 0, sa, mk(2, 1536, 0, 0, 0, 128, 0, 0, 128, 1536)); }});
+  ls.push_back({"rev conv2T m0 pl16<0,2,3,4,2,2,2>", [&] { hipLaunchKernelGGL((umx_gemm_pl_kernel<16, 0, 2, 3, 4, 2, 2, 2>), grid(0, 0, 384), dim3(512), 0, sa, mk(2, 1152, 0, 0, 0, 1152, 0, 0, 384, 384)); }});
+  ls.push_back({"rev conv2T m1 pl16<1,2,2,4,2,2,4>", [&] { hipLaunchKernelGGL((umx_gemm_pl_kernel<16, 1, 2, 2, 4, 2, 2, 4>), grid(1, 1, 256), dim3(512), 0, sa, mk(2, 1152, 384, 640, 256, 1152, 384, 640, 256, 256)); }});
+  ls.push_back({"rev conv1T m0 pl16<0,2,2,4,2,2,4>", [&] { hipLaunchKernelGGL((umx_gemm_pl_kernel<16, 0, 2, 2, 4, 2, 2, 4>), grid(0, 1, 768), dim3(512), 0, sa, mk(2, 1408, 0, 0, 0, 2304, 0, 0, 768, 640)); }});
+  ls.push_back({"rev conv1T m1 pl16<1,2,2,4,2,2,4>", [&] { hipLaunchKernelGGL((umx_gemm_pl_kernel<16, 1, 2, 2, 4, 2, 2, 4>), grid(1, 1, 512), dim3(512), 0, sa, mk(2, 1408, 640, 896, 512, 2304, 768, 1280, 512, 256)); }});
+  ls.push_back({"rev fc3T      pl<0,2,3,4,2,2,2>", [&] { hipLaunchKernelGGL((umx_gemm_pl_kernel<32, 0, 2, 3, 4, 2, 2, 2>), grid(0, 0, 128), dim3(512), 0, sa, mk(2, 1536, 0, 0, 0, 128, 0, 0, 128, 1536)); }});
   for (auto& l : ls) {
     CK(hipMemset(C, 0, cbytes)); CK(hipDeviceSynchronize());
     l.f(); CK(hipDeviceSynchronize());

@@ -41,7 +41,7 @@ typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 // BO = type of the per-lane offsets: long, or unsigned int where the registers count (half-height tiles: B takes twice the rounds; the
 // weight planes are far below 4 GB and A is then the workgroup's own row tile, and a 32-bit lane offset beside a uniform base is an
 // addressing mode of the load itself)
-template <int JA, int JBF, int BHALF_ROUND, int A_BYTES, int TAG, int RND = 8192, class BO = long>
+template <int JA, int JBF, int BHALF_ROUND, int A_BYTES, long TAG, int RND = 8192, class BO = long>
 __device__ __forceinline__ void q3_issue(const unsigned char* A, const unsigned char* B, unsigned char* sbase, const BO (&a_off)[JA],
                                          const BO (&b_off)[JBF + BHALF_ROUND], long kofs_a, long kofs_b, int piece, bool b_tail) {
   BO ao[JA];
@@ -103,7 +103,7 @@ __host__ __device__ constexpr bool q_use_product(int PA, int PB, int NPROD, int 
 // is the same bits in either form; the DMA rounds are half as long (4 KB) and B takes twice as many.  What the second workgroup buys: it
 // runs its k loop while the first one waits for its prologue's DMA round trip or drains its stores (NOTES.md section 13).
 // AL = 1 (AF kernels, forward products): "aligned planes" -- the leading plane of A is quantised to the lane's pass group (qf_align_magic,
-// umx_gemm_pl.h); the weights' leading plane is quantised the same way when the planes are built (umx_api.hip).
+// umx_gemm.h); the weights' leading plane is quantised the same way when the planes are built (umx_api.hip).
 template <int CPLX, int WIDE, int P = 3, int S = 2, int F16 = 0, int NPROD = (P == 3 ? 6 : 3), int PB = P, int AF = 0, int LS = 0, int AL = 0, int MW = 4>
 __global__ __launch_bounds__(MW * 128, MW == 4 ? 1 : 2) void umx_gemm_q_kernel(const GemmPL p) {
   static_assert(!AL || AF, "AL: the float32-A kernels");
@@ -129,10 +129,8 @@ __global__ __launch_bounds__(MW * 128, MW == 4 ? 1 : 2) void umx_gemm_q_kernel(c
   const int wm = wave >> 1, wn = wave & 1;
   const int l31 = lane & 31, h = lane >> 5;
 
-  const int nN = (p.N + BNC - 1) / BNC, nM = (p.M + BMR - 1) / BMR;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int mt = (slot / nN) * 8 + xcd, nt = slot % nN;
-  if (mt >= nM) return;
+  int mt, nt;
+  if (!xcd_tile<BMR, BNC>(p.M, p.N, mt, nt)) return;
 
   const unsigned char* Ab = reinterpret_cast<const unsigned char*>(p.Apl);
   const unsigned char* Bb = reinterpret_cast<const unsigned char*>(p.Bpl);
@@ -147,7 +145,7 @@ __global__ __launch_bounds__(MW * 128, MW == 4 ? 1 : 2) void umx_gemm_q_kernel(c
   for (int j = 0; j < JA; ++j) {
     const int c = tid + NT * j, g = c / CPB, s = c % CPB;
     long grp; int offA;
-    if (CPLX) { grp = (long)mt * (BMR / 4) + (g % (BMR / 4)); offA = (g / (BMR / 4)) ? p.offA1 : p.offA0; }
+    if (CPLX) { grp = (long)mt * (BMR / 4) + cplx_idx<BMR / 4>(g); offA = cplx_half<BMR / 4>(g) ? p.offA1 : p.offA0; }
     else      { grp = (long)mt * (BM / 4) + g;                offA = p.offA0; }
     if (grp >= gA) grp = gA - 1;
     if (AF) a_off[j] = (BOff)((grp * a_blocks + offA / 16) * BLK - a_tile + (s >> 2) * 64 + (((s & 3) ^ (g & 3)) * 16));   // s = row in group * 4 + piece
@@ -157,7 +155,7 @@ __global__ __launch_bounds__(MW * 128, MW == 4 ? 1 : 2) void umx_gemm_q_kernel(c
   for (int j = 0; j < JBF + BHR; ++j) {
     const int c = tid + NT * j, g = (c / CPBB) % (BN / 4), s = c % CPBB; // (% keeps the unused lanes of a half round in range)
     long grp;
-    if (CPLX) { int cg = nt * (BNC / 4) + (g % (BNC / 4)); if (cg >= gN) cg = gN - 1; grp = (long)(g / (BNC / 4)) * (p.bHalf / 4) + cg; }
+    if (CPLX) { int cg = nt * (BNC / 4) + cplx_idx<BNC / 4>(g); if (cg >= gN) cg = gN - 1; grp = (long)cplx_half<BNC / 4>(g) * (p.bHalf / 4) + cg; }
     else      { int cg = nt * (BN / 4) + g; if (cg >= gN) cg = gN - 1; grp = cg; }
     b_off[j] = (BOff)(grp * b_blocks * BLKB + (s ^ q_swz<PB>(g)) * 16);
   }
@@ -197,7 +195,7 @@ __global__ __launch_bounds__(MW * 128, MW == 4 ? 1 : 2) void umx_gemm_q_kernel(c
   int a_ad[2][P], b_ad[TNW][PB];       // byte address of this lane's 16-B fragment piece, per plane (chunk = plane * 2 + half, swizzled)
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
-    const int row = CPLX ? (t * BMR + wm * 32 + l31) : (wm * 64 + t * 32 + l31);
+    const int row = frag_row0<CPLX, 2, 32, BMR>(wm, t) + l31;
 #pragma unroll
     for (int q = 0; q < P; ++q)
       a_ad[t][q] = AF ? ((row >> 2) * 256 + (row & 3) * 64 + ((((h * 2 + (q & 1)) ^ ((row >> 2) & 3))) * 16))     // AF: entries 0 / 1 = the lane's two 16-B pieces
@@ -205,13 +203,13 @@ __global__ __launch_bounds__(MW * 128, MW == 4 ? 1 : 2) void umx_gemm_q_kernel(c
   }
 #pragma unroll
   for (int t = 0; t < TNW; ++t) {
-    const int row = CPLX ? ((t / (TNW / 2)) * BNC + wn * (16 * TNW) + (t % (TNW / 2)) * 32 + l31) : (wn * (32 * TNW) + t * 32 + l31);
+    const int row = frag_row0<CPLX, TNW, 32, BNC>(wn, t) + l31;
 #pragma unroll
     for (int q = 0; q < PB; ++q) b_ad[t][q] = A_BYTES + q_row_off<PB>(row) + ((q * 2 + h) ^ q_swz<PB>(row >> 2)) * 16;
   }
 
   const int nk = p.K / 16;
-  constexpr int TAG = 9000 + S * 100 + P * 10 + CPLX * 2 + WIDE + F16 * 1000 + NPROD * 10000 + PB * 100000 + AF * 10000000 + LS * 100000000 + AL * 500000000 + (MW == 2 ? 1000000000 : 0);   // one q3_issue instance per kernel
+  constexpr long TAG = kernel_tag<CPLX, WIDE, P, S, F16, NPROD, PB, AF, LS, AL, MW>();   // one q3_issue instance per kernel
   constexpr int GI = JA + JBF;                            // DMA instructions per tile per wave (+1 for the waves that fetch the half round)
 #pragma unroll
   for (int t = 0; t < S - 1; ++t)
@@ -230,22 +228,8 @@ __global__ __launch_bounds__(MW * 128, MW == 4 ? 1 : 2) void umx_gemm_q_kernel(c
     bf16x8_t a[2][P], b[TNW][PB];
     if constexpr (AF) {
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const f32x4q_t lo = *reinterpret_cast<const f32x4q_t*>(sb + a_ad[t][0]), hi = *reinterpret_cast<const f32x4q_t*>(sb + a_ad[t][1]);
-        unsigned int w[3][4];
-        if constexpr (AL) {           // the lane's 8 k-values ARE one pass group of this row
-          const float c = qf_align_magic(lo, hi);
-          qf_split2q(lo[0], lo[1], qf_round_q(lo[0], c), qf_round_q(lo[1], c), w[0][0], w[1][0], w[2][0]);
-          qf_split2q(lo[2], lo[3], qf_round_q(lo[2], c), qf_round_q(lo[3], c), w[0][1], w[1][1], w[2][1]);
-          qf_split2q(hi[0], hi[1], qf_round_q(hi[0], c), qf_round_q(hi[1], c), w[0][2], w[1][2], w[2][2]);
-          qf_split2q(hi[2], hi[3], qf_round_q(hi[2], c), qf_round_q(hi[3], c), w[0][3], w[1][3], w[2][3]);
-        } else {
-          qf_split2(lo[0], lo[1], w[0][0], w[1][0], w[2][0]); qf_split2(lo[2], lo[3], w[0][1], w[1][1], w[2][1]);
-          qf_split2(hi[0], hi[1], w[0][2], w[1][2], w[2][2]); qf_split2(hi[2], hi[3], w[0][3], w[1][3], w[2][3]);
-        }
-#pragma unroll
-        for (int q = 0; q < 3; ++q) { const u32x4q_t v{w[q][0], w[q][1], w[q][2], w[q][3]}; a[t][q] = __builtin_bit_cast(bf16x8_t, v); }
-      }
+      for (int t = 0; t < 2; ++t)
+        qf_split<AL>(*reinterpret_cast<const f32x4q_t*>(sb + a_ad[t][0]), *reinterpret_cast<const f32x4q_t*>(sb + a_ad[t][1]), a[t]);
     } else {
 #pragma unroll
       for (int q = 0; q < P; ++q)
@@ -279,12 +263,7 @@ __global__ __launch_bounds__(MW * 128, MW == 4 ? 1 : 2) void umx_gemm_q_kernel(c
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][0], acc[i][j], 0, 0, 0);
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][1], acc[i][j], 0, 0, 0);
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][0], acc[i][j], 0, 0, 0);
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {      // scalar adds (an opaque asm per element): a vector add would be selected as v_pk_add_f32 (NOTES 5 item 14)
-            float v = lo[r];
-            asm("" : "+v"(v));
-            acc[i][j][r] += v;
-          }
+          fold_low(acc[i][j], lo);
         }
     } else if constexpr (F16 && P == 2 && PB == 3 && NPROD == 4) {
       // The engine's fp16 form.  The three small products of a k-step -- A_hi . B_mid, A_lo . B_hi (2^-11 of the leading one) and
@@ -306,12 +285,7 @@ __global__ __launch_bounds__(MW * 128, MW == 4 ? 1 : 2) void umx_gemm_q_kernel(c
           lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a[i][0]), __builtin_bit_cast(f16x8_t, b[j][1]), lo, 0, 0, 0);
           lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a[i][1]), __builtin_bit_cast(f16x8_t, b[j][0]), lo, 0, 0, 0);
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a[i][0]), __builtin_bit_cast(f16x8_t, b[j][0]), acc[i][j], 0, 0, 0);
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {      // scalar adds (an opaque asm per element: no v_pk_add_f32, NOTES 5 item 14)
-            float v = lo[r];
-            asm("" : "+v"(v));
-            acc[i][j][r] += v;
-          }
+          fold_low(acc[i][j], lo);
         }
     } else
 #pragma unroll
@@ -336,16 +310,11 @@ __global__ __launch_bounds__(MW * 128, MW == 4 ? 1 : 2) void umx_gemm_q_kernel(c
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int j = 0; j < TNW; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {        // scalar adds (an opaque asm per element: no v_pk_add_f32, NOTES 5 item 14)
-          float v = low[i][j][r];
-          asm("" : "+v"(v));
-          acc[i][j][r] += v;
-        }
+      for (int j = 0; j < TNW; ++j) fold_low(acc[i][j], low[i][j]);
   }
 
-  // ---- epilogue (C/D map of 32x32 tiles: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)); block-uniform fast path
+  // ---- epilogue: cscale and the sign of the odd rows (row parity = r & 1); the bias is where the accumulators started.  The two store
+  //      forms: cd_row in umx_gemm.h
   const bool full = ((long)mt * BMR + BMR <= p.M) && (nt * BNC + BNC <= p.N);
   if (CPLX) {
 #pragma unroll
@@ -356,14 +325,14 @@ __global__ __launch_bounds__(MW * 128, MW == 4 ? 1 : 2) void umx_gemm_q_kernel(c
       if (full) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          float* cr = c + (long)((r & 3) + 8 * (r >> 2)) * p.ldc;
+          float* cr = c + (long)cd_row<16>(r) * p.ldc;
           cr[p.offC] = ((r & 1) ? cso : cs) * (acc[0][cg][r] - p.conj * acc[1][TNW / 2 + cg][r]);
           cr[p.offCi] = ((r & 1) ? cso : cs) * (acc[1][cg][r] + p.conj * acc[0][TNW / 2 + cg][r]);
         }
       } else if (chan < p.N) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int dr = (r & 3) + 8 * (r >> 2);
+          const int dr = cd_row<16>(r);
           if (e0 + dr < p.M) {
             float* cr = c + (long)dr * p.ldc;
             cr[p.offC] = ((r & 1) ? cso : cs) * (acc[0][cg][r] - p.conj * acc[1][TNW / 2 + cg][r]);
@@ -382,11 +351,11 @@ __global__ __launch_bounds__(MW * 128, MW == 4 ? 1 : 2) void umx_gemm_q_kernel(c
         float* c = p.Cp + row0 * p.ldc + p.offC + col;
         if (full) {
 #pragma unroll
-          for (int r = 0; r < 16; ++r) c[(long)((r & 3) + 8 * (r >> 2)) * p.ldc] = ((r & 1) ? cso : cs) * acc[i][j][r];
+          for (int r = 0; r < 16; ++r) c[(long)cd_row<16>(r) * p.ldc] = ((r & 1) ? cso : cs) * acc[i][j][r];
         } else if (col < p.N) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int dr = (r & 3) + 8 * (r >> 2);
+            const int dr = cd_row<16>(r);
             if (row0 + dr < p.M) c[(long)dr * p.ldc] = ((r & 1) ? cso : cs) * acc[i][j][r];
           }
         }

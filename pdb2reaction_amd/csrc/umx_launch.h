@@ -36,7 +36,7 @@ inline void launch_scan(hipStream_t s, const int* deg, long n, int* row_ptr, int
 // ---- fp32 GEMM launcher ------------------------------------------------------------------------
 GemmP gp_zero() { GemmP p; std::memset(&p, 0, sizeof(p)); p.conj = 1.0f; return p; }
 
-int launch_gemm(umx_engine* eng, const GemmP& p, int amode, int cplx, int epi, int gz = 1) {
+int launch_gemm(umx_engine* eng, const GemmP& p, int amode, int cplx, int gz = 1) {
   if (p.M <= 0) return UMX_OK;
   if (p.K % G_BK != 0) return fail(eng, UMX_ERR_ARG, "gemm: K not a multiple of 32");
   const int bmr = cplx ? 64 : 128, bnc = cplx ? 64 : 128;
@@ -45,20 +45,19 @@ int launch_gemm(umx_engine* eng, const GemmP& p, int amode, int cplx, int epi, i
   dim3 grid((unsigned)blocks, 1, (unsigned)gz), block(256);
   ProfRec* pr;
   CHK(prof_open(eng, &pr, cplx ? 8.0 * p.M * (double)p.N * p.K : 2.0 * p.M * (double)p.N * p.K * gz, 0, p.M, p.N, p.K, amode, cplx, gz));
-  if (eng->node_f64_on && eng->node_ctx && !cplx && epi == E_BIAS && (amode == A_PLAIN || amode == A_SILU)) {
+  if (eng->node_f64_on && eng->node_ctx && !cplx && (amode == A_PLAIN || amode == A_SILU)) {
     const dim3 g64((unsigned)(((p.M + 63) / 64) * ((p.N + 63) / 64)), 1, (unsigned)gz);
     if (amode == A_SILU) hipLaunchKernelGGL(k_gemm_f64acc<A_SILU>, g64, block, 0, eng->stream, p);
     else hipLaunchKernelGGL(k_gemm_f64acc<A_PLAIN>, g64, block, 0, eng->stream, p);
     HIPCHK(eng, hipGetLastError());
     return prof_close(eng, pr);
   }
-  const int key = amode * 100 + cplx * 10 + epi;
-  switch (key) {
-    case A_PLAIN * 100 + 0 + E_BIAS: hipLaunchKernelGGL((umx_gemm_kernel<A_PLAIN, 0, E_BIAS>), grid, block, 0, eng->stream, p); break;
-    case A_PLAIN * 100 + 10 + E_BIAS: hipLaunchKernelGGL((umx_gemm_kernel<A_PLAIN, 1, E_BIAS>), grid, block, 0, eng->stream, p); break;
-    case A_MODUL * 100 + 0 + E_BIAS: hipLaunchKernelGGL((umx_gemm_kernel<A_MODUL, 0, E_BIAS>), grid, block, 0, eng->stream, p); break;
-    case A_MODUL * 100 + 10 + E_BIAS: hipLaunchKernelGGL((umx_gemm_kernel<A_MODUL, 1, E_BIAS>), grid, block, 0, eng->stream, p); break;
-    case A_SILU * 100 + 0 + E_BIAS: hipLaunchKernelGGL((umx_gemm_kernel<A_SILU, 0, E_BIAS>), grid, block, 0, eng->stream, p); break;
+  switch (amode * 10 + cplx) {
+    case A_PLAIN * 10 + 0: hipLaunchKernelGGL((umx_gemm_kernel<A_PLAIN, 0>), grid, block, 0, eng->stream, p); break;
+    case A_PLAIN * 10 + 1: hipLaunchKernelGGL((umx_gemm_kernel<A_PLAIN, 1>), grid, block, 0, eng->stream, p); break;
+    case A_MODUL * 10 + 0: hipLaunchKernelGGL((umx_gemm_kernel<A_MODUL, 0>), grid, block, 0, eng->stream, p); break;
+    case A_MODUL * 10 + 1: hipLaunchKernelGGL((umx_gemm_kernel<A_MODUL, 1>), grid, block, 0, eng->stream, p); break;
+    case A_SILU * 10 + 0: hipLaunchKernelGGL((umx_gemm_kernel<A_SILU, 0>), grid, block, 0, eng->stream, p); break;
     default: return fail(eng, UMX_ERR_ARG, "gemm: variant not instantiated");
   }
   HIPCHK(eng, hipGetLastError());
@@ -74,7 +73,7 @@ int gemm_plain(umx_engine* eng, const float* A, long lda, int offA, const float*
   GemmP p = gp_zero();
   p.A = A; p.lda = lda; p.offA0 = offA; p.B = B; p.ldb = ldb; p.bias = bias; p.Cp = Cp; p.ldc = ldc; p.offC = offC;
   p.M = (int)M; p.N = N; p.K = K; p.zA = zA; p.zC = zC; p.resid = resid; p.ldres = ldres; p.offRes = offRes; p.zRes = zRes;
-  return launch_gemm(eng, p, amode, 0, E_BIAS, gz);
+  return launch_gemm(eng, p, amode, 0, gz);
 }
 
 // the same for a NODE-level linear (rows = atoms): float64 accumulation when the engine asks for it (umx_engine::node_f64_on)
@@ -97,7 +96,7 @@ int gemm_cplx(umx_engine* eng, const float* A, long lda, int offRe, int offIm, c
   GemmP p = gp_zero();
   p.A = A; p.lda = lda; p.offA0 = offRe; p.offA1 = offIm; p.R = R; p.ldr = ldr; p.offR = offR; p.B = B; p.ldb = ldb; p.bHalf = bHalf;
   p.Cp = Cp; p.ldc = ldc; p.offC = offCre; p.offCi = offCim; p.M = (int)M; p.N = N; p.K = K; p.conj = conj;
-  return launch_gemm(eng, p, R ? A_MODUL : A_PLAIN, 1, E_BIAS);
+  return launch_gemm(eng, p, R ? A_MODUL : A_PLAIN, 1);
 }
 
 // SO(3) linear on l-primary node rows: ONE launch, gridDim.z = 9 coefficients, the weights of degree l(z) picked per z (zBl);
@@ -107,7 +106,7 @@ int so3_linear(umx_engine* eng, const float* A, const float* Wl, const float* bi
   p.A = A; p.lda = ROW; p.offA0 = 0; p.B = Wl; p.ldb = C; p.bias = bias; p.Cp = Cp; p.ldc = ROW; p.offC = 0;
   p.M = (int)nn; p.N = C; p.K = C; p.zA = C; p.zC = C; p.resid = resid; p.ldres = ROW; p.offRes = 0; p.zRes = C; p.zBl = (long)C * C;
   NodeCtx node(eng);
-  return launch_gemm(eng, p, A_PLAIN, 0, E_BIAS, S);
+  return launch_gemm(eng, p, A_PLAIN, 0, S);
 }
 
 // ---- split-precision GEMM of the large SO(2) / radial linears ----------------------------------
@@ -115,48 +114,56 @@ int so3_linear(umx_engine* eng, const float* A, const float* Wl, const float* bi
 //   forward, bf16x3 / split-bf16 : A = float32 quad-row blocks split into three bf16 planes by the GEMM in registers, B = three bf16 planes (6 products)
 //   forward, split-f16           : A = two fp16 planes of 16 x activation, B = three exact fp16 planes (4 products)
 //   reverse, bf16x3              : conv^T: A = float32 quad-row blocks (g_msg / g_hg), B = three bf16 planes, 6 products (umx_gemm_q.h);
-//                                  fc3^T: A = float32 ROWS (g_rad, a_f32rows) split by umx_gemm_pl16_kernel<.., AF = 1>
+//                                  fc3^T: A = float32 ROWS (g_rad, a_f32rows) split by umx_gemm_pl_kernel<16, .., AF = 1>
 //   reverse, split-* modes       : A, B = two PL bf16 planes, 3 products (umx_gemm_pl.h)
 // Kernel families: Q_F16 quad-row, two fp16 planes x three fp16 weight planes; Q_BF16 quad-row, float32 A blocks x three bf16 weight
 // planes; PL3_ROWS three PL planes, A = float32 rows (bf16x3 layer fc3^T); PL3 three PL planes (bf16x3 edge-degree fc3^T); PL2_* two PL
 // planes: 256-wide tiles / narrow tiles on the 16x16x32 MFMA / narrow tiles on the 32x32x16 MFMA
 enum PlFamily { Q_F16, Q_BF16, PL3_ROWS, PL3, PL2_WIDE, PL2_M16, PL2_M32 };
 
-// every instantiated plane GEMM, exactly once.  Q_BF16 rows: ls = the low-order plane products accumulate apart, in the form that goes
-// with the tile width (template LS = 1: 256 x 256 tiles, one spare accumulator folded in every k-step; LS = 2: 256 x 128 tiles, a second
-// accumulator set for the whole k loop); al = aligned leading plane of A; half = the half-height form (template MW = 2: 128-row tiles,
-// 256 threads, two workgroups per CU) -- every Q_BF16 kernel has one, bit for bit its full-height form (UMX_HALF rows)
-struct PlKernel { PlFamily fam; bool cplx, wide, ls, al, half; void (*fn)(const GemmPL); };
-#define UMX_PAIR(fam, wide, ls, al, kernel, ...) {fam, false, wide, ls, al, false, kernel<0, __VA_ARGS__>}, {fam, true, wide, ls, al, false, kernel<1, __VA_ARGS__>}
-#define UMX_HALF(wide, ls, al, LS) {Q_BF16, false, wide, ls, al, true, umx_gemm_q_kernel<0, wide, 3, 2, 0, 6, 3, 1, LS, al, 2>}, \
-                                   {Q_BF16, true, wide, ls, al, true, umx_gemm_q_kernel<1, wide, 3, 2, 0, 6, 3, 1, LS, al, 2>}
-const PlKernel pl_kernels[] = {
-    UMX_PAIR(Q_F16, false, false, false, umx_gemm_q_kernel, 0, 2, 2, 1, 4, 3),
-    UMX_PAIR(Q_F16, true, false, false, umx_gemm_q_kernel, 1, 2, 2, 1, 4, 3),
-    UMX_PAIR(Q_BF16, false, false, false, umx_gemm_q_kernel, 0, 3, 2, 0, 6, 3, 1),
-    UMX_PAIR(Q_BF16, true, false, false, umx_gemm_q_kernel, 1, 3, 2, 0, 6, 3, 1),
-    UMX_PAIR(Q_BF16, false, false, true, umx_gemm_q_kernel, 0, 3, 2, 0, 6, 3, 1, 0, 1),
-    UMX_PAIR(Q_BF16, true, false, true, umx_gemm_q_kernel, 1, 3, 2, 0, 6, 3, 1, 0, 1),
-    UMX_PAIR(Q_BF16, false, true, false, umx_gemm_q_kernel, 0, 3, 2, 0, 6, 3, 1, 2),
-    UMX_PAIR(Q_BF16, true, true, false, umx_gemm_q_kernel, 1, 3, 2, 0, 6, 3, 1, 1),
-    UMX_PAIR(Q_BF16, false, true, true, umx_gemm_q_kernel, 0, 3, 2, 0, 6, 3, 1, 2, 1),
-    UMX_PAIR(Q_BF16, true, true, true, umx_gemm_q_kernel, 1, 3, 2, 0, 6, 3, 1, 1, 1),
-    UMX_HALF(0, 0, 0, 0), UMX_HALF(1, 0, 0, 0), UMX_HALF(0, 0, 1, 0), UMX_HALF(1, 0, 1, 0),
-    UMX_HALF(0, 1, 0, 2), UMX_HALF(1, 1, 0, 1), UMX_HALF(0, 1, 1, 2), UMX_HALF(1, 1, 1, 1),
-    {PL3_ROWS, false, false, false, false, false, umx_gemm_pl16_kernel<0, 3, 2, 4, 2, 2, 2, 0, 1>},     // (an 8 x 1 wave layout measured the same)
-    {PL3, false, false, false, false, false, umx_gemm_pl_kernel<0, 3, 2, 4, 2, 2, 2>},
-    UMX_PAIR(PL2_WIDE, true, false, false, umx_gemm_pl16_kernel, 2, 2, 4, 2, 2, 4),
-    UMX_PAIR(PL2_M16, false, false, false, umx_gemm_pl16_kernel, 2, 3, 4, 2, 2, 2),
-    UMX_PAIR(PL2_M32, false, false, false, umx_gemm_pl_kernel, 2, 3, 4, 2, 2, 2),
+// What selects an instantiation: the family, complex or plain, and for Q_BF16 -- ls = the low-order plane products accumulate apart, in
+// the form that goes with the tile width (template LS = 1: 256 x 256 tiles, one spare accumulator folded in every k-step; LS = 2:
+// 256 x 128 tiles, a second accumulator set for the whole k loop); al = aligned leading plane of A; half = the half-height form (template
+// MW = 2: 128-row tiles, 256 threads, two workgroups per CU), bit for bit its full-height form.
+struct PlKey {
+  PlFamily fam = Q_F16; bool cplx = false, wide = false, ls = false, al = false, half = false;
+  bool operator==(const PlKey& o) const { return fam == o.fam && cplx == o.cplx && wide == o.wide && ls == o.ls && al == o.al && half == o.half; }
 };
-#undef UMX_PAIR
-#undef UMX_HALF
+struct PlKernel { PlKey key; void (*fn)(const GemmPL); };
+
+// Every instantiated plane GEMM, exactly once: the 39 keys choose_pl can return over the precision modes, both passes, the engine's product
+// shapes (N x K of the radial fc3 / fc3^T and of the SO(2) blocks, So2Layout below), every documented value of UMX_LOW_SEP,
+// UMX_ALIGN_PLANES and UMX_GEMM_HALF and both sides of `fills` (enumerated with choose_pl itself on the host):
+//   Q_F16     plain and complex, narrow and wide                                  4
+//   Q_BF16    plain: every (wide, ls, al, half); complex: the same without the     28
+//             narrow LS forms -- a complex product has N in {128, 256, 512}, a
+//             multiple of 128, so a complex LS product is always wide
+//   PL3_ROWS, PL3  plain, narrow                                                   2
+//   PL2_WIDE  plain and complex; PL2_M16 plain (K >= 512) and complex;             5
+//             PL2_M32 plain only (a complex narrow product takes PL2_M16)
+#define UMX_Q(cplx, wide, ls, al, half) \
+  {{Q_BF16, cplx != 0, wide != 0, ls != 0, al != 0, half != 0}, umx_gemm_q_kernel<cplx, wide, 3, 2, 0, 6, 3, 1, (ls ? (wide ? 1 : 2) : 0), al, (half ? 2 : 4)>}
+#define UMX_Q4(cplx, wide, ls) UMX_Q(cplx, wide, ls, 0, 0), UMX_Q(cplx, wide, ls, 1, 0), UMX_Q(cplx, wide, ls, 0, 1), UMX_Q(cplx, wide, ls, 1, 1)
+const PlKernel pl_kernels[] = {
+    {{Q_F16, false, false}, umx_gemm_q_kernel<0, 0, 2, 2, 1, 4, 3>}, {{Q_F16, true, false}, umx_gemm_q_kernel<1, 0, 2, 2, 1, 4, 3>},
+    {{Q_F16, false, true}, umx_gemm_q_kernel<0, 1, 2, 2, 1, 4, 3>},  {{Q_F16, true, true}, umx_gemm_q_kernel<1, 1, 2, 2, 1, 4, 3>},
+    UMX_Q4(0, 0, 0), UMX_Q4(0, 0, 1), UMX_Q4(0, 1, 0), UMX_Q4(0, 1, 1),
+    UMX_Q4(1, 0, 0), UMX_Q4(1, 1, 0), UMX_Q4(1, 1, 1),
+    {{PL3_ROWS}, umx_gemm_pl_kernel<16, 0, 3, 2, 4, 2, 2, 2, 1>},     // (an 8 x 1 wave layout measured the same)
+    {{PL3}, umx_gemm_pl_kernel<32, 0, 3, 2, 4, 2, 2, 2>},
+    {{PL2_WIDE, false, true}, umx_gemm_pl_kernel<16, 0, 2, 2, 4, 2, 2, 4>}, {{PL2_WIDE, true, true}, umx_gemm_pl_kernel<16, 1, 2, 2, 4, 2, 2, 4>},
+    {{PL2_M16, false}, umx_gemm_pl_kernel<16, 0, 2, 3, 4, 2, 2, 2>},        {{PL2_M16, true}, umx_gemm_pl_kernel<16, 1, 2, 3, 4, 2, 2, 2>},
+    {{PL2_M32, false}, umx_gemm_pl_kernel<32, 0, 2, 3, 4, 2, 2, 2>},
+};
+#undef UMX_Q
+#undef UMX_Q4
 
 // which instantiation runs one product, with which grid and which leading dimensions (in 2-byte units)
 // (prec: ProfRec::prec -- 24: two fp16 planes, 4 products; 3 / 2: bf16 planes, 6 / 3 products; err: the product has no instantiation)
-struct PlChoice { PlFamily fam; bool wide = false, ls = false, al = false, half = false; unsigned blocks = 0; long lda = 0, ldb = 0; int prec = 0; const char* err = nullptr; };
+struct PlChoice { PlKey key; unsigned blocks = 0; long lda = 0, ldb = 0; int prec = 0; const char* err = nullptr; };
 PlChoice choose_pl(const Precision& pm, Pass pass, bool w_quad, int cplx, long M, int N, int K, int a_cols, bool a_f32rows, int low_sep, int align, int half) {
   PlChoice c;
+  c.key.cplx = cplx != 0;
   const bool fwd = pass == FWD;
   const int P = fwd ? 3 : pm.rev_planes;
   c.prec = (fwd && pm.fwd_fmt == 1) ? 24 : P;
@@ -172,14 +179,14 @@ PlChoice choose_pl(const Precision& pm, Pass pass, bool w_quad, int cplx, long M
   // the complex m > 0 products take rotated l >= 1 components whose signs follow the edge direction, and measured no different with it
   // (c5 energy error, three fixtures: none +1.0e-3 eV, fc3 only +5.9e-4, plain -7e-6, all -3e-5; c3 step 497 / 500 / 511 / 522 ms).
   // UMX_LOW_SEP (dev A/B): 0 none, 1 fc3 only, 2 every forward product, 3 the plain ones (default).
-  c.ls = fwd && pm.fwd_fmt == 3 && (low_sep == 2 || (low_sep == 3 && !cplx) || (low_sep == 1 && !cplx && K == RH));
+  c.key.ls = fwd && pm.fwd_fmt == 3 && (low_sep == 2 || (low_sep == 3 && !cplx) || (low_sep == 1 && !cplx && K == RH));
   // (an LS product picks its tile from N alone: the two LS forms fold the small products in at different points, and an image must get the
   //  same bits whether it is evaluated alone or in a batch -- tests/test_gpu_graph_parallel.py, test_gpu_parity.py batch independence)
-  c.wide = N % (cplx ? 128 : 256) == 0 && (fills || c.ls);
-  int bnc = c.wide ? (cplx ? 128 : 256) : (cplx ? 64 : 128);
+  c.key.wide = N % (cplx ? 128 : 256) == 0 && (fills || c.key.ls);
+  int bnc = c.key.wide ? (cplx ? 128 : 256) : (cplx ? 64 : 128);
   if (fwd && pm.fwd_fmt == 1) {
     // two fp16 planes of 16 x (activations), three exact planes of s_w x (weights): C = (A' . B'^T) / (16 s_w)
-    c.fam = Q_F16; c.lda = (long)a_cols * 2; c.ldb = (long)K * 3;
+    c.key.fam = Q_F16; c.lda = (long)a_cols * 2; c.ldb = (long)K * 3;
   } else if (fwd || (P == 3 && w_quad)) {
     // A = float32 quad-row blocks, split into the three bf16 planes in registers; weights as three bf16 planes.  The 256 x 128 LS form
     // keeps a second accumulator set for the whole k loop (190 VGPRs: one 8-wave workgroup per CU instead of two -- +10 ms at c3 for conv-1 /
@@ -188,20 +195,20 @@ PlChoice choose_pl(const Precision& pm, Pass pass, bool w_quad, int cplx, long M
     // tiles there too: 167-172 VGPRs as compiled (one workgroup per CU all the same); forced into the 128 VGPRs a second workgroup needs
     // it spills 19 registers: +40 ms, and 48 float32 folds per output instead of one move the 20 000-atom energies to -9e-5 eV on two of
     // four cases -- profiles/r06_ls_ab.txt; removed)
-    c.fam = Q_BF16; c.lda = (long)a_cols * 3; c.ldb = (long)K * 3;
-    c.al = fwd && (align == 1 || (align == 2 && !cplx));      // aligned planes: forward products only (the weights' planes were built to match, umx_load_weights)
+    c.key.fam = Q_BF16; c.lda = (long)a_cols * 3; c.ldb = (long)K * 3;
+    c.key.al = fwd && (align == 1 || (align == 2 && !cplx));      // aligned planes: forward products only (the weights' planes were built to match, umx_load_weights)
   } else if (P == 3) {
     // three-plane PL products of the bf16x3 reverse pass: the radial fc3^T of the layers (A = float32 rows, split in registers) and of the
     // edge-degree embedding (A = three PL planes written by k_rotate_back_bwd<3, 3>); both plain, N = 128, 256 x 128 tiles
     if (cplx || N > 128) { c.err = "gemm_pl: three-plane PL products are instantiated for the plain N <= 128 (radial fc3^T) products only"; return c; }
-    c.fam = a_f32rows ? PL3_ROWS : PL3;                       // (wide is false here: N is no multiple of 256)
+    c.key.fam = a_f32rows ? PL3_ROWS : PL3;                       // (wide is false here: N is no multiple of 256)
     if (a_f32rows) c.lda = (long)a_cols * 2;                  // row pitch in 2-byte units
-  } else if (c.wide) {
-    c.fam = PL2_WIDE;
+  } else if (c.key.wide) {
+    c.key.fam = PL2_WIDE;
   } else {
     // MFMA shape per GEMM (measured in the c3 pipeline): 16x16x32 wins 1-7 % on the complex SO(2) GEMMs and on K >= 512,
     // 32x32x16 wins 5-10 % on the short-K plain ones (radial fc3^T, conv-2^T m = 0)
-    c.fam = (cplx || K >= 512) ? PL2_M16 : PL2_M32;
+    c.key.fam = (cplx || K >= 512) ? PL2_M16 : PL2_M32;
   }
   // Half-height tiles (umx_gemm_q.h MW = 2; Q_BF16 only): two 4-wave workgroups per CU, each running while the other waits for its
   // prologue or drains its stores, at the price of fetching the B tile twice as often.  The bits are the same in either form, so this
@@ -214,9 +221,9 @@ PlChoice choose_pl(const Precision& pm, Pass pass, bool w_quad, int cplx, long M
   // was expected to pay (their 190 / 239 VGPRs cost them their co-resident partner in round 5), measured NO gain: c3 step -0.1 ms
   // (narrow) / -0.4 ms (+ fc3) against an A/A spread of 0.8 ms; every Q_BF16 product -6.4 ms, complex only -5.1 ms
   // (profiles/half_tile_ab.txt; NOTES.md section 13).
-  c.half = c.fam == Q_BF16 && (half == 3 || (half == 4 && cplx) || (half == 5 && !c.ls && K >= 256) ||
-                               (fwd && c.ls && (half == 2 || (half == 1 && !c.wide))));
-  const long nMf = c.half ? (M + bmr / 2 - 1) / (bmr / 2) : nM;     // row tiles of the form that runs
+  c.key.half = c.key.fam == Q_BF16 && (half == 3 || (half == 4 && cplx) || (half == 5 && !c.key.ls && K >= 256) ||
+                               (fwd && c.key.ls && (half == 2 || (half == 1 && !c.key.wide))));
+  const long nMf = c.key.half ? (M + bmr / 2 - 1) / (bmr / 2) : nM;     // row tiles of the form that runs
   c.blocks = (unsigned)(((nMf + 7) / 8) * 8 * ((N + bnc - 1) / bnc));
   return c;
 }
@@ -233,17 +240,17 @@ int gemm_pl(umx_engine* eng, int cplx, Pass pass, const unsigned short* Apl, int
   if (c.err) return fail(eng, UMX_ERR_ARG, c.err);
   const PlKernel* k = nullptr;
   for (const PlKernel& e : pl_kernels)
-    if (e.fam == c.fam && e.cplx == (cplx != 0) && e.wide == c.wide && e.ls == c.ls && e.al == c.al && e.half == c.half) { k = &e; break; }
+    if (e.key == c.key) { k = &e; break; }
   if (!k) return fail(eng, UMX_ERR_ARG, "gemm_pl: variant not instantiated");
   GemmPL q;
   std::memset(&q, 0, sizeof(q));
   q.Apl = Apl; q.lda = c.lda; q.offA0 = offA0; q.offA1 = offA1; q.Bpl = w.ptr; q.ldb = c.ldb; q.bHalf = bHalf;
   q.Cp = Cp; q.ldc = ldc; q.offC = offC; q.offCi = offCi; q.bias = bias; q.conj = conj; q.M = (int)M; q.N = N; q.K = K;
   q.odd_sign = eng->odd_sign;
-  if (c.fam == Q_F16) q.cscale = 1.0f / (QF16_SCALE * w.scale);
+  if (c.key.fam == Q_F16) q.cscale = 1.0f / (QF16_SCALE * w.scale);
   ProfRec* pr;
   CHK(prof_open(eng, &pr, cplx ? 8.0 * M * (double)N * K : 2.0 * M * (double)N * K, c.prec, M, N, K, 9, cplx));
-  hipLaunchKernelGGL(k->fn, dim3(c.blocks), dim3(k->half ? 256 : 512), 0, eng->stream, q);
+  hipLaunchKernelGGL(k->fn, dim3(c.blocks), dim3(c.key.half ? 256 : 512), 0, eng->stream, q);
   HIPCHK(eng, hipGetLastError());
   return prof_close(eng, pr);
 }
@@ -275,7 +282,7 @@ int so2_conv(umx_engine* eng, Pass pass, const void* A, const So2Layout& la, flo
   GemmP p = gp_zero();
   p.A = Af; p.lda = la.ld; p.R = R; p.ldr = R ? RAD : 0; p.B = Wm0; p.ldb = la.m0; p.bias = bias;
   p.Cp = Cp; p.ldc = lc.ld; p.M = (int)ne; p.N = lc.m0; p.K = la.m0;
-  CHK(launch_gemm(eng, p, R ? A_MODUL : A_PLAIN, 0, E_BIAS));
+  CHK(launch_gemm(eng, p, R ? A_MODUL : A_PLAIN, 0));
   CHK(gemm_cplx(eng, Af, la.ld, la.m1re, la.m1im, R, R ? RAD : 0, R ? SO2_RAD_M1 : 0, Wm1, la.m1w, lc.m1w, Cp, lc.ld, lc.m1re, lc.m1im, ne, lc.m1w, la.m1w, conj));
   return gemm_cplx(eng, Af, la.ld, la.m2re, la.m2im, R, R ? RAD : 0, R ? SO2_RAD_M2 : 0, Wm2, la.m2w, lc.m2w, Cp, lc.ld, lc.m2re, lc.m2im, ne, lc.m2w, la.m2w, conj);
 }

@@ -81,7 +81,7 @@ struct PlanePacker {
     const size_t off = open(dev, (size_t)rows * K * P, quad, 0.f, rows, K, P, fwdw, false);
     // aligned planes (forward bf16 weights): the value that goes into plane q < 2 is first rounded to a multiple of 2^(e_max - 12), e_max =
     // exponent of the largest magnitude of what is left of the 8 weights the matrix core sees in one pass (k = 8 g ... 8 g + 7 of one row);
-    // the exact remainder goes down the planes, so w0 + w1 + w2 is what it was (umx_gemm_pl.h qf_align_magic does the same to A's leading plane)
+    // the exact remainder goes down the planes, so w0 + w1 + w2 is what it was (umx_gemm.h qf_align_magic does the same to A's leading plane)
     const bool alignw = fwdw && align != 0;
     for (int rr = 0; rr < rows; ++rr)
       for (int k0 = 0; k0 < K; k0 += 8) {                 // (K is a multiple of 32 everywhere)

@@ -35,14 +35,15 @@ def _chain(n, images=1, seed=0):
     return z, pos.astype(np.float32)
 
 
-def _engines(precision):
+def _engines(precision, **switches):
     from pdb2reaction_amd.engine import Engine
 
     w = W.make_synthetic_weights(1)
-    old = os.environ.get("UMX_GEMM_HALF")
+    old = {k: os.environ.get(k) for k in ("UMX_GEMM_HALF", *switches)}
     made = []
     try:
-        for half in ("0", "3"):                  # the switch is read when the engine is created
+        os.environ.update(switches)
+        for half in ("0", "3"):                  # the switches are read when the engine is created
             os.environ["UMX_GEMM_HALF"] = half
             eng = Engine(0, precision=precision)
             made.append(eng)
@@ -53,10 +54,11 @@ def _engines(precision):
             eng.close()
         raise
     finally:
-        if old is None:
-            os.environ.pop("UMX_GEMM_HALF", None)
-        else:
-            os.environ["UMX_GEMM_HALF"] = old
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
     return made
 
 
@@ -96,6 +98,24 @@ def test_half_height_tiles_bit_for_bit(engines, n, edges):
     assert ne_off == edges and ne_on == edges, f"the chain of {n} atoms has {ne_off} / {ne_on} directed edges, not {edges}"
     assert off["rad.deg"].size == edges * 3 * W.SPHERE_CHANNELS and off["hg.0"].size % edges == 0
     _compare(off, on, f"M = {edges}")
+
+
+@pytest.fixture(scope="module")
+def engines_ls_al():
+    """The complex products with LS and aligned planes together (UMX_LOW_SEP=2, UMX_ALIGN_PLANES=1), full- and half-height."""
+    pair = _engines("bf16x3", UMX_LOW_SEP="2", UMX_ALIGN_PLANES="1")
+    yield pair
+    for eng in pair:
+        eng.close()
+
+
+@pytest.mark.parametrize("n,edges", [(66, 130), (130, 258)])
+def test_half_height_tiles_bit_for_bit_ls_aligned(engines_ls_al, n, edges):
+    z, pos = _chain(n)
+    off, ne_off = _evaluate(engines_ls_al[0], z, pos)
+    on, ne_on = _evaluate(engines_ls_al[1], z, pos)
+    assert ne_off == edges and ne_on == edges
+    _compare(off, on, f"LOW_SEP = 2, ALIGN_PLANES = 1, M = {edges}")
 
 
 def test_half_height_tiles_batch_independence(engines):

@@ -13,7 +13,16 @@ from pdb2reaction_amd.engine import Engine                  # noqa: E402
 from pdb2reaction_amd.parallel import LocalEnginePool       # noqa: E402
 
 MODES = ("bf16x3", "split-bf16", "split", "fp32")
-ENVS = ({}, {"UMX_STREAMS": "2", "UMX_LANES_ONE_STREAM": "1"}, {"UMX_FORCE_PARTS": "3"})
+# the last three reach the plane-GEMM instantiations the defaults leave out (umx_launch.h pl_kernels): LS and aligned planes on the complex
+# products, their half-height forms, and the forms without LS, alignment or half height
+ENVS = ({}, {"UMX_STREAMS": "2", "UMX_LANES_ONE_STREAM": "1"}, {"UMX_FORCE_PARTS": "3"},
+        {"UMX_LOW_SEP": "2", "UMX_ALIGN_PLANES": "1"}, {"UMX_LOW_SEP": "2", "UMX_ALIGN_PLANES": "1", "UMX_GEMM_HALF": "3"},
+        {"UMX_LOW_SEP": "0", "UMX_ALIGN_PLANES": "0", "UMX_GEMM_HALF": "0"})
+VALUED = ("UMX_LOW_SEP", "UMX_ALIGN_PLANES", "UMX_GEMM_HALF")        # switches whose value is part of a line's label
+
+
+def env_label(env):
+    return "+".join(f"{k}={env[k]}" if k in VALUED else k for k in sorted(env))
 STEMS = """row_ptr src dst out_ptr out_edge evec frame a2 a2q a2h rad x0 h1pre h2pre xn xrot hid hidq hidh y1q y1h hg msg xmid gridin gridout
 xn2 ffg1 ffg2 x gspre ffh ffhg e_node pre1 pre2 xf g_pre2 g_sil1 g_pre1 g_xf g_xfinal g_gridout g_gsil2 g_ffg2 g_gsil1 g_ffg1 g_gridin g_xn2
 g_xn2a g_ffhg g_ffh g_gs g_xmid gmsgq gmsgpl g_msg g_hid ghgq ghgpl g_hg g_y1 gradq gradpl g_xrot g_rad g_a2 dedd_rad g_xn g_xin dedd tau
@@ -43,13 +52,15 @@ def line(label, fn):
     print(f"{label}: {res}", flush=True)
 
 
-def engine_lines(label, eng, p, env):
-    """The plan kinds of one engine created under `env`, for the system it has bound."""
+def engine_lines(label, eng, p, env, big=False):
+    """The plan kinds of one engine created under `env`, for the system it has bound (big: the plain plan only, with its edge count)."""
     ef = lambda q=p: sha(*eng.energy_forces(q))              # noqa: E731
+    if big:
+        return line(f"{label} {env_label(env) or 'plain'}", lambda: ef() + f" {eng.graph_stats()[0]} edges")
     if env:
-        line(f"{label} {'+'.join(sorted(env))}", ef)
+        line(f"{label} {env_label(env)}", ef)
         eng.set_recompute(2)
-        line(f"{label} {'+'.join(sorted(env))} recompute2", ef)
+        line(f"{label} {env_label(env)} recompute2", ef)
         return eng.set_recompute(0)
     line(f"{label} plain", ef)
     line(f"{label} energy-only", lambda: sha(eng.energy_forces(p, forces=False)[0]))
@@ -76,6 +87,10 @@ def main():
     for name, n, mn in (("T17", 17, 3), ("T13", 13, 5)):     # the truncated systems of tests/test_gpu_edge_links.py, three jittered copies
         z, pos = synth.make_cluster(n)
         systems.append((name, z, np.stack([pos + 0.01 * k * np.sin(pos[:, ::-1]) for k in range(3)]).astype(np.float32), {"max_neigh": mn}))
+    # one image with more than 32 640 directed edges: the smallest count at which a wide grid of the complex N = 128 products fills the
+    # chip (choose_pl `fills`), so the wide complex forms without LS run
+    z560, p560 = synth.make_cluster(560)
+    systems.append(("S560", z560, p560[None].astype(np.float32), {}))
     for ff in ("spectral", "grid"):
         w = W.make_synthetic_weights(0, **({"ff_type": "grid"} if ff == "grid" else {}))
         for mode in MODES:
@@ -85,11 +100,11 @@ def main():
                 eng.load_weights(w)
                 for name, z, p, kw in systems:
                     eng.set_system(z, **kw)
-                    engine_lines(f"{mode} {ff} {name}", eng, p, env)
+                    engine_lines(f"{mode} {ff} {name}", eng, p, env, big=name == "S560")
                 eng.close()
                 [os.environ.pop(k) for k in env]
             with LocalEnginePool.create([0, 0], w, precision=mode) as pool:
-                for name, z, p, kw in systems:
+                for name, z, p, kw in systems[:-1]:
                     pool.set_system(z, **kw)
                     line(f"{mode} {ff} {name} pool-gp", lambda: sha(*pool.energy_forces(p[:1])) + f" {pool.last_route}")
                     line(f"{mode} {ff} {name} pool-gp+virial", lambda: sha(*pool.energy_forces_virial(p[:1], graph_parallel=True)) + f" {pool.last_route}")

@@ -52,7 +52,7 @@ out = {
     "workload": "c3: 2000 atoms x 16 images, 1 GPU, precision mode " + (sys.argv[5] if len(sys.argv) > 5 else "auto (= bf16x3)"),
     "csrc_sha256": source_digest(),
     "hbm_bytes_per_iteration": total / iters,
-    "dominant_family": {"kernel": "umx_gemm_q_kernel<*> + umx_gemm_pl16_kernel<*> + umx_gemm_pl_kernel<*>", "launches_per_iteration": fam_n / iters,
+    "dominant_family": {"kernel": "umx_gemm_q_kernel<*> + umx_gemm_pl_kernel<*>", "launches_per_iteration": fam_n / iters,
                         "hbm_bytes_per_launch_avg": fam_b / max(fam_n, 1), "hbm_bytes_per_iteration": fam_b / iters},
     "fp32_gemm_family_hbm_bytes_per_iteration": f32_b / iters,
     "radial_hbm_bytes_per_iteration": rad_b / iters,
