@@ -11,7 +11,7 @@
 #include "umx_engine.h"      // engine state, precision descriptor, WS / Plan types, error and buffer helpers
 #include "umx_launch.h"      // profiling bracket, GEMM launchers, the plane-GEMM dispatch table
 #include "umx_workspace.h"   // carving the workspace arena
-#include "umx_periodic.h"    // periodic boundary conditions: the translation table, the wrapped copy, the graph-kernel launchers
+#include "umx_periodic.h"    // host side of the graph stage: the bound cells, the wrapped copy, the dispatcher and the graph-kernel launchers
 #include "umx_virial.h"      // the strain derivative of every image: the two reduction kernels behind k_force_edge and their launcher
 #include "umx_plan.h"        // the launch plan of one chunk, its executors, and one evaluation as its phases
 #include "umx_weights.h"     // the weight loader
@@ -146,8 +146,8 @@ int pin_graph_impl(umx_engine* eng, const P* pos) {
   HIPCHK(eng, hipMemsetAsync(n_tix, 0, eb * sizeof(int), s));
   HIPCHK(eng, hipMemsetAsync(n_wrap, 0, (size_t)N * 3 * sizeof(int), s));
   hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, eng->d_deg_all, (long)N, t_row, t_row + N + 1);
-  launch_graph_fill_pin(eng, s, trunc, dp, (long)N, eng->d_cand_all, t_row, n_src, n_dst, t_evec, n_tix);
-  if (eng->pbc_on) launch_wrap_index_of(eng, s, d_stage, n_wrap);
+  launch_graph_fill(eng, s, trunc, dp, (long)N, eng->d_cand_all, t_row, n_src, n_dst, t_evec, 0, (long)N, 0, n_tix);
+  launch_wrap_index(eng, s, PosPtr(d_stage), n_wrap);
   HIPCHK(eng, hipGetLastError());
   std::vector<int> deg((size_t)N), code(eb);
   HIPCHK(eng, hipMemcpyAsync(deg.data(), eng->d_deg_all, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -244,7 +244,7 @@ int umx_destroy(umx_engine* eng) {
   (void)hipSetDevice(eng->dev);
   (void)hipStreamSynchronize(eng->stream);
   for (auto& r : eng->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-  void* ptrs[] = {eng->d_w, eng->d_dw, eng->d_bw, eng->d_gmu, eng->d_z, eng->d_sysemb, eng->arena, eng->d_deg_all, eng->d_cand_all, eng->d_img_edges, eng->d_io_pos, eng->d_io_e, eng->d_io_f, eng->d_flags, eng->d_dtab, eng->d_part_deg, eng->d_part_f, eng->d_ex, eng->d_mjobs, eng->d_pjobs, eng->d_mx, eng->d_shifts, eng->d_cells, eng->d_shifts_pk, eng->d_wrap, eng->d_wrap64, eng->d_lats, eng->d_io_pos64, eng->d_vir_part, eng->d_vir_wp, eng->d_io_w, eng->d_pin_src, eng->d_pin_dst, eng->d_pin_tix, eng->d_pin_wrap, eng->d_pin_deg, eng->d_pin_shifts};
+  void* ptrs[] = {eng->d_w, eng->d_dw, eng->d_bw, eng->d_gmu, eng->d_z, eng->d_sysemb, eng->arena, eng->d_deg_all, eng->d_cand_all, eng->d_img_edges, eng->d_io_pos, eng->d_io_e, eng->d_io_f, eng->d_flags, eng->d_dtab, eng->d_part_deg, eng->d_part_f, eng->d_ex, eng->d_mjobs, eng->d_pjobs, eng->d_mx, eng->d_cells, eng->d_shifts_pk, eng->d_wrap, eng->d_wrap64, eng->d_lats, eng->d_io_pos64, eng->d_vir_part, eng->d_vir_wp, eng->d_io_w, eng->d_pin_src, eng->d_pin_dst, eng->d_pin_tix, eng->d_pin_wrap, eng->d_pin_deg, eng->d_pin_shifts};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   (void)hipStreamSynchronize(eng->stream2);
   (void)hipEventDestroy(eng->ev_fork); (void)hipEventDestroy(eng->ev_join);
@@ -411,8 +411,8 @@ int umx_gp_begin_virial(umx_engine* eng, const float* d_pos, int node_lo, int no
                                   "keeps every rank's activations stored: set mode 0 or 1 on the engines that take part");
   if (eng->pin_on)
     return fail(eng, UMX_ERR_ARG, "umx_gp_begin: a graph is pinned (umx_pin_graph) and the graph-parallel entries build their own: call umx_unpin_graph first");
-  if (eng->pbc_on && eng->n_cells > 1)
-    return fail(eng, UMX_ERR_ARG, "umx_gp_begin: one image, but umx_set_cells bound cells for " + std::to_string(eng->n_cells) +
+  if (eng->pbc_on && !eng->cells_shared && eng->n_cells() > 1)
+    return fail(eng, UMX_ERR_ARG, "umx_gp_begin: one image, but umx_set_cells bound cells for " + std::to_string(eng->n_cells()) +
                                   " images: the graph-parallel mode takes per-image cells only when exactly one is bound");
   if (eng->gp_plan) gp_clear(eng);                       // an abandoned evaluation
   HIPCHK(eng, hipSetDevice(eng->dev));
@@ -557,13 +557,13 @@ int umx_last_graph_stats(const umx_engine* eng, int64_t* n_edges_total, int32_t*
 int umx_set_cell(umx_engine* eng, const double cell[9], const int pbc[3]) {
   if (!eng) return UMX_ERR_ARG;
   if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_set_cell: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
-  CHK(set_cell_impl(eng, cell, pbc));
+  CHK(set_cells_impl(eng, "umx_set_cell", true, 1, cell, pbc));
   return pin_after_cell(eng);
 }
 int umx_set_cells(umx_engine* eng, int n_images, const double* cells, const int pbc[3]) {
   if (!eng) return UMX_ERR_ARG;
   if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_set_cells: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
-  CHK(set_cells_impl(eng, n_images, cells, pbc));
+  CHK(set_cells_impl(eng, "umx_set_cells", false, n_images, cells, pbc));
   return pin_after_cell(eng);
 }
 int umx_last_graph_shifts(const umx_engine* eng) { return eng ? eng->last_shifts : 0; }

@@ -26,6 +26,7 @@
 #include "umx_gemm_q.h"
 #include "umx_kernels_pl.h"
 #include "umx_kernels.h"
+#include "umx_graph.h"
 #include "umx_radial.h"
 #include "umx_peer.h"
 
@@ -315,20 +316,18 @@ struct umx_engine {
   double* d_io_w = nullptr; long io_w_cap = 0;
   // stats / profiling / debug
   int64_t last_edges = 0; int32_t last_maxdeg = 0;
-  // periodic boundary conditions (umx_periodic.h): ONE cell for all images of a call (umx_set_cell), or one cell per image
-  // (umx_set_cells, n_cells > 0: then `cell` / `per` / `d_shifts` are not in use); either persists across umx_set_system
+  // periodic boundary conditions (umx_periodic.h): the bound cells -- ONE, shared by all images of a call (umx_set_cell), or one per
+  // image (umx_set_cells); they persist across umx_set_system
   bool pbc_on = false;
-  double cell[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; int pbc[3] = {0, 0, 0};
-  Lattice64 lat{};                 // the float64 lattice and dual vectors of `cell`: what the double-position kernels read next to `per`
-  Periodic per{};                  // what the periodic graph kernels read, built for the cutoff per_cutoff (rebuilt when umx_set_system changes it)
-  float per_cutoff = 0.f;
-  float4* d_shifts = nullptr;      // the translation table [PBC_MAX_SHIFTS]
-  int n_cells = 0;                 // umx_set_cells: the images the bound cells belong to (0: one shared cell, or open boundaries)
-  std::vector<double> cells;       // [n_cells][9], kept for a rebuild at another cutoff
-  std::vector<int> cell_shifts;    // [n_cells] table entries of every image
-  Periodic* d_cells = nullptr; long cells_cap = 0;          // [n_cells] what the per-image instantiations read; `shifts` points into d_shifts_pk
-  Lattice64* d_lats = nullptr;                              // [n_cells] their float64 lattices (double positions), grown with d_cells
-  float4* d_shifts_pk = nullptr; long shifts_pk_cap = 0;    // the images' tables, packed: sum of n_shifts entries
+  int pbc[3] = {0, 0, 0};
+  std::vector<double> cells;       // [n][9] the bound cells, kept for a rebuild at another cutoff and for the translations of a pinned graph
+  bool cells_shared = true;        // cells holds one cell and every image reads it; false: cell k belongs to image k of a call
+  std::vector<int> cell_shifts;    // [n] translation-table entries of every cell
+  float per_cutoff = 0.f;          // the cutoff the device copies below were built for (rebuilt when umx_set_system changes it)
+  Periodic* d_cells = nullptr; long cells_cap = 0;          // [n] what the periodic graph kernels read; `shifts` points into d_shifts_pk
+  Lattice64* d_lats = nullptr;                              // [n] their float64 lattices (double positions), grown with d_cells
+  float4* d_shifts_pk = nullptr; long shifts_pk_cap = 0;    // the cells' tables, packed: sum of n_shifts entries
+  long n_cells() const { return (long)(cells.size() / 9); }
   float* d_wrap = nullptr; long wrap_cap = 0;   // positions wrapped into the cell: the copy the graph kernels read
   double* d_wrap64 = nullptr; long wrap64_cap = 0;   // the same for double positions, wrapped in float64
   int last_shifts = 0;             // lattice translations the most recent evaluation searched (umx_last_graph_shifts; 0: open boundaries)

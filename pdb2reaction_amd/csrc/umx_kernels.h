@@ -1,5 +1,6 @@
-// umx_kernels.h -- HBM-bound stages of the UMA-S engine: radius graph, edge frames, gather/rotate,
-// rotate-back + segmented reduction, norms, gates, radial LayerNorm, readout and force assembly.
+// umx_kernels.h -- HBM-bound stages of the UMA-S engine: edge frames, gather/rotate, rotate-back +
+// segmented reduction, norms, gates, radial LayerNorm, readout and force assembly.  (The neighbour
+// graph, K1, is umx_graph.h.)
 //
 // Conventions: one 64-lane wave per edge or per node, 4 waves per 256-thread block; a lane owns 2
 // (or 4) adjacent channels so every row access is a coalesced 512-B (1-KiB) segment; edges are
@@ -15,587 +16,6 @@ namespace umx {
   const int lane = threadIdx.x & 63;                                                  \
   const long idx = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6))); \
   if (idx >= (count)) return;
-
-// one definition of the squared distance so every site rounds identically (the candidate ranking compares them)
-__device__ __forceinline__ float dist2_f(float dx, float dy, float dz) { return fmaf(dz, dz, fmaf(dy, dy, dx * dx)); }
-
-// ------------------------------------------------------------------------------------------------
-// Periodic boundary conditions (umx_set_cell): what the periodic instantiations of the two graph kernels read.  Built on the host in
-// float64 from the cell (umx_periodic.h), passed by value (one cell) or read from an array with one entry per image (umx_set_cells).  A candidate of target i is (source j, translation t) with
-// 0 < |r_j + t - r_i| <= cutoff; t runs over the table, entry k = ((na + Na) (2 Nb + 1) + (nb + Nb)) (2 Nc + 1) + (nc + Nc) for
-// t = na a + nb b + nc c, |n| <= N per periodic axis (N = 0 on an open axis).  The kernels read positions WRAPPED into the cell
-// (k_wrap_cell), so the fractional coordinates of two atoms differ by less than one along every periodic axis.
-// ------------------------------------------------------------------------------------------------
-constexpr int GF_MAXC = 1024;                     // candidates the truncating fill ranks in LDS (see k_graph_fill)
-constexpr int PBC_MAX_AXIS = 4;                   // the cap: lattice translations -4 .. +4 per periodic axis
-constexpr int PBC_MAX_SHIFTS = 729;               // (2 * PBC_MAX_AXIS + 1)^3 table entries
-struct Periodic {
-  float a[3][3];          // lattice vectors (rows); zero for an open axis
-  float b[3][3];          // dual vectors of the periodic sub-lattice: fractional coordinate k = r . b[k]; zero for an open axis
-  float gmax[3];          // pruning: a translated cell whose nearest face is more than gmax[k] (fractional, cutoff / plane distance + margin) away is skipped
-  int n_shifts, zero;     // table entries, index of the zero translation
-  const float4* shifts;   // (tx, ty, tz, bits of (na + 8) | (nb + 8) << 8 | (nc + 8) << 16)
-};
-// Per-image cells (umx_set_cells): one Periodic per image of the call in device memory, every entry's `shifts` pointing into one packed
-// table buffer.  img0: the index within the call of the first image the launch covers (a chunk, a lane, one partitioned image).
-struct PeriodicImages {
-  const Periodic* cells;
-  int img0;
-};
-// Double positions (umx_energy_forces_f64; P = double below): the lattice and the dual vectors once more, in float64, next to the
-// float32 Periodic.  The wrap and the translation of a candidate are formed from these; the table, the pruning and everything that is
-// decided on the rounded edge vector stay with the float32 struct.
-struct Lattice64 {
-  double a[3][3];         // lattice vectors (rows); zero for an open axis
-  double b[3][3];         // dual vectors, as Periodic::b
-};
-struct NoLattice {};      // P = float: the table entry IS the translation
-struct Periodic64 { Periodic per; Lattice64 lat; };
-struct PeriodicImages64 {
-  const Periodic* cells;
-  const Lattice64* lats;  // one per image, next to cells
-  int img0;
-};
-// what a graph kernel takes as its last argument: the one cell by value (IMG = false; also the unused argument of the open-boundary
-// instantiations), or the array of cells (IMG = true); P = double: the same with the float64 lattice
-template <bool IMG, typename P = float> struct PeriodicArgOf { using type = Periodic; };
-template <> struct PeriodicArgOf<true, float> { using type = PeriodicImages; };
-template <> struct PeriodicArgOf<false, double> { using type = Periodic64; };
-template <> struct PeriodicArgOf<true, double> { using type = PeriodicImages64; };
-template <bool IMG, typename P = float> using PeriodicArg = typename PeriodicArgOf<IMG, P>::type;
-
-// The cell of the wave's node.  IMG: the image index is wave-uniform, and taken through readfirstlane so that the struct (and, through
-// its `shifts`, the table entries) arrive through scalar loads, as the kernel argument does.
-__device__ __forceinline__ Periodic periodic_of_node(const Periodic& arg, long, int) { return arg; }
-__device__ __forceinline__ Periodic periodic_of_node(const PeriodicImages& arg, long node, int natoms) {
-  const int img = __builtin_amdgcn_readfirstlane(arg.img0 + (int)(node / natoms));
-  return arg.cells[img];
-}
-__device__ __forceinline__ Periodic periodic_of_node(const Periodic64& arg, long, int) { return arg.per; }
-__device__ __forceinline__ Periodic periodic_of_node(const PeriodicImages64& arg, long node, int natoms) {
-  const int img = __builtin_amdgcn_readfirstlane(arg.img0 + (int)(node / natoms));
-  return arg.cells[img];
-}
-// The float64 lattice of the wave's node (double positions), through the same wave-uniform image index; nothing for float positions.
-__device__ __forceinline__ NoLattice lattice_of_node(const Periodic&, long, int) { return NoLattice(); }
-__device__ __forceinline__ NoLattice lattice_of_node(const PeriodicImages&, long, int) { return NoLattice(); }
-__device__ __forceinline__ Lattice64 lattice_of_node(const Periodic64& arg, long, int) { return arg.lat; }
-__device__ __forceinline__ Lattice64 lattice_of_node(const PeriodicImages64& arg, long node, int natoms) {
-  const int img = __builtin_amdgcn_readfirstlane(arg.img0 + (int)(node / natoms));
-  return arg.lats[img];
-}
-
-// one definition of the edge vector of a candidate, used by count and fill alike (see dist2_f)
-__device__ __forceinline__ void pbc_delta(const float* __restrict__ pj, float xi, float yi, float zi, const float4 sh, const NoLattice&, float& dx, float& dy, float& dz) {
-  dx = (pj[0] - xi) + sh.x; dy = (pj[1] - yi) + sh.y; dz = (pj[2] - zi) + sh.z;
-}
-// double positions: the translation n_a a + n_b b + n_c c in float64 from the integer triple packed in sh.w and the float64 lattice,
-// r_j + t - r_i in float64, ONE rounding to float32 -- from there on the candidate is decided and stored as above
-__device__ __forceinline__ void pbc_delta(const double* __restrict__ pj, double xi, double yi, double zi, const float4 sh, const Lattice64& lat, float& dx, float& dy, float& dz) {
-  const unsigned code = __float_as_uint(sh.w);
-  const double na = (double)((int)(code & 255u) - 8), nb = (double)((int)((code >> 8) & 255u) - 8), nc = (double)((int)((code >> 16) & 255u) - 8);
-  dx = (float)((pj[0] + fma(nc, lat.a[2][0], fma(nb, lat.a[1][0], na * lat.a[0][0]))) - xi);
-  dy = (float)((pj[1] + fma(nc, lat.a[2][1], fma(nb, lat.a[1][1], na * lat.a[0][1]))) - yi);
-  dz = (float)((pj[2] + fma(nc, lat.a[2][2], fma(nb, lat.a[1][2], na * lat.a[0][2]))) - zi);
-}
-// open boundaries: the difference in the positions' own type, rounded to float32 (P = float: today's subtraction, nothing to round)
-template <typename P>
-__device__ __forceinline__ float open_delta(P a, P b) { return (float)(a - b); }
-
-// The translations that can reach the target at (x, y, z) within the cutoff, compacted in ascending index order into the wave's
-// LDS slice `act`; returns their number.  Wave-uniform decision per translation: the translated cell holds fractional coordinates
-// [n, n + 1) along axis k, the target sits at f, so every source of that image is at least gap = max(n - f, f - (n + 1), 0) plane
-// distances away.  The margin inside gmax covers the float32 rounding of the wrap and of f (1e-3 of a plane distance against 1e-6).
-__device__ __forceinline__ int pbc_active_shifts(const Periodic& per, float x, float y, float z, int lane, unsigned short* act) {
-  float f[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) f[k] = fmaf(z, per.b[k][2], fmaf(y, per.b[k][1], x * per.b[k][0]));
-  int na = 0;
-  for (int t0 = 0; t0 < per.n_shifts; t0 += 64) {
-    const int t = t0 + lane;
-    bool ok = t < per.n_shifts;
-    if (ok) {
-      const unsigned code = __float_as_uint(per.shifts[t].w);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const float n = (float)((int)((code >> (8 * k)) & 255u) - 8);
-        const float gap = fmaxf(fmaxf(n - f[k], f[k] - (n + 1.0f)), 0.0f);
-        ok = ok && gap <= per.gmax[k];
-      }
-    }
-    const unsigned long long m = __ballot(ok);
-    if (ok) act[na + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)t;
-    na += __popcll(m);
-  }
-  // the slice is private to this wave and its DS operations execute in order: only the compiler must not move the reads up
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  return na;
-}
-
-// wrap every atom into the cell along the periodic axes (a scratch copy only the graph kernels read: a per-atom lattice translation
-// changes no edge vector, hence no energy or force).  n = 0 leaves the coordinate bits as they are.
-// IMG (umx_set_cells): atom i is wrapped into the cell of its image i / natoms (a thread per atom: a wave may span two images, so
-// here the cell comes in through vector loads).
-// P = double: the same wrap in float64 with the float64 lattice and dual vectors, into a float64 copy.
-template <bool IMG, typename P = float>
-__global__ void k_wrap_cell(const P* __restrict__ pos, P* __restrict__ out, long nt, int natoms, const PeriodicArg<IMG, P> parg) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nt) return;
-  if constexpr (std::is_same_v<P, double>) {
-    const Lattice64* lp;
-    if constexpr (IMG) lp = parg.lats + (parg.img0 + (int)(i / natoms));
-    else lp = &parg.lat;
-    const Lattice64& lat = *lp;
-    const double x = pos[i * 3 + 0], y = pos[i * 3 + 1], z = pos[i * 3 + 2];
-    double n[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) n[k] = floor(fma(z, lat.b[k][2], fma(y, lat.b[k][1], x * lat.b[k][0])));
-    out[i * 3 + 0] = x - fma(n[2], lat.a[2][0], fma(n[1], lat.a[1][0], n[0] * lat.a[0][0]));
-    out[i * 3 + 1] = y - fma(n[2], lat.a[2][1], fma(n[1], lat.a[1][1], n[0] * lat.a[0][1]));
-    out[i * 3 + 2] = z - fma(n[2], lat.a[2][2], fma(n[1], lat.a[1][2], n[0] * lat.a[0][2]));
-  } else {                                                            // float positions: the body below is as it was
-  const Periodic* pp;
-  if constexpr (IMG) pp = parg.cells + (parg.img0 + (int)(i / natoms));
-  else pp = &parg;
-  const Periodic& per = *pp;
-  const float x = pos[i * 3 + 0], y = pos[i * 3 + 1], z = pos[i * 3 + 2];
-  float n[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) n[k] = floorf(fmaf(z, per.b[k][2], fmaf(y, per.b[k][1], x * per.b[k][0])));
-  out[i * 3 + 0] = x - fmaf(n[2], per.a[2][0], fmaf(n[1], per.a[1][0], n[0] * per.a[0][0]));
-  out[i * 3 + 1] = y - fmaf(n[2], per.a[2][1], fmaf(n[1], per.a[1][1], n[0] * per.a[0][1]));
-  out[i * 3 + 2] = z - fmaf(n[2], per.a[2][2], fmaf(n[1], per.a[1][2], n[0] * per.a[0][2]));
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// K1 radius graph: brute force inside each image, wave per target, ballot compaction (ascending
-// source order => CSR rows sorted by source).  pos: [NT][3] f32 -- or f64 (P = double, umx_energy_forces_f64): the edge vector is then
-// the float64 difference rounded once to float32, and everything decided on it (d^2, the cutoff test, the rank key) is the float32
-// arithmetic below, unchanged.
-// ------------------------------------------------------------------------------------------------
-// [lo, hi): the target nodes whose incoming edges this engine builds (all of them normally; one rank's share in the graph-parallel
-// single-image mode, where every other node gets an empty row).
-// flag: bit 1 of the engine's sticky status word -- a non-finite coordinate (every comparison with it is false, so the atom would just
-// lose its edges); the device-pointer entries read the word right behind this kernel and refuse the evaluation (ABI v7)
-// PBC = true (umx_set_cell): candidates are (source, translation) pairs; pos is the wrapped copy.  flag bit 2: a target of the periodic
-// form has more candidates than the truncating fill can rank (GF_MAXC) while max_neigh binds -- refused by the host.
-// IMG = true (umx_set_cells, PBC only): the cell is that of the node's image, read from the array behind parg.
-template <bool PBC, bool IMG = false, typename P = float>
-__global__ __launch_bounds__(256) void k_graph_count(const P* __restrict__ pos, int natoms, long nt, float rc2, int max_neigh,
-                                                     int* __restrict__ deg, int* __restrict__ cand, long lo, long hi, int* __restrict__ flag,
-                                                     const PeriodicArg<IMG, P> parg) {
-  static_assert(PBC || !IMG, "per-image cells are periodic");
-  UMX_WAVE_ITEM(node, nt)
-  const Periodic per = periodic_of_node(parg, node, natoms);
-  const P xi = pos[node * 3 + 0], yi = pos[node * 3 + 1], zi = pos[node * 3 + 2];
-  if (lane == 0 && !(isfinite(xi) && isfinite(yi) && isfinite(zi))) atomicOr(flag, 2);
-  if (node < lo || node >= hi) {                 // wave-uniform
-    if (lane == 0) { cand[node] = 0; deg[node] = 0; }
-    return;
-  }
-  const long base = (node / natoms) * natoms;
-  int cnt = 0;
-  if constexpr (PBC) {
-    __shared__ unsigned short act_s[4][PBC_MAX_SHIFTS];
-    unsigned short* act = act_s[threadIdx.x >> 6];
-    const auto lat = lattice_of_node(parg, node, natoms);
-    const int na = pbc_active_shifts(per, (float)xi, (float)yi, (float)zi, lane, act);   // (a conservative filter: on the rounded coordinate for P = double)
-    const int self = (int)(node - base);
-    for (int a = 0; a < na; ++a) {
-      const int t = __builtin_amdgcn_readfirstlane((int)act[a]);
-      const float4 sh = per.shifts[t];
-      for (int j0 = 0; j0 < natoms; j0 += 64) {
-        const int j = j0 + lane;
-        bool ok = false;
-        if (j < natoms) {
-          float dx, dy, dz;
-          pbc_delta(pos + (base + j) * 3, xi, yi, zi, sh, lat, dx, dy, dz);
-          const float d2 = dist2_f(dx, dy, dz);
-          ok = (d2 <= rc2) && (d2 > 0.0f) && !(j == self && t == per.zero);   // an atom's own image (t != 0) is an edge
-        }
-        cnt += __popcll(__ballot(ok));
-      }
-    }
-    if (lane == 0 && cnt > max_neigh && cnt > GF_MAXC) atomicOr(flag, 4);
-  } else {
-  for (int j0 = 0; j0 < natoms; j0 += 64) {
-    const int j = j0 + lane;
-    bool ok = false;
-    if (j < natoms) {
-      const float dx = open_delta(pos[(base + j) * 3 + 0], xi), dy = open_delta(pos[(base + j) * 3 + 1], yi), dz = open_delta(pos[(base + j) * 3 + 2], zi);
-      const float d2 = dist2_f(dx, dy, dz);
-      ok = (d2 <= rc2) && (d2 > 0.0f) && (base + j != node);        // 0 < d <= cutoff
-    }
-    cnt += __popcll(__ballot(ok));
-  }
-  }
-  if (lane == 0) { cand[node] = cnt; deg[node] = cnt < max_neigh ? cnt : max_neigh; }
-}
-
-// exclusive scan of deg[0..n) into row_ptr[0..n]; single block of 1024 threads; also max degree
-__global__ __launch_bounds__(1024) void k_scan(const int* __restrict__ deg, long n, int* __restrict__ row_ptr,
-                                               int* __restrict__ stats /*[0]=total,[1]=maxdeg*/) {
-  __shared__ int part[1024];
-  __shared__ int pmax[1024];
-  const int t = threadIdx.x;
-  const long chunk = (n + 1023) / 1024;
-  const long lo = t * chunk, hi = (lo + chunk < n) ? lo + chunk : n;
-  int s = 0, mx = 0;
-  for (long i = lo; i < hi; ++i) { s += deg[i]; mx = deg[i] > mx ? deg[i] : mx; }
-  part[t] = s; pmax[t] = mx;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    int v = (t >= off) ? part[t - off] : 0;
-    int m = (t >= off) ? pmax[t - off] : 0;
-    __syncthreads();
-    part[t] += v; pmax[t] = pmax[t] > m ? pmax[t] : m;
-    __syncthreads();
-  }
-  int run = (t == 0) ? 0 : part[t - 1];
-  for (long i = lo; i < hi; ++i) { row_ptr[i] = run; run += deg[i]; }
-  if (t == 1023) { row_ptr[n] = part[1023]; stats[0] = part[1023]; stats[1] = pmax[1023]; }
-}
-
-// Rows keep ascending source order.  A target with more than max_neigh candidates keeps its max_neigh nearest
-// (rank by (d^2, source index), the oracle's stable argsort).  Round 5: the cap is the checkpoint's to choose (uma_pysis.py:301-309), and
-// with a binding cap EVERY atom takes this path -- measured on c3 with max_neigh = 30: 16.5 ms per launch (7 % of the step) for the
-// first form, which re-scanned the whole image once per candidate chunk (O(N^2 / 64) shuffles per node).  Now the wave compacts the
-// target's candidates as 64-bit keys (d^2 bits << 32 | source: unique, ordered like the oracle's comparator) into its own LDS slice,
-// ranks each key against the others with broadcast reads (cand^2 / 64 compares per lane) and writes the kept ones in source order.
-// More than GF_MAXC candidates (> 1 atom / A^3 at a 6 A cutoff) keep the slow form.
-// TRUNC = false (the common case: the host knows the batch's largest candidate count, read with the edge counts, and it is below max_neigh):
-// no truncation code and NO LDS -- the static 32-KiB key array of the truncating form would cap the resident blocks of this HBM-bound
-// kernel on every launch for a path that is never taken.
-// PBC = true: rows in ascending (source, translation index) order.  The truncating form ranks the candidates of ALL images by the
-// key (d^2 bits << 32 | translation index * natoms + source) -- equal-distance images of one source cannot tie -- finds the key of
-// rank max_neigh - 1 and keeps every candidate up to it; then (both forms) every lane counts the kept candidates of its source over
-// the active translations, a prefix sum over the lanes gives its first slot, and it writes them in translation order.
-// IMG = true (umx_set_cells, PBC only): the cell of the node's image, as in k_graph_count -- both take the image index from the same
-// (img0, node / natoms), so the rows the count sized are the rows the fill writes.
-// P = double: as in k_graph_count -- both form a candidate's edge vector through the same pbc_delta / open_delta, so they decide alike.
-// TOUT = true (PBC only; the pinning call umx_pin_graph alone): etr[slot] receives the translation the edge took, as the bits of its
-// table entry's w ((na + 8) | (nb + 8) << 8 | (nc + 8) << 16).  Every other instantiation ignores etr and keeps its code.
-template <bool TRUNC, bool PBC, bool IMG = false, typename P = float, bool TOUT = false>
-__global__ __launch_bounds__(256) void k_graph_fill(const P* __restrict__ pos, int natoms, long nt, float rc2, int max_neigh,
-                                                    const int* __restrict__ cand, const int* __restrict__ row_ptr, int* __restrict__ esrc,
-                                                    int* __restrict__ edst, float* __restrict__ evec, long lo, long hi, const PeriodicArg<IMG, P> parg,
-                                                    int* __restrict__ etr = nullptr) {
-  static_assert(PBC || !IMG, "per-image cells are periodic");
-  static_assert(PBC || !TOUT, "open boundaries have no translation to report");
-  UMX_WAVE_ITEM(node, nt)
-  if (node < lo || node >= hi) return;           // wave-uniform: rows outside the owned target range are empty
-  const Periodic per = periodic_of_node(parg, node, natoms);
-  const long base = (node / natoms) * natoms;
-  const P xi = pos[node * 3 + 0], yi = pos[node * 3 + 1], zi = pos[node * 3 + 2];
-  const int nc = cand[node];
-  const bool truncate = TRUNC && nc > max_neigh;
-  int w = row_ptr[node];
-  if constexpr (PBC) {
-    __shared__ unsigned short act_s[4][PBC_MAX_SHIFTS];
-    unsigned short* act = act_s[threadIdx.x >> 6];
-    const auto lat = lattice_of_node(parg, node, natoms);
-    const int na = pbc_active_shifts(per, (float)xi, (float)yi, (float)zi, lane, act);
-    const int self = (int)(node - base);
-    const int wend = row_ptr[node + 1];
-    unsigned long long kth = ~0ull;                                    // the largest key kept
-    // one definition of a candidate and its key for the three passes below
-    auto candidate = [&](int j, int t, const float4 sh, float& dx, float& dy, float& dz, unsigned long long& key) -> bool {
-      pbc_delta(pos + (base + j) * 3, xi, yi, zi, sh, lat, dx, dy, dz);
-      const float d2 = dist2_f(dx, dy, dz);
-      key = ((unsigned long long)__float_as_uint(d2) << 32) | ((unsigned)t * (unsigned)natoms + (unsigned)j);
-      return (d2 <= rc2) && (d2 > 0.0f) && !(j == self && t == per.zero);
-    };
-    if constexpr (TRUNC) if (truncate) {                              // wave-uniform; nc <= GF_MAXC (else the degree pass refused)
-      __shared__ unsigned long long gf_keys[4][GF_MAXC];
-      unsigned long long* keys = gf_keys[threadIdx.x >> 6];
-      int c = 0;
-      for (int a = 0; a < na; ++a) {
-        const int t = __builtin_amdgcn_readfirstlane((int)act[a]);
-        const float4 sh = per.shifts[t];
-        for (int j0 = 0; j0 < natoms; j0 += 64) {
-          const int j = j0 + lane;
-          float dx, dy, dz;
-          unsigned long long key = 0ull;
-          const bool ok = j < natoms && candidate(j, t, sh, dx, dy, dz, key);
-          const unsigned long long m = __ballot(ok);
-          const int at = c + __popcll(m & ((1ull << lane) - 1ull));
-          if (ok && at < GF_MAXC) keys[at] = key;
-          c += __popcll(m);
-        }
-      }
-      c = c < GF_MAXC ? c : GF_MAXC;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      for (int c0 = 0; c0 < c; c0 += 64) {
-        const int ci = c0 + lane;
-        const bool have = ci < c;
-        const unsigned long long k = have ? keys[ci] : ~0ull;
-        int rank = 0;
-        for (int q = 0; q < c; ++q) rank += keys[q] < k ? 1 : 0;
-        const unsigned long long m = __ballot(have && rank == max_neigh - 1);     // keys are unique: at most one lane
-        if (m) {
-          const int from = __ffsll((long long)m) - 1;
-          const unsigned hi32 = __shfl((unsigned)(k >> 32), from, 64), lo32 = __shfl((unsigned)(k & 0xffffffffull), from, 64);
-          kth = ((unsigned long long)hi32 << 32) | lo32;
-        }
-      }
-    }
-    for (int j0 = 0; j0 < natoms; j0 += 64) {
-      const int j = j0 + lane;
-      int mine = 0;
-      if (j < natoms)
-#pragma clang loop vectorize(disable) interleave(disable)   // (two translations per lane would come out as packed-fp32 instructions: build.py refuses them)
-        for (int a = 0; a < na; ++a) {
-          const int t = act[a];
-          float dx, dy, dz;
-          unsigned long long key;
-          if (candidate(j, t, per.shifts[t], dx, dy, dz, key) && key <= kth) ++mine;
-        }
-      int incl = mine;                                                 // inclusive prefix sum over the lanes
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(incl, o, 64); if (lane >= o) incl += v; }
-      int slot = w + incl - mine;
-      if (mine)
-#pragma clang loop vectorize(disable) interleave(disable)
-        for (int a = 0; a < na; ++a) {
-          const int t = act[a];
-          float dx, dy, dz;
-          unsigned long long key;
-          if (candidate(j, t, per.shifts[t], dx, dy, dz, key) && key <= kth && slot < wend) {
-            const float d = sqrtf(__uint_as_float((unsigned)(key >> 32))), inv = 1.0f / d;
-            esrc[slot] = (int)(base + j);
-            edst[slot] = (int)node;
-            *reinterpret_cast<float4*>(evec + (long)slot * 4) = make_float4(dx * inv, dy * inv, dz * inv, d);
-            if constexpr (TOUT) etr[slot] = (int)__float_as_uint(per.shifts[t].w);
-            ++slot;
-          }
-        }
-      w += __shfl(incl, 63, 64);
-    }
-  } else {                                                            // open boundaries: the body below is as it was
-  if constexpr (TRUNC) if (truncate && nc <= GF_MAXC) {               // wave-uniform
-    __shared__ unsigned long long gf_keys[4][GF_MAXC];
-    unsigned long long* keys = gf_keys[threadIdx.x >> 6];
-    int c = 0;
-    for (int j0 = 0; j0 < natoms; j0 += 64) {
-      const int j = j0 + lane;
-      bool ok = false;
-      float d2 = 0.f;
-      if (j < natoms) {
-        const float dx = open_delta(pos[(base + j) * 3 + 0], xi), dy = open_delta(pos[(base + j) * 3 + 1], yi), dz = open_delta(pos[(base + j) * 3 + 2], zi);
-        d2 = dist2_f(dx, dy, dz);
-        ok = (d2 <= rc2) && (d2 > 0.0f) && (base + j != node);
-      }
-      const unsigned long long m = __ballot(ok);
-      if (ok) keys[c + __popcll(m & ((1ull << lane) - 1ull))] = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)j;
-      c += __popcll(m);
-    }
-    // the slice is private to this wave and its DS operations execute in order: only the compiler must not move the reads up
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    for (int c0 = 0; c0 < c; c0 += 64) {
-      const int ci = c0 + lane;
-      const bool have = ci < c;
-      const unsigned long long k = have ? keys[ci] : ~0ull;
-      int rank = 0;
-      for (int q = 0; q < c; ++q) rank += keys[q] < k ? 1 : 0;
-      const bool keep = have && rank < max_neigh;
-      const unsigned long long m = __ballot(keep);
-      if (keep) {
-        const int j = (int)(unsigned)(k & 0xffffffffull);
-        const float dx = open_delta(pos[(base + j) * 3 + 0], xi), dy = open_delta(pos[(base + j) * 3 + 1], yi), dz = open_delta(pos[(base + j) * 3 + 2], zi);
-        const float d = sqrtf(__uint_as_float((unsigned)(k >> 32))), inv = 1.0f / d;
-        const int slot = w + __popcll(m & ((1ull << lane) - 1ull));
-        esrc[slot] = (int)(base + j);
-        edst[slot] = (int)node;
-        *reinterpret_cast<float4*>(evec + (long)slot * 4) = make_float4(dx * inv, dy * inv, dz * inv, d);
-      }
-      w += __popcll(m);
-    }
-    return;
-  }
-  for (int j0 = 0; j0 < natoms; j0 += 64) {
-    const int j = j0 + lane;
-    bool ok = false;
-    float dx = 0.f, dy = 0.f, dz = 0.f, d2 = 0.f;
-    if (j < natoms) {
-      dx = open_delta(pos[(base + j) * 3 + 0], xi); dy = open_delta(pos[(base + j) * 3 + 1], yi); dz = open_delta(pos[(base + j) * 3 + 2], zi);
-      d2 = dist2_f(dx, dy, dz);
-      ok = (d2 <= rc2) && (d2 > 0.0f) && (base + j != node);
-    }
-    if (truncate && __ballot(ok)) {
-      int rank = 0;
-      for (int q0 = 0; q0 < natoms; q0 += 64) {
-        const int q = q0 + lane;
-        float e2 = -1.0f;                                             // -1 marks "not a candidate"
-        if (q < natoms && base + q != node) {
-          const float ex = open_delta(pos[(base + q) * 3 + 0], xi), ey = open_delta(pos[(base + q) * 3 + 1], yi), ez = open_delta(pos[(base + q) * 3 + 2], zi);
-          const float t = dist2_f(ex, ey, ez);
-          if (t <= rc2 && t > 0.0f) e2 = t;
-        }
-        for (int l = 0; l < 64; ++l) {
-          const float o2 = __shfl(e2, l, 64);
-          if (o2 >= 0.0f && q0 + l != j && (o2 < d2 || (o2 == d2 && q0 + l < j))) ++rank;
-        }
-      }
-      ok = ok && rank < max_neigh;
-    }
-    const unsigned long long m = __ballot(ok);
-    if (ok) {
-      const int slot = w + __popcll(m & ((1ull << lane) - 1ull));
-      const float d = sqrtf(d2), inv = 1.0f / d;
-      esrc[slot] = (int)(base + j);
-      edst[slot] = (int)node;
-      *reinterpret_cast<float4*>(evec + (long)slot * 4) = make_float4(dx * inv, dy * inv, dz * inv, d);
-    }
-    w += __popcll(m);
-  }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Pinned graph (umx_pin_graph): the edge set of ONE reference image, kept and replayed for every image of every evaluation while the
-// pin holds.  Per directed edge of the reference the engine keeps the source and the target (atom indices within the image), and an
-// index into the distinct lattice translations the reference edges took; per atom the integer wrap offset n of k_wrap_cell at pin time.
-// ------------------------------------------------------------------------------------------------
-// the wrap offsets of k_wrap_cell (the same expressions), as integers: out[3 i + k] = n_k of atom i.  Run once, by the pinning call.
-template <bool IMG, typename P = float>
-__global__ void k_wrap_index(const P* __restrict__ pos, int* __restrict__ out, long nt, int natoms, const PeriodicArg<IMG, P> parg) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nt) return;
-  if constexpr (std::is_same_v<P, double>) {
-    const Lattice64* lp;
-    if constexpr (IMG) lp = parg.lats + (parg.img0 + (int)(i / natoms));
-    else lp = &parg.lat;
-    const Lattice64& lat = *lp;
-    const double x = pos[i * 3 + 0], y = pos[i * 3 + 1], z = pos[i * 3 + 2];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out[i * 3 + k] = (int)floor(fma(z, lat.b[k][2], fma(y, lat.b[k][1], x * lat.b[k][0])));
-  } else {
-    const Periodic* pp;
-    if constexpr (IMG) pp = parg.cells + (parg.img0 + (int)(i / natoms));
-    else pp = &parg;
-    const Periodic& per = *pp;
-    const float x = pos[i * 3 + 0], y = pos[i * 3 + 1], z = pos[i * 3 + 2];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out[i * 3 + k] = (int)floorf(fmaf(z, per.b[k][2], fmaf(y, per.b[k][1], x * per.b[k][0])));
-  }
-}
-
-// a position shifted by the stored wrap offset n in the cell at hand: the expressions of k_wrap_cell
-__device__ __forceinline__ void wrap_by(const Periodic& per, const int* __restrict__ n, float& x, float& y, float& z) {
-  const float n0 = (float)n[0], n1 = (float)n[1], n2 = (float)n[2];
-  x = x - fmaf(n2, per.a[2][0], fmaf(n1, per.a[1][0], n0 * per.a[0][0]));
-  y = y - fmaf(n2, per.a[2][1], fmaf(n1, per.a[1][1], n0 * per.a[0][1]));
-  z = z - fmaf(n2, per.a[2][2], fmaf(n1, per.a[1][2], n0 * per.a[0][2]));
-}
-__device__ __forceinline__ void wrap_by(const Lattice64& lat, const int* __restrict__ n, double& x, double& y, double& z) {
-  const double n0 = (double)n[0], n1 = (double)n[1], n2 = (double)n[2];
-  x = x - fma(n2, lat.a[2][0], fma(n1, lat.a[1][0], n0 * lat.a[0][0]));
-  y = y - fma(n2, lat.a[2][1], fma(n1, lat.a[1][1], n0 * lat.a[0][1]));
-  z = z - fma(n2, lat.a[2][2], fma(n1, lat.a[1][2], n0 * lat.a[0][2]));
-}
-
-// The replay: one thread per edge of the chunk.  Reference edges [e0, e0 + ecnt) -- all of them, or the contiguous rows of one
-// target-node partition -- are written for each of the chunk's images: output edge k * ecnt + (e - e0) of image k gets source and target
-// with the image's node offset, and the edge vector r_src + t - r_dst of the image's positions.  No cutoff test, no ranking: an edge
-// that has grown beyond the cutoff stays, k_edge_geom gives it envelope 0.
-// BC: 0 open boundaries, 1 one cell (umx_set_cell), 2 per-image cells (umx_set_cells; cell parg.img0 + k for image k).
-// P = float: the expression of the float k_graph_fill (pbc_delta / open_delta) on positions shifted by the stored wrap offsets, with
-// the translation read from pshift -- [cells][nd] entries the host forms with the routine that fills the translation table, so at the
-// pin-time cell they are the table's bits.  P = double: one float64 difference rounded once, as k_graph_fill<..., double>.
-// flag: bit 1 of the sticky status word for a non-finite coordinate, as k_graph_count sets it.
-template <int BC, typename P = float>
-__global__ __launch_bounds__(256) void k_graph_replay(const P* __restrict__ pos, int natoms, long e0, long ecnt, long total,
-                                                      const int* __restrict__ psrc, const int* __restrict__ pdst, const int* __restrict__ ptix,
-                                                      const int* __restrict__ pwrap, const float4* __restrict__ pshift, int nd,
-                                                      int* __restrict__ esrc, int* __restrict__ edst, float* __restrict__ evec, int* __restrict__ flag,
-                                                      const PeriodicArg<BC == 2, P> parg) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const long img = i / ecnt;
-  const long e = e0 + (i - img * ecnt);
-  const int js = psrc[e], jd = pdst[e];
-  const long base = img * natoms;
-  const P* ps = pos + (base + js) * 3;
-  const P* pd = pos + (base + jd) * 3;
-  P sx = ps[0], sy = ps[1], sz = ps[2], xi = pd[0], yi = pd[1], zi = pd[2];
-  if (!(isfinite(sx) && isfinite(sy) && isfinite(sz) && isfinite(xi) && isfinite(yi) && isfinite(zi))) atomicOr(flag, 2);
-  float dx, dy, dz;
-  if constexpr (BC == 0) {
-    dx = open_delta(sx, xi); dy = open_delta(sy, yi); dz = open_delta(sz, zi);
-  } else {
-    int cell = 0;
-    if constexpr (BC == 2) cell = parg.img0 + (int)img;
-    const float4 sh = pshift[(long)cell * nd + ptix[e]];
-    if constexpr (std::is_same_v<P, double>) {
-      const Lattice64* lp;
-      if constexpr (BC == 2) lp = parg.lats + cell;
-      else lp = &parg.lat;
-      wrap_by(*lp, pwrap + js * 3, sx, sy, sz);
-      wrap_by(*lp, pwrap + jd * 3, xi, yi, zi);
-      const double pj[3] = {sx, sy, sz};
-      pbc_delta(pj, xi, yi, zi, sh, *lp, dx, dy, dz);
-    } else {
-      const Periodic* pp;
-      if constexpr (BC == 2) pp = parg.cells + cell;
-      else pp = &parg;
-      wrap_by(*pp, pwrap + js * 3, sx, sy, sz);
-      wrap_by(*pp, pwrap + jd * 3, xi, yi, zi);
-      const float pj[3] = {sx, sy, sz};
-      pbc_delta(pj, xi, yi, zi, sh, NoLattice(), dx, dy, dz);
-    }
-  }
-  const float d = sqrtf(dist2_f(dx, dy, dz)), inv = 1.0f / d;
-  esrc[i] = (int)(base + js);
-  edst[i] = (int)(base + jd);
-  *reinterpret_cast<float4*>(evec + i * 4) = make_float4(dx * inv, dy * inv, dz * inv, d);
-}
-
-// CSR by SOURCE (out-edges), valid for any graph (max_neigh truncation makes it asymmetric): count, scan (k_scan), fill
-// through per-row cursors, then sort every row by edge id so the summation order is deterministic.
-__global__ void k_out_count(const int* __restrict__ esrc, long ne, int* __restrict__ out_deg) {
-  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < ne) atomicAdd(out_deg + esrc[e], 1);
-}
-__global__ void k_out_fill(const int* __restrict__ esrc, long ne, const int* __restrict__ out_ptr, int* __restrict__ cursor,
-                           int* __restrict__ out_edge) {
-  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= ne) return;
-  const int n = esrc[e];
-  out_edge[out_ptr[n] + atomicAdd(cursor + n, 1)] = (int)e;
-}
-// sort each node's out-edge list by edge id (deterministic summation order): one wave per node, rank sort -- every lane counts the
-// entries smaller than its own (ids are unique), all reads finish before the first write because the wave runs in lockstep
-__global__ __launch_bounds__(256) void k_out_sort(const int* __restrict__ out_ptr, long nt, int* __restrict__ out_edge) {
-  UMX_WAVE_ITEM(n, nt)
-  const int b = out_ptr[n], d = out_ptr[n + 1] - b;
-  if (d <= 1) return;
-  if (d <= 320) {
-    int v[5], rk[5];
-#pragma unroll
-    for (int t = 0; t < 5; ++t) { const int i = lane + 64 * t; v[t] = i < d ? out_edge[b + i] : 0x7fffffff; rk[t] = 0; }
-    for (int j = 0; j < d; ++j) {
-      const int u = out_edge[b + j];
-#pragma unroll
-      for (int t = 0; t < 5; ++t) rk[t] += (u < v[t]) ? 1 : 0;
-    }
-#pragma unroll
-    for (int t = 0; t < 5; ++t) if (lane + 64 * t < d) out_edge[b + rk[t]] = v[t];
-  } else if (lane == 0) {          // very long lists (neighbour cap raised above 320): plain insertion sort
-    for (int i = b + 1; i < b + d; ++i) {
-      const int v = out_edge[i];
-      int k = i - 1;
-      while (k >= b && out_edge[k] > v) { out_edge[k + 1] = out_edge[k]; --k; }
-      out_edge[k + 1] = v;
-    }
-  }
-}
 
 // K2 edge frames: R (R nhat = +y, minimal rotation, flipped branch for nhat_y < -0.9), D2, envelope.
 // Carried in DOUBLE from the float32 unit vector and rounded to float32 once per entry (round 3): the frame formulas are full of

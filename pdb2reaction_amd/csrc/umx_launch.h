@@ -28,7 +28,7 @@ inline unsigned vgrid(const umx_engine* eng, unsigned blocks) {
   return (eng->throttle && eng->stream_cap > 0 && blocks > (unsigned)eng->stream_cap) ? (unsigned)eng->stream_cap : blocks;
 }
 
-// k_scan is a single block of 1024 threads (umx_kernels.h)
+// k_scan is a single block of 1024 threads (umx_graph.h)
 inline void launch_scan(hipStream_t s, const int* deg, long n, int* row_ptr, int* stats) {
   hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, deg, n, row_ptr, stats);
 }

@@ -1,7 +1,8 @@
-// umx_periodic.h -- host side: periodic boundary conditions (umx_set_cell, umx_set_cells).  A cell is turned, in float64, into what the periodic
-// instantiations of the graph kernels read (struct Periodic, umx_kernels.h): the lattice vectors, the dual vectors of the periodic
-// sub-lattice (fractional coordinates for the wrap and for pruning), and the table of lattice translations.  Also here: the wrapped
-// copy of the positions and the two launchers that pick the open-boundary or the periodic instantiation.
+// umx_periodic.h -- host side of the neighbour-graph stage (umx_graph.h).  A cell is turned, in float64, into what the periodic
+// instantiations of the graph kernels read (struct Periodic): the lattice vectors, the dual vectors of the periodic sub-lattice
+// (fractional coordinates for the wrap and for pruning), and the table of lattice translations.  The bound cells are ONE list -- a
+// single cell every image shares (umx_set_cell) or one per image (umx_set_cells) -- with one upload routine.  Also here: the wrapped
+// copy of the positions, the dispatcher that resolves (boundary kind, position type, cell argument) once, and one launcher per kernel.
 //
 // Translations per periodic axis k: N_k = floor(cutoff / h_k + 1e-4) + 1, h_k the distance between the lattice planes of axis k within
 // the periodic sub-lattice -- the whole cells the cutoff spans, plus one because two wrapped atoms may be almost a cell apart (the 1e-4
@@ -11,7 +12,7 @@
 
 namespace {
 
-struct PeriodicHost { Periodic per{}; Lattice64 lat{}; std::vector<float4> table; };   // lat: what the double-position kernels read next to per
+struct PeriodicHost { Periodic per{}; Lattice64 lat{}; std::vector<float4> table; };   // one cell; lat: what the double-position kernels read next to per
 
 inline void cross3(const double* u, const double* v, double* o) {
   o[0] = u[1] * v[2] - u[2] * v[1]; o[1] = u[2] * v[0] - u[0] * v[2]; o[2] = u[0] * v[1] - u[1] * v[0];
@@ -102,46 +103,19 @@ bool build_periodic(const double cell[9], const int pbc[3], double cutoff, Perio
   return true;
 }
 
-// build the table of the stored cell for the bound cutoff and put it on the device
-int periodic_upload(umx_engine* eng, const PeriodicHost& ph) {
-  HIPCHK(eng, hipSetDevice(eng->dev));
-  HIPCHK(eng, hipStreamSynchronize(eng->stream));                     // no evaluation may still be reading the old table
-  if (eng->ran_on_caller) HIPCHK(eng, hipEventSynchronize(eng->ev_done));
-  if (!eng->d_shifts) HIPCHK(eng, hipMalloc(&eng->d_shifts, PBC_MAX_SHIFTS * sizeof(float4)));
-  HIPCHK(eng, hipMemcpy(eng->d_shifts, ph.table.data(), ph.table.size() * sizeof(float4), hipMemcpyHostToDevice));
-  eng->per = ph.per;
-  eng->per.shifts = eng->d_shifts;
-  eng->lat = ph.lat;
-  eng->per_cutoff = eng->cutoff;
-  return UMX_OK;
-}
-
-int set_cell_impl(umx_engine* eng, const double* cell, const int* pbc) {
-  if (!cell || !pbc || !(pbc[0] || pbc[1] || pbc[2])) { eng->pbc_on = false; eng->n_cells = 0; return UMX_OK; }
-  PeriodicHost ph;
-  std::string why;
-  if (!build_periodic(cell, pbc, eng->cutoff, &ph, &why)) return fail(eng, UMX_ERR_ARG, "umx_set_cell: " + why);   // (the engine keeps the cell it had)
-  CHK(periodic_upload(eng, ph));
-  std::memcpy(eng->cell, cell, sizeof(eng->cell));
-  for (int k = 0; k < 3; ++k) eng->pbc[k] = pbc[k] != 0;
-  eng->pbc_on = true;
-  eng->n_cells = 0;
-  return UMX_OK;
-}
-
-// ---- per-image cells (umx_set_cells) -----------------------------------------------------------------------------------------------
-// every cell through build_periodic for the bound cutoff; false + *why (which names the image): one of them is refused
-bool build_periodic_images(int n, const double* cells, const int pbc[3], double cutoff, std::vector<PeriodicHost>* out, std::string* why) {
+// ---- the bound cells: one list, shared by all images (umx_set_cell) or one cell per image (umx_set_cells) ---------------------------
+// every cell through build_periodic for the bound cutoff; false + *why (per-image cells: it names the image): one of them is refused
+bool build_cells(long n, const double* cells, const int pbc[3], double cutoff, bool shared, std::vector<PeriodicHost>* out, std::string* why) {
   out->resize(n);
-  for (int k = 0; k < n; ++k) {
+  for (long k = 0; k < n; ++k) {
     std::string w;
-    if (!build_periodic(cells + (size_t)k * 9, pbc, cutoff, &(*out)[k], &w)) { *why = "image " + std::to_string(k) + ": " + w; return false; }
+    if (!build_periodic(cells + (size_t)k * 9, pbc, cutoff, &(*out)[k], &w)) { *why = shared ? w : "image " + std::to_string(k) + ": " + w; return false; }
   }
   return true;
 }
 
-// put the images' structs and their tables, packed one behind the other, on the device
-int periodic_upload_images(umx_engine* eng, const std::vector<PeriodicHost>& ph) {
+// put the cells' structs and their tables, packed one behind the other, on the device
+int periodic_upload(umx_engine* eng, const std::vector<PeriodicHost>& ph) {
   const long n = (long)ph.size();
   long total = 0;
   for (const PeriodicHost& h : ph) total += (long)h.table.size();
@@ -169,54 +143,64 @@ int periodic_upload_images(umx_engine* eng, const std::vector<PeriodicHost>& ph)
   return UMX_OK;
 }
 
-int set_cells_impl(umx_engine* eng, int n_images, const double* cells, const int* pbc) {
-  if (!cells || !pbc || !(pbc[0] || pbc[1] || pbc[2])) { eng->pbc_on = false; eng->n_cells = 0; return UMX_OK; }
-  if (n_images <= 0) return fail(eng, UMX_ERR_ARG, "umx_set_cells: n_images must be positive when cells are given");
+// umx_set_cell (`shared`: one cell, n = 1) and umx_set_cells; a refused cell leaves the cells in force
+int set_cells_impl(umx_engine* eng, const char* who, bool shared, int n, const double* cells, const int* pbc) {
+  if (!cells || !pbc || !(pbc[0] || pbc[1] || pbc[2])) { eng->pbc_on = false; eng->cells_shared = true; return UMX_OK; }
+  if (n <= 0) return fail(eng, UMX_ERR_ARG, "umx_set_cells: n_images must be positive when cells are given");
   std::vector<PeriodicHost> ph;
   std::string why;
-  if (!build_periodic_images(n_images, cells, pbc, eng->cutoff, &ph, &why)) return fail(eng, UMX_ERR_ARG, "umx_set_cells: " + why);   // (the cells in force stay)
-  CHK(periodic_upload_images(eng, ph));
-  eng->cells.assign(cells, cells + (size_t)n_images * 9);
+  if (!build_cells(n, cells, pbc, eng->cutoff, shared, &ph, &why)) return fail(eng, UMX_ERR_ARG, std::string(who) + ": " + why);
+  CHK(periodic_upload(eng, ph));
+  eng->cells.assign(cells, cells + (size_t)n * 9);
+  eng->cells_shared = shared;
   for (int k = 0; k < 3; ++k) eng->pbc[k] = pbc[k] != 0;
   eng->pbc_on = true;
-  eng->n_cells = n_images;
   return UMX_OK;
 }
 
 // Per-image cells bound for another number of images than the evaluation holds: refused before anything runs (`who`: the entry).
 int periodic_check_images(umx_engine* eng, long K, const char* who) {
-  if (!eng->pbc_on || eng->n_cells == 0 || K == eng->n_cells) return UMX_OK;
-  return fail(eng, UMX_ERR_ARG, std::string(who) + ": " + std::to_string(K) + " images, but umx_set_cells bound cells for " + std::to_string(eng->n_cells) +
+  if (!eng->pbc_on || eng->cells_shared || K == eng->n_cells()) return UMX_OK;
+  return fail(eng, UMX_ERR_ARG, std::string(who) + ": " + std::to_string(K) + " images, but umx_set_cells bound cells for " + std::to_string(eng->n_cells()) +
               " (cell k belongs to image k: bind one cell per image, or one cell for all with umx_set_cell)");
 }
 
-// Start of an evaluation.  Open boundaries: nothing.  Periodic: the table(s) follow the bound cutoff, the positions of all images are
+// ---- one dispatcher for the graph kernels ----------------------------------------------------------------------------------------------
+// f(pos, cells): the positions in their own type and the boundary argument of the instantiation to launch -- NoCells, or Cells<P> for
+// the cells in force.  img0: the index within the call of the image pos starts at (per-image cells: image img0 + k reads cell img0 + k;
+// a shared cell: every image reads cell 0).
+template <typename F>
+void with_boundary(const umx_engine* eng, PosPtr pos, long img0, F&& f) {
+  const int first = eng->cells_shared ? 0 : (int)img0, stride = eng->cells_shared ? 0 : 1;
+  if (!eng->pbc_on) { if (pos.d) f(pos.d, NoCells{}); else f(pos.f, NoCells{}); }
+  else if (pos.d) f(pos.d, Cells<double>{eng->d_cells, eng->d_lats, first, stride});
+  else f(pos.f, Cells<float>{eng->d_cells, first, stride});
+}
+template <typename F> void with_flag(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <typename P> using pos_t = std::remove_const_t<std::remove_pointer_t<P>>;
+
+// the wrapped copy of positions of one type: its buffer and its capacity
+inline std::pair<float*&, long&> wrap_copy(umx_engine* eng, const float*) { return {eng->d_wrap, eng->wrap_cap}; }
+inline std::pair<double*&, long&> wrap_copy(umx_engine* eng, const double*) { return {eng->d_wrap64, eng->wrap64_cap}; }
+
+// Start of an evaluation.  Open boundaries: nothing.  Periodic: the tables follow the bound cutoff, the positions of all images are
 // wrapped into the scratch copy (every image into its own cell, if umx_set_cells bound them), and *d_pos is pointed at it -- a float64
 // copy, wrapped in float64, for double positions.
 int periodic_prepare(umx_engine* eng, hipStream_t s, long K, PosPtr* d_pos) {
   eng->last_shifts = 0;
   if (!eng->pbc_on) return UMX_OK;
-  const bool img = eng->n_cells > 0;
+  const bool img = !eng->cells_shared;
   CHK(periodic_check_images(eng, K, "umx_energy_forces"));
   if (eng->per_cutoff != eng->cutoff) {          // umx_set_system changed the cutoff since umx_set_cell / umx_set_cells
+    std::vector<PeriodicHost> ph;
     std::string why;
-    if (img) {
-      std::vector<PeriodicHost> ph;
-      if (!build_periodic_images(eng->n_cells, eng->cells.data(), eng->pbc, eng->cutoff, &ph, &why))
-        return fail(eng, UMX_ERR_ARG, "umx_energy_forces: the cells set by umx_set_cells and the bound cutoff: " + why);
-      CHK(periodic_upload_images(eng, ph));
-    } else {
-      PeriodicHost ph;
-      if (!build_periodic(eng->cell, eng->pbc, eng->cutoff, &ph, &why)) return fail(eng, UMX_ERR_ARG, "umx_energy_forces: the cell set by umx_set_cell and the bound cutoff: " + why);
-      CHK(periodic_upload(eng, ph));
-    }
+    if (!build_cells(eng->n_cells(), eng->cells.data(), eng->pbc, eng->cutoff, !img, &ph, &why))
+      return fail(eng, UMX_ERR_ARG, std::string("umx_energy_forces: the cell") + (img ? "s set by umx_set_cells" : " set by umx_set_cell") + " and the bound cutoff: " + why);
+    CHK(periodic_upload(eng, ph));
   }
-  // the rank key of the truncating fill carries translation index * n_atoms + source in its low 32 bits
-  int most = eng->per.n_shifts, most_at = -1;
-  if (img) {
-    most_at = (int)(std::max_element(eng->cell_shifts.begin(), eng->cell_shifts.end()) - eng->cell_shifts.begin());   // (the largest table decides for every image)
-    most = eng->cell_shifts[most_at];
-  }
+  // the rank key of the truncating fill carries translation index * n_atoms + source in its low 32 bits (the largest table decides)
+  const int most_at = (int)(std::max_element(eng->cell_shifts.begin(), eng->cell_shifts.end()) - eng->cell_shifts.begin());
+  const int most = eng->cell_shifts[most_at];
   if ((unsigned long long)most * (unsigned long long)eng->natoms > 0xffffffffull)
     return fail(eng, UMX_ERR_ARG, "umx_energy_forces: " + (img ? "image " + std::to_string(most_at) + ": " : std::string()) + std::to_string(most) + " lattice translations x " +
                 std::to_string(eng->natoms) + " atoms do not fit the 32-bit candidate index of the periodic graph");
@@ -225,118 +209,60 @@ int periodic_prepare(umx_engine* eng, hipStream_t s, long K, PosPtr* d_pos) {
     return UMX_OK;
   }
   const long nt = K * eng->natoms;
-  if (d_pos->d) {
-    if (eng->wrap64_cap < nt) CHK(grow(eng, eng->wrap64_cap, nt, {s}, {DevBuf(eng->d_wrap64, (size_t)nt * 3)}));
-    if (img) hipLaunchKernelGGL((k_wrap_cell<true, double>), dim3(nblk(nt, 256)), dim3(256), 0, s, d_pos->d, eng->d_wrap64, nt, eng->natoms, PeriodicImages64{eng->d_cells, eng->d_lats, 0});
-    else hipLaunchKernelGGL((k_wrap_cell<false, double>), dim3(nblk(nt, 256)), dim3(256), 0, s, d_pos->d, eng->d_wrap64, nt, eng->natoms, Periodic64{eng->per, eng->lat});
-    HIPCHK(eng, hipGetLastError());
-    *d_pos = PosPtr(eng->d_wrap64);
-    eng->last_shifts = most;
-    return UMX_OK;
-  }
-  if (eng->wrap_cap < nt) CHK(grow(eng, eng->wrap_cap, nt, {s}, {DevBuf(eng->d_wrap, (size_t)nt * 3)}));
-  if (img) hipLaunchKernelGGL(k_wrap_cell<true>, dim3(nblk(nt, 256)), dim3(256), 0, s, d_pos->f, eng->d_wrap, nt, eng->natoms, PeriodicImages{eng->d_cells, 0});
-  else hipLaunchKernelGGL(k_wrap_cell<false>, dim3(nblk(nt, 256)), dim3(256), 0, s, d_pos->f, eng->d_wrap, nt, eng->natoms, eng->per);
+  int st = UMX_OK;
+  with_boundary(eng, *d_pos, 0, [&](auto* pos, auto cells) {
+    if constexpr (is_periodic<decltype(cells)>) {
+      auto [buf, cap] = wrap_copy(eng, pos);
+      if (cap < nt && (st = grow(eng, cap, nt, {s}, {DevBuf(buf, (size_t)nt * 3)})) != UMX_OK) return;
+      hipLaunchKernelGGL((k_wrap_cell<pos_t<decltype(pos)>>), dim3(nblk(nt, 256)), dim3(256), 0, s, pos, buf, nt, eng->natoms, cells);
+      *d_pos = PosPtr(buf);
+    }
+  });
+  CHK(st);
   HIPCHK(eng, hipGetLastError());
-  *d_pos = PosPtr(eng->d_wrap);
   eng->last_shifts = most;
   return UMX_OK;
 }
 
-// ---- the two graph kernels: open-boundary, one-cell or per-image instantiation, for float or double positions ---------------------
-// the last argument of an instantiation for the cell(s) in force: PeriodicArg<IMG, P> (umx_kernels.h)
-template <bool IMG, typename P> PeriodicArg<IMG, P> periodic_arg(const umx_engine* eng, long img0, bool on = true);
-template <> Periodic periodic_arg<false, float>(const umx_engine* eng, long, bool on) { return on ? eng->per : Periodic(); }
-template <> PeriodicImages periodic_arg<true, float>(const umx_engine* eng, long img0, bool) { return PeriodicImages{eng->d_cells, (int)img0}; }
-template <> Periodic64 periodic_arg<false, double>(const umx_engine* eng, long, bool on) { return on ? Periodic64{eng->per, eng->lat} : Periodic64(); }
-template <> PeriodicImages64 periodic_arg<true, double>(const umx_engine* eng, long img0, bool) { return PeriodicImages64{eng->d_cells, eng->d_lats, (int)img0}; }
-
-// img0: the index within the call of the image d_pos starts at (per-image cells: image img0 + node / natoms reads cell img0 + node / natoms)
-template <typename P>
-void launch_graph_count_of(umx_engine* eng, hipStream_t s, const P* d_pos, long nt, int* deg, int* cand, long lo, long hi, long img0) {
-  const float rc2 = eng->cutoff * eng->cutoff;
-  const dim3 grid(nblk(nt, 4)), block(256);
-  const int N = eng->natoms, mn = eng->max_neigh;
-  if (eng->pbc_on && eng->n_cells > 0)
-    hipLaunchKernelGGL((k_graph_count<true, true, P>), grid, block, 0, s, d_pos, N, nt, rc2, mn, deg, cand, lo, hi, eng->d_flags, periodic_arg<true, P>(eng, img0));
-  else if (eng->pbc_on) hipLaunchKernelGGL((k_graph_count<true, false, P>), grid, block, 0, s, d_pos, N, nt, rc2, mn, deg, cand, lo, hi, eng->d_flags, periodic_arg<false, P>(eng, 0));
-  else hipLaunchKernelGGL((k_graph_count<false, false, P>), grid, block, 0, s, d_pos, N, nt, rc2, mn, deg, cand, lo, hi, eng->d_flags, periodic_arg<false, P>(eng, 0, false));
-}
+// ---- the launchers: one site per kernel ------------------------------------------------------------------------------------------------
 void launch_graph_count(umx_engine* eng, hipStream_t s, PosPtr d_pos, long nt, int* deg, int* cand, long lo, long hi, long img0) {
-  if (d_pos.d) launch_graph_count_of(eng, s, d_pos.d, nt, deg, cand, lo, hi, img0);
-  else launch_graph_count_of(eng, s, d_pos.f, nt, deg, cand, lo, hi, img0);
+  with_boundary(eng, d_pos, img0, [&](auto* pos, auto cells) {
+    hipLaunchKernelGGL((k_graph_count<pos_t<decltype(pos)>, decltype(cells)>), dim3(nblk(nt, 4)), dim3(256), 0, s, pos, eng->natoms, nt, eng->cutoff * eng->cutoff,
+                       eng->max_neigh, deg, cand, lo, hi, eng->d_flags, cells);
+  });
 }
-template <typename P>
-void launch_graph_fill_of(umx_engine* eng, hipStream_t s, bool trunc, const P* d_pos, long nn, const int* cand, const int* row_ptr, int* esrc, int* edst,
-                          float* evec, long lo, long hi, long img0) {
-  const float rc2 = eng->cutoff * eng->cutoff;
-  const dim3 grid(nblk(nn, 4)), block(256);
-  const int N = eng->natoms, mn = eng->max_neigh;
-  if (eng->pbc_on && eng->n_cells > 0) {
-    const auto pi = periodic_arg<true, P>(eng, img0);
-    if (trunc) hipLaunchKernelGGL((k_graph_fill<true, true, true, P>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, pi);
-    else hipLaunchKernelGGL((k_graph_fill<false, true, true, P>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, pi);
-  } else {
-    const auto per = periodic_arg<false, P>(eng, 0, eng->pbc_on);
-    if (eng->pbc_on) {
-      if (trunc) hipLaunchKernelGGL((k_graph_fill<true, true, false, P>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, per);
-      else hipLaunchKernelGGL((k_graph_fill<false, true, false, P>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, per);
-    } else {
-      if (trunc) hipLaunchKernelGGL((k_graph_fill<true, false, false, P>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, per);
-      else hipLaunchKernelGGL((k_graph_fill<false, false, false, P>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, lo, hi, per);
-    }
-  }
-}
+// etr (the pinning call's fill of the periodic reference image): the translation of every edge as one more output, the packed integer
+// triple.  Open boundaries have no translation to report and leave etr as it is.
 void launch_graph_fill(umx_engine* eng, hipStream_t s, bool trunc, PosPtr d_pos, long nn, const int* cand, const int* row_ptr, int* esrc, int* edst,
-                       float* evec, long lo, long hi, long img0) {
-  if (d_pos.d) launch_graph_fill_of(eng, s, trunc, d_pos.d, nn, cand, row_ptr, esrc, edst, evec, lo, hi, img0);
-  else launch_graph_fill_of(eng, s, trunc, d_pos.f, nn, cand, row_ptr, esrc, edst, evec, lo, hi, img0);
+                       float* evec, long lo, long hi, long img0, int* etr = nullptr) {
+  with_boundary(eng, d_pos, img0, [&](auto* pos, auto cells) {
+    with_flag(trunc, [&](auto TRUNC) {
+      with_flag(etr != nullptr && is_periodic<decltype(cells)>, [&](auto TOUT) {
+        if constexpr (is_periodic<decltype(cells)> || !TOUT())
+          hipLaunchKernelGGL((k_graph_fill<TRUNC(), TOUT(), pos_t<decltype(pos)>, decltype(cells)>), dim3(nblk(nn, 4)), dim3(256), 0, s, pos, eng->natoms, nn,
+                             eng->cutoff * eng->cutoff, eng->max_neigh, cand, row_ptr, esrc, edst, evec, lo, hi, cells, etr);
+      });
+    });
+  });
 }
-
-// ---- pinned graph (umx_pin_graph) ------------------------------------------------------------------------------------------------------
-// The pinning call's fill of the periodic reference image: k_graph_fill with the translation of every edge as one more output (etr: the
-// packed integer triple).  Open boundaries take the ordinary launcher: there is no translation to report.
-template <typename P>
-void launch_graph_fill_pin_of(umx_engine* eng, hipStream_t s, bool trunc, const P* d_pos, long nn, const int* cand, const int* row_ptr, int* esrc, int* edst,
-                              float* evec, int* etr) {
-  const float rc2 = eng->cutoff * eng->cutoff;
-  const dim3 grid(nblk(nn, 4)), block(256);
-  const int N = eng->natoms, mn = eng->max_neigh;
-  if (eng->n_cells > 0) {
-    const auto pi = periodic_arg<true, P>(eng, 0);
-    if (trunc) hipLaunchKernelGGL((k_graph_fill<true, true, true, P, true>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, 0L, nn, pi, etr);
-    else hipLaunchKernelGGL((k_graph_fill<false, true, true, P, true>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, 0L, nn, pi, etr);
-  } else {
-    const auto per = periodic_arg<false, P>(eng, 0);
-    if (trunc) hipLaunchKernelGGL((k_graph_fill<true, true, false, P, true>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, 0L, nn, per, etr);
-    else hipLaunchKernelGGL((k_graph_fill<false, true, false, P, true>), grid, block, 0, s, d_pos, N, nn, rc2, mn, cand, row_ptr, esrc, edst, evec, 0L, nn, per, etr);
-  }
-}
-void launch_graph_fill_pin(umx_engine* eng, hipStream_t s, bool trunc, PosPtr d_pos, long nn, const int* cand, const int* row_ptr, int* esrc, int* edst,
-                           float* evec, int* etr) {
-  if (!eng->pbc_on) { launch_graph_fill(eng, s, trunc, d_pos, nn, cand, row_ptr, esrc, edst, evec, 0, nn, 0); return; }
-  if (d_pos.d) launch_graph_fill_pin_of(eng, s, trunc, d_pos.d, nn, cand, row_ptr, esrc, edst, evec, etr);
-  else launch_graph_fill_pin_of(eng, s, trunc, d_pos.f, nn, cand, row_ptr, esrc, edst, evec, etr);
-}
-// the wrap offsets of the reference image (d_pos: the caller's positions, not the wrapped copy); open boundaries: zeros
-template <typename P>
-void launch_wrap_index_of(umx_engine* eng, hipStream_t s, const P* d_pos, int* out) {
+// the wrap offsets of the reference image of a pin (d_pos: the caller's positions, not the wrapped copy); open boundaries: out stays zero
+void launch_wrap_index(umx_engine* eng, hipStream_t s, PosPtr d_pos, int* out) {
   const long N = eng->natoms;
-  if (eng->n_cells > 0) hipLaunchKernelGGL((k_wrap_index<true, P>), dim3(nblk(N, 256)), dim3(256), 0, s, d_pos, out, N, eng->natoms, periodic_arg<true, P>(eng, 0));
-  else hipLaunchKernelGGL((k_wrap_index<false, P>), dim3(nblk(N, 256)), dim3(256), 0, s, d_pos, out, N, eng->natoms, periodic_arg<false, P>(eng, 0));
+  with_boundary(eng, d_pos, 0, [&](auto* pos, auto cells) {
+    if constexpr (is_periodic<decltype(cells)>)
+      hipLaunchKernelGGL((k_wrap_index<pos_t<decltype(pos)>>), dim3(nblk(N, 256)), dim3(256), 0, s, pos, out, N, eng->natoms, cells);
+  });
 }
 
 // The translations of the pinned edges in the cell(s) in force, [cells][distinct triples], through shift_entry -- at pinning, and again
 // when umx_set_cell / umx_set_cells bind other cells under the pin.  `into`: the buffer to fill (grown when too small).
 int pin_upload_shifts(umx_engine* eng, const std::vector<unsigned>& codes, float4** into, long* cap) {
-  const long nc = eng->n_cells > 0 ? eng->n_cells : 1, nd = (long)codes.size();
+  const long nc = eng->n_cells(), nd = (long)codes.size();
   if (!eng->pbc_on || nd == 0) return UMX_OK;
   std::vector<float4> tab((size_t)(nc * nd));
-  for (long k = 0; k < nc; ++k) {
-    const double* cell = eng->n_cells > 0 ? eng->cells.data() + (size_t)k * 9 : eng->cell;
+  for (long k = 0; k < nc; ++k)
     for (long t = 0; t < nd; ++t)
-      tab[(size_t)(k * nd + t)] = shift_entry(cell, (int)(codes[t] & 255u) - 8, (int)((codes[t] >> 8) & 255u) - 8, (int)((codes[t] >> 16) & 255u) - 8);
-  }
+      tab[(size_t)(k * nd + t)] = shift_entry(eng->cells.data() + (size_t)k * 9, (int)(codes[t] & 255u) - 8, (int)((codes[t] >> 8) & 255u) - 8, (int)((codes[t] >> 16) & 255u) - 8);
   if (*cap < nc * nd) {
     if (*into) HIPCHK(eng, hipFree(*into));
     *into = nullptr; *cap = 0;
@@ -348,22 +274,14 @@ int pin_upload_shifts(umx_engine* eng, const std::vector<unsigned>& codes, float
 }
 
 // the replay of the pinned graph for the nimg images d_pos starts at: reference edges [e0, e0 + ecnt) of each (k_graph_replay)
-template <typename P>
-void launch_graph_replay_of(umx_engine* eng, hipStream_t s, const P* d_pos, long nimg, long e0, long ecnt, int* esrc, int* edst, float* evec, long img0) {
+void launch_graph_replay(umx_engine* eng, hipStream_t s, PosPtr d_pos, long nimg, long e0, long ecnt, int* esrc, int* edst, float* evec, long img0) {
   const long total = nimg * ecnt;
   if (total <= 0) return;
-  const dim3 grid(nblk(total, 256)), block(256);
-  const int N = eng->natoms, nd = (int)eng->pin_codes.size();
-#define UMX_REPLAY(BC, ARG) hipLaunchKernelGGL((k_graph_replay<BC, P>), grid, block, 0, s, d_pos, N, e0, ecnt, total, eng->d_pin_src, eng->d_pin_dst, eng->d_pin_tix, \
-                                               eng->d_pin_wrap, eng->d_pin_shifts, nd, esrc, edst, evec, eng->d_flags, ARG)
-  if (eng->pbc_on && eng->n_cells > 0) UMX_REPLAY(2, (periodic_arg<true, P>(eng, img0)));
-  else if (eng->pbc_on) UMX_REPLAY(1, (periodic_arg<false, P>(eng, 0)));
-  else UMX_REPLAY(0, (periodic_arg<false, P>(eng, 0, false)));
-#undef UMX_REPLAY
-}
-void launch_graph_replay(umx_engine* eng, hipStream_t s, PosPtr d_pos, long nimg, long e0, long ecnt, int* esrc, int* edst, float* evec, long img0) {
-  if (d_pos.d) launch_graph_replay_of(eng, s, d_pos.d, nimg, e0, ecnt, esrc, edst, evec, img0);
-  else launch_graph_replay_of(eng, s, d_pos.f, nimg, e0, ecnt, esrc, edst, evec, img0);
+  with_boundary(eng, d_pos, img0, [&](auto* pos, auto cells) {
+    hipLaunchKernelGGL((k_graph_replay<pos_t<decltype(pos)>, decltype(cells)>), dim3(nblk(total, 256)), dim3(256), 0, s, pos, eng->natoms, e0, ecnt, total,
+                       eng->d_pin_src, eng->d_pin_dst, eng->d_pin_tix, eng->d_pin_wrap, eng->d_pin_shifts, (int)eng->pin_codes.size(), esrc, edst, evec,
+                       eng->d_flags, cells);
+  });
 }
 
 }  // namespace

@@ -1,6 +1,10 @@
 """Fingerprint of every kind of launch plan: one line per configuration with the sha256 of the energies, the forces, the virial where
 asked and, with captures on, of every debug capture in name order.  A host-code refactor must leave every line as it was: run it on both
-trees (python tools/gpu_plan_fingerprint.py > out.txt) and compare the files.  An engine error prints as the line's result."""
+trees (python tools/gpu_plan_fingerprint.py > out.txt) and compare the files.  An engine error prints as the line's result.
+
+The ``graph`` section (lines that start with "graph"; ``python tools/gpu_plan_fingerprint.py graph`` prints it alone, ``plans`` the
+rest) holds the neighbour-graph stage: the six graph captures, energies and forces, ``graph_stats()`` and ``last_graph_shifts()`` of
+every geometry of tests/graph_cases.py and tests/cells_cases.py, through every instantiation of the graph kernels."""
 import hashlib
 import os
 import sys
@@ -110,5 +114,123 @@ def main():
                     line(f"{mode} {ff} {name} pool-gp+virial", lambda: sha(*pool.energy_forces_virial(p[:1], graph_parallel=True)) + f" {pool.last_route}")
 
 
+# ---- the neighbour-graph stage ---------------------------------------------------------------------------------------------------
+GRAPH_NAMES = ("row_ptr", "src", "dst", "out_ptr", "out_edge", "evec")
+
+
+def graph_line(label, eng, pos, double=False):
+    """sha256 of the six graph captures, of the energies and forces, graph_stats() and last_graph_shifts() of one evaluation (several
+    chunks: the captures are the last chunk's)"""
+    def run():
+        e, f = eng.energy_forces(pos, double_positions=double)
+        caps = [eng.debug_fetch(n, np.uint8) for n in GRAPH_NAMES]
+        return f"{sha(*caps)} E,F {sha(e, f)} stats {eng.graph_stats()} shifts {eng.last_graph_shifts()}"
+    line(f"graph {label}{' f64' if double else ''}", run)
+
+
+def graph_engine(w, env=None):
+    os.environ.update(env or {})
+    eng = Engine(0)
+    [os.environ.pop(k) for k in env or {}]
+    eng.load_weights(w)
+    eng.debug_keep(True)
+    return eng
+
+
+def displaced(x):
+    return x + 0.01 * np.sin(3.0 * x[..., ::-1])
+
+
+def graph_main():
+    """Every geometry of tests/graph_cases.py and the cell families of tests/cells_cases.py through every instantiation of the graph
+    kernels: open / one cell / per-image cells x float / double x the truncating forms x the pinning fill and the replay."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import graph_cases as G
+    import cells_cases as CC
+
+    os.environ["UMX_DEBUG_ONLY"] = G.NAMES
+    w = W.make_synthetic_weights(0)
+    eng = graph_engine(w)
+    for name in G.OPEN:
+        z, pos, radius, mn = G.open_case(name)
+        eng.set_system(z, radius=radius, max_neigh=mn)
+        for dbl in (False, True):
+            graph_line(f"open {name} cap {mn}", eng, pos, dbl)
+    for n in (63, 64, 65, 129):
+        z, pos = G.seam_case(n)
+        for mn in (8, None):
+            eng.set_system(z, radius=6.0, max_neigh=mn)
+            for dbl in (False, True):
+                graph_line(f"seam {n} cap {mn}", eng, pos, dbl)
+    for n, k in ((205, 5), (129, 9)):
+        z, imgs = G.batch_case(n, k)
+        one = graph_engine(w, {"UMX_STREAMS": "1"})
+        one.set_system(z, radius=6.0, max_neigh=20)
+        for dbl in (False, True):
+            graph_line(f"batch {k} x {n} cap 20", one, imgs, dbl)
+        one.close()
+    z, pos, radius, mn = G.open_case("G10")
+    parts = graph_engine(w, {"UMX_FORCE_PARTS": "3"})
+    parts.set_system(z, radius=radius, max_neigh=mn)
+    for dbl in (False, True):
+        graph_line("open G10 UMX_FORCE_PARTS=3", parts, pos, dbl)
+    parts.close()
+    # cells: one shared cell or identical per-image cells, two images; the binding cap reaches the truncating periodic form; Cap at 50
+    # is refused (more candidates than the truncating fill ranks) and the refusal is the line's result
+    for name in G.CELLS:
+        z, pos, cell, pbc, radius = G.cell_case(name)
+        p2 = np.stack([pos, pos])
+        for mn in ((50, 2000) if name == "Cap" else (None, 20)):
+            eng.set_system(z, radius=radius, max_neigh=mn)
+            for how in ("set_cell", "set_cells"):
+                eng.set_cell(cell, pbc) if how == "set_cell" else eng.set_cells(np.stack([cell, cell]), pbc)
+                for dbl in (False, True):
+                    graph_line(f"cells {name} cap {mn} {how}", eng, p2, dbl)
+    eng.set_cell(None)
+    # distinct per-image cells: in one chunk, and one image per chunk (a non-zero first image reaches the kernels)
+    for fam in CC.FAMILIES:
+        z, imgs, cells, pbc = CC.family(fam)
+        eng.set_system(z)
+        eng.set_cells(cells, pbc)
+        for chunk in (None, "1"):
+            if chunk:
+                os.environ["UMX_MAX_CHUNK_IMAGES"] = chunk
+            for dbl in (False, True):
+                graph_line(f"family {fam} {len(cells)} cells{' chunk1' if chunk else ''}", eng, imgs, dbl)
+            os.environ.pop("UMX_MAX_CHUNK_IMAGES", None)
+    eng.set_cell(None)
+    # pinned graph, evaluated on displaced geometries
+    z, pos = G.seam_case(65)
+    for mn in (None, 8):
+        eng.set_system(z, radius=6.0, max_neigh=mn)
+        for dbl in (False, True):
+            eng.pin_graph(pos, double_positions=dbl)
+            graph_line(f"pinned open seam 65 cap {mn}", eng, np.stack([pos, displaced(pos)]), dbl)
+            eng.unpin_graph()
+    z, imgs, cells, pbc = CC.family("triclinic")
+    for mn in (None, 7):                                       # 7: the pinning fill truncates (TOUT with TRUNC)
+        eng.set_system(z, max_neigh=mn)
+        for dbl in (False, True):
+            eng.set_cell(cells[0], pbc)
+            eng.pin_graph(imgs[0], double_positions=dbl)
+            graph_line(f"pinned one cell cap {mn}", eng, np.stack([imgs[0], displaced(imgs[0])]), dbl)
+            eng.set_cell(cells[4], pbc)                        # the strained cell under the pin
+            graph_line(f"pinned one cell cap {mn}, re-bound to the strained cell", eng, np.stack([imgs[4], displaced(imgs[4])]), dbl)
+            eng.unpin_graph()
+            eng.set_cells(cells[:1], pbc)
+            eng.pin_graph(imgs[0], double_positions=dbl)
+            eng.set_cells(cells, pbc)
+            for chunk in (None, "1"):
+                if chunk:
+                    os.environ["UMX_MAX_CHUNK_IMAGES"] = chunk
+                graph_line(f"pinned per-image cells cap {mn}{' chunk1' if chunk else ''}", eng, displaced(imgs), dbl)
+                os.environ.pop("UMX_MAX_CHUNK_IMAGES", None)
+            eng.unpin_graph()
+    eng.close()
+
+
 if __name__ == "__main__":
-    main()
+    if "graph" not in sys.argv[1:]:
+        main()
+    if "plans" not in sys.argv[1:]:
+        graph_main()

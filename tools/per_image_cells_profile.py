@@ -7,7 +7,8 @@ cell (``set_cell``) or with 16 identical per-image cells (``set_cells``); or the
     python tools/per_image_cells_profile.py stats <name>_kernel_stats.csv <evaluations + 1>
 
 ``--tree DIR`` (last two arguments) takes the package and the test helpers from another checkout (the parent commit: mode ``cell`` only).
-``stats`` sums the periodic graph kernels (k_wrap_cell, k_graph_count<true, ...>, k_graph_fill<., true, ...>) of a kernel-stats file."""
+``stats`` sums the periodic graph kernels (k_wrap_cell, k_graph_count<P, Cells<P>>, k_graph_fill<., ., P, Cells<P>>; on a tree from before
+csrc/umx_graph.h: k_graph_count<true, ...>, k_graph_fill<., true, ...>) of a kernel-stats file."""
 import csv
 import os
 import re
@@ -23,7 +24,8 @@ if "--tree" in args:
     args = args[:args.index("--tree")]
 sys.path[:0] = [tree, os.path.join(tree, "tests")]
 
-PERIODIC = re.compile(r"k_wrap_cell|k_graph_count<true|k_graph_fill<(true|false), true")
+# the periodic instantiations take Cells<P> (csrc/umx_graph.h); before the graph stage had its own header they were <true, ...> / <., true, ...>
+PERIODIC = re.compile(r"k_wrap_cell|k_graph_(count|fill)<[^()]*umx::Cells<|k_graph_count<true|k_graph_fill<(true|false), true")
 
 
 def stats(path, evaluations):
@@ -31,7 +33,7 @@ def stats(path, evaluations):
     with open(path, newline="") as f:
         for row in csv.DictReader(f):
             if PERIODIC.search(row["Name"]):
-                name = re.search(r"k_\w+(<[^>]*>)?", row["Name"]).group(0)
+                name = re.search(r"k_\w+[^(]*", row["Name"]).group(0).replace("umx::", "")
                 rows.append((name, int(row["Calls"]), float(row["TotalDurationNs"])))
                 total += float(row["TotalDurationNs"])
     for name, calls, ns in sorted(rows):
