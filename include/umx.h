@@ -464,7 +464,10 @@ int umx_debug_keep(umx_engine* eng, int on);
 /* umx_debug_fetch also answers, on demand and without umx_debug_keep: "weights:w", "weights:dw", "weights:bw" -- the three weight arenas
  * as they are on the device (float32 data section, float32 derived weights, 16-bit plane copies); "weights:table" -- the tensor table of
  * "weights:w" as text, one "<name> <first float> <floats>" per line; "experts:kernel_ms" -- one float, the milliseconds between the events
- * around the merge and packing kernels of the last umx_set_expert_coefficients.                                                          */
+ * around the merge and packing kernels of the last umx_set_expert_coefficients; "gemm:table" -- the table of plane-GEMM instantiations as
+ * text, one "<family> <cplx> <wide> <ls> <al> <half>" per row; "gemm:launches" -- one line per plane-GEMM launch of the most recent
+ * evaluation's last chunk, in launch order: "fwd|rev <the six key fields> <M> <N> <K> <blocks>" (recorded only while umx_debug_keep is on,
+ * cleared when a chunk starts).                                                                                                         */
 
 #ifdef __cplusplus
 }

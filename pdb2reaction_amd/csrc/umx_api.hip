@@ -652,13 +652,24 @@ int umx_profile_read(umx_engine* eng, umx_profile_stats* out, int reset) {
 int umx_debug_keep(umx_engine* eng, int on) {
   if (!eng) return UMX_ERR_ARG;
   eng->dbg_on = on != 0;
-  if (!on) eng->dbg.clear();
+  if (!on) { eng->dbg.clear(); eng->gemm_log.clear(); }
   return UMX_OK;
 }
 
 int umx_debug_fetch(umx_engine* eng, const char* name, void* host_buf, size_t capacity, size_t* nbytes_out) {
   if (!eng || !name) return UMX_ERR_ARG;
   const std::string nm(name);
+  if (nm == "gemm:table" || nm == "gemm:launches") {
+    // text, host side only: the rows of pl_kernels ("fam cplx wide ls al half"), and the gemm_pl launches of the most recent evaluation's
+    // last chunk in launch order ("fwd|rev fam cplx wide ls al half M N K blocks"; recorded while umx_debug_keep is on)
+    const std::string text = nm == "gemm:table" ? pl_table_text() : eng->gemm_log;
+    if (nbytes_out) *nbytes_out = text.size();
+    if (host_buf) {
+      if (capacity < text.size()) return fail(eng, UMX_ERR_ARG, "umx_debug_fetch: buffer too small");
+      std::memcpy(host_buf, text.data(), text.size());
+    }
+    return UMX_OK;
+  }
   if (nm.rfind("weights:", 0) == 0 || nm.rfind("experts:", 0) == 0) {
     // fetched on demand: the three weight arenas as they are on the device, the tensor table of d_w ("<name> <first float> <floats>" per
     // line), and the kernel time of the last umx_set_expert_coefficients (one float, milliseconds between its two events)

@@ -350,6 +350,7 @@ struct umx_engine {
   size_t prof_used = 0;
   bool dbg_on = false;
   std::map<std::string, std::vector<char>> dbg;
+  std::string gemm_log;          // umx_debug_fetch "gemm:launches": one line per gemm_pl launch of the last chunk, kept while dbg_on
 };
 
 namespace {

@@ -157,6 +157,17 @@ const PlKernel pl_kernels[] = {
 };
 #undef UMX_Q
 #undef UMX_Q4
+// a key as text, "fam cplx wide ls al half" (umx_debug_fetch "gemm:table", "gemm:launches")
+std::string pl_key_text(const PlKey& k) {
+  static const char* const fam[] = {"Q_F16", "Q_BF16", "PL3_ROWS", "PL3", "PL2_WIDE", "PL2_M16", "PL2_M32"};
+  return std::string(fam[k.fam]) + " " + std::to_string(k.cplx) + " " + std::to_string(k.wide) + " " + std::to_string(k.ls) + " " + std::to_string(k.al) + " " +
+         std::to_string(k.half);
+}
+std::string pl_table_text() {
+  std::string t;
+  for (const PlKernel& e : pl_kernels) t += pl_key_text(e.key) + "\n";
+  return t;
+}
 
 // which instantiation runs one product, with which grid and which leading dimensions (in 2-byte units)
 // (prec: ProfRec::prec -- 24: two fp16 planes, 4 products; 3 / 2: bf16 planes, 6 / 3 products; err: the product has no instantiation)
@@ -252,6 +263,9 @@ int gemm_pl(umx_engine* eng, int cplx, Pass pass, const unsigned short* Apl, int
   CHK(prof_open(eng, &pr, cplx ? 8.0 * M * (double)N * K : 2.0 * M * (double)N * K, c.prec, M, N, K, 9, cplx));
   hipLaunchKernelGGL(k->fn, dim3(c.blocks), dim3(c.key.half ? 256 : 512), 0, eng->stream, q);
   HIPCHK(eng, hipGetLastError());
+  if (eng->dbg_on)
+    eng->gemm_log += std::string(pass == FWD ? "fwd " : "rev ") + pl_key_text(c.key) + " " + std::to_string(M) + " " + std::to_string(N) + " " + std::to_string(K) + " " +
+                     std::to_string(c.blocks) + "\n";
   return prof_close(eng, pr);
 }
 

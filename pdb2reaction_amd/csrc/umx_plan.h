@@ -164,6 +164,7 @@ struct ChunkCtx {
 // K1 graph: row pointers, edge list, out-lists, frames, element pairs
 int graph_build(const ChunkCtx& c, const WS& w) {
   UMX_STAGE(c);
+  eng->gemm_log.clear();                        // a chunk starts here: "gemm:launches" names the last chunk's launches
   launch_scan(s, c.d_deg, nn, w.row_ptr, w.stats);
   if (c.pinned) launch_graph_replay(eng, s, c.d_pos, c.nimg, c.pin_e0, c.pin_ecnt, w.esrc, w.edst, w.evec, c.img0);
   else launch_graph_fill(eng, s, c.may_trunc, c.d_pos, nn, c.d_cand, w.row_ptr, w.esrc, w.edst, w.evec, c.g_lo, c.g_hi, c.img0);

@@ -38,6 +38,7 @@ from oracle.staged import silu_grad
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import gemm_ledger as GL  # noqa: E402
 import test_gpu_edge_links as EL  # noqa: E402
 from test_gpu_edge_links import HG, RAD, ROW, SIZES, T64, U, XROT, Graph, Report, _t, gamma, host_ulps, ratio  # noqa: E402
 from test_gpu_reverse_links import _unblock  # noqa: E402
@@ -524,6 +525,7 @@ def _case(mode, size, monkeypatch):
         eng.debug_keep(True)
         e, _ = eng.energy_forces(pos.astype(np.float32), forces=False)
         assert np.all(np.isfinite(e))
+        assert GL.keys(eng, fwd=True) == GL.KEYS_FORWARD_LINKS[(mode, size)], sorted(GL.keys(eng))      # the table rows this case holds (the ledger)
         print()
         _CASES[(mode, size)] = replay_case(mode, size, lambda name, dtype=np.float32: eng.debug_fetch(name, dtype), z, orc, w)
     finally:

@@ -34,6 +34,7 @@ from oracle.staged import ln_silu_bwd
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import gemm_ledger as GL  # noqa: E402
 import mfma_model as MM  # noqa: E402
 from test_reverse_precision_cpu import TWO_PLANE, U, kappa, link_stats, t24  # noqa: E402
 
@@ -94,7 +95,7 @@ def _engine_run(precision, n_atoms, layers, monkeypatch):
         eng.set_system(z)
         eng.debug_keep(True)
         eng.energy_forces(pos.astype(np.float32), forces=True)
-        cap = {}
+        cap = {"gemm:keys": GL.keys(eng, fwd=False)}
         for name in keep:
             try:
                 cap[name] = eng.debug_fetch(name)
@@ -192,6 +193,7 @@ def test_reverse_links_against_float64(mode, size, monkeypatch):
     layers = LAYERS[size]
     w, cap = _engine_run(mode, SIZES[size], layers, monkeypatch)
     ne = cap[f"g_hid.{layers[0]}"].size // ROW
+    assert cap["gemm:keys"] == GL.KEYS_REVERSE_LINKS[(mode, size)], sorted(cap["gemm:keys"])     # the table rows this case holds (the ledger)
     print(f"\n[{mode} {size}] ne = {ne} (ne % 256 = {ne % 256}, ne % 4 = {ne % 4}), radial tiles of 64 edges: {(ne + 63) // 64}")
     # ---- coverage preconditions (a change to synth or to gemm_pl's dispatch must not drop them silently)
     regimes = {}
