@@ -310,13 +310,49 @@ int umx_energy_forces_f64_dev(umx_engine* eng, int n_images, const double* d_pos
  * umx_set_cell / umx_set_cells keep the pin while the pbc flags are those of pin time (the translations follow the new cells) and unpin
  * otherwise; umx_gp_begin[_virial] refuse while a graph is pinned; pinning while a graph-parallel evaluation is in progress is refused;
  * a non-finite reference position is refused.  A failed pin leaves the previous state (pinned or not).  Pinning again replaces the pin.
- * Not provided: a pin for the graph-parallel entries, automatic re-pinning or a skin criterion, one graph per image of a batch.
+ * Not provided: a pin for the graph-parallel entries, automatic re-pinning or a skin criterion.
  * Corresponds to: what the reference's hessian_calc_mode="Analytical" differentiates -- autograd at the graph of the geometry it was
  * given (uma_pysis.py:394-417).                                                                                                      */
 int umx_pin_graph(umx_engine* eng, const float* pos_ang);
 int umx_pin_graph_f64(umx_engine* eng, const double* pos_ang);
 int umx_unpin_graph(umx_engine* eng);
 int umx_pinned_graph(const umx_engine* eng, int64_t* n_edges, int32_t* max_degree);
+
+/* PINNED GRAPHS PER IMAGE (additive to ABI v10; opt-in).  A batch of DIFFERENT images -- the images of a string, one geometry per cell of a
+ * variable-cell scan, finite differences at reactant, transition state and product -- wants one fixed edge set per image, not one for all.
+ * umx_pin_graphs[_f64]: pos_ang is [n_refs][n_atoms][3] float32 (float64), HOST pointer.  Every reference gets exactly the graph an
+ * evaluation of it builds, with the radius, max_neigh, cell and pbc flags in force, all of them in ONE batched graph build (the kernels of
+ * an ordinary evaluation of that batch).  Kept per reference what umx_pin_graph keeps of its one: source, target and translation index of
+ * every directed edge, the rows' order, the degrees, the wrap offsets; the distinct lattice translations are one table for all
+ * references.  Nothing a caller passes is ever used as an index on the device except the reference numbers of umx_pin_assign, which the
+ * host has range-checked.
+ * umx_pin_assign: image k of the evaluations that follow replays reference ref_of_image[k] (HOST pointer, n_images entries); the replay
+ * is that of umx_pin_graph, so image k is bit for bit (E, F, W) what an engine with umx_pin_graph(reference ref_of_image[k]) gives for it
+ * alone -- in any batch, chunking, lane, recompute plan or partition count.  (The GEMM operands alternate the sign of their odd rows,
+ * UMX_ALT_ROWS, so an edge's float32 rounding depends on the parity of its row in the chunk; with several references pinned a chunk
+ * therefore ends behind an odd number of edges and every image starts at an even row, as it does alone.  Batches of odd counts run in
+ * more chunks.  One pinned reference and unpinned batches keep their chunks: there an image behind an odd count differs from the image
+ * alone by that rounding, measured 1e-6 eV.)  n_images == 0 or NULL restores the default:
+ *   - n_refs > 1: identity -- an evaluation has n_refs images, and image k replays reference k;
+ *   - n_refs == 1: every image of any batch replays reference 0.  This is umx_pin_graph, which is umx_pin_graphs(eng, 1, pos_ang).
+ * With an assignment of n entries an evaluation of any other number of images is refused (the rule of umx_set_cells).  Pinning again,
+ * through either entry, resets the assignment to the default.
+ * umx_pinned_graphs: RETURNS the number of pinned references (0: nothing pinned; negative: an error code) and fills n_edges[r] for
+ * r < min(capacity, references) and *max_degree, the largest in-degree among them (either pointer may be NULL).  umx_pinned_graph reports
+ * the total over the references and the same largest in-degree.  umx_last_graph_stats after a pinned evaluation: the sum of the assigned
+ * references' edge counts and the largest in-degree among them; still no device-to-host read in a pinned evaluation.  A reference, an
+ * image, or a whole chunk without edges is allowed.
+ * Rules (UMX_ERR_ARG): as umx_pin_graph, and: several references are refused while umx_set_cells has per-image cells bound (references
+ * are built open or in the one cell of umx_set_cell); after pinning, umx_set_cell / umx_set_cells with the pbc flags of pin time keep
+ * the pins -- image k then takes cell k and reference ref_of_image[k], its translations formed for the cell in force -- and other flags
+ * unpin; umx_set_system unpins; umx_gp_begin[_virial] refuse; an entry of ref_of_image outside [0, n_refs) is refused and the previous
+ * assignment stays; umx_pin_assign with nothing pinned is refused; a non-finite reference coordinate refuses the whole call, names the
+ * reference, and leaves the previous state (pinned or not).
+ * Not provided: pins in the graph-parallel entries; a skin criterion or automatic re-pinning; references built under per-image cells.   */
+int umx_pin_graphs(umx_engine* eng, int n_refs, const float* pos_ang);
+int umx_pin_graphs_f64(umx_engine* eng, int n_refs, const double* pos_ang);
+int umx_pin_assign(umx_engine* eng, int n_images, const int32_t* ref_of_image);
+int umx_pinned_graphs(const umx_engine* eng, int capacity, int64_t* n_edges, int32_t* max_degree);
 
 /* Graph-parallel evaluation of ONE image across several engines / ranks (ABI v5) -- the reference's `workers > 1` semantics
  * (ParallelMLIPPredictUnit: the atoms' graph partitioned over workers, uma_pysis.py:220-242), for single large systems when there are

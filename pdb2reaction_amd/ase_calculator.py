@@ -212,6 +212,28 @@ class UMXCalculator(_AseBase):
         self._last = None                # a result cached without the pin is not the pinned one
         return _Pinned(eng, np.array(atoms.get_positions(), dtype=np.float64), self._dp_kw())
 
+    def pinned_each(self, images, per_image_cells: bool = False):
+        """``with calc.pinned_each(images): e, f = calc.calculate_images(images)`` -- every image pinned at its own geometry
+        (``Engine.pin_graphs``: image k of the calls inside replays the graph of ``images[k]``), all in the cell and pbc flags of the
+        first image, and unpinned on the way out, also on an exception.  The references are built in ONE cell: images that differ in
+        their cell or flags, and ``per_image_cells=True``, raise ``ValueError`` here, before anything is pinned."""
+        from .engine import _Pinned
+
+        if not images:
+            raise ValueError("empty image list")
+        if per_image_cells:
+            raise ValueError("pinned_each: references are built open or in one cell, not under per-image cells (per_image_cells=True)")
+        z0, cell0 = _numbers(images[0]), _cell_pbc(images[0])
+        for im in images[1:]:
+            if not np.array_equal(_numbers(im), z0):
+                raise ValueError("all images must share atom order and elements")
+            if _cell_pbc(im) != cell0:
+                raise ValueError("pinned_each: all images must share the cell and the pbc flags of the first image (the references are built in one cell)")
+        eng = self._ensure(images[0])
+        self._last = None                # a result cached without the pin is not the pinned one
+        refs = np.stack([np.asarray(im.get_positions(), dtype=np.float64) for im in images])
+        return _Pinned(eng, refs, self._dp_kw(), "pin_graphs")
+
     def _stress_kw(self) -> dict:
         """What ``energy_forces_stress`` is called with: the graph-parallel opt-in when this calculator runs a pool of engines."""
         return {"graph_parallel": True} if self.gp_stress and len(self.local_devices or []) > 1 else {}

@@ -93,41 +93,45 @@ int pin_after_cell(umx_engine* eng) {
   return st;
 }
 
-// Build the graph of ONE reference image exactly as an evaluation of it does -- wrapped copy, degree pass, scan, fill -- with the
-// translation of every edge as one more output of the fill, and keep its structure.  Everything that can fail happens on new buffers:
-// a failed pin leaves the previous state.
+// Build the graphs of R reference images exactly as an evaluation of that batch does -- wrapped copy, degree pass, scan, fill -- with the
+// translation of every edge as one more output of the fill, and keep their structure.  Everything that can fail happens on new buffers:
+// a failed pin leaves the previous state.  `who`: the entry (umx_pin_graph is R = 1).
 template <typename P>
-int pin_graph_impl(umx_engine* eng, const P* pos) {
+int pin_graphs_impl(umx_engine* eng, const char* who, int R, const P* pos) {
   if (!eng) return UMX_ERR_ARG;
-  if (eng->need_merge()) return fail(eng, UMX_ERR_ARG, "umx_pin_graph: " NOT_MERGED);
-  if (!eng->have_system) return fail(eng, UMX_ERR_ARG, "umx_pin_graph: bind a system first (umx_set_system)");
-  if (!pos) return fail(eng, UMX_ERR_ARG, "umx_pin_graph: bad arguments");
-  if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_pin_graph: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
-  CHK(periodic_check_images(eng, 1, "umx_pin_graph"));
+  const std::string me(who);
+  if (eng->need_merge()) return fail(eng, UMX_ERR_ARG, me + ": " NOT_MERGED);
+  if (!eng->have_system) return fail(eng, UMX_ERR_ARG, me + ": bind a system first (umx_set_system)");
+  if (!pos || R < 1) return fail(eng, UMX_ERR_ARG, me + ": bad arguments");
+  if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, me + ": a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
+  if (R > 1 && eng->pbc_on && !eng->cells_shared)
+    return fail(eng, UMX_ERR_ARG, me + ": per-image cells are bound (umx_set_cells): several references are built open or in the one cell of umx_set_cell");
+  CHK(periodic_check_images(eng, R, who));
   const int N = eng->natoms;
-  for (long i = 0; i < (long)N * 3; ++i)
-    if (!std::isfinite(pos[i])) return fail(eng, UMX_ERR_ARG, "umx_pin_graph: non-finite position");
+  const long NT = (long)R * N;
+  for (long i = 0; i < NT * 3; ++i)
+    if (!std::isfinite(pos[i])) return fail(eng, UMX_ERR_ARG, me + ": non-finite position (reference " + std::to_string(i / ((long)N * 3)) + ")");
   HIPCHK(eng, hipSetDevice(eng->dev));
   hipStream_t s = eng->stream;
-  HIPCHK(eng, hipStreamSynchronize(s));                              // no evaluation may still be replaying the graph this one replaces
+  HIPCHK(eng, hipStreamSynchronize(s));                              // no evaluation may still be replaying the graphs these replace
   if (eng->ran_on_caller) HIPCHK(eng, hipEventSynchronize(eng->ev_done));
-  if (eng->io_cap < N) CHK(grow(eng, eng->io_cap, (long)N, {s}, {DevBuf(eng->d_io_pos, (size_t)N * 3), DevBuf(eng->d_io_f, (size_t)N * 3)}));
+  if (eng->io_cap < NT) CHK(grow(eng, eng->io_cap, NT, {s}, {DevBuf(eng->d_io_pos, (size_t)NT * 3), DevBuf(eng->d_io_f, (size_t)NT * 3)}));
   P* d_stage;
   if constexpr (std::is_same_v<P, double>) {
-    if (eng->io64_cap < N) CHK(grow(eng, eng->io64_cap, (long)N, {s}, {DevBuf(eng->d_io_pos64, (size_t)N * 3)}));
+    if (eng->io64_cap < NT) CHK(grow(eng, eng->io64_cap, NT, {s}, {DevBuf(eng->d_io_pos64, (size_t)NT * 3)}));
     d_stage = eng->d_io_pos64;
   } else d_stage = eng->d_io_pos;
-  HIPCHK(eng, hipMemcpyAsync(d_stage, pos, (size_t)N * 3 * sizeof(P), hipMemcpyHostToDevice, s));
-  // the ordinary graph of the image: the pin in force (if any) stands aside, and what the engine reports of its last evaluation stays
+  HIPCHK(eng, hipMemcpyAsync(d_stage, pos, (size_t)NT * 3 * sizeof(P), hipMemcpyHostToDevice, s));
+  // the ordinary graph of the batch: the pin in force (if any) stands aside, and what the engine reports of its last evaluation stays
   struct Keep {
     umx_engine* e; bool pin; int64_t edges; int32_t maxdeg; int shifts; bool trunc;
     ~Keep() { e->pin_on = pin; e->last_edges = edges; e->last_maxdeg = maxdeg; e->last_shifts = shifts; e->may_truncate = trunc; }
   } keep{eng, eng->pin_on, eng->last_edges, eng->last_maxdeg, eng->last_shifts, eng->may_truncate};
   eng->pin_on = false;
   PosPtr dp(d_stage);
-  CHK(periodic_prepare(eng, s, 1, &dp));
+  CHK(periodic_prepare(eng, s, R, &dp));
   ImageEdges ie;
-  CHK(degree_pass(eng, s, 1, dp, ie));
+  CHK(degree_pass(eng, s, R, dp, ie));
   const long E = ie.etot;
   const bool trunc = eng->may_truncate;
   // new buffers: source, target, translation (first the packed triple, then its index), wrap offsets; scratch: row_ptr, edge vectors
@@ -140,23 +144,31 @@ int pin_graph_impl(umx_engine* eng, const P* pos) {
   HIPCHK(eng, hipMalloc(&n_src, eb * sizeof(int)));
   HIPCHK(eng, hipMalloc(&n_dst, eb * sizeof(int)));
   HIPCHK(eng, hipMalloc(&n_tix, eb * sizeof(int)));
-  HIPCHK(eng, hipMalloc(&n_wrap, (size_t)N * 3 * sizeof(int)));
-  HIPCHK(eng, hipMalloc(&t_row, ((size_t)N + 3) * sizeof(int)));
+  HIPCHK(eng, hipMalloc(&n_wrap, (size_t)NT * 3 * sizeof(int)));
+  HIPCHK(eng, hipMalloc(&t_row, ((size_t)NT + 3) * sizeof(int)));
   HIPCHK(eng, hipMalloc(&t_evec, eb * 4 * sizeof(float)));
   HIPCHK(eng, hipMemsetAsync(n_tix, 0, eb * sizeof(int), s));
-  HIPCHK(eng, hipMemsetAsync(n_wrap, 0, (size_t)N * 3 * sizeof(int), s));
-  hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, eng->d_deg_all, (long)N, t_row, t_row + N + 1);
-  launch_graph_fill(eng, s, trunc, dp, (long)N, eng->d_cand_all, t_row, n_src, n_dst, t_evec, 0, (long)N, 0, n_tix);
-  launch_wrap_index(eng, s, PosPtr(d_stage), n_wrap);
+  HIPCHK(eng, hipMemsetAsync(n_wrap, 0, (size_t)NT * 3 * sizeof(int), s));
+  hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, eng->d_deg_all, NT, t_row, t_row + NT + 1);
+  launch_graph_fill(eng, s, trunc, dp, NT, eng->d_cand_all, t_row, n_src, n_dst, t_evec, 0, NT, 0, n_tix);
+  if (R > 1 && E > 0) hipLaunchKernelGGL(k_pin_local, dim3(nblk(E, 256)), dim3(256), 0, s, n_src, n_dst, E, N);
+  launch_wrap_index(eng, s, PosPtr(d_stage), R, n_wrap);
   HIPCHK(eng, hipGetLastError());
-  std::vector<int> deg((size_t)N), code(eb);
-  HIPCHK(eng, hipMemcpyAsync(deg.data(), eng->d_deg_all, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
+  std::vector<int> deg((size_t)NT), code(eb);
+  HIPCHK(eng, hipMemcpyAsync(deg.data(), eng->d_deg_all, (size_t)NT * sizeof(int), hipMemcpyDeviceToHost, s));
   if (E > 0) HIPCHK(eng, hipMemcpyAsync(code.data(), n_tix, (size_t)E * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(eng, hipStreamSynchronize(s));
-  std::vector<long> row((size_t)N + 1, 0);
+  // every reference: its rows' prefix sums, its largest in-degree, and where its edges start among all of them
+  std::vector<long> row((size_t)R * (N + 1), 0), e0((size_t)R + 1, 0);
+  std::vector<int> ref_maxdeg((size_t)R, 0);
   int maxdeg = 0;
-  for (int i = 0; i < N; ++i) { row[i + 1] = row[i] + deg[i]; maxdeg = std::max(maxdeg, deg[i]); }
-  if (row[N] != E) return fail(eng, UMX_ERR_HIP, "umx_pin_graph: the degrees and the edge count of the reference graph disagree");
+  for (int r = 0; r < R; ++r) {
+    long* rw = row.data() + (size_t)r * (N + 1);
+    for (int i = 0; i < N; ++i) { rw[i + 1] = rw[i] + deg[(size_t)r * N + i]; ref_maxdeg[r] = std::max(ref_maxdeg[r], deg[(size_t)r * N + i]); }
+    if (rw[N] != ie.per_image[r]) return fail(eng, UMX_ERR_HIP, me + ": the degrees and the edge count of reference " + std::to_string(r) + " disagree");
+    e0[(size_t)r + 1] = e0[r] + rw[N];
+    maxdeg = std::max(maxdeg, ref_maxdeg[r]);
+  }
   // the distinct translations, in ascending order of their packed triple, and every edge's index among them
   std::vector<unsigned> codes;
   if (eng->pbc_on && E > 0) {
@@ -166,14 +178,18 @@ int pin_graph_impl(umx_engine* eng, const P* pos) {
     HIPCHK(eng, hipMemcpy(n_tix, code.data(), (size_t)E * sizeof(int), hipMemcpyHostToDevice));
   }
   CHK(pin_upload_shifts(eng, codes, &n_shifts, &n_shifts_cap));
-  // nothing below fails: the new graph replaces the old one
+  // nothing below fails: the new graphs replace the old ones
   bufs.drop = false;
-  void* old[] = {eng->d_pin_src, eng->d_pin_dst, eng->d_pin_tix, eng->d_pin_wrap, eng->d_pin_shifts, eng->d_pin_deg, t_row, t_evec};
+  void* old[] = {eng->d_pin_src, eng->d_pin_dst, eng->d_pin_tix, eng->d_pin_wrap, eng->d_pin_shifts, eng->d_pin_deg, eng->d_pin_img, t_row, t_evec};
   for (void* q : old) if (q) (void)hipFree(q);
   eng->d_pin_src = n_src; eng->d_pin_dst = n_dst; eng->d_pin_tix = n_tix; eng->d_pin_wrap = n_wrap;
   eng->d_pin_shifts = n_shifts; eng->pin_shifts_cap = n_shifts_cap;
-  eng->d_pin_deg = nullptr; eng->pin_deg_imgs = 0;
+  eng->d_pin_deg = nullptr; eng->d_pin_img = nullptr; eng->pin_deg_imgs = 0;
+  eng->pin_dev_for.clear(); eng->pin_cur.clear();
+  eng->pin_assign.clear();                                           // pinning again: the default assignment
+  eng->pin_refs = R;
   eng->pin_deg = std::move(deg); eng->pin_row = std::move(row); eng->pin_codes = std::move(codes);
+  eng->pin_ref_e0 = std::move(e0); eng->pin_ref_maxdeg = std::move(ref_maxdeg);
   eng->pin_edges = E; eng->pin_maxdeg = maxdeg;
   eng->pin_pbc_on = eng->pbc_on;
   for (int k = 0; k < 3; ++k) eng->pin_pbc[k] = eng->pbc_on ? eng->pbc[k] : 0;
@@ -244,7 +260,7 @@ int umx_destroy(umx_engine* eng) {
   (void)hipSetDevice(eng->dev);
   (void)hipStreamSynchronize(eng->stream);
   for (auto& r : eng->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-  void* ptrs[] = {eng->d_w, eng->d_dw, eng->d_bw, eng->d_gmu, eng->d_z, eng->d_sysemb, eng->arena, eng->d_deg_all, eng->d_cand_all, eng->d_img_edges, eng->d_io_pos, eng->d_io_e, eng->d_io_f, eng->d_flags, eng->d_dtab, eng->d_part_deg, eng->d_part_f, eng->d_ex, eng->d_mjobs, eng->d_pjobs, eng->d_mx, eng->d_cells, eng->d_shifts_pk, eng->d_wrap, eng->d_wrap64, eng->d_lats, eng->d_io_pos64, eng->d_vir_part, eng->d_vir_wp, eng->d_io_w, eng->d_pin_src, eng->d_pin_dst, eng->d_pin_tix, eng->d_pin_wrap, eng->d_pin_deg, eng->d_pin_shifts};
+  void* ptrs[] = {eng->d_w, eng->d_dw, eng->d_bw, eng->d_gmu, eng->d_z, eng->d_sysemb, eng->arena, eng->d_deg_all, eng->d_cand_all, eng->d_img_edges, eng->d_io_pos, eng->d_io_e, eng->d_io_f, eng->d_flags, eng->d_dtab, eng->d_part_deg, eng->d_part_f, eng->d_ex, eng->d_mjobs, eng->d_pjobs, eng->d_mx, eng->d_cells, eng->d_shifts_pk, eng->d_wrap, eng->d_wrap64, eng->d_lats, eng->d_io_pos64, eng->d_vir_part, eng->d_vir_wp, eng->d_io_w, eng->d_pin_src, eng->d_pin_dst, eng->d_pin_tix, eng->d_pin_wrap, eng->d_pin_deg, eng->d_pin_img, eng->d_pin_shifts};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   (void)hipStreamSynchronize(eng->stream2);
   (void)hipEventDestroy(eng->ev_fork); (void)hipEventDestroy(eng->ev_join);
@@ -568,8 +584,29 @@ int umx_set_cells(umx_engine* eng, int n_images, const double* cells, const int 
 }
 int umx_last_graph_shifts(const umx_engine* eng) { return eng ? eng->last_shifts : 0; }
 
-int umx_pin_graph(umx_engine* eng, const float* pos_ang) { return pin_graph_impl(eng, pos_ang); }
-int umx_pin_graph_f64(umx_engine* eng, const double* pos_ang) { return pin_graph_impl(eng, pos_ang); }
+int umx_pin_graph(umx_engine* eng, const float* pos_ang) { return pin_graphs_impl(eng, "umx_pin_graph", 1, pos_ang); }
+int umx_pin_graph_f64(umx_engine* eng, const double* pos_ang) { return pin_graphs_impl(eng, "umx_pin_graph", 1, pos_ang); }
+int umx_pin_graphs(umx_engine* eng, int n_refs, const float* pos_ang) { return pin_graphs_impl(eng, "umx_pin_graphs", n_refs, pos_ang); }
+int umx_pin_graphs_f64(umx_engine* eng, int n_refs, const double* pos_ang) { return pin_graphs_impl(eng, "umx_pin_graphs", n_refs, pos_ang); }
+int umx_pin_assign(umx_engine* eng, int n_images, const int32_t* ref_of_image) {
+  if (!eng) return UMX_ERR_ARG;
+  if (!eng->pin_on) return fail(eng, UMX_ERR_ARG, "umx_pin_assign: nothing is pinned (umx_pin_graphs)");
+  if (n_images < 0) return fail(eng, UMX_ERR_ARG, "umx_pin_assign: bad arguments");
+  if (n_images == 0 || !ref_of_image) { eng->pin_assign.clear(); return UMX_OK; }
+  for (int k = 0; k < n_images; ++k)
+    if (ref_of_image[k] < 0 || ref_of_image[k] >= eng->pin_refs)
+      return fail(eng, UMX_ERR_ARG, "umx_pin_assign: image " + std::to_string(k) + " names reference " + std::to_string(ref_of_image[k]) + ", but " +
+                  std::to_string(eng->pin_refs) + " are pinned");
+  eng->pin_assign.assign(ref_of_image, ref_of_image + n_images);
+  return UMX_OK;
+}
+int umx_pinned_graphs(const umx_engine* eng, int capacity, int64_t* n_edges, int32_t* max_degree) {
+  if (!eng) return UMX_ERR_ARG;
+  const int R = eng->pin_on ? eng->pin_refs : 0;
+  for (int r = 0; r < R && r < capacity && n_edges; ++r) n_edges[r] = (int64_t)eng->pin_ref_edges(r);
+  if (max_degree) *max_degree = R ? (int32_t)eng->pin_maxdeg : 0;
+  return R;
+}
 int umx_unpin_graph(umx_engine* eng) {
   if (!eng) return UMX_ERR_ARG;
   pin_clear(eng);

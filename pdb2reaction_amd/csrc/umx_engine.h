@@ -331,19 +331,29 @@ struct umx_engine {
   float* d_wrap = nullptr; long wrap_cap = 0;   // positions wrapped into the cell: the copy the graph kernels read
   double* d_wrap64 = nullptr; long wrap64_cap = 0;   // the same for double positions, wrapped in float64
   int last_shifts = 0;             // lattice translations the most recent evaluation searched (umx_last_graph_shifts; 0: open boundaries)
-  // pinned graph (umx_pin_graph): the edge set of one reference image, replayed for every image while pin_on (k_graph_replay).  Persistent
-  // buffers, a few bytes per reference edge; the host keeps the degrees, so a pinned evaluation plans without reading anything back
+  // pinned graphs (umx_pin_graph / umx_pin_graphs): the edge sets of the reference images, one of them replayed for every image while
+  // pin_on (k_graph_replay).  Persistent buffers, a few bytes per reference edge, the references one behind the other; the host keeps the
+  // degrees, so a pinned evaluation plans without reading anything back
   bool pin_on = false;
-  long pin_edges = 0; int pin_maxdeg = 0;          // directed edges and largest in-degree of the reference
+  int pin_refs = 0;                                // references pinned (1: umx_pin_graph)
+  long pin_edges = 0; int pin_maxdeg = 0;          // directed edges of all references together and the largest in-degree among them
   bool pin_pbc_on = false; int pin_pbc[3] = {0, 0, 0};   // the boundary conditions of pin time (other flags unpin)
-  std::vector<int> pin_deg;                        // [natoms] in-degrees
-  std::vector<long> pin_row;                       // [natoms + 1] their prefix sums: target-node partitions take contiguous edge ranges
-  std::vector<unsigned> pin_codes;                 // the distinct lattice translations of the reference edges, packed as in the table's w
+  std::vector<long> pin_ref_e0;                    // [pin_refs + 1] where a reference's edges start in d_pin_src / dst / tix
+  std::vector<int> pin_ref_maxdeg;                 // [pin_refs] largest in-degree of every reference
+  std::vector<int> pin_deg;                        // [pin_refs][natoms] in-degrees
+  std::vector<long> pin_row;                       // [pin_refs][natoms + 1] their prefix sums within the reference: target-node partitions take contiguous edge ranges
+  std::vector<unsigned> pin_codes;                 // the distinct lattice translations of all reference edges, packed as in the table's w
+  std::vector<int> pin_assign;                     // umx_pin_assign: the reference of image k; empty = the default (pin_resolve)
+  std::vector<int> pin_cur;                        // the reference of every image of the evaluation at hand
+  std::vector<int> pin_dev_for;                    // the references d_pin_deg / d_pin_img hold, image by image
   int *d_pin_src = nullptr, *d_pin_dst = nullptr;  // [pin_edges] source / target atom of every edge, rows in the reference's order
   int* d_pin_tix = nullptr;                        // [pin_edges] index into pin_codes
-  int* d_pin_wrap = nullptr;                       // [natoms][3] the wrap offsets of pin time
-  int* d_pin_deg = nullptr; long pin_deg_imgs = 0; // the degrees repeated for pin_deg_imgs images: what k_scan reads for a chunk
+  int* d_pin_wrap = nullptr;                       // [pin_refs][natoms][3] the wrap offsets of pin time
+  int* d_pin_deg = nullptr; long pin_deg_imgs = 0; // the assigned references' degrees, image by image, room for pin_deg_imgs images: what k_scan reads for a chunk
+  PinImage* d_pin_img = nullptr;                   // [pin_deg_imgs] what the replay reads of every image of a call (grown with d_pin_deg)
   float4* d_pin_shifts = nullptr; long pin_shifts_cap = 0;   // [cells in force][pin_codes] translation vectors (pin_upload_shifts)
+  long pin_ref_edges(int r) const { return pin_ref_e0[(size_t)r + 1] - pin_ref_e0[(size_t)r]; }
+  const long* pin_row_of(int r) const { return pin_row.data() + (size_t)r * ((size_t)natoms + 1); }
   bool may_truncate = true;      // the largest degree of the evaluation being planned reaches max_neigh: k_graph_fill takes its truncating (LDS) form
   bool prof_on = false;
   std::vector<ProfRec> prof;

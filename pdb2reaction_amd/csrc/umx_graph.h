@@ -337,7 +337,7 @@ __global__ __launch_bounds__(1024) void k_scan(const int* __restrict__ deg, long
 // every candidate up to it; then (both forms) every lane counts the kept candidates of its source over the active translations, a
 // prefix sum over the lanes gives its first slot, and it writes them in translation order.  More than GF_MAXC candidates under a
 // binding cap: the degree pass has refused.
-// TOUT = true (cells only; the pinning call umx_pin_graph alone): etr[slot] receives the translation the edge took, as the bits of its
+// TOUT = true (cells only; the pinning calls umx_pin_graph / umx_pin_graphs alone): etr[slot] receives the translation the edge took, as the bits of its
 // table entry's w ((na + 8) | (nb + 8) << 8 | (nc + 8) << 16).
 // ------------------------------------------------------------------------------------------------
 template <bool TRUNC, bool TOUT, typename P, typename B>
@@ -446,41 +446,63 @@ __global__ __launch_bounds__(256) void k_graph_fill(const P* __restrict__ pos, i
 }
 
 // ------------------------------------------------------------------------------------------------
-// Pinned graph (umx_pin_graph): the edge set of ONE reference image, kept and replayed for every image of every evaluation while the
-// pin holds.  Per directed edge of the reference the engine keeps the source and the target (atom indices within the image), and an
-// index into the distinct lattice translations the reference edges took; per atom the integer wrap offset n of pin time (k_wrap_index).
+// Pinned graphs (umx_pin_graph / umx_pin_graphs): the edge sets of R reference images, kept, and one of them replayed for every image
+// of every evaluation while the pin holds.  Per directed edge of a reference the engine keeps the source and the target (atom indices
+// within the image), and an index into the distinct lattice translations the reference edges took (one list for all references); per
+// atom of every reference the integer wrap offset n of pin time (k_wrap_index).  The references' edges lie one behind the other.
 //
-// The replay: one thread per edge of the chunk.  Reference edges [e0, e0 + ecnt) -- all of them, or the contiguous rows of one
-// target-node partition -- are written for each of the chunk's images: output edge k * ecnt + (e - e0) of image k gets source and target
-// with the image's node offset, and the edge vector r_src + t - r_dst of the image's positions: open_delta, or pbc_delta on positions
-// shifted by the stored wrap offsets in the image's cell (wrap_by), with the translation read from pshift -- [cells][nd] entries the
-// host forms with the routine that fills the translation table, so at the pin-time cell they are the table's bits.  No cutoff test,
-// no ranking: an edge that has grown beyond the cutoff stays, k_edge_geom gives it envelope 0.
+// The replay: one thread per edge of the chunk, ONE launch per chunk.  img[k] says of image k of the chunk which reference it replays,
+// where that reference's edges start (src0), how many they are (cnt), and where the image's edges start among those of the call (out0:
+// the chunk's own offsets are out0 - img[0].out0).  Images differ in their edge counts, so a thread finds its image by a binary search
+// for the last k with out0 - img[0].out0 <= its edge: an image without edges shares its offset with its successor and is never found,
+// and a chunk without edges launches nothing.  A target-node partition (one image; sub_cnt >= 0) replays the contiguous rows of its
+// reference that start sub0 edges into it instead.  Output edge out0 + (e - src0) gets source and target with the image's node offset,
+// and the edge vector r_src + t - r_dst of the image's positions: open_delta, or pbc_delta on positions shifted by the stored wrap
+// offsets in the image's cell (wrap_by), with the translation read from pshift -- [cells][nd] entries the host forms with the routine
+// that fills the translation table, so at the pin-time cell they are the table's bits.  No cutoff test, no ranking: an edge that has
+// grown beyond the cutoff stays, k_edge_geom gives it envelope 0.
 // flag: bit 1 of the sticky status word for a non-finite coordinate, as k_graph_count sets it.
 // ------------------------------------------------------------------------------------------------
+struct PinImage {
+  long long out0;         // edges of the call's images before this one
+  long long src0;         // the first edge of the image's reference in psrc / pdst / ptix
+  int cnt, ref;           // the reference's edges; the reference (its wrap offsets: pwrap + ref * natoms * 3)
+};
 template <typename P, typename B>
-__global__ __launch_bounds__(256) void k_graph_replay(const P* __restrict__ pos, int natoms, long e0, long ecnt, long total,
-                                                      const int* __restrict__ psrc, const int* __restrict__ pdst, const int* __restrict__ ptix,
+__global__ __launch_bounds__(256) void k_graph_replay(const P* __restrict__ pos, int natoms, const PinImage* __restrict__ img, int nimg, long sub0, long sub_cnt,
+                                                      long total, const int* __restrict__ psrc, const int* __restrict__ pdst, const int* __restrict__ ptix,
                                                       const int* __restrict__ pwrap, const float4* __restrict__ pshift, int nd,
                                                       int* __restrict__ esrc, int* __restrict__ edst, float* __restrict__ evec, int* __restrict__ flag,
                                                       const B cells) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
-  const long img = i / ecnt;
-  const long e = e0 + (i - img * ecnt);
+  int k = 0;
+  long at = i;                                     // the edge within its image
+  if (sub_cnt < 0) {
+    const long long first = img[0].out0;
+    int hi = nimg;                                 // the last k in [0, nimg) with img[k].out0 - first <= i
+    while (hi - k > 1) {
+      const int mid = (k + hi) >> 1;
+      if (img[mid].out0 - first <= (long long)i) k = mid; else hi = mid;
+    }
+    at = i - (long)(img[k].out0 - first);
+  }
+  const PinImage im = img[k];
+  const long e = (long)im.src0 + (sub_cnt < 0 ? 0 : sub0) + at;
   const int js = psrc[e], jd = pdst[e];
-  const long base = img * natoms;
+  const long base = (long)k * natoms;
   const P* ps = pos + (base + js) * 3;
   const P* pd = pos + (base + jd) * 3;
   P sx = ps[0], sy = ps[1], sz = ps[2], xi = pd[0], yi = pd[1], zi = pd[2];
   if (!(isfinite(sx) && isfinite(sy) && isfinite(sz) && isfinite(xi) && isfinite(yi) && isfinite(zi))) atomicOr(flag, 2);
   float dx, dy, dz;
   if constexpr (is_periodic<B>) {
-    const int cell = cell_index(cells, img);
+    const int cell = cell_index(cells, k);
     const float4 sh = pshift[(long)cell * nd + ptix[e]];
     const auto& lat = lattice_of(cells, cell);
-    const P ws[3] = {(P)pwrap[js * 3 + 0], (P)pwrap[js * 3 + 1], (P)pwrap[js * 3 + 2]};
-    const P wd[3] = {(P)pwrap[jd * 3 + 0], (P)pwrap[jd * 3 + 1], (P)pwrap[jd * 3 + 2]};
+    const int* wrap = pwrap + (long)im.ref * natoms * 3;
+    const P ws[3] = {(P)wrap[js * 3 + 0], (P)wrap[js * 3 + 1], (P)wrap[js * 3 + 2]};
+    const P wd[3] = {(P)wrap[jd * 3 + 0], (P)wrap[jd * 3 + 1], (P)wrap[jd * 3 + 2]};
     wrap_by(lat, ws, sx, sy, sz);
     wrap_by(lat, wd, xi, yi, zi);
     const P pj[3] = {sx, sy, sz};
@@ -489,6 +511,13 @@ __global__ __launch_bounds__(256) void k_graph_replay(const P* __restrict__ pos,
     dx = open_delta(sx, xi); dy = open_delta(sy, yi); dz = open_delta(sz, zi);
   }
   store_edge(esrc, edst, evec, i, (int)(base + js), (int)(base + jd), dx, dy, dz, dist2_f(dx, dy, dz));
+}
+// the pinning call, several references: the fill wrote sources and targets as nodes of the batch -- back to atoms within their image
+__global__ void k_pin_local(int* __restrict__ src, int* __restrict__ dst, long ne, int natoms) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= ne) return;
+  const int base = (dst[e] / natoms) * natoms;
+  src[e] -= base; dst[e] -= base;
 }
 
 // CSR by SOURCE (out-edges), valid for any graph (max_neigh truncation makes it asymmetric): count, scan (k_scan), fill

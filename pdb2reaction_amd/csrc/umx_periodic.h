@@ -245,12 +245,13 @@ void launch_graph_fill(umx_engine* eng, hipStream_t s, bool trunc, PosPtr d_pos,
     });
   });
 }
-// the wrap offsets of the reference image of a pin (d_pos: the caller's positions, not the wrapped copy); open boundaries: out stays zero
-void launch_wrap_index(umx_engine* eng, hipStream_t s, PosPtr d_pos, int* out) {
-  const long N = eng->natoms;
+// the wrap offsets of the nref reference images of a pin (d_pos: the caller's positions, not the wrapped copy; the one shared cell); open
+// boundaries: out stays zero
+void launch_wrap_index(umx_engine* eng, hipStream_t s, PosPtr d_pos, long nref, int* out) {
+  const long nt = nref * eng->natoms;
   with_boundary(eng, d_pos, 0, [&](auto* pos, auto cells) {
     if constexpr (is_periodic<decltype(cells)>)
-      hipLaunchKernelGGL((k_wrap_index<pos_t<decltype(pos)>>), dim3(nblk(N, 256)), dim3(256), 0, s, pos, out, N, eng->natoms, cells);
+      hipLaunchKernelGGL((k_wrap_index<pos_t<decltype(pos)>>), dim3(nblk(nt, 256)), dim3(256), 0, s, pos, out, nt, eng->natoms, cells);
   });
 }
 
@@ -273,14 +274,15 @@ int pin_upload_shifts(umx_engine* eng, const std::vector<unsigned>& codes, float
   return UMX_OK;
 }
 
-// the replay of the pinned graph for the nimg images d_pos starts at: reference edges [e0, e0 + ecnt) of each (k_graph_replay)
-void launch_graph_replay(umx_engine* eng, hipStream_t s, PosPtr d_pos, long nimg, long e0, long ecnt, int* esrc, int* edst, float* evec, long img0) {
-  const long total = nimg * ecnt;
+// the replay of the pinned graphs for the nimg images d_pos starts at, `total` edges in all (k_graph_replay): img describes them one by
+// one; sub_cnt >= 0: one image, rows of its reference that start sub0 edges into it (a target-node partition).  Nothing to write: no launch
+void launch_graph_replay(umx_engine* eng, hipStream_t s, PosPtr d_pos, long nimg, const PinImage* img, long sub0, long sub_cnt, long total, int* esrc, int* edst,
+                         float* evec, long img0) {
   if (total <= 0) return;
   with_boundary(eng, d_pos, img0, [&](auto* pos, auto cells) {
-    hipLaunchKernelGGL((k_graph_replay<pos_t<decltype(pos)>, decltype(cells)>), dim3(nblk(total, 256)), dim3(256), 0, s, pos, eng->natoms, e0, ecnt, total,
-                       eng->d_pin_src, eng->d_pin_dst, eng->d_pin_tix, eng->d_pin_wrap, eng->d_pin_shifts, (int)eng->pin_codes.size(), esrc, edst, evec,
-                       eng->d_flags, cells);
+    hipLaunchKernelGGL((k_graph_replay<pos_t<decltype(pos)>, decltype(cells)>), dim3(nblk(total, 256)), dim3(256), 0, s, pos, eng->natoms, img, (int)nimg, sub0,
+                       sub_cnt, total, eng->d_pin_src, eng->d_pin_dst, eng->d_pin_tix, eng->d_pin_wrap, eng->d_pin_shifts, (int)eng->pin_codes.size(), esrc, edst,
+                       evec, eng->d_flags, cells);
   });
 }
 

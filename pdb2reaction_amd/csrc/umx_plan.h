@@ -150,8 +150,9 @@ struct ChunkCtx {
   long img0;                     // the index within the call of the chunk's first image (d_pos, d_deg, d_cand and the outputs start there; per-image cells are indexed by it)
   bool gp;                       // graph-parallel: partial sums over this rank's edges + exchange points
   long g_lo, g_hi;               // ... of the targets [g_lo, g_hi)
-  bool pinned;                   // pinned graph: the reference edges this chunk replays per image -- all of them, or the contiguous rows
-  long pin_e0, pin_ecnt;         // [g_lo, g_hi) of a partition
+  bool pinned;                   // pinned graphs: what the replay reads of the chunk's images (pin_img), all edges of every image's reference --
+  const PinImage* pin_img;       // or (pin_cnt >= 0: a partition, one image) the contiguous rows [g_lo, g_hi) of its reference, which start
+  long pin_sub0, pin_cnt;        // pin_sub0 edges into it
   bool may_trunc;                // some node of this call has more candidates than max_neigh (known on the host)
   bool rc;                       // recompute plan: one activation slot (carve_acts), replayed layer by layer in the reverse pass
   bool fused_rev;                // k_modrot_bwd_pl produces g_xn itself (fp32 mode with debug captures: the unfused kernels, which expose xrot / g_xrot)
@@ -166,7 +167,7 @@ int graph_build(const ChunkCtx& c, const WS& w) {
   UMX_STAGE(c);
   eng->gemm_log.clear();                        // a chunk starts here: "gemm:launches" names the last chunk's launches
   launch_scan(s, c.d_deg, nn, w.row_ptr, w.stats);
-  if (c.pinned) launch_graph_replay(eng, s, c.d_pos, c.nimg, c.pin_e0, c.pin_ecnt, w.esrc, w.edst, w.evec, c.img0);
+  if (c.pinned) launch_graph_replay(eng, s, c.d_pos, c.nimg, c.pin_img, c.pin_sub0, c.pin_cnt, ne, w.esrc, w.edst, w.evec, c.img0);
   else launch_graph_fill(eng, s, c.may_trunc, c.d_pos, nn, c.d_cand, w.row_ptr, w.esrc, w.edst, w.evec, c.g_lo, c.g_hi, c.img0);
   HIPCHK(eng, hipMemsetAsync(w.out_cur, 0, (nn + 1) * sizeof(int), s));
   if (ne > 0) UMX_LAUNCH(k_out_count, nblk(ne, 256), w.esrc, ne, w.out_cur);
@@ -518,8 +519,9 @@ void plan_chunk(umx_engine* eng, WS& w, const PosPtr d_pos, const int* d_deg, co
                 float* d_forces, Plan& P, const VirialOut vir = VirialOut()) {
   const bool gp = eng->gp, pinned = eng->pin_on;
   const long nn = nimg * eng->natoms, g_lo = gp ? eng->gp_lo : 0, g_hi = gp ? eng->gp_hi : nn;
-  const long pin_e0 = pinned && gp ? eng->pin_row[g_lo] : 0, pin_ecnt = pinned ? (gp ? eng->pin_row[g_hi] - pin_e0 : eng->pin_edges) : 0;
-  const ChunkCtx c{eng, nn, ne, nimg, img0, gp, g_lo, g_hi, pinned, pin_e0, pin_ecnt, eng->may_truncate, eng->rc_active && d_forces != nullptr,
+  const long* pin_row = pinned && gp ? eng->pin_row_of(eng->pin_cur[(size_t)img0]) : nullptr;      // (a partition: of the image's own reference)
+  const long pin_sub0 = pin_row ? pin_row[g_lo] : 0, pin_cnt = pin_row ? pin_row[g_hi] - pin_sub0 : -1;
+  const ChunkCtx c{eng, nn, ne, nimg, img0, gp, g_lo, g_hi, pinned, pinned ? eng->d_pin_img + img0 : nullptr, pin_sub0, pin_cnt, eng->may_truncate, eng->rc_active && d_forces != nullptr,
                    eng->prec.planes || !eng->dbg_on, d_pos, d_deg, d_cand, d_energy, d_forces, vir};
   plan_graph(P, w, c);
   for (int i = 0; i < NL; ++i) plan_layer_fwd(P, w, c, i);
@@ -644,6 +646,21 @@ int read_degree_pass(umx_engine* eng, hipStream_t s, const int* d_cnt, size_t n,
   return fail(eng, UMX_ERR_RANGE, std::string("the previous device-pointer evaluation produced a non-finite energy") + eng->prec.range_hint());
 }
 
+// The reference every image of a pinned evaluation of K images replays.  An assignment (umx_pin_assign) holds for exactly its own number
+// of images; without one, several references are replayed one per image, in order, and a single reference by every image of any batch.
+int pin_resolve(umx_engine* eng, long K, std::vector<int>& out) {
+  const long R = eng->pin_refs, A = (long)eng->pin_assign.size();
+  if (A > 0 && K != A)
+    return fail(eng, UMX_ERR_ARG, "umx_energy_forces: " + std::to_string(K) + " images, but umx_pin_assign assigned references to " + std::to_string(A) +
+                " (entry k belongs to image k: assign one reference per image, or restore the default with umx_pin_assign(eng, 0, NULL))");
+  if (A == 0 && R > 1 && K != R)
+    return fail(eng, UMX_ERR_ARG, "umx_energy_forces: " + std::to_string(K) + " images, but " + std::to_string(R) + " graphs are pinned and image k replays "
+                "reference k by default: evaluate one image per reference, or say which reference each image replays (umx_pin_assign)");
+  if (A > 0) out = eng->pin_assign;
+  else { out.resize((size_t)K); for (long k = 0; k < K; ++k) out[k] = R > 1 ? (int)k : 0; }
+  return UMX_OK;
+}
+
 // directed edges per image of the batch at hand, and what the planning below asks of them
 // (per_image: [K], the largest degree behind them; emax / etot: the largest image's edges, all edges)
 struct ImageEdges { std::vector<int> per_image; long emax = 0, etot = 0; };
@@ -653,19 +670,41 @@ int degree_pass(umx_engine* eng, hipStream_t s, long K, const PosPtr d_pos, Imag
   const int N = eng->natoms;
   const long nt = K * N;
   if (eng->pin_on) {
-    // pinned graph: every image has the reference's edges; nothing is launched and nothing read back.  (Only a call of more images
-    // than any before it extends the repeated degrees k_scan reads.)
-    if (eng->pin_deg_imgs < K) {
-      std::vector<int> rep((size_t)nt);
-      for (long k = 0; k < K; ++k) std::copy(eng->pin_deg.begin(), eng->pin_deg.end(), rep.begin() + k * N);
-      CHK(grow(eng, eng->pin_deg_imgs, K, {s, eng->stream2}, {DevBuf(eng->d_pin_deg, (size_t)nt)}));
-      HIPCHK(eng, hipMemcpy(eng->d_pin_deg, rep.data(), rep.size() * sizeof(int), hipMemcpyHostToDevice));
+    // pinned graphs: every image has the edges of its reference; nothing is launched and nothing read back.  (Only a call whose
+    // images replay other references than the device copies hold image by image -- after a pin or umx_pin_assign, or more images than
+    // any call before it -- writes the degrees k_scan reads and the table of the replay anew.)
+    CHK(pin_resolve(eng, K, eng->pin_cur));
+    const std::vector<int>& a = eng->pin_cur;
+    if ((long)eng->pin_dev_for.size() < K || !std::equal(a.begin(), a.end(), eng->pin_dev_for.begin())) {
+      std::vector<int> deg((size_t)nt);
+      std::vector<PinImage> img((size_t)K);
+      long long out0 = 0;
+      for (long k = 0; k < K; ++k) {
+        std::copy(eng->pin_deg.begin() + (size_t)a[k] * N, eng->pin_deg.begin() + ((size_t)a[k] + 1) * N, deg.begin() + k * N);
+        img[k] = PinImage{out0, (long long)eng->pin_ref_e0[a[k]], (int)eng->pin_ref_edges(a[k]), a[k]};
+        out0 += img[k].cnt;
+      }
+      eng->pin_dev_for.clear();
+      // no earlier evaluation may still be reading what is replaced or overwritten
+      for (hipStream_t q : {s, eng->stream2}) HIPCHK(eng, hipStreamSynchronize(q));
+      HIPCHK(eng, hipEventSynchronize(eng->ev_done));
+      if (eng->pin_deg_imgs < K) CHK(grow(eng, eng->pin_deg_imgs, K, {}, {DevBuf(eng->d_pin_deg, (size_t)nt), DevBuf(eng->d_pin_img, (size_t)K)}));
+      HIPCHK(eng, hipMemcpy(eng->d_pin_deg, deg.data(), deg.size() * sizeof(int), hipMemcpyHostToDevice));
+      HIPCHK(eng, hipMemcpy(eng->d_pin_img, img.data(), img.size() * sizeof(PinImage), hipMemcpyHostToDevice));
+      eng->pin_dev_for = a;
     }
-    ie.per_image.assign((size_t)K + 1, (int)eng->pin_edges);
-    ie.per_image[K] = eng->pin_maxdeg;
-    eng->last_maxdeg = eng->pin_maxdeg;
+    ie.per_image.assign((size_t)K + 1, 0);
+    ie.emax = ie.etot = 0;
+    int maxdeg = 0;
+    for (long k = 0; k < K; ++k) {
+      const long e = eng->pin_ref_edges(a[k]);
+      ie.per_image[k] = (int)e;
+      ie.emax = std::max(ie.emax, e); ie.etot += e;
+      maxdeg = std::max(maxdeg, eng->pin_ref_maxdeg[a[k]]);
+    }
+    ie.per_image[K] = maxdeg;
+    eng->last_maxdeg = maxdeg;
     eng->may_truncate = false;
-    ie.emax = eng->pin_edges; ie.etot = K * eng->pin_edges;
     eng->last_edges = ie.etot;
     return UMX_OK;
   }
@@ -700,16 +739,20 @@ int eval_partitioned(umx_engine* eng, hipStream_t s, long img, const PosPtr d_po
   std::vector<long> lo(P), hi(P);
   std::vector<int> cnt;
   if (eng->pin_on) {
-    // pinned graph: partition p takes the rows [lo, hi) of the reference -- its degrees there, zero elsewhere -- and the host knows the counts
+    // pinned graphs: partition p takes the rows [lo, hi) of the image's reference -- its degrees there, zero elsewhere -- and the host
+    // knows the counts
+    const int ref = eng->pin_cur[(size_t)img];
+    const long* row = eng->pin_row_of(ref);
+    const int* ref_deg = eng->d_pin_deg + (size_t)img * N;
     cnt.assign((size_t)P + 1, 0);
     for (int p = 0; p < P; ++p) {
       lo[p] = (long)N * p / P; hi[p] = (long)N * (p + 1) / P;
       int* deg = eng->d_part_deg + (size_t)(2 * p) * N;
       HIPCHK(eng, hipMemsetAsync(deg, 0, (size_t)N * sizeof(int), s));
-      if (hi[p] > lo[p]) HIPCHK(eng, hipMemcpyAsync(deg + lo[p], eng->d_pin_deg + lo[p], (size_t)(hi[p] - lo[p]) * sizeof(int), hipMemcpyDeviceToDevice, s));
-      cnt[p] = (int)(eng->pin_row[hi[p]] - eng->pin_row[lo[p]]);
+      if (hi[p] > lo[p]) HIPCHK(eng, hipMemcpyAsync(deg + lo[p], ref_deg + lo[p], (size_t)(hi[p] - lo[p]) * sizeof(int), hipMemcpyDeviceToDevice, s));
+      cnt[p] = (int)(row[hi[p]] - row[lo[p]]);
     }
-    cnt[P] = eng->pin_maxdeg;
+    cnt[P] = eng->pin_ref_maxdeg[ref];
     eng->may_truncate = false;
   } else {
   HIPCHK(eng, hipMemsetAsync(d_cnt, 0, (P + 1) * sizeof(int), s));
@@ -850,9 +893,14 @@ struct Chunks { std::vector<std::pair<long, long>> img; long need_nodes = 0, nee
 int plan_chunks(umx_engine* eng, long K, const ImageEdges& ie, long cap, size_t budget, Chunks& c) {
   const int N = eng->natoms;
   c = Chunks();
+  // Several pinned references: image k is promised to be, bit for bit, its evaluation alone.  The GEMM producers negate the operand rows
+  // of odd index (umx_kernels_pl.h, sign-alternating rows), so the rounding of an edge depends on the parity of its row in the chunk:
+  // an image never starts at an odd row -- behind an odd number of edges the chunk ends.  (Alone, an image starts at row 0.)
+  const bool even_rows = eng->pin_on && eng->pin_refs > 1;
   for (long k0 = 0; k0 < K;) {
     long k1 = k0, e = 0;
     while (k1 < K && (k1 - k0) < cap) {
+      if (even_rows && (e & 1)) break;
       const long e2 = e + ie.per_image[k1];
       if (k1 > k0 && ws_bytes(eng, (k1 - k0 + 1) * N, e2) > budget) break;
       e = e2; ++k1;
@@ -931,8 +979,8 @@ int run_chunks(umx_engine* eng, hipStream_t s, int lanes, const ImageEdges& ie, 
     for (long k = k0; k < k1; ++k) e += ie.per_image[k];
     VirialOut vir;       // the partials' slots follow the image's position in the call: the two lanes never share one
     if (eng->vir_out && d_forces) { vir.out = eng->vir_out + k0 * 9; vir.part = eng->d_vir_part + k0 * eng->vir_slabs * 9; vir.slabs = eng->vir_slabs; }
-    // (pinned graph: every image has the reference's degrees -- the repeated copy from its start; no candidate counts)
-    plan_chunk(eng, wl[lane], d_pos.atom(k0 * N), eng->pin_on ? eng->d_pin_deg : eng->d_deg_all + k0 * N, eng->pin_on ? nullptr : eng->d_cand_all + k0 * N, k0, k1 - k0, e, d_energy + k0,
+    // (pinned graphs: every image has its reference's degrees; no candidate counts)
+    plan_chunk(eng, wl[lane], d_pos.atom(k0 * N), (eng->pin_on ? eng->d_pin_deg : eng->d_deg_all) + k0 * N, eng->pin_on ? nullptr : eng->d_cand_all + k0 * N, k0, k1 - k0, e, d_energy + k0,
                d_forces ? d_forces + k0 * N * 3 : nullptr, P, vir);
   };
   if (lanes == 2) {          // chunks in pairs, one per lane, matrix segments alternating between the lanes (run_plans_alternating)

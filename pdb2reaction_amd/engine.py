@@ -95,6 +95,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "umx_pin_graph_f64": ([vp, dp], i32),
         "umx_unpin_graph": ([vp], i32),
         "umx_pinned_graph": ([vp, i64p, C.POINTER(C.c_int32)], i32),
+        "umx_pin_graphs": ([vp, i32, fp], i32),
+        "umx_pin_graphs_f64": ([vp, i32, dp], i32),
+        "umx_pin_assign": ([vp, i32, C.POINTER(C.c_int32)], i32),
+        "umx_pinned_graphs": ([vp, i32, i64p, C.POINTER(C.c_int32)], i32),
         "umx_last_partitions": ([vp], i32),
         "umx_last_lanes": ([vp], i32),
         "umx_set_recompute": ([vp, i32], i32),
@@ -143,13 +147,14 @@ EXPORTED_SYMBOLS = (
     "umx_set_expert_coefficients", "umx_expert_count", "umx_set_recompute", "umx_last_recompute", "umx_workspace_bytes",
     "umx_set_cell", "umx_set_cells", "umx_last_graph_shifts", "umx_energy_forces_virial", "umx_energy_forces_virial_dev",
     "umx_gp_begin_virial", "umx_pin_graph", "umx_unpin_graph", "umx_pinned_graph",
+    "umx_pin_graphs", "umx_pin_assign", "umx_pinned_graphs",
 )
 # The float64-position entries, listed apart: tests/test_boundary_cpu.py holds EXPORTED_SYMBOLS to the names it reads out of the header
 # with a pattern of letters and underscores, which a name with a digit in it does not match.  load_library declares (and so demands)
 # these like every other entry; tests/test_double_positions_cpu.py holds them to the header.  build() in __graft_entry__.py and
 # test_library_exports_every_declared_symbol in tests/test_boundary_cpu.py iterate EXPORTED_SYMBOLS only, so neither sees these two: once that
 # test's pattern admits digits, fold the two lists into one.
-EXPORTED_SYMBOLS_F64 = ("umx_energy_forces_f64", "umx_energy_forces_f64_dev", "umx_pin_graph_f64")
+EXPORTED_SYMBOLS_F64 = ("umx_energy_forces_f64", "umx_energy_forces_f64_dev", "umx_pin_graph_f64", "umx_pin_graphs_f64")
 
 
 def workspace_bytes(n_nodes: int, n_edges: int, parts: int = 0, recompute: int = 0, engine: Optional["Engine"] = None) -> int:
@@ -220,7 +225,8 @@ class Engine:
         self.dataset_list = tuple(W.DATASET_LIST)      # order of the rows of the loaded blob's dataset_embedding.weight (load_weights)
         self._cells = None              # (cells (K,3,3) float64, pbc flags (3,)) set_cells accepted last; it and _cell exclude each other
         self._cell = None               # (cell (3,3) float64, pbc flags (3,)) the engine accepted last (set_cell), None for open boundaries
-        self._pin = None                # (reference positions (N,3), double_positions, pbc flags | None) of the graph pinned now, else None
+        self._pin = None                # (reference positions (N,3) | (R,N,3) of pin_graphs, double_positions, pbc flags | None) of the graph(s) pinned now, else None
+        self._pin_assign = None         # the assignment given to pin_assign last (a tuple), None for the default
         if precision is not None:
             self._chk(self.lib.umx_set_precision(self._h, precision.encode()), "umx_set_precision")
         if recompute is not None:
@@ -296,7 +302,7 @@ class Engine:
                   "umx_set_system")
         self.natoms = len(z)
         self._system = (z.copy(), int(charge), int(spin), task, radius, max_neigh)
-        self._pin = None                # umx_set_system unpins
+        self._pin = self._pin_assign = None      # umx_set_system unpins
 
     def set_cell(self, cell=None, pbc=None):
         """Periodic boundary conditions (``umx_set_cell``): ``cell`` (3,3) lattice vectors as rows in Angstrom, ``pbc`` one flag per axis
@@ -358,12 +364,59 @@ class Engine:
             self._chk(self.lib.umx_pin_graph_f64(self._h, p.ctypes.data_as(C.POINTER(C.c_double))), "umx_pin_graph_f64")
         else:
             self._chk(self.lib.umx_pin_graph(self._h, p.ctypes.data_as(C.POINTER(C.c_float))), "umx_pin_graph")
-        self._pin = (p[0].copy(), bool(double_positions), self._pbc_flags())
+        self._pin, self._pin_assign = (p[0].copy(), bool(double_positions), self._pbc_flags()), None
+
+    def pin_graphs(self, refs, double_positions: bool = False, assign=None):
+        """Pin one neighbour graph per reference image (``umx_pin_graphs`` / ``umx_pin_graphs_f64``): ``refs`` (R,N,3) Angstrom, each
+        reference built as ``pin_graph`` builds its one, all in one batched graph build, open or in the one cell of ``set_cell``
+        (``UmxError`` while ``set_cells`` has per-image cells bound).  Image k of the evaluations that follow replays the edge set of
+        reference ``assign[k]`` (``pin_assign``); without an assignment, reference k when R > 1 -- an evaluation then has R images --
+        and reference 0 for every image of any batch when R == 1, which is ``pin_graph``.  A refused pin leaves the previous state."""
+        p = self._positions(refs, double_positions)
+        if double_positions:
+            self._chk(self.lib.umx_pin_graphs_f64(self._h, p.shape[0], p.ctypes.data_as(C.POINTER(C.c_double))), "umx_pin_graphs_f64")
+        else:
+            self._chk(self.lib.umx_pin_graphs(self._h, p.shape[0], p.ctypes.data_as(C.POINTER(C.c_float))), "umx_pin_graphs")
+        self._pin, self._pin_assign = (p.copy(), bool(double_positions), self._pbc_flags()), None      # pinning resets the assignment
+        if assign is not None:
+            try:
+                self.pin_assign(assign)
+            except Exception:
+                self.unpin_graph()
+                raise
+
+    def pin_assign(self, assign=None):
+        """Which reference image k of the evaluations that follow replays (``umx_pin_assign``): a sequence of reference indices, one
+        per image -- evaluations of any other number of images are then refused -- or ``None`` for the default (``pin_graphs``).  An
+        entry outside [0, R) raises ``UmxError`` and the previous assignment stays."""
+        if assign is None or len(assign) == 0:
+            self._chk(self.lib.umx_pin_assign(self._h, 0, None), "umx_pin_assign")
+            self._pin_assign = None
+            return
+        a = np.ascontiguousarray(assign, dtype=np.int32).reshape(-1)
+        self._chk(self.lib.umx_pin_assign(self._h, len(a), a.ctypes.data_as(C.POINTER(C.c_int32))), "umx_pin_assign")
+        self._pin_assign = tuple(int(x) for x in a)
 
     def unpin_graph(self):
         """Back to a graph rebuilt from the positions of every evaluation (``umx_unpin_graph``), bit for bit what it was."""
         self._chk(self.lib.umx_unpin_graph(self._h), "umx_unpin_graph")
-        self._pin = None
+        self._pin = self._pin_assign = None
+
+    def pinned_graphs(self) -> Optional[Tuple[Tuple[int, ...], int]]:
+        """(directed edges of every pinned reference, largest in-degree among them) (``umx_pinned_graphs``), or None when nothing is pinned."""
+        if getattr(self, "_pin", None) is None:
+            return None
+        md = C.c_int32()
+        n = int(self.lib.umx_pinned_graphs(self._h, 0, None, C.byref(md)))
+        if n < 0:
+            self._chk(n, "umx_pinned_graphs")
+        ne = (C.c_int64 * max(n, 1))()
+        self.lib.umx_pinned_graphs(self._h, n, ne, C.byref(md))
+        return tuple(int(ne[r]) for r in range(n)), int(md.value)
+
+    def pinned_each(self, refs, assign=None, double_positions: bool = False):
+        """``with engine.pinned_each(refs, assign): ...`` -- ``pin_graphs`` for the block, ``unpin_graph()`` on the way out, also on an exception."""
+        return _Pinned(self, refs, dict(dp_kw(double_positions), assign=assign), "pin_graphs")
 
     def pinned_graph(self) -> Optional[Tuple[int, int]]:
         """(directed edges, largest in-degree) of the pinned graph (``umx_pinned_graph``), or None when nothing is pinned."""
@@ -380,7 +433,7 @@ class Engine:
     def _pin_follow(self):
         """After ``set_cell`` / ``set_cells``: the engine dropped the pin when the pbc flags are no longer those of pin time."""
         if getattr(self, "_pin", None) is not None and self._pbc_flags() != self._pin[2]:
-            self._pin = None
+            self._pin = self._pin_assign = None
 
     def _pbc_flags(self):
         """The pbc flags in force (a tuple of three bools), None for open boundaries."""
@@ -507,10 +560,13 @@ class Engine:
         self.precision, self.widened = wider, True
         self.load_weights(self._blob)
         z, charge, spin, task, radius, max_neigh = self._system
-        pin = getattr(self, "_pin", None)
+        pin, assign = getattr(self, "_pin", None), getattr(self, "_pin_assign", None)
         self.set_system(z, charge, spin, task, radius, max_neigh)
-        if pin is not None:             # set_system unpinned: the same graph again (the graph does not depend on the arithmetic)
-            self.pin_graph(pin[0], double_positions=pin[1])
+        if pin is not None:             # set_system unpinned: the same graph(s) again (a graph does not depend on the arithmetic)
+            if pin[0].ndim == 3:
+                self.pin_graphs(pin[0], double_positions=pin[1], assign=assign)
+            else:
+                self.pin_graph(pin[0], double_positions=pin[1])
         return True
 
     def energy_forces_dev(self, n_images: int, d_pos: int, d_energy: int, d_forces: Optional[int], stream: int = 0, double_positions: bool = False):
@@ -632,13 +688,14 @@ class Engine:
 
 
 class _Pinned:
-    """Context manager behind ``Engine.pinned`` / ``LocalEnginePool.pinned`` / ``UMXCalculator.pinned``: pin on entry, unpin on exit."""
+    """Context manager behind ``pinned`` (``how="pin_graph"``) and ``pinned_each`` (``"pin_graphs"``) of ``Engine``, ``LocalEnginePool`` and
+    ``UMXCalculator``: pin on entry, unpin on exit."""
 
-    def __init__(self, target, pos_ang, kw: dict):
-        self.target, self.pos, self.kw = target, pos_ang, kw
+    def __init__(self, target, pos_ang, kw: dict, how: str = "pin_graph"):
+        self.target, self.pos, self.kw, self.how = target, pos_ang, kw, how
 
     def __enter__(self):
-        self.target.pin_graph(self.pos, **self.kw)
+        getattr(self.target, self.how)(self.pos, **self.kw)
         return self.target
 
     def __exit__(self, *exc):

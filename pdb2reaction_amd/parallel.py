@@ -465,6 +465,9 @@ class LocalEnginePool:
         self._cells_on = [None] * len(self.engines)   # what engine r has bound of them: its block (lo, hi), or "single" for cells[0] alone
         self.recompute = None                   # what ``create`` / ``set_recompute`` gave every engine (None: the engines' own setting)
         self._pinned = False                    # a graph is pinned on every engine (``pin_graph``): a single geometry goes to engine 0 alone
+        self._pin_refs = 0                      # references pinned on every engine (``pin_graphs``; 1: ``pin_graph``)
+        self._pin_assign = None                 # the reference of image k of a call (``pin_assign``), None: the engines' default
+        self._assign_on = [None] * len(self.engines)   # the slice of the assignment engine r holds now (a tuple), None: its default
         if len(set(self.devices)) < len(self.devices):
             free = free_bytes or (lambda d: torch.cuda.mem_get_info(d)[0])
             for eng, lim in zip(self.engines, shared_workspace_limits(self.devices, free)):
@@ -517,7 +520,7 @@ class LocalEnginePool:
             eng.set_system(atomic_numbers, **kw)
         self.natoms = len(atomic_numbers)
         self._gp_buf = self._gp_wbuf = None
-        self._pinned = False                    # (umx_set_system unpins)
+        self._unpinned()                        # (umx_set_system unpins)
 
     # ---- pinned neighbour graph ----------------------------------------------------------------------------------------------------
     def pin_graph(self, pos_ang, double_positions: bool = False) -> None:
@@ -534,9 +537,80 @@ class LocalEnginePool:
         except Exception:
             for eng in done:
                 eng.unpin_graph()
-            self._pinned = False
+            self._unpinned()
             raise
-        self._pinned = True
+        self._unpinned()
+        self._pinned, self._pin_refs = True, 1
+
+    def _unpinned(self) -> None:
+        self._pinned, self._pin_refs, self._pin_assign, self._assign_on = False, 0, None, [None] * len(self.engines)
+
+    def pin_graphs(self, refs, double_positions: bool = False, assign=None) -> None:
+        """``Engine.pin_graphs`` on EVERY engine: each pins all references, so that whichever block of a batch an engine is dealt, the
+        references its images name are there.  ``assign`` as ``pin_assign``.  Routing and failure as ``pin_graph``."""
+        from .engine import dp_kw
+
+        r_count = int(np.asarray(refs).shape[0]) if np.asarray(refs).ndim == 3 else 1
+        done = []
+        try:
+            for eng in self.engines:
+                eng.pin_graphs(refs, **dp_kw(double_positions))
+                done.append(eng)
+            self._unpinned()
+            self._pinned, self._pin_refs = True, r_count
+            self.pin_assign(assign)
+        except Exception:
+            for eng in done:
+                eng.unpin_graph()
+            self._unpinned()
+            raise
+
+    def pin_assign(self, assign=None) -> None:
+        """Which reference image k of the calls that follow replays (``Engine.pin_assign``), for the WHOLE call: the pool keeps the
+        assignment and gives every engine the slice of its contiguous block right before that engine evaluates.  ``None``: the
+        default -- reference k for image k when several are pinned, the one reference for every image otherwise.  An entry outside
+        [0, R) raises ``ValueError`` and the previous assignment stays."""
+        if not self._pinned:
+            raise ValueError("pin_assign: nothing is pinned (pin_graphs)")
+        if assign is None or len(assign) == 0:
+            self._pin_assign = None
+            for r, eng in enumerate(self.engines):          # (with one reference nothing is dealt: the engines' own default again)
+                if self._assign_on[r] is not None:
+                    eng.pin_assign(None)
+                    self._assign_on[r] = None
+            return
+        a = tuple(int(x) for x in np.asarray(assign).reshape(-1))
+        if any(x < 0 or x >= self._pin_refs for x in a):
+            raise ValueError(f"pin_assign: entries must lie in [0, {self._pin_refs}), got {a}")
+        self._pin_assign = a
+
+    def _bind_assign(self, k: int, blocks) -> None:
+        """Pinned references: make every engine hold the slice of the call's assignment that belongs to its block (None: one geometry,
+        engine 0 alone).  The call's assignment is the one of ``pin_assign``, else reference k for image k when several are pinned."""
+        if not self._pinned or (self._pin_assign is None and self._pin_refs <= 1):
+            return
+        a = self._pin_assign if self._pin_assign is not None else tuple(range(self._pin_refs))
+        if len(a) != k:
+            raise ValueError(f"{k} images, but " + (f"pin_assign assigned references to {len(a)}" if self._pin_assign is not None
+                                                      else f"{len(a)} graphs are pinned and image k replays reference k by default"))
+        for r, eng in enumerate(self.engines):
+            lo, hi = (0, 1 if r == 0 else 0) if blocks is None else blocks[r]
+            if hi <= lo or a[lo:hi] == self._assign_on[r]:
+                continue
+            self._assign_on[r] = None
+            eng.pin_assign(a[lo:hi])
+            self._assign_on[r] = a[lo:hi]
+
+    def pinned_graphs(self):
+        """Engine 0's ``pinned_graphs()``: (edges of every reference, max_degree), or None when nothing is pinned."""
+        return self.engines[0].pinned_graphs() if self._pinned else None
+
+    def pinned_each(self, refs, assign=None, double_positions: bool = False):
+        """``with pool.pinned_each(refs, assign): ...`` -- ``pin_graphs`` on every engine for the block, unpinned on the way out, also on
+        an exception."""
+        from .engine import _Pinned, dp_kw
+
+        return _Pinned(self, refs, dict(dp_kw(double_positions), assign=assign), "pin_graphs")
 
     def unpin_graph(self) -> None:
         """``Engine.unpin_graph`` on every engine (all are tried; the first error is raised afterwards)."""
@@ -546,7 +620,7 @@ class LocalEnginePool:
                 eng.unpin_graph()
             except Exception as exc:      # noqa: BLE001
                 first = first or exc
-        self._pinned = False
+        self._unpinned()
         if first is not None:
             raise first
 
@@ -668,6 +742,7 @@ class LocalEnginePool:
         busy = [r for r in range(g) if blocks[r][1] > blocks[r][0]]
         self.last_route, self.last_blocks = "batch", blocks
         self._bind_cells(k, blocks)
+        self._bind_assign(k, blocks)
         for attempt in range(2):
             was_wide = [bool(getattr(eng, "widened", False)) for eng in self.engines]
             res = self._run_all(lambda r: call(self.engines[r], p[blocks[r][0]: blocks[r][1]]), busy)
@@ -695,6 +770,7 @@ class LocalEnginePool:
             if self.gp and len(self.engines) > 1 and self.recompute != 2 and not double_positions and not self._pinned:
                 return self._graph_parallel(p[0], forces)
             self.last_route, self.last_blocks = "single", [(0, 1)]
+            self._bind_assign(1, None)
             return self.engines[0].energy_forces(p, forces=forces, **kw)
         res = self._deal(p, lambda eng, block: eng.energy_forces(block, forces=forces, **kw))
         e = np.concatenate([r[0] for r in res])
@@ -729,6 +805,7 @@ class LocalEnginePool:
                 return self._graph_parallel(p[0], True, virial=True)
             self._bind_cells(1, None)
             self.last_route, self.last_blocks = "single", [(0, 1)]
+            self._bind_assign(1, None)
             return self.engines[0].energy_forces_virial(p, **kw)
         res = self._deal(p, lambda eng, block: eng.energy_forces_virial(block, **kw))
         return tuple(np.concatenate([r[i] for r in res]) for i in range(3))
