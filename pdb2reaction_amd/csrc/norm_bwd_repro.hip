@@ -4,7 +4,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-#include "umx_kernels_pl.h"
 #include "umx_kernels.h"
 using namespace umx;
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e), __FILE__, __LINE__); exit(1); } } while (0)

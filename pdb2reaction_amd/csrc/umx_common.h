@@ -23,6 +23,13 @@ constexpr float LN_EPS = 1e-5f;
 constexpr float DEG_RESCALE = 5.0f;
 constexpr float SQRT3 = 1.7320508075688772f;
 
+// m-primary rows of a node / message: [m0: l0, l1, l2 | m1 re: l1, l2 | m1 im: l1, l2 | m2 re: l2 | m2 im: l2].
+// The radial row (of the 6 x 256 radial weights of conv 1) that modulates m-primary row r: the two parts of an m share one.
+struct RadRow { int of[S]; };
+constexpr RadRow RAD_ROW = {{0, 1, 2, 3, 4, 3, 4, 5, 5}};
+// the degree of m-primary row r > 0 is 1 (else 2): which of the two SO(2) gates scales it
+__host__ __device__ constexpr bool row_is_l1(int r) { return r == 1 || r == 3 || r == 5; }
+
 // Accurate (<= 1 ulp, unbiased) transcendentals on purpose: every atom shares the same weights, so the
 // deterministic error of the fast v_exp/v_rsq approximations does not average out over atoms -- it showed up
 // as a same-sign per-atom energy bias of ~1e-7 eV that grows linearly with N.  These ops live in HBM-bound
@@ -61,6 +68,12 @@ __device__ __forceinline__ float silu_grad_f(float x) {
   const float s = sigmoid_f(x);
   return s * (1.0f + x * (1.0f - s));
 }
+
+// One 64-lane wave per item (edge or node), 4 waves per 256-thread block: the kernel body follows the macro.
+#define UMX_WAVE_ITEM(idx, count)                                                     \
+  const int lane = threadIdx.x & 63;                                                  \
+  const long idx = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6))); \
+  if (idx >= (count)) return;
 
 // Grid-stride forms ("virtual blocks"): the kernel body is the loop body, so ANY grid size does the same work in the same per-item
 // arithmetic order.  Launched with the full grid it is one iteration per wave (as UMX_WAVE_ITEM); launched with a capped grid

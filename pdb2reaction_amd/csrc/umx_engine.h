@@ -24,8 +24,8 @@
 #include "umx_gemm.h"
 #include "umx_gemm_pl.h"
 #include "umx_gemm_q.h"
-#include "umx_kernels_pl.h"
 #include "umx_kernels.h"
+#include "umx_edge.h"
 #include "umx_graph.h"
 #include "umx_radial.h"
 #include "umx_peer.h"
@@ -70,7 +70,7 @@ struct ProfRec { hipEvent_t a, b; double flops; int M, N, K, amode, cplx, prec, 
 struct Precision {
   const char* name = "bf16x3";     // canonical name (umx_precision_mode)
   bool planes = true;              // split-precision plane GEMMs for the large SO(2) / radial linears; false (fp32): fp32 MFMA everywhere
-  int fwd_fmt = 3;                 // forward operand format (QFmt, umx_kernels_pl.h): 1 = two fp16 planes (split-f16),
+  int fwd_fmt = 3;                 // forward operand format (QFmt, umx_edge.h): 1 = two fp16 planes (split-f16),
                                    // 3 = plain float32 quad-row blocks, split into three bf16 planes by the GEMM in registers (bf16x3, split-bf16)
   int rev_planes = 3;              // bf16 planes of the REVERSE-pass operands: 2 (3 products, 16-bit) or 3 (6 products, 24-bit: bf16x3)
   bool fwd_f16() const { return planes && fwd_fmt == 1; }
@@ -213,7 +213,7 @@ struct umx_engine {
                                    // weights' planes in every forward product (free); 1: A's in every forward product; 0: the plain nearest-bf16 leading
                                    // planes of rounds 4-5.  20 000 atoms, four cases (profiles/r06_energy_bias.txt): 0: -9e-7 ... -1.63e-4 eV, 1: -1.3e-5 ...
                                    // +3.9e-5, 2: +4e-7 ... -5.0e-5; c3 step 517.9 / 526.3 / 523.0 ms
-  float odd_sign = -1.0f;          // sign-alternating operand rows (umx_kernels_pl.h): -1 = on (default), +1 = off (UMX_ALT_ROWS=0, dev A/B)
+  float odd_sign = -1.0f;          // sign-alternating operand rows (umx_edge.h): -1 = on (default), +1 = off (UMX_ALT_ROWS=0, dev A/B)
   bool node_ctx = false;           // set around the node-level launches (NodeCtx): only those take the float64-accumulating kernel
   bool node_f64_on = true;         // UMX_NODE_F64=0: node-level linears (atom-wise SO(3) linears, scalar MLP, readout and their transposes) on the
                                    // fp32 MFMA instead of the float64-accumulating kernel (k_gemm_f64acc).  Measured (round 3): the fp32-MFMA form of

@@ -42,7 +42,7 @@ struct GemmPL {
   float conj;
   int M, N, K;       // CPLX: M = edges, N = channels per half
   float cscale;      // fp16-plane kernels only (umx_gemm_q.h, F16 = 1): C = cscale * (A' . B'^T) undoes the power-of-two operand scales
-  float odd_sign;    // +1, or -1 when the producer stored the A rows of ODD index negated (sign-alternating rows, umx_kernels_pl.h): the
+  float odd_sign;    // +1, or -1 when the producer stored the A rows of ODD index negated (sign-alternating rows, umx_edge.h): the
                      // epilogue multiplies the accumulators of odd rows by it, so C is what it would be -- with the matrix core's one-sided
                      // rounding error reversed on every second row.  0 is read as +1 (dev programs that memset the struct).
 };

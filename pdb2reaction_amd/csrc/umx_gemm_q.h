@@ -2,7 +2,7 @@
 //
 //   C[M x N] (fp32) = cscale * sum_{(i,j) in products} A_i[M x K] . B_j[N x K]^T ,   A_i, B_j 16-bit planes (q_use_product below)
 //
-// Two operand formats (producers: umx_kernels_pl.h QFmt; weights: umx_api.hip):
+// Two operand formats (producers: umx_edge.h QFmt; weights: umx_api.hip):
 //   default : IEEE-half planes -- A = 2 planes of 16 x activation (256-B blocks), B = 3 planes of s x weight (exact; 384-B blocks),
 //             4 products on v_mfma_f32_32x32x16_f16
 //   "Q3"    : bf16 planes, 3 x 3 (384-B blocks both sides), 6 products on v_mfma_f32_32x32x16_bf16 (UMX_PRECISION=split-bf16)
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(MW * 128, MW == 4 ? 1 : 2) void umx_gemm_q_kernel(c
   // result shares a binade -- up to half an ulp per column, coherent over all edges, i.e. an energy error that grows with N (NOTES 11).
   // Started from the bias, every rounding of the chain sees edge-dependent low bits and the errors are zero-mean.
   const float cs = F16 ? p.cscale : 1.f;          // a power of two: exact (bf16 planes are unscaled, the multiply folds away)
-  const float cso = p.odd_sign < 0.f ? -cs : cs;  // odd rows: the producer stored them negated (sign-alternating rows, umx_kernels_pl.h); row parity = r & 1
+  const float cso = p.odd_sign < 0.f ? -cs : cs;  // odd rows: the producer stored them negated (sign-alternating rows, umx_edge.h); row parity = r & 1
   f32x16 acc[2][TNW];
   f32x16 low[LS == 2 ? 2 : 1][LS == 2 ? TNW : 1];      // LS = 2 (below)
   if constexpr (LS == 2) {

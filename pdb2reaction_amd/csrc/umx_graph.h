@@ -7,8 +7,7 @@
 // (open boundaries) or Cells<P> (umx_set_cell / umx_set_cells).  The host side is umx_periodic.h.
 #pragma once
 #include <type_traits>
-#include "umx_common.h"
-#include "umx_kernels.h"      // UMX_WAVE_ITEM
+#include "umx_common.h"         // UMX_WAVE_ITEM
 
 namespace umx {
 

@@ -1,6 +1,6 @@
-// umx_kernels.h -- HBM-bound stages of the UMA-S engine: edge frames, gather/rotate, rotate-back +
-// segmented reduction, norms, gates, radial LayerNorm, readout and force assembly.  (The neighbour
-// graph, K1, is umx_graph.h.)
+// umx_kernels.h -- HBM-bound stages of the UMA-S engine: edge frames, the node-level kernels (norms,
+// gates, grid transforms, readout), rotate-back + segmented reduction and force assembly.  (The
+// neighbour graph, K1, is umx_graph.h; the edge links between the GEMMs are umx_edge.h.)
 //
 // Conventions: one 64-lane wave per edge or per node, 4 waves per 256-thread block; a lane owns 2
 // (or 4) adjacent channels so every row access is a coalesced 512-B (1-KiB) segment; edges are
@@ -11,11 +11,6 @@
 #include "umx_common.h"
 
 namespace umx {
-
-#define UMX_WAVE_ITEM(idx, count)                                                     \
-  const int lane = threadIdx.x & 63;                                                  \
-  const long idx = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6))); \
-  if (idx >= (count)) return;
 
 // K2 edge frames: R (R nhat = +y, minimal rotation, flipped branch for nhat_y < -0.9), D2, envelope.
 // Carried in DOUBLE from the float32 unit vector and rounded to float32 once per entry (round 3): the frame formulas are full of
@@ -303,83 +298,8 @@ __global__ __launch_bounds__(256) void k_energy(const float* __restrict__ e_node
 }
 
 // ------------------------------------------------------------------------------------------------
-// edge-level kernels
+// edges -> nodes  (the edge links between the GEMMs are umx_edge.h)
 // ------------------------------------------------------------------------------------------------
-// K7a gather + rotate: xrot[e] = W_e [xn[src] | xn[dst]]   (m-primary rows, 256 channels)
-__global__ __launch_bounds__(256) void k_gather_rotate(const float* __restrict__ xn, const int* __restrict__ esrc,
-                                                       const int* __restrict__ edst, const float* __restrict__ frame,
-                                                       float* __restrict__ xrot, long ne) {
-  UMX_WAVE_ITEM(e, ne)
-  const int c0 = lane * 2;
-  const float* f = frame + e * FRAME;
-  const long js = esrc[e], jd = edst[e];
-  float sx[9], sy[9], dx[9], dy[9];
-#pragma unroll
-  for (int r = 0; r < 9; ++r) {
-    const float2 a = *reinterpret_cast<const float2*>(xn + js * ROW + r * C + c0);
-    const float2 b = *reinterpret_cast<const float2*>(xn + jd * ROW + r * C + c0);
-    sx[r] = a.x; sy[r] = a.y; dx[r] = b.x; dy[r] = b.y;
-  }
-  float* out = xrot + e * XROT;
-  float p[9], q[9];
-  rot_fwd(f, sx, p); rot_fwd(f, sy, q);
-#pragma unroll
-  for (int r = 0; r < 9; ++r) *reinterpret_cast<float2*>(out + r * 2 * C + c0) = make_float2(p[r], q[r]);
-  rot_fwd(f, dx, p); rot_fwd(f, dy, q);
-#pragma unroll
-  for (int r = 0; r < 9; ++r) *reinterpret_cast<float2*>(out + r * 2 * C + C + c0) = make_float2(p[r], q[r]);
-}
-
-// SO(2) gate on the edge hidden state hg = [gate(256) | hpre(9x128)] -> hid (9x128)
-__global__ void k_gate_edge_fwd(const float* __restrict__ hg, float* __restrict__ hid, long ne) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= ne * (H / 4)) return;
-  const long e = i / (H / 4);
-  const int c = (int)(i % (H / 4)) * 4;
-  const float* p = hg + e * HG;
-  const float4 g1 = *reinterpret_cast<const float4*>(p + c), g2 = *reinterpret_cast<const float4*>(p + H + c);
-  const float4 s1 = make_float4(sigmoid_f(g1.x), sigmoid_f(g1.y), sigmoid_f(g1.z), sigmoid_f(g1.w));
-  const float4 s2 = make_float4(sigmoid_f(g2.x), sigmoid_f(g2.y), sigmoid_f(g2.z), sigmoid_f(g2.w));
-  float* o = hid + e * ROW + c;
-#pragma unroll
-  for (int r = 0; r < 9; ++r) {
-    const float4 v = *reinterpret_cast<const float4*>(p + 2 * H + r * H + c);
-    float4 w;
-    if (r == 0) w = make_float4(silu_f(v.x), silu_f(v.y), silu_f(v.z), silu_f(v.w));
-    else {
-      // m-primary degrees: rows {1,3,5} -> l=1, rows {2,4,6,7,8} -> l=2
-      const bool l1 = (r == 1 || r == 3 || r == 5);
-      const float4 s = l1 ? s1 : s2;
-      w = make_float4(v.x * s.x, v.y * s.y, v.z * s.z, v.w * s.w);
-    }
-    *reinterpret_cast<float4*>(o + r * H) = w;
-  }
-}
-
-// backward of the edge gate: ghid (9x128), hg (forward) -> ghg = [ggate | ghpre]
-__global__ void k_gate_edge_bwd(const float* __restrict__ ghid, const float* __restrict__ hg, float* __restrict__ ghg, long ne) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= ne * H) return;
-  const long e = i / H;
-  const int c = (int)(i % H);
-  const float* p = hg + e * HG;
-  const float s1 = sigmoid_f(p[c]), s2 = sigmoid_f(p[H + c]);
-  const float* g = ghid + e * ROW + c;
-  const float* hp = p + 2 * H + c;
-  float* o = ghg + e * HG;
-  o[2 * H + c] = g[0] * silu_grad_f(hp[0]);
-  float a1 = 0.f, a2 = 0.f;
-#pragma unroll
-  for (int r = 1; r < 9; ++r) {
-    const bool l1 = (r == 1 || r == 3 || r == 5);
-    const float gv = g[r * H], hv = hp[r * H];
-    o[2 * H + r * H + c] = gv * (l1 ? s1 : s2);
-    if (l1) a1 += gv * hv; else a2 += gv * hv;
-  }
-  o[c] = a1 * s1 * (1.0f - s1);
-  o[H + c] = a2 * s2 * (1.0f - s2);
-}
-
 // K7b rotate back + segmented reduction over incoming edges: xout[n] = xin[n] + sum_e env_e W_e^T msg_e
 // NROWS = 9 (SO(2) messages, ROW floats per edge) or 3 (edge-degree embedding, m=0 rows only, /5)
 template <int NROWS>
@@ -429,125 +349,6 @@ __global__ __launch_bounds__(256) void k_rotate_back_reduce(const float* __restr
     *reinterpret_cast<float2*>(xout + node * ROW + r * C + c0) = make_float2((float)((double)b.x + ax[r]), (float)((double)b.y + ay[r]));
   }
   }
-}
-
-// backward of K7b: g_msg[e] = scale env_e (W_e g[dst e]) ; dedd[e] += denv_e scale <W g, msg>;
-// tau[e] -= <g_msg, L msg>.   msg has NROWS rows (rows >= NROWS are zero); g_msg stores NROWS rows -- as fp32 rows, or (PLOUT, gmsg is
-// then an unsigned short buffer) as PLP (2 or 3) bf16 planes in the PL layout: the A operand of the split fc3^T GEMM of the edge-degree MLP.
-template <int NROWS, int PLP = 0>
-__global__ __launch_bounds__(256) void k_rotate_back_bwd(const float* __restrict__ gnode, const float* __restrict__ msg,
-                                                         const float* __restrict__ frame, const int* __restrict__ edst,
-                                                         float* __restrict__ gmsg, float* __restrict__ dedd,
-                                                         float* __restrict__ tau, long ne, float div, float odd_sign = 1.0f) {
-  UMX_WAVE_ITEM(e, ne)
-  const int c0 = lane * 2;
-  const float* f = frame + e * FRAME;
-  const long jd = edst[e];
-  float gx[9], gy[9], lx[9], ly[9], mx[9], my[9];
-#pragma unroll
-  for (int r = 0; r < 9; ++r) {
-    const float2 t = *reinterpret_cast<const float2*>(gnode + jd * ROW + r * C + c0);
-    gx[r] = t.x; gy[r] = t.y;
-    if (r < NROWS) { const float2 m = *reinterpret_cast<const float2*>(msg + e * (NROWS * C) + r * C + c0); mx[r] = m.x; my[r] = m.y; }
-    else { mx[r] = 0.f; my[r] = 0.f; }
-  }
-  rot_fwd(f, gx, lx); rot_fwd(f, gy, ly);
-  const float sc = f[34] / div;
-  float s = 0.f, tx = 0.f, ty = 0.f, tz = 0.f;
-#pragma unroll
-  for (int r = 0; r < 9; ++r) {
-    s += lx[r] * mx[r] + ly[r] * my[r];
-    lx[r] *= sc; ly[r] *= sc;
-  }
-  torque_acc(lx, mx, -1.0f, tx, ty, tz);
-  torque_acc(ly, my, -1.0f, tx, ty, tz);
-#pragma unroll
-  for (int r = 0; r < NROWS; ++r) {
-    if (PLP) pl_store2<(PLP ? PLP : 2)>(reinterpret_cast<unsigned short*>(gmsg) + e * (long)(NROWS * C * PLP), r * C + c0, row_sign(e, odd_sign) * lx[r], row_sign(e, odd_sign) * ly[r]);
-    else *reinterpret_cast<float2*>(gmsg + e * (NROWS * C) + r * C + c0) = make_float2(lx[r], ly[r]);
-  }
-  s = wave_sum(s); tx = wave_sum(tx); ty = wave_sum(ty); tz = wave_sum(tz);
-  if (lane == 0) {
-    dedd[e] += f[35] / div * s;
-    tau[e * 4 + 0] += tx; tau[e * 4 + 1] += ty; tau[e * 4 + 2] += tz;
-  }
-}
-
-// backward of the radial modulation: gy1 (9x256, in/out -> gxrot), xrot, rad -> grad (1536); tau += <gxrot, L xrot>
-__global__ __launch_bounds__(256) void k_modulate_bwd(float* __restrict__ gy1, const float* __restrict__ xrot,
-                                                      const float* __restrict__ rad, float* __restrict__ grad,
-                                                      float* __restrict__ tau, long ne) {
-  UMX_WAVE_ITEM(e, ne)
-  const int c0 = lane * 4;
-  float* g = gy1 + e * XROT + c0;
-  const float* x = xrot + e * XROT + c0;
-  const float* rd = rad + e * RAD + c0;
-  float* gr = grad + e * RAD + c0;
-  float4 gv[9], xv[9];
-#pragma unroll
-  for (int r = 0; r < 9; ++r) {
-    gv[r] = *reinterpret_cast<const float4*>(g + r * 2 * C);
-    xv[r] = *reinterpret_cast<const float4*>(x + r * 2 * C);
-  }
-  // radial row of each m-primary row: m0 rows 0,1,2 -> 0,1,2 ; m1 rows (3,4 | 5,6) -> 3,4 ; m2 rows (7 | 8) -> 5
-  float4 rv[6];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) rv[k] = *reinterpret_cast<const float4*>(rd + k * 2 * C);
-  const int ridx[9] = {0, 1, 2, 3, 4, 3, 4, 5, 5};
-  float4 gacc[6];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) gacc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-  for (int r = 0; r < 9; ++r) {
-    const int k = ridx[r];
-    gacc[k].x += gv[r].x * xv[r].x; gacc[k].y += gv[r].y * xv[r].y; gacc[k].z += gv[r].z * xv[r].z; gacc[k].w += gv[r].w * xv[r].w;
-    gv[r].x *= rv[k].x; gv[r].y *= rv[k].y; gv[r].z *= rv[k].z; gv[r].w *= rv[k].w;
-    *reinterpret_cast<float4*>(g + r * 2 * C) = gv[r];
-  }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) *reinterpret_cast<float4*>(gr + k * 2 * C) = gacc[k];
-  float tx = 0.f, ty = 0.f, tz = 0.f;
-  float ga[9], xa[9];
-#pragma unroll
-  for (int comp = 0; comp < 4; ++comp) {
-#pragma unroll
-    for (int r = 0; r < 9; ++r) {
-      ga[r] = comp == 0 ? gv[r].x : comp == 1 ? gv[r].y : comp == 2 ? gv[r].z : gv[r].w;
-      xa[r] = comp == 0 ? xv[r].x : comp == 1 ? xv[r].y : comp == 2 ? xv[r].z : xv[r].w;
-    }
-    torque_acc(ga, xa, 1.0f, tx, ty, tz);
-  }
-  tx = wave_sum(tx); ty = wave_sum(ty); tz = wave_sum(tz);
-  if (lane == 0) { tau[e * 4 + 0] += tx; tau[e * 4 + 1] += ty; tau[e * 4 + 2] += tz; }
-}
-
-// backward of K7a (gather+rotate): g_xn[n] = sum_{e in in(n)} W_e^T gxrot[e][:, dst half] + sum_{e in out(n)} W_e^T gxrot[e][:, src half]
-__global__ __launch_bounds__(256) void k_gather_rotate_bwd(const float* __restrict__ gxrot, const float* __restrict__ frame,
-                                                           const int* __restrict__ row_ptr, const int* __restrict__ out_ptr,
-                                                           const int* __restrict__ out_edge, float* __restrict__ gxn, long nt) {
-  UMX_WAVE_ITEM(node, nt)
-  const int c0 = lane * 2;
-  float ax[9], ay[9];
-#pragma unroll
-  for (int r = 0; r < 9; ++r) { ax[r] = 0.f; ay[r] = 0.f; }
-  float vx[9], vy[9];
-  for (int e = row_ptr[node]; e < row_ptr[node + 1]; ++e) {
-    const float* a = gxrot + (long)e * XROT + C + c0;
-#pragma unroll
-    for (int r = 0; r < 9; ++r) { const float2 t = *reinterpret_cast<const float2*>(a + r * 2 * C); vx[r] = t.x; vy[r] = t.y; }
-    const float* f = frame + (long)e * FRAME;
-    rot_bwd_acc(f, vx, 1.0f, ax); rot_bwd_acc(f, vy, 1.0f, ay);
-  }
-  for (int k = out_ptr[node]; k < out_ptr[node + 1]; ++k) {
-    const long e = out_edge[k];
-    const float* b = gxrot + e * XROT + c0;
-#pragma unroll
-    for (int r = 0; r < 9; ++r) { const float2 t = *reinterpret_cast<const float2*>(b + r * 2 * C); vx[r] = t.x; vy[r] = t.y; }
-    const float* f = frame + e * FRAME;
-    rot_bwd_acc(f, vx, 1.0f, ax); rot_bwd_acc(f, vy, 1.0f, ay);
-  }
-#pragma unroll
-  for (int r = 0; r < 9; ++r) *reinterpret_cast<float2*>(gxn + node * ROW + r * C + c0) = make_float2(ax[r], ay[r]);
 }
 
 // dst = a + b (a may alias dst); graph-parallel mode: residual + the all-reduced sum of the ranks' partial aggregates

@@ -16,7 +16,7 @@ namespace {
 // tests/test_gpu_forward_links.py and test_gpu_edge_links.py the producers.  Odd rows are negated in every split-mode format.
 enum OpFmt {
   OP_QUAD,      // <base>q:  float32 quad-row blocks, rows padded to 4 (bf16x3; the forward operands of split-bf16)
-  OP_HALVES,    // <base>h:  the raw halves of the two-plane fp16 "Q2H" blocks (umx_kernels_pl.h): 4-row-padded rows x columns x 2 (split-f16 forward)
+  OP_HALVES,    // <base>h:  the raw halves of the two-plane fp16 "Q2H" blocks (umx_edge.h): 4-row-padded rows x columns x 2 (split-f16 forward)
   OP_PLANES,    // <base>pl: PL bf16 planes of the rows themselves (the 16-bit reverse operands; the edge-degree fc3^T operand of every split mode)
   OP_ROWS       // <base>:   plain float32 rows (fp32 mode; g_rad of the bf16x3 reverse pass, which the fc3^T GEMM splits in registers)
 };
@@ -31,9 +31,8 @@ int dbg_operand(umx_engine* eng, const char* base, int slot, OpFmt fmt, const vo
 }
 
 // ---- the edge links between the GEMMs ------------------------------------------------------------
-// One launcher per link: it picks the instantiation the precision mode runs, computes the grid, launches on eng->stream and captures the
-// operand it wrote.  (The fp32 mode's own kernels -- k_gather_rotate, k_gate_edge_fwd / _bwd, k_rotate_back_bwd<9> -- are launched by the
-// one-segment fp32 branches of plan_edge_fwd / plan_edge_bwd.)
+// One launcher per link, in every precision mode: it picks the instantiation the mode runs (mode -> operand layout, umx_edge.h), computes
+// the grid, launches on eng->stream and, in the split modes, captures the operand it wrote.
 #define UMX_LAUNCH(kernel, grid, ...) hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, eng->stream, __VA_ARGS__)
 
 // The radial MLP is split into its small layers (one fused kernel: "streaming" work) and the one large fc3 GEMM, so that the two-lane
@@ -52,8 +51,13 @@ int link_radial_head(umx_engine* eng, const WS& w, const RadialW& r, int slot, l
   HIPCHK(eng, hipGetLastError());
   return dbg_operand(eng, "a2", slot, fwd_operand(eng->prec), eng->prec.planes ? (const void*)w.a2pl : (const void*)w.ra, ne, RH);
 }
-// K7a gather + rotate + radial modulation -> y1, conv 1's A operand
-int link_gather_rotate_mod(umx_engine* eng, const WS& w, int i, long ne) {
+// K7a gather + rotate.  Split modes: + the radial modulation -> y1, conv 1's A operand.  fp32: the bare rotation -> xrot (conv 1 reads `rad`)
+int link_gather_rotate(umx_engine* eng, const WS& w, int i, long ne) {
+  if (!eng->prec.planes) {
+    UMX_LAUNCH(k_gather_rotate, nblk(ne, 4), w.xn[i], w.esrc, w.edst, w.frame, w.xrot, ne);
+    HIPCHK(eng, hipGetLastError());
+    return UMX_OK;                             // (xrot is captured with the layer's forward captures, aggregate_fwd)
+  }
   auto k = eng->prec.fwd_fmt == 1 ? k_gather_rotate_mod_q3<1> : k_gather_rotate_mod_q3<3>;
   UMX_LAUNCH(k, vgrid(eng, (nblk(ne, 4) + 7) / 8 * 8), w.xn[i], w.esrc, w.edst, w.frame, w.rad[i], w.y1pl, ne, eng->odd_sign);
   HIPCHK(eng, hipGetLastError());
@@ -61,30 +65,50 @@ int link_gather_rotate_mod(umx_engine* eng, const WS& w, int i, long ne) {
 }
 // gate forward: hg = [gate | hpre] -> hid, conv 2's A operand
 int link_gate_fwd(umx_engine* eng, const WS& w, int i, long ne) {
+  if (!eng->prec.planes) {
+    UMX_LAUNCH(k_gate_edge_fwd, nblk(ne * (H / 4), 256), w.hg[i], w.hid, ne);
+    HIPCHK(eng, hipGetLastError());
+    return UMX_OK;                             // (hid: aggregate_fwd)
+  }
   auto k = eng->prec.fwd_fmt == 1 ? k_gate_edge_fwd_q3<1> : k_gate_edge_fwd_q3<3>;
   UMX_LAUNCH(k, vgrid(eng, nblk(ne, 8)), w.hg[i], w.hidpl, ne, eng->odd_sign);
   HIPCHK(eng, hipGetLastError());
   return dbg_operand(eng, "hid", i, fwd_operand(eng->prec), w.hidpl, ne, ROW);
 }
-// rotate-back backward of a layer: g_xmid (G2) -> g_msg, conv 2^T's A operand (+ dE/dd and the torque of the rotation)
-int link_rotate_back_bwd(umx_engine* eng, const WS& w, int i, long ne) {
-  auto k = eng->prec.rev_quad() ? k_rotate_back_bwd_q3<3> : k_rotate_back_bwd_pl<2>;
-  UMX_LAUNCH(k, vgrid(eng, (nblk(ne, 4) + 7) / 8 * 8), w.G2, w.msg[i], w.frame, w.edst, w.gmsgpl, w.dedd, w.tau, ne, eng->odd_sign);
-  HIPCHK(eng, hipGetLastError());
-  return dbg_operand(eng, "gmsg", i, rev_operand(eng->prec), w.gmsgpl, ne, ROW);
-}
-// ... and of the edge-degree embedding: g_x0 (G0) -> the gradient of the edge-degree radial output, the fc3^T operand.  Split modes: straight
-// into the PL planes of the fc3^T GEMM (gmsgpl is free here), three planes in the bf16x3 mode; else float32 rows in gmsg.
+// rotate-back backward (+ dE/dd and the torque of the rotation).  Of layer `slot`: g_xmid (G2) -> g_msg, conv 2^T's A operand.  Of the
+// edge-degree embedding (slot NL): g_x0 (G0) -> the gradient of the edge-degree radial output, the fc3^T operand -- in the split modes
+// straight into the PL planes of the fc3^T GEMM (gmsgpl is free here), three planes in the bf16x3 mode; else float32 rows in gmsg.
 bool deg_rev_planes(const umx_engine* eng) { return eng->prec.planes && eng->planes.count(eng->rdeg.w3T) != 0; }
-int link_rotate_back_bwd_deg(umx_engine* eng, const WS& w, long ne) {
-  const bool dpl = deg_rev_planes(eng);
-  auto k = !dpl ? k_rotate_back_bwd<3, 0> : eng->prec.rev_planes == 3 ? k_rotate_back_bwd<3, 3> : k_rotate_back_bwd<3, 2>;
-  UMX_LAUNCH(k, nblk(ne, 4), w.G0, w.rad_deg, w.frame, w.edst, dpl ? reinterpret_cast<float*>(w.gmsgpl) : w.gmsg, w.dedd, w.tau, ne, DEG_RESCALE,
-             dpl ? eng->odd_sign : 1.0f);
-  return dpl ? dbg_operand(eng, "grad", NL, OP_PLANES, w.gmsgpl, ne, 3 * C, eng->prec.rev_planes) : UMX_OK;
+int link_rotate_back_bwd(umx_engine* eng, const WS& w, int slot, long ne) {
+  const Precision& p = eng->prec;
+  if (slot == NL) {
+    const bool dpl = deg_rev_planes(eng);
+    auto run = [&](auto k, auto* out) {
+      UMX_LAUNCH(k, nblk(ne, 4), w.G0, w.rad_deg, w.frame, w.edst, out, w.dedd, w.tau, ne, DEG_RESCALE, dpl ? eng->odd_sign : 1.0f);
+    };
+    if (!dpl) run(k_rotate_back_bwd<3, 0>, w.gmsg);
+    else if (p.rev_planes == 3) run(k_rotate_back_bwd<3, 3>, w.gmsgpl);
+    else run(k_rotate_back_bwd<3, 2>, w.gmsgpl);
+    HIPCHK(eng, hipGetLastError());
+    return dpl ? dbg_operand(eng, "grad", NL, OP_PLANES, w.gmsgpl, ne, 3 * C, p.rev_planes) : UMX_OK;
+  }
+  if (!p.planes) {
+    UMX_LAUNCH(k_rotate_back_bwd<9>, nblk(ne, 4), w.G2, w.msg[slot], w.frame, w.edst, w.gmsg, w.dedd, w.tau, ne, 1.0f, 1.0f);
+    HIPCHK(eng, hipGetLastError());
+    return UMX_OK;                             // (g_msg: plan_edge_bwd)
+  }
+  auto k = p.rev_quad() ? k_rotate_back_bwd_q3<3> : k_rotate_back_bwd_pl<2>;
+  UMX_LAUNCH(k, vgrid(eng, (nblk(ne, 4) + 7) / 8 * 8), w.G2, w.msg[slot], w.frame, w.edst, w.gmsgpl, w.dedd, w.tau, ne, eng->odd_sign);
+  HIPCHK(eng, hipGetLastError());
+  return dbg_operand(eng, "gmsg", slot, rev_operand(p), w.gmsgpl, ne, ROW);
 }
 // gate backward: g_hid -> g_hg, conv 1^T's A operand
 int link_gate_bwd(umx_engine* eng, const WS& w, int i, long ne) {
+  if (!eng->prec.planes) {
+    UMX_LAUNCH(k_gate_edge_bwd, nblk(ne * (H / 4), 256), w.hid, w.hg[i], w.ghg, ne, 1.0f);
+    HIPCHK(eng, hipGetLastError());
+    return UMX_OK;                             // (g_hg: plan_edge_bwd)
+  }
   const bool quad = eng->prec.rev_quad();
   auto k = quad ? k_gate_edge_bwd_q3<3> : k_gate_edge_bwd_pl<2>;
   UMX_LAUNCH(k, vgrid(eng, quad ? nblk(ne, 8) : nblk(ne * (H / 4), 256)), w.hid, w.hg[i], w.ghgpl, ne, eng->odd_sign);
@@ -93,7 +117,7 @@ int link_gate_bwd(umx_engine* eng, const WS& w, int i, long ne) {
 }
 // One node-centric kernel: modulation backward + rotate-back + segmented sum -> g_xn in G1 (g_xrot stays in registers); g_rad, the fc3^T
 // operand, as float32 rows (sign-alternating; split by the fc3^T GEMM in registers) in the bf16x3 mode, as two PL bf16 planes in the
-// 16-bit-reverse modes.  Round 4: the fp32 mode takes it too (P = 0, rows in w.grad, no alternating sign) instead of k_gather_rotate +
+// 16-bit-reverse modes.  Round 4: the fp32 mode takes it too (rows in w.grad, no alternating sign) instead of k_gather_rotate +
 // k_modulate_bwd + k_gather_rotate_bwd -- the rotated message and g_xrot never touch HBM (-27 KB per edge and layer).
 int link_modrot_bwd(umx_engine* eng, const WS& w, int i, long nn, long ne) {
   const bool pl = eng->prec.planes, rows = !pl || eng->prec.rev_quad();
@@ -104,6 +128,7 @@ int link_modrot_bwd(umx_engine* eng, const WS& w, int i, long nn, long ne) {
   if (!pl) return UMX_OK;                      // (fp32: with captures on the unfused kernels run, see plan_edge_bwd)
   return rows ? dbg_operand(eng, "gradq", i, OP_ROWS, w.gradpl, ne, RAD) : dbg_operand(eng, "grad", i, OP_PLANES, w.gradpl, ne, RAD);
 }
+
 
 // ---- radial MLP: the fc3 GEMM and the reverse pass -------------------------------------------------
 int radial_fwd_fc3(umx_engine* eng, const WS& w, const RadialW& r, long ne, float* rad_out) {
@@ -229,7 +254,7 @@ void plan_edge_fwd(Plan& P, WS& w, const ChunkCtx& c, int i, bool replay) {
       return link_radial_head(c.eng, w, L->rad, i, c.ne);
     });
     P.matrix([=, &w]() -> int { return radial_fwd_fc3(c.eng, w, L->rad, c.ne, w.rad[i]); });
-    P.stream([=, &w]() -> int { return link_gather_rotate_mod(c.eng, w, i, c.ne); });
+    P.stream([=, &w]() -> int { return link_gather_rotate(c.eng, w, i, c.ne); });
     // SO(2) conv 1 on the pre-modulated planes -> hg = [gate | hpre]
     P.matrix([=, &w]() -> int { return so2_conv(c.eng, FWD, w.y1pl, SO2_Y1, w.hg[i], SO2_HG, L->c1m0, L->c1m1, L->c1m2, L->c1m0b, c.ne, 1.0f); });
     P.stream([=, &w]() -> int { return link_gate_fwd(c.eng, w, i, c.ne); });
@@ -242,11 +267,11 @@ void plan_edge_fwd(Plan& P, WS& w, const ChunkCtx& c, int i, bool replay) {
     UMX_STAGE(c);
     if (!replay) norm1_fwd(c, w, i);
     if (ne > 0) {
-      UMX_LAUNCH(k_gather_rotate, nblk(ne, 4), w.xn[i], w.esrc, w.edst, w.frame, w.xrot, ne);
+      CHK(link_gather_rotate(eng, w, i, ne));
       CHK(radial_fwd(eng, w, L->rad, i, ne, w.rad[i]));
       // SO(2) conv 1 (radially modulated) -> hg = [gate | hpre]
       CHK(so2_conv(eng, FWD, w.xrot, SO2_Y1, w.hg[i], SO2_HG, L->c1m0, L->c1m1, L->c1m2, L->c1m0b, ne, 1.0f, w.rad[i]));
-      UMX_LAUNCH(k_gate_edge_fwd, nblk(ne * (H / 4), 256), w.hg[i], w.hid, ne);
+      CHK(link_gate_fwd(eng, w, i, ne));
       // SO(2) conv 2 -> msg
       CHK(so2_conv(eng, FWD, w.hid, SO2_MSG, w.msg[i], SO2_MSG, L->c2m0, L->c2m1, L->c2m2, L->c2m0b, ne, 1.0f));
     }
@@ -449,15 +474,15 @@ void plan_edge_bwd(Plan& P, WS& w, const ChunkCtx& c, int i) {
   P.stream([=, &w]() -> int {
     UMX_STAGE(c);
     const std::string t = "." + std::to_string(i);
-    UMX_LAUNCH(k_rotate_back_bwd<9>, nblk(ne, 4), w.G2, w.msg[i], w.frame, w.edst, w.gmsg, w.dedd, w.tau, ne, 1.0f);
+    CHK(link_rotate_back_bwd(eng, w, i, ne));
     CHK(so2_conv(eng, REV, w.gmsg, SO2_MSG, w.hid, SO2_MSG, L->c2m0T, L->c2m1T, L->c2m2T, nullptr, ne, -1.0f));
     DBG("g_msg" + t, w.gmsg, ne * ROW); DBG("g_hid" + t, w.hid, ne * ROW);
-    UMX_LAUNCH(k_gate_edge_bwd, nblk(ne * H, 256), w.hid, w.hg[i], w.ghg, ne);
+    CHK(link_gate_bwd(eng, w, i, ne));
     CHK(so2_conv(eng, REV, w.ghg, SO2_HG, w.gy1, SO2_Y1, L->c1m0T, L->c1m1T, L->c1m2T, nullptr, ne, -1.0f));
     DBG("g_hg" + t, w.ghg, ne * HG); DBG("g_y1" + t, w.gy1, ne * XROT);      // (k_modulate_bwd below turns g_y1 into g_xrot in place)
     if (c.fused_rev) CHK(link_modrot_bwd(eng, w, i, nn, ne));
     else {       // with debug captures on the unfused kernels run: they expose xrot / g_xrot to the stage-by-stage test
-      UMX_LAUNCH(k_gather_rotate, nblk(ne, 4), w.xn[i], w.esrc, w.edst, w.frame, w.xrot, ne);
+      CHK(link_gather_rotate(eng, w, i, ne));
       UMX_LAUNCH(k_modulate_bwd, nblk(ne, 4), w.gy1, w.xrot, w.rad[i], w.grad, w.tau, ne);
       DBG("g_xrot" + t, w.gy1, ne * XROT); DBG("g_rad" + t, w.grad, ne * RAD);
     }
@@ -500,7 +525,7 @@ int force_assembly(const ChunkCtx& c, const WS& w) {
       CHK(link_radial_head(eng, w, eng->rdeg, NL, ne));
       CHK(radial_fwd_fc3(eng, w, eng->rdeg, ne, w.rad_deg));
     }
-    CHK(link_rotate_back_bwd_deg(eng, w, ne));
+    CHK(link_rotate_back_bwd(eng, w, NL, ne));
     CHK(radial_bwd(eng, w, eng->rdeg, NL, ne, w.gmsg, deg_rev_planes(eng) ? w.gmsgpl : nullptr));
     if (c.fused_rev) UMX_LAUNCH(k_add4, nblk(ne, 256), w.tau, w.tau2, ne);
     UMX_LAUNCH(k_force_edge, nblk(ne, 256), w.dedd, w.dedd_rad, w.tau, w.frame, w.evec, w.gvec, ne);
@@ -894,7 +919,7 @@ int plan_chunks(umx_engine* eng, long K, const ImageEdges& ie, long cap, size_t 
   const int N = eng->natoms;
   c = Chunks();
   // Several pinned references: image k is promised to be, bit for bit, its evaluation alone.  The GEMM producers negate the operand rows
-  // of odd index (umx_kernels_pl.h, sign-alternating rows), so the rounding of an edge depends on the parity of its row in the chunk:
+  // of odd index (umx_edge.h, sign-alternating rows), so the rounding of an edge depends on the parity of its row in the chunk:
   // an image never starts at an odd row -- behind an odd number of edges the chunk ends.  (Alone, an image starts at row 0.)
   const bool even_rows = eng->pin_on && eng->pin_refs > 1;
   for (long k0 = 0; k0 < K;) {

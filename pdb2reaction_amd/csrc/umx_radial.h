@@ -16,7 +16,7 @@
 #include "umx_common.h"
 #include "umx_gemm.h"
 #include "umx_gemm_q.h"
-#include "umx_kernels_pl.h"
+#include "umx_edge.h"
 
 namespace umx {
 

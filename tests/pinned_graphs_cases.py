@@ -8,7 +8,7 @@ The open sets scale one cluster: x 2.0 thins the graph, x 50 leaves no atom with
 the 40-atom counts (1206, 764, 288) are above 256 and no multiple of 64, so an image's edges cross block and wave boundaries.  The
 periodic sets are the noisy copies of ``stress_oracle.make_case``; in the triclinic cell a cap of 50 binds on some atoms only.
 
-Row parity.  The engine's GEMM operands alternate the sign of their ODD rows (umx_kernels_pl.h, "sign-alternating rows"), so the
+Row parity.  The engine's GEMM operands alternate the sign of their ODD rows (umx_edge.h, "sign-alternating rows"), so the
 rounding of an edge depends on whether its row in the chunk is even or odd.  With several references pinned the planner therefore ends
 a chunk behind an odd number of edges, and every image is bitwise its evaluation alone; an UNPINNED batch keeps its chunks, so there an
 image behind an odd count differs from the image alone by float32 rounding.  ``behind_odd`` names the sets in which, in reference

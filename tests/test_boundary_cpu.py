@@ -270,7 +270,7 @@ def test_build_dependency_list_covers_every_kernel_header(monkeypatch):
     assert all(os.path.exists(d) for d in deps)
     real = os.path.getmtime
     t_lib = real(B.OUT)
-    for touched in ("umx_gemm_q.h", "umx_generators.h", "umx_kernels_pl.h", "umx.h"):
+    for touched in ("umx_gemm_q.h", "umx_generators.h", "umx_edge.h", "umx.h"):
         monkeypatch.setattr(os.path, "getmtime", lambda p, t=touched: t_lib + 5.0 if os.path.basename(p) == t else min(real(p), t_lib))
         assert B.needs_build(), touched
     monkeypatch.setattr(os.path, "getmtime", lambda p: min(real(p), t_lib))
@@ -317,7 +317,7 @@ def test_library_has_no_packed_fp32(tmp_path):
 
     assert "-fno-slp-vectorize" in build.FLAGS
     src = tmp_path / "probe.hip"
-    src.write_text('#include "umx_kernels_pl.h"\n#include "umx_kernels.h"\n')
+    src.write_text('#include "umx_edge.h"\n#include "umx_kernels.h"\n')
     out = tmp_path / "probe.s"
     subprocess.run([build.find_hipcc(), *build.FLAGS, "-I", build.CSRC, "-S", "--cuda-device-only", str(src), "-o", str(out)], check=True, timeout=600)
     text = out.read_text()

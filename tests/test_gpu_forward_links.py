@@ -9,7 +9,7 @@ and say nothing about the fast mode's fp16 operands.  Here, from the engine's OW
     A2  h1pre                             -> h2pre      hi + lo LayerNorm, SiLU, fc2 seeded with its bias
     A3  h2pre                             -> a2q | a2 | a2h   LayerNorm, SiLU, row sign, operand store
   Part B  the fp16 "Q2H" operand planes (split): y1h.i (k_gather_rotate_mod_q3<1>), hidh.i (k_gate_edge_fwd_q3<1>), a2h.* (k_radial_head<2>):
-          decoded by the layout rule of umx_kernels_pl.h, against the float64 replays of tests/test_gpu_edge_links.py; the split law
+          decoded by the layout rule of umx_edge.h, against the float64 replays of tests/test_gpu_edge_links.py; the split law
   Part C  the fp16 forward GEMM umx_gemm_q_kernel<CPLX, WIDE, 2, 2, 1, 4, 3> (split): A exactly as captured (hi and lo planes apart), B planes
           rebuilt on the host from the float32 weight by the rule of umx_weights.h, float64 sum of exactly the four products; the projection
           statistic ("gain") of A_hi . B_lo2 and of A_lo . B_hi
@@ -165,7 +165,7 @@ def silu_k_host(y):
     return host_ulps(y.numpy().astype(np.float32))["silu"]
 
 
-# ---- Part B: the Q2H decoder, written from the layout comment of umx_kernels_pl.h ----------------------------------------------------------
+# ---- Part B: the Q2H decoder, written from the layout comment of umx_edge.h ----------------------------------------------------------
 def q2h_index(rows, cols, q, plane_bytes=32):
     """index, in halves, of element (r, k, plane q) of a `cols`-wide matrix: byte ((r/4)(cols/16) + k/16) 256 + (r%4) 64 + q 32 + (k%16) 2"""
     r, k = np.asarray(rows, np.int64)[:, None], np.arange(cols, dtype=np.int64)[None, :]

@@ -640,27 +640,39 @@ def test_two_lane_execution_is_bitwise_identical(weights, monkeypatch):
     Round 3: this test failed about once in ten suite runs (forces of one image 1e-6...1e-4 eV/A off).  Cause: the packed-fp32
     instructions hipcc's SLP vectoriser emits (v_pk_mul/add/fma_f32) are timing-sensitive on gfx950 -- beside other kernels on the same
     SIMDs single waves come out 0.1-1 % off (csrc/norm_bwd_repro.hip); the library is built with -fno-slp-vectorize since
-    (build.py, NOTES.md section 5 item 14).  test_library_has_no_packed_fp32 keeps it that way."""
+    (build.py, NOTES.md section 5 item 14).  test_library_has_no_packed_fp32 keeps it that way.
+    Second case: `split` mode, two images of 120 atoms with one image per chunk.  Each image has more than 4096 edges, so the capped grids
+    (512 workgroups of 4 or 8 edges) of the staged kernels and of the PL writers of the 16-bit reverse pass (k_rotate_back_bwd_pl<2>,
+    k_gate_edge_bwd_pl<2>) go round their grid-stride loops twice, which the first case's 260-atom chunks of the default mode do not
+    make the PL writers do."""
     from pdb2reaction_amd.engine import Engine
 
-    z, imgs, _ = synth.make_images(260, 5, seed=21)
-    res = {}
-    for lanes, cap, one_stream in (("1", "512", False), ("2", "512", False), ("2", "512", True)):
-        monkeypatch.setenv("UMX_STREAMS", lanes)
-        if one_stream:
-            monkeypatch.setenv("UMX_LANES_ONE_STREAM", "1")
-        else:
-            monkeypatch.delenv("UMX_LANES_ONE_STREAM", raising=False)
-        eng = Engine(0)
-        try:
-            eng.load_weights(weights)
-            eng.set_system(z)
-            res[(lanes, cap, one_stream)] = eng.energy_forces(imgs)
-        finally:
-            eng.close()
-    e0, f0 = res[("1", "512", False)]
-    for key, (e, f) in res.items():
-        assert np.array_equal(e, e0) and np.array_equal(f, f0), key
+    for mode, (z, imgs, _), chunk in ((None, synth.make_images(260, 5, seed=21), None), ("split", synth.make_images(120, 2, seed=21), "1")):
+        if chunk:
+            monkeypatch.setenv("UMX_MAX_CHUNK_IMAGES", chunk)
+        res = {}
+        for lanes, cap, one_stream in (("1", "512", False), ("2", "512", False), ("2", "512", True)):
+            monkeypatch.setenv("UMX_STREAMS", lanes)
+            if one_stream:
+                monkeypatch.setenv("UMX_LANES_ONE_STREAM", "1")
+            else:
+                monkeypatch.delenv("UMX_LANES_ONE_STREAM", raising=False)
+            eng = Engine(0, **({"precision": mode} if mode else {}))
+            try:
+                eng.load_weights(weights)
+                eng.set_system(z)
+                if chunk and lanes == "1":               # the premise of the second case, from the engine: every image loops a capped grid
+                    for k in range(len(imgs)):
+                        eng.energy_forces(imgs[k:k + 1])
+                        assert eng.graph_stats()[0] > 4096, (k, eng.graph_stats())
+                res[(lanes, cap, one_stream)] = eng.energy_forces(imgs)
+                if chunk:
+                    assert eng.last_lanes() == int(lanes), (lanes, eng.last_lanes())
+            finally:
+                eng.close()
+        e0, f0 = res[("1", "512", False)]
+        for key, (e, f) in res.items():
+            assert np.array_equal(e, e0) and np.array_equal(f, f0), (mode, key)
 
 
 def test_reserve_images_allocates_the_workspace_once(weights):

@@ -175,7 +175,7 @@ def test_image_for_image(weights, image_cases, monkeypatch, name, setting):
     """Image k of the batch Y[0..4] with assignment [2, 0, 0, 1, 2] is bitwise (E, F, W) Y[k] alone on ``pin_graph(refs[a[k]])``.
 
     ``open12_capped`` and ``triclinic_mid`` put images behind an odd number of edges (47, 595).  The GEMM producers negate the operand
-    rows of odd index and the epilogues restore the sign (umx_kernels_pl.h, "sign-alternating rows"; on by default), so the float32
+    rows of odd index and the epilogues restore the sign (umx_edge.h, "sign-alternating rows"; on by default), so the float32
     rounding of an edge depends on the parity of its row in the chunk; at an odd row the image would differ from the image alone by
     rounding (measured before the planner knew: max|dE| = 1.0e-06 eV, max|dF| = 3.6e-07 eV/A, max|dW| = 1.4e-06 eV,
     profiles/pinned_graphs.txt part 1).  With several references pinned the planner ends a chunk behind an odd count, so every image

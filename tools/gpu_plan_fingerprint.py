@@ -1,6 +1,7 @@
 """Fingerprint of every kind of launch plan: one line per configuration with the sha256 of the energies, the forces, the virial where
 asked and, with captures on, of every debug capture in name order.  A host-code refactor must leave every line as it was: run it on both
 trees (python tools/gpu_plan_fingerprint.py > out.txt) and compare the files.  An engine error prints as the line's result.
+The ``S120x2`` lines run two lanes with one image of more than 4096 edges per chunk: the capped grids of the stream kernels loop twice.
 
 The ``graph`` section (lines that start with "graph"; ``python tools/gpu_plan_fingerprint.py graph`` prints it alone, ``plans`` the
 rest) holds the neighbour-graph stage: the six graph captures, energies and forces, ``graph_stats()`` and ``last_graph_shifts()`` of
@@ -112,6 +113,20 @@ def main():
                     pool.set_system(z, **kw)
                     line(f"{mode} {ff} {name} pool-gp", lambda: sha(*pool.energy_forces(p[:1])) + f" {pool.last_route}")
                     line(f"{mode} {ff} {name} pool-gp+virial", lambda: sha(*pool.energy_forces_virial(p[:1], graph_parallel=True)) + f" {pool.last_route}")
+    # two lanes with one image per chunk, each image with more than 4096 edges: the capped grids of the throttled stream kernels (512
+    # workgroups of 4 or 8 edges) walk their grid-stride loops twice -- nothing above does
+    z120, p120, _ = synth.make_images(120, 2, seed=21)
+    env = {"UMX_STREAMS": "2", "UMX_MAX_CHUNK_IMAGES": "1"}
+    w = W.make_synthetic_weights(0)
+    for mode in MODES:
+        os.environ.update(env)
+        eng = Engine(0, precision=mode)
+        eng.load_weights(w)
+        eng.set_system(z120)
+        line(f"{mode} spectral S120x2 {env_label(env)}",
+             lambda: sha(*eng.energy_forces(p120.astype(np.float32))) + f" {eng.graph_stats()[0]} edges {eng.last_lanes()} lanes")
+        eng.close()
+        [os.environ.pop(k) for k in env]
 
 
 # ---- the neighbour-graph stage ---------------------------------------------------------------------------------------------------
