@@ -492,6 +492,24 @@ int umx_bond_changes(umx_engine* eng, int n, const double* r1, const double* r2,
                      double bond_factor, double margin_fraction, double delta_fraction, double* d1, double* d2,
                      uint8_t* code);
 
+/* BOND CHANGES IN A PERIODIC CELL (additive to ABI v10).  umx_bond_changes on MINIMUM-IMAGE distances: same outputs, same
+ * classification rule.  cell: the lattice vectors row by row IN THE UNIT OF THE COORDINATES (usually Bohr); pbc: one flag per axis.
+ * The engine's bound cell (umx_set_cell, Angstrom) is not read; no weights and no bound system are needed.
+ *   - The distance, all in float64: with b_k the dual vectors and h_k the plane distances of the periodic sub-lattice (those of
+ *     umx_set_cell), d = r_j - r_i, n_k = rint(d . b_k) on periodic axes (0 on open ones), d0 = d - sum n_k a_k:
+ *     D_ij = min |d0 + sum m_k a_k| over |m_k| <= M_k = floor(R / h_k + 1/2), R = half the summed lengths of the periodic vectors
+ *     (M_k = 0 on open axes).  |d0| <= R and every translate beyond M_k is longer than R, so D_ij is the minimum over ALL lattice
+ *     translations -- in a skewed cell the nearest image is often not the rounded one.  Translates whose lower bound
+ *     (|m_k| - 1/2) h_k exceeds the best length found are skipped.  The diagonal is 0 and D_ij == D_ji bit for bit.
+ *   - cell == NULL, pbc == NULL or no flag set: umx_bond_changes, the same kernel and the same bits.
+ *   - UMX_ERR_ARG, outputs untouched: a non-finite cell entry; a degenerate periodic sub-lattice (the messages of umx_set_cell);
+ *     M_k > 4 on some axis (at most 9^3 = 729 candidates are searched).
+ *   - cost per pair: up to prod (2 M_k + 1) distance evaluations (125 in a cubic cell, M_k = 2), fewer with the skipping.
+ * Not provided: many pairs of geometries in one call.  No reference counterpart (compare_structures measures open-space distances). */
+int umx_bond_changes_cell(umx_engine* eng, int n, const double* r1, const double* r2, const double* cov, const double cell[9],
+                          const int pbc[3], double bond_factor, double margin_fraction, double delta_fraction, double* d1,
+                          double* d2, uint8_t* code);
+
 /* Test hook: copy a named intermediate buffer of the most recent evaluation's last chunk to the
  * host.  Returns the buffer size in bytes through *nbytes_out when host_buf == NULL.           */
 int umx_debug_fetch(umx_engine* eng, const char* name, void* host_buf, size_t capacity,

@@ -3,6 +3,7 @@
 Reference: ``pdb2reaction/bond_changes.py`` -- ``compare_structures`` (:142-187, pairwise ``torch.cdist`` in float64 and
 boolean masks), ``summarize_changes`` (:196-232), ``BondChangeResult`` (:93-100).  Here the two distance matrices and the
 formed/broken classification come from ONE HIP kernel (``umx_bond_changes`` in ``include/umx.h``); there is no CPU path.
+With ``cell=`` / ``pbc=`` the distances are minimum-image distances in that cell (``umx_bond_changes_cell``).
 
 Covalent radii: the reference takes ``pysisyphus.elem_data.COVALENT_RADII`` (third-party, absent here).  The table below
 restates the published Cordero et al. 2008 single-bond radii (Dalton Trans. 2008, 2832) in Angstrom and converts them to
@@ -75,19 +76,23 @@ def _engine(device: str = "cuda"):
 
 def compare_structures(geom1, geom2, device: str = "cuda", bond_factor: float = 1.20, margin_fraction: float = 0.05,
                        delta_fraction: float = 0.05, *, engine=None, radii: Optional[Dict[str, float]] = None,
-                       unit_scale: float = ANG2BOHR) -> BondChangeResult:
+                       unit_scale: float = ANG2BOHR, cell=None, pbc=None) -> BondChangeResult:
     """Formed / broken covalent bonds between two geometries with identical atoms (``.atoms``, ``.coords3d`` [N,3]).
 
     bonded(i,j) <=> D_ij <= T - margin_fraction*T with T = bond_factor*(r_i + r_j); a pair changes only when
     |D2 - D1| >= delta_fraction*T (reference bond_changes.py:160-176).  ``device`` is accepted for signature
     compatibility; the computation always runs on the engine's GPU.
+
+    ``cell`` (3,3, rows as lattice vectors, IN THE UNIT OF THE COORDINATES -- Bohr for pysisyphus geometries) and ``pbc`` (a bool or
+    three flags): D is the minimum-image distance over all lattice translations (``umx_bond_changes_cell``), so a bond across the
+    boundary is a bond.  Without them the open-space call as it was.  No reference counterpart.
     """
     if list(geom1.atoms) != list(geom2.atoms):
         raise AssertionError("Atom types and ordering must be identical.")
     _, cov = element_radii(geom1.atoms, unit_scale, radii)
     eng = engine if engine is not None else _engine(device)
     d1, d2, code = eng.bond_changes(np.asarray(geom1.coords3d, dtype=np.float64), np.asarray(geom2.coords3d, dtype=np.float64), cov,
-                                    bond_factor, margin_fraction, delta_fraction)
+                                    bond_factor, margin_fraction, delta_fraction, **({} if cell is None or pbc is None else {"cell": cell, "pbc": pbc}))
     formed = set(map(tuple, np.argwhere(code == 1).tolist()))
     broken = set(map(tuple, np.argwhere(code == 2).tolist()))
     return BondChangeResult(formed_covalent=formed, broken_covalent=broken, distances_1=d1, distances_2=d2)

@@ -745,31 +745,40 @@ int umx_debug_fetch(umx_engine* eng, const char* name, void* host_buf, size_t ca
   return UMX_OK;
 }
 
-int umx_bond_changes(umx_engine* eng, int n, const double* r1, const double* r2, const double* cov, double bond_factor,
-                     double margin_fraction, double delta_fraction, double* d1, double* d2, uint8_t* code) {
-  if (!eng) return UMX_ERR_ARG;
-  if (n <= 0 || !r1 || !r2 || !cov || !code) return fail(eng, UMX_ERR_ARG, "umx_bond_changes: bad arguments");
-  if ((long)n * n > (1L << 31)) return fail(eng, UMX_ERR_CAPACITY, "umx_bond_changes: n*n exceeds 2^31 pairs");
+// umx_bond_changes and umx_bond_changes_cell: `cell` == nullptr launches the open kernel, else the minimum-image one on `cand`
+static int bond_changes_run(umx_engine* eng, const char* who, int n, const double* r1, const double* r2, const double* cov, const umx::BondCell* cell,
+                            const std::vector<double>& cand, double bond_factor, double margin_fraction, double delta_fraction, double* d1, double* d2,
+                            uint8_t* code) {
+  const std::string w = who;
+  if (n <= 0 || !r1 || !r2 || !cov || !code) return fail(eng, UMX_ERR_ARG, w + ": bad arguments");
+  if ((long)n * n > (1L << 31)) return fail(eng, UMX_ERR_CAPACITY, w + ": n*n exceeds 2^31 pairs");
   HIPCHK(eng, hipSetDevice(eng->dev));
-  const size_t nn = (size_t)n * n, vb = (size_t)n * 3 * sizeof(double);
+  const size_t nn = (size_t)n * n, vb = (size_t)n * 3 * sizeof(double), cb = cand.size() * sizeof(double);
   double *d_r = nullptr, *d_d = nullptr; unsigned char* d_c = nullptr;
-  HIPCHK(eng, hipMalloc(&d_r, 2 * vb + (size_t)n * sizeof(double)));
+  HIPCHK(eng, hipMalloc(&d_r, 2 * vb + (size_t)n * sizeof(double) + cb));
   hipError_t e1 = hipMalloc(&d_d, 2 * nn * sizeof(double)), e2 = hipMalloc(&d_c, nn);
   if (e1 != hipSuccess || e2 != hipSuccess) {
     (void)hipFree(d_r); if (d_d) (void)hipFree(d_d); if (d_c) (void)hipFree(d_c);
-    return fail(eng, UMX_ERR_HIP, "umx_bond_changes: hipMalloc of the pair matrices failed");
+    return fail(eng, UMX_ERR_HIP, w + ": hipMalloc of the pair matrices failed");
   }
-  double* d_r2 = d_r + (size_t)n * 3; double* d_cov = d_r2 + (size_t)n * 3;
+  double* d_r2 = d_r + (size_t)n * 3; double* d_cov = d_r2 + (size_t)n * 3; double* d_cand = d_cov + n;
   hipStream_t s = eng->stream;
   int st = UMX_OK;
   auto ok = [&](hipError_t e, const char* what) { if (e != hipSuccess && st == UMX_OK) st = fail(eng, UMX_ERR_HIP, std::string(what) + ": " + hipGetErrorName(e)); };
   ok(hipMemcpyAsync(d_r, r1, vb, hipMemcpyHostToDevice, s), "copy r1");
   ok(hipMemcpyAsync(d_r2, r2, vb, hipMemcpyHostToDevice, s), "copy r2");
   ok(hipMemcpyAsync(d_cov, cov, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s), "copy cov");
+  if (cell) ok(hipMemcpyAsync(d_cand, cand.data(), cb, hipMemcpyHostToDevice, s), "copy the candidate translations");
   if (st == UMX_OK) {
     dim3 grid((n + 63) / 64, (n + 3) / 4);
-    umx::k_bond_changes<<<grid, 256, 0, s>>>(d_r, d_r2, d_cov, n, bond_factor, margin_fraction, delta_fraction, d_d, d_d + nn, d_c);
-    ok(hipGetLastError(), "k_bond_changes");
+    if (cell) {
+      umx::k_bond_changes_cell<<<grid, 256, 0, s>>>(d_r, d_r2, d_cov, n, *cell, d_cand, (int)(cand.size() / 4), bond_factor, margin_fraction, delta_fraction,
+                                                    d_d, d_d + nn, d_c);
+      ok(hipGetLastError(), "k_bond_changes_cell");
+    } else {
+      umx::k_bond_changes<<<grid, 256, 0, s>>>(d_r, d_r2, d_cov, n, bond_factor, margin_fraction, delta_fraction, d_d, d_d + nn, d_c);
+      ok(hipGetLastError(), "k_bond_changes");
+    }
     if (d1) ok(hipMemcpyAsync(d1, d_d, nn * sizeof(double), hipMemcpyDeviceToHost, s), "copy d1");
     if (d2) ok(hipMemcpyAsync(d2, d_d + nn, nn * sizeof(double), hipMemcpyDeviceToHost, s), "copy d2");
     ok(hipMemcpyAsync(code, d_c, nn, hipMemcpyDeviceToHost, s), "copy code");
@@ -777,6 +786,24 @@ int umx_bond_changes(umx_engine* eng, int n, const double* r1, const double* r2,
   ok(hipStreamSynchronize(s), "sync");
   (void)hipFree(d_r); (void)hipFree(d_d); (void)hipFree(d_c);
   return st;
+}
+
+int umx_bond_changes(umx_engine* eng, int n, const double* r1, const double* r2, const double* cov, double bond_factor,
+                     double margin_fraction, double delta_fraction, double* d1, double* d2, uint8_t* code) {
+  if (!eng) return UMX_ERR_ARG;
+  return bond_changes_run(eng, "umx_bond_changes", n, r1, r2, cov, nullptr, {}, bond_factor, margin_fraction, delta_fraction, d1, d2, code);
+}
+
+int umx_bond_changes_cell(umx_engine* eng, int n, const double* r1, const double* r2, const double* cov, const double cell[9], const int pbc[3],
+                          double bond_factor, double margin_fraction, double delta_fraction, double* d1, double* d2, uint8_t* code) {
+  if (!eng) return UMX_ERR_ARG;
+  if (!cell || !pbc || !(pbc[0] || pbc[1] || pbc[2]))
+    return bond_changes_run(eng, "umx_bond_changes", n, r1, r2, cov, nullptr, {}, bond_factor, margin_fraction, delta_fraction, d1, d2, code);
+  umx::BondCell bc;
+  std::vector<double> cand;
+  std::string why;
+  if (!bond_cell_candidates(cell, pbc, &bc, &cand, &why)) return fail(eng, UMX_ERR_ARG, "umx_bond_changes_cell: " + why);
+  return bond_changes_run(eng, "umx_bond_changes_cell", n, r1, r2, cov, &bc, cand, bond_factor, margin_fraction, delta_fraction, d1, d2, code);
 }
 
 }  // extern "C"

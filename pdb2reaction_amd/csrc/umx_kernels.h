@@ -433,4 +433,54 @@ __global__ __launch_bounds__(256) void k_bond_changes(const double* __restrict__
   code[o] = c;
 }
 
+// The same classification on MINIMUM-IMAGE distances in a periodic cell (umx_bond_changes_cell): same pair-per-thread shape, same
+// explicit sums, the open kernel above left as it is.  BondCell: lattice vectors a (rows) and dual vectors b of the periodic
+// sub-lattice as build_periodic forms them, both zero on an open axis -- so an open axis rounds to n = 0 by itself.
+// For d = r_j - r_i: n_k = rint(d . b_k); d0 = d - sum_k n_k a_k; D = min over the candidate translations t of |d0 + t|.
+// cand: [n_cand][4] float64 (tx, ty, tz, lb2), formed once on the host, read by every thread at the same index.  lb2 is a lower bound
+// of |d0 + t|^2 that holds for every d0 with fractional coordinates in [-1/2, 1/2] (host: bond_cell_candidates), the entries ascend in
+// it and the zero translation comes first with lb2 = 0: the search stops at the first entry whose bound exceeds the best so far.
+// D_ij == D_ji bit for bit: negation is exact through every product, sum and rint, and the table holds -t bit for bit next to every t.
+struct BondCell { double a[3][3], b[3][3]; };
+
+__global__ __launch_bounds__(256) void k_bond_changes_cell(const double* __restrict__ r1, const double* __restrict__ r2,
+                                                           const double* __restrict__ cov, int n, BondCell cell,
+                                                           const double* __restrict__ cand, int n_cand, double bf, double mf, double df,
+                                                           double* __restrict__ d1, double* __restrict__ d2,
+                                                           unsigned char* __restrict__ code) {
+  const int j = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int i = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (i >= n || j >= n) return;
+  auto sum3 = [](double x, double y, double z) { return __dadd_rn(__dadd_rn(x, y), z); };
+  auto dist = [&](const double* r, int p, int q) {
+    const double dx = r[q * 3 + 0] - r[p * 3 + 0], dy = r[q * 3 + 1] - r[p * 3 + 1], dz = r[q * 3 + 2] - r[p * 3 + 2];
+    double m[3];
+    for (int k = 0; k < 3; ++k) m[k] = rint(sum3(__dmul_rn(dx, cell.b[k][0]), __dmul_rn(dy, cell.b[k][1]), __dmul_rn(dz, cell.b[k][2])));
+    const double x0 = __dsub_rn(dx, sum3(__dmul_rn(m[0], cell.a[0][0]), __dmul_rn(m[1], cell.a[1][0]), __dmul_rn(m[2], cell.a[2][0])));
+    const double y0 = __dsub_rn(dy, sum3(__dmul_rn(m[0], cell.a[0][1]), __dmul_rn(m[1], cell.a[1][1]), __dmul_rn(m[2], cell.a[2][1])));
+    const double z0 = __dsub_rn(dz, sum3(__dmul_rn(m[0], cell.a[0][2]), __dmul_rn(m[1], cell.a[1][2]), __dmul_rn(m[2], cell.a[2][2])));
+    double best = sum3(__dmul_rn(x0, x0), __dmul_rn(y0, y0), __dmul_rn(z0, z0));      // cand[0]: the zero translation
+    for (int t = 1; t < n_cand; ++t) {
+      const double* c = cand + (size_t)t * 4;
+      if (c[3] > best) break;
+      const double x = __dadd_rn(x0, c[0]), y = __dadd_rn(y0, c[1]), z = __dadd_rn(z0, c[2]);
+      best = fmin(best, sum3(__dmul_rn(x, x), __dmul_rn(y, y), __dmul_rn(z, z)));
+    }
+    return sqrt(best);
+  };
+  const double a = dist(r1, i, j), b = dist(r2, i, j);
+  const long o = (long)i * n + j;
+  if (d1) d1[o] = a;
+  if (d2) d2[o] = b;
+  unsigned char c = 0;
+  if (i < j) {
+    const double T = __dmul_rn(bf, __dadd_rn(cov[i], cov[j]));
+    const double thr = __dsub_rn(T, __dmul_rn(mf, T));
+    const bool A1 = a <= thr, A2 = b <= thr;
+    const bool need = fabs(__dsub_rn(b, a)) >= __dmul_rn(df, T);
+    c = need ? ((!A1 && A2) ? 1 : (A1 && !A2) ? 2 : 0) : 0;
+  }
+  code[o] = c;
+}
+
 }  // namespace umx

@@ -103,6 +103,54 @@ bool build_periodic(const double cell[9], const int pbc[3], double cutoff, Perio
   return true;
 }
 
+// What k_bond_changes_cell reads for a cell in the unit of its coordinates (umx_bond_changes_cell): the lattice and dual vectors of
+// build_periodic (no cutoff enters them: it is called with cutoff 0) and the candidate translations of the minimum-image search.
+// With R = 1/2 sum over the periodic axes of |a_k| and h_k = 1 / |b_k| the plane distance, M_k = floor(R / h_k + 1/2): the rounded
+// difference d0 has fractional coordinates within 1/2, so |d0| <= R, while a translate with |m_k| > M_k lies more than
+// (M_k + 1/2) h_k > R from the origin along axis k -- the minimum over m in prod [-M_k, M_k] is the minimum over the whole lattice.
+// Entry (tx, ty, tz, lb2): lb = max_k (|m_k| - 1/2) h_k bounds |d0 + t| from below for every such d0; it is stored shortened by 1e-9
+// (the rounding of the device's d0, n and sums is ~1e-16) and squared, and the entries ascend in it, the zero translation first.
+// false + *why: the cell is refused (build_periodic's reasons, or M_k > PBC_MAX_AXIS)
+bool bond_cell_candidates(const double cell[9], const int pbc[3], umx::BondCell* bc, std::vector<double>* cand, std::string* why) {
+  PeriodicHost ph;
+  if (!build_periodic(cell, pbc, 0.0, &ph, why)) return false;
+  double R = 0.0, h[3] = {0, 0, 0};
+  int M[3] = {0, 0, 0};
+  for (int k = 0; k < 3; ++k) {
+    for (int c = 0; c < 3; ++c) { bc->a[k][c] = ph.lat.a[k][c]; bc->b[k][c] = ph.lat.b[k][c]; }
+    if (pbc[k]) R += 0.5 * norm3(ph.lat.a[k]);
+  }
+  for (int k = 0; k < 3; ++k) {
+    if (!pbc[k]) continue;
+    h[k] = 1.0 / norm3(ph.lat.b[k]);
+    const double m = std::floor(R / h[k] + 0.5);
+    if (!(m <= (double)PBC_MAX_AXIS)) {
+      char buf[256];
+      std::snprintf(buf, sizeof(buf), "the lattice planes of axis %c are %.4g apart in a cell of half perimeter %.4g: the minimum-image search needs more than the %d "
+                    "lattice translations per direction this engine searches", "abc"[k], h[k], R, PBC_MAX_AXIS);
+      *why = buf;
+      return false;
+    }
+    M[k] = (int)m;
+  }
+  struct Entry { double t[3], lb2; };
+  std::vector<Entry> es;
+  for (int a = -M[0]; a <= M[0]; ++a)
+    for (int b = -M[1]; b <= M[1]; ++b)
+      for (int c = -M[2]; c <= M[2]; ++c) {
+        const int m[3] = {a, b, c};
+        double lb = 0.0;
+        for (int k = 0; k < 3; ++k) lb = std::max(lb, (std::abs(m[k]) - 0.5) * h[k]);
+        lb *= 1.0 - 1e-9;
+        es.push_back({{a * cell[0] + b * cell[3] + c * cell[6], a * cell[1] + b * cell[4] + c * cell[7], a * cell[2] + b * cell[5] + c * cell[8]},
+                      (a || b || c) ? lb * lb : 0.0});
+      }
+  std::stable_sort(es.begin(), es.end(), [](const Entry& x, const Entry& y) { return x.lb2 < y.lb2; });
+  cand->clear();
+  for (const Entry& e : es) cand->insert(cand->end(), {e.t[0], e.t[1], e.t[2], e.lb2});
+  return true;
+}
+
 // ---- the bound cells: one list, shared by all images (umx_set_cell) or one cell per image (umx_set_cells) ---------------------------
 // every cell through build_periodic for the bound cutoff; false + *why (per-image cells: it names the image): one of them is refused
 bool build_cells(long n, const double* cells, const int pbc[3], double cutoff, bool shared, std::vector<PeriodicHost>* out, std::string* why) {

@@ -109,6 +109,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "umx_profile_enable": ([vp, i32], i32),
         "umx_profile_read": ([vp, C.POINTER(ProfileStats), i32], i32),
         "umx_bond_changes": ([vp, i32, dp, dp, dp, C.c_double, C.c_double, C.c_double, dp, dp, C.POINTER(C.c_uint8)], i32),
+        "umx_bond_changes_cell": ([vp, i32, dp, dp, dp, dp, C.POINTER(C.c_int), C.c_double, C.c_double, C.c_double, dp, dp, C.POINTER(C.c_uint8)], i32),
         "umx_debug_fetch": ([vp, C.c_char_p, vp, C.c_size_t, C.POINTER(C.c_size_t)], i32),
         "umx_debug_keep": ([vp, i32], i32),
     }
@@ -147,7 +148,7 @@ EXPORTED_SYMBOLS = (
     "umx_set_expert_coefficients", "umx_expert_count", "umx_set_recompute", "umx_last_recompute", "umx_workspace_bytes",
     "umx_set_cell", "umx_set_cells", "umx_last_graph_shifts", "umx_energy_forces_virial", "umx_energy_forces_virial_dev",
     "umx_gp_begin_virial", "umx_pin_graph", "umx_unpin_graph", "umx_pinned_graph",
-    "umx_pin_graphs", "umx_pin_assign", "umx_pinned_graphs",
+    "umx_pin_graphs", "umx_pin_assign", "umx_pinned_graphs", "umx_bond_changes_cell",
 )
 # The float64-position entries, listed apart: tests/test_boundary_cpu.py holds EXPORTED_SYMBOLS to the names it reads out of the header
 # with a pattern of letters and underscores, which a name with a digit in it does not match.  load_library declares (and so demands)
@@ -613,8 +614,12 @@ class Engine:
         self._chk(self.lib.umx_synchronize(self._h), "umx_synchronize")
 
     def bond_changes(self, r1: np.ndarray, r2: np.ndarray, cov: np.ndarray, bond_factor: float = 1.20,
-                     margin_fraction: float = 0.05, delta_fraction: float = 0.05, distances: bool = True):
-        """Pairwise float64 distances of two geometries + formed/broken code matrix (uint8, i<j: 1 formed, 2 broken)."""
+                     margin_fraction: float = 0.05, delta_fraction: float = 0.05, distances: bool = True, cell=None, pbc=None):
+        """Pairwise float64 distances of two geometries + formed/broken code matrix (uint8, i<j: 1 formed, 2 broken).  With ``cell``
+        (3,3), rows as lattice vectors IN THE UNIT OF THE COORDINATES, and ``pbc`` (a bool or three flags) the distances are minimum-image
+        distances over all lattice translations (``umx_bond_changes_cell``); the cell bound by ``set_cell`` is not read.  ``None`` for
+        either, or no flag set: the open-space call as it was.  A non-finite or degenerate cell, or one so skewed that the search would
+        need more than 4 translations per direction, raises ``UmxError``."""
         a = np.ascontiguousarray(r1, dtype=np.float64).reshape(-1, 3)
         b = np.ascontiguousarray(r2, dtype=np.float64).reshape(-1, 3)
         c = np.ascontiguousarray(cov, dtype=np.float64).reshape(-1)
@@ -625,10 +630,17 @@ class Engine:
         d1 = np.empty((n, n), dtype=np.float64) if distances else None
         d2 = np.empty((n, n), dtype=np.float64) if distances else None
         code = np.empty((n, n), dtype=np.uint8)
-        self._chk(self.lib.umx_bond_changes(self._h, n, a.ctypes.data_as(dp), b.ctypes.data_as(dp), c.ctypes.data_as(dp),
-                                            float(bond_factor), float(margin_fraction), float(delta_fraction),
-                                            d1.ctypes.data_as(dp) if distances else None, d2.ctypes.data_as(dp) if distances else None,
-                                            code.ctypes.data_as(C.POINTER(C.c_uint8))), "umx_bond_changes")
+        out = (d1.ctypes.data_as(dp) if distances else None, d2.ctypes.data_as(dp) if distances else None, code.ctypes.data_as(C.POINTER(C.c_uint8)))
+        flags = None if pbc is None else np.broadcast_to(np.asarray(pbc, dtype=bool), (3,))
+        if cell is None or flags is None or not flags.any():
+            self._chk(self.lib.umx_bond_changes(self._h, n, a.ctypes.data_as(dp), b.ctypes.data_as(dp), c.ctypes.data_as(dp),
+                                                float(bond_factor), float(margin_fraction), float(delta_fraction), *out), "umx_bond_changes")
+            return d1, d2, code
+        lat = np.ascontiguousarray(np.asarray(cell, dtype=np.float64).reshape(3, 3))
+        f = np.ascontiguousarray(flags, dtype=np.intc)
+        self._chk(self.lib.umx_bond_changes_cell(self._h, n, a.ctypes.data_as(dp), b.ctypes.data_as(dp), c.ctypes.data_as(dp), lat.ctypes.data_as(dp),
+                                                 f.ctypes.data_as(C.POINTER(C.c_int)), float(bond_factor), float(margin_fraction), float(delta_fraction),
+                                                 *out), "umx_bond_changes_cell")
         return d1, d2, code
 
     # ---- diagnostics -----------------------------------------------------------------------------

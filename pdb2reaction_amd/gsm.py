@@ -37,6 +37,8 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import periodic as PBC
+from ._calculator_base import ANG2BOHR
 from ._host import with_small_host_math
 from .string import select_hei_index
 
@@ -109,6 +111,8 @@ class GSMResult:
     force_evaluations: int          # image evaluations (sum over cycles of images in the batch)
     history: List[Dict[str, float]] = field(default_factory=list)
     timing: Dict[str, float] = field(default_factory=dict)   # seconds: total wall, inside the evaluator, host share = the rest
+    cell: Optional[np.ndarray] = None       # (3, 3) Bohr, the cell the string was unwrapped in; None: open boundaries
+    pbc: Optional[Tuple[bool, bool, bool]] = None
 
 
 # ---- tangents, placement, L-BFGS: torch, any device, no host synchronisation ---------------------------------------------------
@@ -312,13 +316,20 @@ class GrowingStringDriver:
     with the same numpy contract ``evaluate(x[k,3N]) -> (E[k], F[k,3N])``.  ``evaluate_device`` is the device contract:
     ``evaluate_device(x: torch[k,3N] on `device`) -> (E: torch[k], F: torch[k,3N])`` on the same device, nothing crossing PCIe
     (``parallel.EngineStringEvaluator``: the engine's device-pointer entry, sharded over the ranks of a process group).
+
+    PERIODIC CELL.  ``cell`` (3,3) lattice vectors as rows in BOHR, like the coordinates, and ``pbc`` (a bool or three flags) say that
+    the evaluator works in that cell.  The driver then makes the string CONTINUOUS once, at construction, on the host: the product is
+    replaced by ``r + min_image(p - r)`` atom by atom (``periodic.min_image``), and the rows of ``images=`` are unwrapped each onto its
+    predecessor -- a product atom that a relaxation wrapped across the boundary is otherwise dragged through the whole cell by the
+    interpolation.  ``unwrap=False`` keeps the endpoints as given, for an atom that really travels more than half a cell.  Nothing else
+    changes: images stay unwrapped Cartesian coordinates, the engine wraps its own scratch copy, and the driver never re-wraps.
     """
 
     def __init__(self, atoms: Sequence[str], reactant: np.ndarray, product: np.ndarray, calc: Any = None,
                  evaluate: Optional[Callable[[np.ndarray], Any]] = None, gs_kw: Optional[Dict[str, Any]] = None,
                  stopt_kw: Optional[Dict[str, Any]] = None, log: Optional[Callable[[str], None]] = None,
                  evaluate_device: Optional[Callable[[torch.Tensor], Any]] = None, device: Optional[torch.device] = None,
-                 geom_kw: Optional[Dict[str, Any]] = None, images: Optional[np.ndarray] = None):
+                 geom_kw: Optional[Dict[str, Any]] = None, images: Optional[np.ndarray] = None, cell=None, pbc=None, unwrap: bool = True):
         """images: (max_nodes + 2, 3N) Bohr -- start from this FULLY GROWN string (a restart, or a path from another method) instead of
         growing one from the endpoints; its first / last rows must be the reactant / product."""
         self.atoms = list(atoms)
@@ -329,6 +340,13 @@ class GrowingStringDriver:
         p = np.asarray(product, dtype=np.float64).reshape(-1)
         if r.shape != p.shape or r.size != 3 * len(self.atoms):
             raise ValueError("reactant/product must both be (3N,) for the given atoms")
+        self.pbc = PBC.pbc_flags(pbc) if cell is not None else None
+        self.cell = np.array(cell, dtype=np.float64).reshape(3, 3) if self.pbc is not None else None
+        p_given = p
+        if self.cell is not None:
+            PBC.lattice(self.cell, self.pbc)                 # ValueError: a cell the minimum-image search refuses
+            if unwrap:
+                p = PBC.unwrap_onto(r, p, self.cell, self.pbc)
         self.calc, self._evaluate, self._evaluate_device, self.log = calc, evaluate, evaluate_device, (log or (lambda s: None))
         self.device = torch.device(device) if device is not None else torch.device("cpu")
         if evaluate_device is None and self.device.type != "cpu":
@@ -346,8 +364,12 @@ class GrowingStringDriver:
             right = [p - step * (p - r), p]
         if images is not None:
             im = np.asarray(images, dtype=np.float64).reshape(len(images), -1)
-            if im.shape != (self.max_images, r.size) or not (np.array_equal(im[0], r) and np.array_equal(im[-1], p)):
+            if im.shape != (self.max_images, r.size) or not (np.array_equal(im[0], r) and np.array_equal(im[-1], p_given)):
                 raise ValueError(f"images must be ({self.max_images}, {r.size}) with the reactant / product as first / last row")
+            if self.cell is not None and unwrap:             # every row onto its predecessor: the product follows the chain
+                im = im.copy()
+                for k in range(1, len(im)):
+                    im[k] = PBC.unwrap_onto(im[k - 1], im[k], self.cell, self.pbc)
             left, right = list(im[: self.max_images // 2]), list(im[self.max_images // 2:])
         self._x = torch.as_tensor(np.stack(left + right), dtype=torch.float64, device=self.device)
         self._nl = len(left)
@@ -374,7 +396,18 @@ class GrowingStringDriver:
         """The driver for a ``pdb2reaction_amd.uma_pysis`` calculator, DEVICE RESIDENT when the calculator runs on the HIP engine: the string
         lives on the engine's GPU and is evaluated through ``parallel.EngineStringEvaluator`` (device-pointer entry, frozen rows zeroed,
         images sharded over the ranks of `group` when torch.distributed is initialised) -- per image exactly what ``calc.get_forces``
-        returns.  Any other calculator (a stand-in, a core without an engine, the graph-parallel mode) gets the numpy evaluator."""
+        returns.  Any other calculator (a stand-in, a core without an engine, the graph-parallel mode) gets the numpy evaluator.
+
+        A calculator with a periodic cell (``calc.cell`` in Angstrom, ``calc.pbc``) hands it to the driver in Bohr; the engine's own
+        cell persists, so the evaluator needs nothing.  An explicit ``cell=`` (Bohr) wins, but must describe the calculator's cell to
+        1e-9 relative -- ``ValueError`` otherwise: the string would be unwrapped in another cell than it is evaluated in."""
+        if hasattr(calc, "cell") and hasattr(calc, "pbc"):
+            c_cell = None if calc.cell is None else np.asarray(calc.cell, dtype=np.float64) * ANG2BOHR
+            if kw.get("cell") is None:
+                kw = {**kw, "cell": c_cell, "pbc": calc.pbc}
+            elif not PBC.same_cell(kw["cell"], kw.get("pbc"), c_cell, calc.pbc):
+                raise ValueError("GrowingStringDriver.from_calculator: cell= / pbc= (Bohr) do not describe the cell the calculator evaluates in "
+                                 f"(calculator: {None if c_cell is None else c_cell.tolist()} Bohr, pbc={calc.pbc})")
         core = calc._ensure_core(atoms) if hasattr(calc, "_ensure_core") else None
         engine = getattr(core, "engine", None)
         if engine is None or getattr(core, "_gp", None) is not None or not hasattr(engine, "energy_forces_dev"):
@@ -703,4 +736,5 @@ class GrowingStringDriver:
                          timing={"total_s": t_total, "evaluator_s": self.t_eval, "host_s": t_total - self.t_eval,
                                  "redo_steps": float(self.redo_steps), "lanczos_evals": float(self.lanczos_evals),
                                  "lanczos_calls": float(self.lanczos_calls), "lanczos_warm_calls": float(self.lanczos_warm_calls),
-                                 "lanczos_warm_rejected": float(self.lanczos_warm_rejected)})
+                                 "lanczos_warm_rejected": float(self.lanczos_warm_rejected)},
+                         cell=None if self.cell is None else self.cell.copy(), pbc=self.pbc)

@@ -31,20 +31,37 @@ def optimize_path_gsm(elem: Sequence[str], reactant_ang: np.ndarray, product_ang
                       fix_ends: bool = False, thresh: Optional[str] = None, preopt: bool = False, preopt_max_cycles: int = 10000,
                       sopt_kind: str = "lbfgs", sopt_cfg: Optional[Dict[str, Any]] = None, align: bool = True, align_kw: Optional[Dict[str, Any]] = None,
                       gs_kw: Optional[Dict[str, Any]] = None, stopt_kw: Optional[Dict[str, Any]] = None, out_dir: Optional[str] = None,
-                      group=None, log=None) -> Dict[str, Any]:
+                      group=None, log=None, cell=None, pbc=None) -> Dict[str, Any]:
     """Minimum-energy path between two endpoint geometries (Angstrom) by the growing-string method on the HIP engine.
 
     calc: a ``uma_pysis`` instance shared by every step (created from ``calc_kw`` + ``freeze_atoms`` when None, as ``path_opt.py:823``).
     Returns ``{"images_ang" (K, N, 3), "energies" (K,) Hartree, "hei_index", "converged", "cycles", "force_evaluations", "fully_grown",
-    "preopt": [...], "align": [...], "files": {...}}``; with ``out_dir`` the reference's ``final_geometries.trj`` and ``hei.xyz`` are written."""
+    "preopt": [...], "align": [...], "files": {...}, "cell", "pbc"}``; with ``out_dir`` the reference's ``final_geometries.trj`` and ``hei.xyz``
+    are written.
+
+    cell (3,3) lattice vectors as rows in ANGSTROM, pbc a bool or three flags: the path in one fixed periodic cell.  The calculator is
+    created with the cell, or a given one must carry the same cell (``ValueError`` otherwise; a calculator that carries a cell hands it
+    over when none is passed).  The pre-optimisation runs as it is; the rigid alignment is NOT run -- a rotation is no symmetry of a
+    lattice -- and reported as ``"align": [{"skipped": "periodic cell"}]``: the driver's minimum-image unwrapping of the product onto the
+    reactant takes its place.  The images come back unwrapped, as the driver holds them; the file formats do not change."""
     log = log or (lambda s: None)
     elem = [str(e).capitalize() for e in elem]
     n = len(elem)
     freeze = sorted({int(i) for i in freeze_atoms})
+    from . import periodic as PBC
+
+    if cell is not None and PBC.pbc_flags(pbc) is None:
+        cell = pbc = None                                        # no flag set: open boundaries
     if calc is None:
         from .uma_pysis import uma_pysis
 
-        calc = uma_pysis(**{**(calc_kw or {}), "freeze_atoms": freeze})
+        calc = uma_pysis(**{**(calc_kw or {}), "freeze_atoms": freeze, **({} if cell is None else {"cell": cell, "pbc": pbc})})
+    elif cell is None:
+        cell, pbc = getattr(calc, "cell", None), getattr(calc, "pbc", None)
+    elif hasattr(calc, "cell") and not PBC.same_cell(cell, pbc, calc.cell, getattr(calc, "pbc", None)):
+        raise ValueError(f"optimize_path_gsm: cell= / pbc= do not describe the cell the given calculator evaluates in ({getattr(calc, 'cell', None)}, "
+                         f"pbc={getattr(calc, 'pbc', None)})")
+    periodic = cell is not None and PBC.pbc_flags(pbc) is not None
     geoms = [np.asarray(reactant_ang, dtype=np.float64).reshape(n, 3) * ANG2BOHR, np.asarray(product_ang, dtype=np.float64).reshape(n, 3) * ANG2BOHR]
 
     # optional endpoint pre-optimisation (path_opt.py:826-868): a failure keeps the input geometry, as the reference does
@@ -65,7 +82,9 @@ def optimize_path_gsm(elem: Sequence[str], reactant_ang: np.ndarray, product_ang
 
     # rigid alignment + staged anchor scan of the product onto the reactant (path_opt.py:871-886); skipped with a note on failure
     align_info = []
-    if align:
+    if periodic:
+        align_info = [{"skipped": "periodic cell"}]
+    elif align:
         from .prestep import align_and_refine_sequence
 
         try:
@@ -77,7 +96,8 @@ def optimize_path_gsm(elem: Sequence[str], reactant_ang: np.ndarray, product_ang
     g = {"max_nodes": int(max_nodes), "climb": bool(climb), "climb_lanczos": bool(climb) and GS_KW["climb_lanczos"], "fix_first": bool(fix_ends),
          "fix_last": bool(fix_ends), **(gs_kw or {})}
     o = {"max_cycles": int(max_cycles), "stop_in_when_full": int(max_cycles), **({"thresh": thresh} if thresh else {}), **(stopt_kw or {})}
-    drv = GrowingStringDriver.from_calculator(elem, geoms[0].reshape(-1), geoms[1].reshape(-1), calc, group=group, gs_kw=g, stopt_kw=o, log=log)
+    drv = GrowingStringDriver.from_calculator(elem, geoms[0].reshape(-1), geoms[1].reshape(-1), calc, group=group, gs_kw=g, stopt_kw=o, log=log,
+                                              **({"cell": np.asarray(cell, dtype=np.float64).reshape(3, 3) * ANG2BOHR, "pbc": pbc} if periodic else {}))
     res = drv.run()
     images_ang = res.coords.reshape(len(res.coords), n, 3) * BOHR2ANG
     hei = select_hei_index(res.energies)                         # path_opt.py:259-273
@@ -90,4 +110,5 @@ def optimize_path_gsm(elem: Sequence[str], reactant_ang: np.ndarray, product_ang
         formats.write_xyz(elem, images_ang[hei], files["hei"], energy_hartree=float(res.energies[hei]))
     return {"images_ang": images_ang, "energies": res.energies, "hei_index": int(hei), "converged": bool(res.converged), "cycles": int(res.cycles),
             "force_evaluations": int(res.force_evaluations), "fully_grown": bool(res.fully_grown), "history": res.history, "timing": res.timing,
-            "device": str(drv.device), "preopt": pre, "align": align_info, "files": files, "defaults": {"GS_KW": dict(GS_KW), "STOPT_KW": dict(STOPT_KW)}}
+            "device": str(drv.device), "preopt": pre, "align": align_info, "files": files, "defaults": {"GS_KW": dict(GS_KW), "STOPT_KW": dict(STOPT_KW)},
+            "cell": None if not periodic else np.array(cell, dtype=np.float64).reshape(3, 3), "pbc": PBC.pbc_flags(pbc) if periodic else None}

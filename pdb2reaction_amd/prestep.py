@@ -264,8 +264,18 @@ def scan_toward_target(calc, elem, ref_bohr: np.ndarray, mob_bohr: np.ndarray, a
     return (q[0] if single else q), (info[0] if single else info)
 
 
+def _refuse_periodic(calc, who: str) -> None:
+    """A rigid rotation is not a symmetry of a lattice: the Kabsch fit would rotate the geometry against the cell the calculator evaluates in."""
+    pbc = getattr(calc, "pbc", None)
+    if pbc is not None and np.any(pbc):
+        raise ValueError(f"{who}: the calculator evaluates in a periodic cell (pbc={tuple(bool(x) for x in np.broadcast_to(pbc, (3,)))}); a rigid "
+                         "alignment would rotate the geometry against the lattice.  Unwrap the images instead (gsm.GrowingStringDriver(cell=...))")
+
+
 def align_and_refine_pair(calc, elem, ref_bohr, mob_bohr, freeze_ref=(), freeze_mob=(), **scan_kw):
-    """Rigid alignment then the staged scan for one (reference, mobile) pair (reference ``align_and_refine_pair_inplace``)."""
+    """Rigid alignment then the staged scan for one (reference, mobile) pair (reference ``align_and_refine_pair_inplace``).
+    ``ValueError`` for a calculator whose ``pbc`` has a flag set."""
+    _refuse_periodic(calc, "align_and_refine_pair")
     n = np.asarray(ref_bohr).reshape(-1, 3).shape[0]
     idx = freeze_union(freeze_ref, freeze_mob, n)
     aligned, a_info = align_second_to_first(ref_bohr, mob_bohr, idx)
@@ -282,7 +292,9 @@ def align_and_refine_sequence(calc, elem, coords_list, freeze_list=None, *, batc
     anchors and scanned TOGETHER (one batched E+F per L-BFGS cycle instead of one per image).  Other cases (1-2 anchors,
     differing freeze lists) run pair after pair exactly in the reference's order.
     Returns (list of coordinates, list of {"align", "scan"} per pair); element 0 is returned unchanged.
+    ``ValueError`` for a calculator whose ``pbc`` has a flag set.
     """
+    _refuse_periodic(calc, "align_and_refine_sequence")
     geoms = [np.asarray(c, dtype=float).reshape(-1, 3) for c in coords_list]
     m = len(geoms)
     fl = [list(f) for f in (freeze_list if freeze_list is not None else [[]] * m)]

@@ -17,6 +17,11 @@ uses the batched path (the 2*3N_active displaced geometries are images of one ba
 reference's arithmetic: float32 forces, central difference with h = 1e-3 A, columns assembled in
 float64 when ``hessian_double``.
 
+Own keywords, taken out of ``**kwargs`` so that the reference's signature stays: ``precision``, ``recompute``,
+``double_positions``, ``hessian_pin_graph``, and ``cell`` (3,3, Angstrom) / ``pbc`` -- ONE fixed periodic cell, bound on
+the engine after the system (``Engine.set_cell``), in which every energy, force and Hessian is then evaluated
+(``uma_pysis.set_cell`` re-binds it).  The reference never sets a cell (``:292-327``).
+
 There is no CPU fallback: importing works anywhere, evaluating requires a gfx950 GPU and the built
 library, and fails loudly otherwise.
 """
@@ -164,6 +169,8 @@ class UMAcore:
         precision: Optional[str] = None,
         recompute: Optional[int] = None,
         double_positions: bool = False,
+        cell=None,
+        pbc=None,
     ):
         from .engine import Engine  # raises ImportError loudly when libumx.so is missing
 
@@ -231,6 +238,8 @@ class UMAcore:
             self.engine.load_weights(weights)
             self.engine.set_system(self.z, charge=charge, spin=spin, task=task_name, radius=radius, max_neigh=max_neigh)
         self.local_devices = list(pool_devices) if pool_devices is not None else [dev_index]   # ordinals in use by this core
+        if cell is not None:                              # one periodic cell (A) for every geometry of this core, bound after the system
+            self.set_cell(cell, pbc)
         self._gp = None
         if self.workers > 1 and os.environ.get("UMX_WORKERS_GP", "1") != "0":
             # the reference's workers > 1 IS graph-parallel inference of one structure over `workers` processes
@@ -257,6 +266,12 @@ class UMAcore:
 
     def reserve_images(self, n_images: int) -> None:
         (self._pool if self._pool is not None else self.engine).reserve_images(int(n_images))
+
+    def set_cell(self, cell=None, pbc=None) -> None:
+        """``Engine.set_cell`` (cell (3,3) in A, pbc a bool or three flags; None: open boundaries) on the engine, or on every engine of
+        an in-process pool.  It persists: every later ``compute`` / ``compute_batch`` / ``compute_batch_dev``, the graph-parallel mode
+        included (``umx_gp_begin`` honours the bound cell), evaluates in that cell."""
+        (self._pool if getattr(self, "_pool", None) is not None else self.engine).set_cell(cell, pbc)
 
     def enable_graph_parallel(self, on: bool = True, group=None) -> None:
         """Evaluate every geometry with its GRAPH partitioned over the ranks of `group` (default: the world) -- the reference's
@@ -399,6 +414,11 @@ class uma_pysis(Calculator):
         # through max_neigh) -- the graph held fixed is what the reference's "Analytical" mode differentiates (:394-417).  Not with the
         # graph-parallel mode, whose entries build their own graph.
         self.hessian_pin_graph = bool(kwargs.pop("hessian_pin_graph", False))
+        # likewise: one periodic cell for every geometry this calculator sees -- cell (3,3) lattice vectors as rows in ANGSTROM (the unit of
+        # Engine.set_cell and of ASE, not the Bohr of the coordinates), pbc a bool or three flags.  Bound on the engine right after the
+        # system; everything behind it (energies, forces, batches, the FD Hessian with or without hessian_pin_graph / double_positions) is
+        # the engine with that cell.  The reference never sets a cell (:292-327).
+        self.cell, self.pbc = _cell_and_flags(kwargs.pop("cell", None), kwargs.pop("pbc", None))
         super().__init__(charge=charge, mult=spin, **kwargs)
         self._core: Optional[UMAcore] = None
         self._core_kw = dict(
@@ -408,6 +428,8 @@ class uma_pysis(Calculator):
         )
         if self.double_positions:                 # (only then: a stand-in core keeps the reference's signature)
             self._core_kw["double_positions"] = True
+        if self.cell is not None:                 # (likewise)
+            self._core_kw.update(cell=self.cell, pbc=self.pbc)
         self._reserve_images = 0
         self.out_hess_torch = out_hess_torch
         self.hessian_calc_mode = hessian_calc_mode
@@ -433,6 +455,17 @@ class uma_pysis(Calculator):
         self._reserve_images = max(0, int(n_images))
         if getattr(self._core, "engine", None) is not None:
             (self._core if hasattr(self._core, "reserve_images") else self._core.engine).reserve_images(self._reserve_images)
+
+    def set_cell(self, cell=None, pbc=None) -> None:
+        """Bind another cell (A; ``None`` or no flag set: open boundaries) without rebuilding the core: weights, system and workspace
+        stay, the next call evaluates in the new cell.  Before the first call it only changes what the core will be built with."""
+        self.cell, self.pbc = _cell_and_flags(cell, pbc)
+        for key in ("cell", "pbc"):
+            self._core_kw.pop(key, None)
+        if self.cell is not None:
+            self._core_kw.update(cell=self.cell, pbc=self.pbc)
+        if self._core is not None:
+            self._core.set_cell(self.cell, self.pbc)
 
     def close(self) -> None:
         """Release the engine (HBM workspace, weights) now instead of at garbage collection; the calculator can be used
@@ -558,6 +591,22 @@ class uma_pysis(Calculator):
         f_ev = H.mask_frozen(res["forces"], self.freeze_atoms)
         return {"energy": res["energy"] * EV2AU, "forces": (np.asarray(f_ev, dtype=np.float64) * F_EVAA_2_AU).reshape(-1),
                 "hessian": H.hessian_to_au(hess, double=self.hessian_double, as_torch=self.out_hess_torch)}
+
+
+def _cell_and_flags(cell, pbc):
+    """(cell (3,3) float64 copy, three bools), or (None, None) for open boundaries: no cell, or no flag set.  A cell without flags is
+    refused rather than read as open or as fully periodic."""
+    if cell is None:
+        return None, None
+    if pbc is None:
+        raise ValueError("uma_pysis: a cell needs pbc (a bool or three flags)")
+    flags = tuple(bool(x) for x in np.broadcast_to(np.asarray(pbc, dtype=bool), (3,)))
+    if not any(flags):
+        return None, None
+    c = np.array(cell, dtype=np.float64).reshape(3, 3)
+    if not np.isfinite(c).all():
+        raise ValueError("uma_pysis: non-finite cell entry")
+    return c, flags
 
 
 def _bohr_to_ang(coords) -> np.ndarray:
