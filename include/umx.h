@@ -519,7 +519,8 @@ int umx_debug_keep(umx_engine* eng, int on);
  * as they are on the device (float32 data section, float32 derived weights, 16-bit plane copies); "weights:table" -- the tensor table of
  * "weights:w" as text, one "<name> <first float> <floats>" per line; "experts:kernel_ms" -- one float, the milliseconds between the events
  * around the merge and packing kernels of the last umx_set_expert_coefficients; "gemm:table" -- the table of plane-GEMM instantiations as
- * text, one "<family> <cplx> <wide> <ls> <al> <half>" per row; "gemm:launches" -- one line per plane-GEMM launch of the most recent
+ * text, one "<family> <cplx> <wide> <ls> <al> <half>" per row; "gemm:table_gate" -- likewise the conv-2^T kernels that carry the
+ * gate-reverse epilogue (family "Q_BF16_GATE"; UMX_GATE_EPI); "gemm:launches" -- one line per plane-GEMM launch of the most recent
  * evaluation's last chunk, in launch order: "fwd|rev <the six key fields> <M> <N> <K> <blocks>" (recorded only while umx_debug_keep is on,
  * cleared when a chunk starts).                                                                                                         */
 

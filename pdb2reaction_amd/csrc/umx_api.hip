@@ -235,6 +235,7 @@ int umx_create(umx_engine** out, int device_ordinal) {
   if (const char* ev = std::getenv("UMX_ALT_ROWS")) e->odd_sign = std::atoi(ev) != 0 ? -1.0f : 1.0f;
   if (const char* ev = std::getenv("UMX_LOW_SEP")) e->low_sep = std::atoi(ev);
   if (const char* ev = std::getenv("UMX_GEMM_HALF")) e->gemm_half = std::atoi(ev);
+  if (const char* ev = std::getenv("UMX_GATE_EPI")) e->gate_epi = std::max(0, std::min(2, std::atoi(ev)));
   if (const char* ev = std::getenv("UMX_ALIGN_PLANES")) e->align = std::atoi(ev);
   // stream2 (the second lane) is created with the highest priority (as measured in rounds 3-5; priorities change little on this pool)
   int prio_lo = 0, prio_hi = 0;
@@ -696,10 +697,10 @@ int umx_debug_keep(umx_engine* eng, int on) {
 int umx_debug_fetch(umx_engine* eng, const char* name, void* host_buf, size_t capacity, size_t* nbytes_out) {
   if (!eng || !name) return UMX_ERR_ARG;
   const std::string nm(name);
-  if (nm == "gemm:table" || nm == "gemm:launches") {
-    // text, host side only: the rows of pl_kernels ("fam cplx wide ls al half"), and the gemm_pl launches of the most recent evaluation's
+  if (nm == "gemm:table" || nm == "gemm:table_gate" || nm == "gemm:launches") {
+    // text, host side only: the rows of pl_kernels / of pl_gate_kernels ("fam cplx wide ls al half"), and the gemm_pl launches of the most recent evaluation's
     // last chunk in launch order ("fwd|rev fam cplx wide ls al half M N K blocks"; recorded while umx_debug_keep is on)
-    const std::string text = nm == "gemm:table" ? pl_table_text() : eng->gemm_log;
+    const std::string text = nm == "gemm:table" ? pl_table_text() : nm == "gemm:table_gate" ? pl_gate_table_text() : eng->gemm_log;
     if (nbytes_out) *nbytes_out = text.size();
     if (host_buf) {
       if (capacity < text.size()) return fail(eng, UMX_ERR_ARG, "umx_debug_fetch: buffer too small");

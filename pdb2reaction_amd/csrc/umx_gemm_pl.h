@@ -45,6 +45,10 @@ struct GemmPL {
   float odd_sign;    // +1, or -1 when the producer stored the A rows of ODD index negated (sign-alternating rows, umx_edge.h): the
                      // epilogue multiplies the accumulators of odd rows by it, so C is what it would be -- with the matrix core's one-sided
                      // rounding error reversed on every second row.  0 is read as +1 (dev programs that memset the struct).
+  // the gate-reverse epilogue of the conv-2^T products (umx_gemm_q.h, EP = 1; unused elsewhere): hg = the forward [gate | hpre] rows,
+  // ghg = g_hg as float32 quad-row blocks, gate_acc = the per-edge gate sums (2 x 128 floats), ep_mode = which product of the convolution
+  // (0: m = 0 starts the sums, 1: m = 1 completes degree 1, 2: m = 2 completes degree 2)
+  const float* hg; float* ghg; float* gate_acc; int ep_mode;
 };
 
 template <int N> __device__ __forceinline__ void wait_vmcnt() {

@@ -93,6 +93,70 @@ __host__ __device__ constexpr bool q_use_product(int PA, int PB, int NPROD, int 
   return NPROD == 4 ? true : (qa + qb < 2);
 }
 
+// ---- EP = 1: the gate-reverse epilogue of the conv-2^T products (bf16x3 reverse pass) -----------------------------------------------
+// The finished element g = g_hid[e, r * 128 + c] is not stored: the epilogue applies gate^T to it (gate_bwd_row / gate_bwd_gate of
+// umx_edge.h, the same float32 operations in the same order, so g_hg is bit for bit what k_gate_edge_bwd_q3<3> writes from a stored g_hid)
+// and writes g_hg, conv-1^T's quad-row operand, itself.  What it needs beside g is in the forward hg row of the edge.  The two gate sums
+// a_l = sum over the rows of degree l of g . hpre travel through `gate_acc` (E x 2 x 128 floats) between the convolution's three launches,
+// which run m = 0, 1, 2 on one stream with one writer per element: m = 0 stores (rows 1 | 2), m = 1 adds rows 3, 5 | 4, 6 and completes
+// degree 1, m = 2 adds rows 7, 8 and completes degree 2 -- the order gate_bwd_row adds them in.  Every multiply-add of a sum is ONE fma, as
+// the compiler contracts `a += g * h` there (checked in the ISA of k_gate_edge_bwd_q3); here it is written out so that it cannot change.
+// dword index of element (row, k) of a `cols`-column float32 quad-row operand (q_ptr<3>, umx_edge.h)
+__device__ __forceinline__ long qf_index(long row, int cols, int k) { return ((row >> 2) * (cols >> 4) + (k >> 4)) * 64 + (row & 3) * 16 + (k & 15); }
+// One lane's 16 rows (edges e0 + cd_row(r)) of one channel; g(v, r) = the element of register r (v = 0 / 1: re / im of a complex product).
+// MODE 0: the plain m = 0 product, col = row * 128 + c with row = 0, 1, 2.  MODE 1 / 2: the complex m = 1 / m = 2 product; m = 1:
+// col = (degree - 1) * 128 + c, rows 3 + d (re), 5 + d (im); m = 2: rows 7, 8, degree 2.  FULL: the tile lies inside M; else rows >= M of the
+// last row group are stored as zeros (the GEMM behind reads whole groups of four rows) and rows beyond it are not stored.
+// Four rows (one row group: whole 64-byte pieces of g_hg's blocks) at a time; the inputs of the next four are requested before the
+// stores of the current ones are issued, so a wave waits for one round trip per tile column, not four.
+template <int MODE, bool FULL, class G>
+__device__ __forceinline__ void gate_epilogue(const GemmPL& p, long e0, int col, G g) {
+  constexpr int NV = MODE == 0 ? 1 : 2;
+  const int c = col & (H - 1), blk = col >> 7;                                  // (wave-uniform: a lane group spans 32 aligned columns)
+  const int deg = MODE == 0 ? blk - 1 : MODE == 1 ? blk : 1;                    // 0 / 1: degree 1 / 2; -1: the l = 0 row (SiLU)
+  const int row_o[2] = {MODE == 0 ? blk : MODE == 1 ? 3 + blk : 7, MODE == 0 ? blk : MODE == 1 ? 5 + blk : 8};
+  const bool finish = (MODE == 1 && deg == 0) || MODE == 2;                     // this launch completes the degree's sum
+  const long M4 = ((long)p.M + 3) & ~3L;
+  float gate[2][4], hp[2][NV][4], a[2][4];
+  auto request = [&](int b, int q4) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const long e = e0 + 8 * q4 + q;
+      const float* hr = p.hg + (FULL || e < p.M ? e : (long)p.M - 1) * HG;      // (padding rows: any finite input; zeros are stored)
+      gate[b][q] = deg >= 0 ? hr[deg * H + c] : 0.f;
+#pragma unroll
+      for (int v = 0; v < NV; ++v) hp[b][v][q] = hr[2 * H + row_o[v] * H + c];
+      a[b][q] = (MODE != 0 && (FULL || e < p.M)) ? p.gate_acc[e * (2 * H) + deg * H + c] : 0.f;
+    }
+  };
+  request(0, 0);
+#pragma unroll
+  for (int q4 = 0; q4 < 4; ++q4) {
+    const int b = q4 & 1;
+    if (q4 < 3) request(b ^ 1, q4 + 1);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int r = 4 * q4 + q;                                                 // cd_row<16>(r) = 8 q4 + q
+      const long e = e0 + 8 * q4 + q;
+      const bool in = FULL || e < p.M;
+      if (!FULL && e >= M4) continue;
+      const float rs = (q & 1) ? p.odd_sign : 1.0f;                             // row_sign(e): the tile origin is even
+      float s = 0.f, acc = a[b][q];
+      if (deg >= 0) s = sigmoid_f(gate[b][q]);
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        const float gv = g(v, r);
+        const float w = deg < 0 ? gv * silu_grad_f(hp[b][v][q]) : gv * s;
+        p.ghg[qf_index(e, HG, 2 * H + row_o[v] * H + c)] = in ? rs * w : 0.f;
+        if (deg >= 0) acc = __builtin_fmaf(gv, hp[b][v][q], acc);
+      }
+      if (deg < 0) continue;
+      if (finish) p.ghg[qf_index(e, HG, deg * H + c)] = in ? rs * (acc * s * (1.0f - s)) : 0.f;
+      else if (in) p.gate_acc[e * (2 * H) + deg * H + c] = acc;
+    }
+  }
+}
+
 // P / PB = planes of the A / B operand (PB defaults to P).  F16 = 1: the planes are IEEE half (11-bit significands) and the products
 // run on v_mfma_f32_32x32x16_f16, else bf16.  NPROD = number of plane products (q_use_product).  The engine uses <.., 3, 2, 0, 6, 3, 1>
 // (bf16x3 / split-bf16: A as float32, AF) and <.., 2, 2, 1, 4, 3> (split: fp16 planes, exact weights); the other forms are gemm_bench's.
@@ -104,9 +168,12 @@ __host__ __device__ constexpr bool q_use_product(int PA, int PB, int NPROD, int 
 // runs its k loop while the first one waits for its prologue's DMA round trip or drains its stores (NOTES.md section 13).
 // AL = 1 (AF kernels, forward products): "aligned planes" -- the leading plane of A is quantised to the lane's pass group (qf_align_magic,
 // umx_gemm.h); the weights' leading plane is quantised the same way when the planes are built (umx_api.hip).
-template <int CPLX, int WIDE, int P = 3, int S = 2, int F16 = 0, int NPROD = (P == 3 ? 6 : 3), int PB = P, int AF = 0, int LS = 0, int AL = 0, int MW = 4>
+// EP = 1 (AF kernels without LS / AL; conv 2^T of the bf16x3 reverse pass): the gate-reverse epilogue above instead of the store of C; k loop,
+// tile map, accumulators and product order are those of EP = 0.  Instantiated apart from the dispatch table (pl_gate_kernels, umx_launch.h).
+template <int CPLX, int WIDE, int P = 3, int S = 2, int F16 = 0, int NPROD = (P == 3 ? 6 : 3), int PB = P, int AF = 0, int LS = 0, int AL = 0, int MW = 4, int EP = 0>
 __global__ __launch_bounds__(MW * 128, MW == 4 ? 1 : 2) void umx_gemm_q_kernel(const GemmPL p) {
   static_assert(!AL || AF, "AL: the float32-A kernels");
+  static_assert(!EP || (AF && !LS && !AL && (CPLX || !WIDE)), "EP (gate-reverse epilogue): the six-product float32-A form; plain narrow, complex narrow or wide");
   static_assert(!LS || (P == 3 && PB == 3 && !F16 && NPROD == 6), "LS: the six-product bf16 form");
   static_assert(LS != 2 || !WIDE, "LS = 2 (second accumulator set): 256 x 128 tiles only");
   static_assert(MW == 4 || MW == 2, "waves along M: 4 (256-row tiles) or 2 (half-height tiles, two workgroups per CU)");
@@ -209,7 +276,7 @@ __global__ __launch_bounds__(MW * 128, MW == 4 ? 1 : 2) void umx_gemm_q_kernel(c
   }
 
   const int nk = p.K / 16;
-  constexpr long TAG = kernel_tag<CPLX, WIDE, P, S, F16, NPROD, PB, AF, LS, AL, MW>();   // one q3_issue instance per kernel
+  constexpr long TAG = kernel_tag<CPLX, WIDE, P, S, F16, NPROD, PB, AF, LS, AL, MW, EP>();   // one q3_issue instance per kernel
   constexpr int GI = JA + JBF;                            // DMA instructions per tile per wave (+1 for the waves that fetch the half round)
 #pragma unroll
   for (int t = 0; t < S - 1; ++t)
@@ -316,7 +383,38 @@ __global__ __launch_bounds__(MW * 128, MW == 4 ? 1 : 2) void umx_gemm_q_kernel(c
   // ---- epilogue: cscale and the sign of the odd rows (row parity = r & 1); the bias is where the accumulators started.  The two store
   //      forms: cd_row in umx_gemm.h
   const bool full = ((long)mt * BMR + BMR <= p.M) && (nt * BNC + BNC <= p.N);
-  if (CPLX) {
+  if constexpr (EP != 0) {
+    // EP = 1: the same elements, sign and conj applied, go through gate^T into g_hg instead of being stored (gate_epilogue above)
+    if constexpr (CPLX) {
+      auto column = [&](auto cg_) {                // (a constant, not a loop counter: the loop is not unrolled around the asm below, and acc would go to scratch)
+        constexpr int cg = decltype(cg_)::value;
+        int chan = nt * BNC + wn * (16 * TNW) + cg * 32 + l31;
+        long e0 = (long)mt * BMR + wm * 32 + 4 * h;
+        asm volatile("" : "+v"(chan), "+v"(e0));   // opaque: the epilogue's addresses are computed here, not hoisted above the k loop (where they would spill)
+        auto g = [&](int v, int r) -> float {
+          // (re = a0 - conj a1, im = a1 + conj a0, each ONE fma as the compiler contracts them in the EP = 0 store below -- its ISA holds
+          //  one v_fma / v_fmac per stored element and no separate multiply; written out here so that the two cannot drift apart)
+          return v == 0 ? ((r & 1) ? cso : cs) * __builtin_fmaf(-p.conj, acc[1][TNW / 2 + cg][r], acc[0][cg][r])
+                        : ((r & 1) ? cso : cs) * __builtin_fmaf(p.conj, acc[0][TNW / 2 + cg][r], acc[1][cg][r]);
+        };
+        if (p.ep_mode == 2) { if (full) gate_epilogue<2, true>(p, e0, chan, g); else if (chan < p.N) gate_epilogue<2, false>(p, e0, chan, g); }
+        else                { if (full) gate_epilogue<1, true>(p, e0, chan, g); else if (chan < p.N) gate_epilogue<1, false>(p, e0, chan, g); }
+      };
+      column(std::integral_constant<int, 0>());
+      if constexpr (TNW / 2 > 1) column(std::integral_constant<int, 1>());
+    } else {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < TNW; ++j) {
+          int col = nt * BN + wn * (32 * TNW) + j * 32 + l31;
+          long row0 = (long)mt * BM + wm * 64 + i * 32 + 4 * h;
+          asm volatile("" : "+v"(col), "+v"(row0));   // opaque: the epilogue's addresses are computed here, not hoisted above the k loop
+          auto g = [&](int, int r) -> float { return ((r & 1) ? cso : cs) * acc[i][j][r]; };
+          if (full) gate_epilogue<0, true>(p, row0, col, g); else if (col < p.N) gate_epilogue<0, false>(p, row0, col, g);
+        }
+    }
+  } else if (CPLX) {
 #pragma unroll
     for (int cg = 0; cg < TNW / 2; ++cg) {
       const int chan = nt * BNC + wn * (16 * TNW) + cg * 32 + l31;

@@ -155,17 +155,29 @@ const PlKernel pl_kernels[] = {
     {{PL2_M16, false}, umx_gemm_pl_kernel<16, 0, 2, 3, 4, 2, 2, 2>},        {{PL2_M16, true}, umx_gemm_pl_kernel<16, 1, 2, 3, 4, 2, 2, 2>},
     {{PL2_M32, false}, umx_gemm_pl_kernel<32, 0, 2, 3, 4, 2, 2, 2>},
 };
+// The conv-2^T products of the bf16x3 reverse pass with the gate-reverse epilogue (umx_gemm_q.h EP = 1): a table of their own, the forms
+// choose_pl can pick for a reverse Q_BF16 product of those shapes (plain: N = 384, narrow; complex: N = 256 / 128, narrow or wide; either
+// height).  Logged as family "Q_BF16_GATE" (umx_debug_fetch "gemm:table_gate", "gemm:launches").
+struct GateEpi { const float* hg; float* ghg; float* acc; int mode; };     // GemmPL::hg, ghg, gate_acc, ep_mode
+#define UMX_QG(cplx, wide, half) {{Q_BF16, cplx != 0, wide != 0, false, false, half != 0}, umx_gemm_q_kernel<cplx, wide, 3, 2, 0, 6, 3, 1, 0, 0, (half ? 2 : 4), 1>}
+const PlKernel pl_gate_kernels[] = {UMX_QG(0, 0, 0), UMX_QG(0, 0, 1), UMX_QG(1, 0, 0), UMX_QG(1, 0, 1), UMX_QG(1, 1, 0), UMX_QG(1, 1, 1)};
+#undef UMX_QG
 #undef UMX_Q
 #undef UMX_Q4
 // a key as text, "fam cplx wide ls al half" (umx_debug_fetch "gemm:table", "gemm:launches")
-std::string pl_key_text(const PlKey& k) {
+std::string pl_key_text(const PlKey& k, bool gate = false) {
   static const char* const fam[] = {"Q_F16", "Q_BF16", "PL3_ROWS", "PL3", "PL2_WIDE", "PL2_M16", "PL2_M32"};
-  return std::string(fam[k.fam]) + " " + std::to_string(k.cplx) + " " + std::to_string(k.wide) + " " + std::to_string(k.ls) + " " + std::to_string(k.al) + " " +
+  return std::string(fam[k.fam]) + (gate ? "_GATE " : " ") + std::to_string(k.cplx) + " " + std::to_string(k.wide) + " " + std::to_string(k.ls) + " " + std::to_string(k.al) + " " +
          std::to_string(k.half);
 }
 std::string pl_table_text() {
   std::string t;
   for (const PlKernel& e : pl_kernels) t += pl_key_text(e.key) + "\n";
+  return t;
+}
+std::string pl_gate_table_text() {
+  std::string t;
+  for (const PlKernel& e : pl_gate_kernels) t += pl_key_text(e.key, true) + "\n";
   return t;
 }
 
@@ -232,6 +244,11 @@ PlChoice choose_pl(const Precision& pm, Pass pass, bool w_quad, int cplx, long M
   // was expected to pay (their 190 / 239 VGPRs cost them their co-resident partner in round 5), measured NO gain: c3 step -0.1 ms
   // (narrow) / -0.4 ms (+ fc3) against an A/A spread of 0.8 ms; every Q_BF16 product -6.4 ms, complex only -5.1 ms
   // (profiles/half_tile_ab.txt; NOTES.md section 13).
+  // The conv-2^T products with the gate-reverse epilogue (pl_gate_kernels) INHERIT this rule through the same key: under the default 5 the
+  // plain 384 x 384 and the complex 256 x 256 product run on half-height tiles, the complex 128 x 128 product (K < 256) at full height.  The
+  // rule is not re-fitted to the fused forms: tests/test_gpu_gate_epilogue.py requires a fused launch to have the tile form of the unfused
+  // product.  The per-launch times of the three fused shapes at full against half height (UMX_GEMM_HALF 0 / 3), as far as they were
+  // measured, are in profiles/gate_epilogue_ab.txt section 3.
   c.key.half = c.key.fam == Q_BF16 && (half == 3 || (half == 4 && cplx) || (half == 5 && !c.key.ls && K >= 256) ||
                                (fwd && c.key.ls && (half == 2 || (half == 1 && !c.key.wide))));
   const long nMf = c.key.half ? (M + bmr / 2 - 1) / (bmr / 2) : nM;     // row tiles of the form that runs
@@ -241,7 +258,8 @@ PlChoice choose_pl(const Precision& pm, Pass pass, bool w_quad, int cplx, long M
 
 // Wkey = fp32 device pointer of the weight (its plane copy is looked up); a_cols = total columns of the A matrix; offsets in columns.
 int gemm_pl(umx_engine* eng, int cplx, Pass pass, const unsigned short* Apl, int a_cols, int offA0, int offA1, const float* Wkey, int bHalf,
-            const float* bias, float* Cp, long ldc, int offC, int offCi, long M, int N, int K, float conj, bool a_f32rows = false) {
+            const float* bias, float* Cp, long ldc, int offC, int offCi, long M, int N, int K, float conj, bool a_f32rows = false,
+            const GateEpi* gate = nullptr) {
   if (M <= 0) return UMX_OK;
   auto it = eng->planes.find(Wkey);
   if (it == eng->planes.end()) return fail(eng, UMX_ERR_ARG, "gemm_pl: weight has no PL copy");
@@ -250,7 +268,11 @@ int gemm_pl(umx_engine* eng, int cplx, Pass pass, const unsigned short* Apl, int
   const PlChoice c = choose_pl(eng->prec, pass, w.quad, cplx, M, N, K, a_cols, a_f32rows, eng->low_sep, eng->align, eng->gemm_half);
   if (c.err) return fail(eng, UMX_ERR_ARG, c.err);
   const PlKernel* k = nullptr;
-  for (const PlKernel& e : pl_kernels)
+  // gate: the product's elements go through gate^T into g_hg (so2_conv, conv 2^T of the bf16x3 reverse pass) -- the same key, and so the
+  // same tile form, looked up in the table of the kernels with that epilogue
+  if (gate && (c.key.fam != Q_BF16 || pass != REV || N % 128 != 0)) return fail(eng, UMX_ERR_ARG, "gemm_pl: the gate-reverse epilogue goes with the reverse Q_BF16 products");
+  if (gate) { for (const PlKernel& e : pl_gate_kernels) if (e.key == c.key) { k = &e; break; } }
+  else for (const PlKernel& e : pl_kernels)
     if (e.key == c.key) { k = &e; break; }
   if (!k) return fail(eng, UMX_ERR_ARG, "gemm_pl: variant not instantiated");
   GemmPL q;
@@ -258,13 +280,14 @@ int gemm_pl(umx_engine* eng, int cplx, Pass pass, const unsigned short* Apl, int
   q.Apl = Apl; q.lda = c.lda; q.offA0 = offA0; q.offA1 = offA1; q.Bpl = w.ptr; q.ldb = c.ldb; q.bHalf = bHalf;
   q.Cp = Cp; q.ldc = ldc; q.offC = offC; q.offCi = offCi; q.bias = bias; q.conj = conj; q.M = (int)M; q.N = N; q.K = K;
   q.odd_sign = eng->odd_sign;
+  if (gate) { q.hg = gate->hg; q.ghg = gate->ghg; q.gate_acc = gate->acc; q.ep_mode = gate->mode; }
   if (c.key.fam == Q_F16) q.cscale = 1.0f / (QF16_SCALE * w.scale);
   ProfRec* pr;
   CHK(prof_open(eng, &pr, cplx ? 8.0 * M * (double)N * K : 2.0 * M * (double)N * K, c.prec, M, N, K, 9, cplx));
   hipLaunchKernelGGL(k->fn, dim3(c.blocks), dim3(c.key.half ? 256 : 512), 0, eng->stream, q);
   HIPCHK(eng, hipGetLastError());
   if (eng->dbg_on)
-    eng->gemm_log += std::string(pass == FWD ? "fwd " : "rev ") + pl_key_text(c.key) + " " + std::to_string(M) + " " + std::to_string(N) + " " + std::to_string(K) + " " +
+    eng->gemm_log += std::string(pass == FWD ? "fwd " : "rev ") + pl_key_text(c.key, gate != nullptr) + " " + std::to_string(M) + " " + std::to_string(N) + " " + std::to_string(K) + " " +
                      std::to_string(c.blocks) + "\n";
   return prof_close(eng, pr);
 }
@@ -285,12 +308,15 @@ constexpr int SO2_RAD_M1 = 768, SO2_RAD_M2 = 1280;
 // Split-precision modes: A = the pre-split operand planes (gemm_pl).  fp32 mode: A = float32 rows; R != nullptr (conv 1 forward): the
 // A operand is modulated by the radial rows R while it is staged.
 int so2_conv(umx_engine* eng, Pass pass, const void* A, const So2Layout& la, float* Cp, const So2Layout& lc, const float* Wm0, const float* Wm1,
-             const float* Wm2, const float* bias, long ne, float conj, const float* R = nullptr) {
+             const float* Wm2, const float* bias, long ne, float conj, const float* R = nullptr, const GateEpi* gate = nullptr) {
   if (eng->prec.planes) {
     const unsigned short* Apl = static_cast<const unsigned short*>(A);
-    CHK(gemm_pl(eng, 0, pass, Apl, la.ld, 0, 0, Wm0, 0, bias, Cp, lc.ld, 0, 0, ne, lc.m0, la.m0, 1.0f));
-    CHK(gemm_pl(eng, 1, pass, Apl, la.ld, la.m1re, la.m1im, Wm1, lc.m1w, nullptr, Cp, lc.ld, lc.m1re, lc.m1im, ne, lc.m1w, la.m1w, conj));
-    return gemm_pl(eng, 1, pass, Apl, la.ld, la.m2re, la.m2im, Wm2, lc.m2w, nullptr, Cp, lc.ld, lc.m2re, lc.m2im, ne, lc.m2w, la.m2w, conj);
+    // gate (conv 2^T, bf16x3 reverse): C = g_hid is not written; the three products apply gate^T and write g_hg (GateEpi::mode = m)
+    GateEpi g[3];
+    for (int m = 0; m < 3 && gate; ++m) { g[m] = *gate; g[m].mode = m; }
+    CHK(gemm_pl(eng, 0, pass, Apl, la.ld, 0, 0, Wm0, 0, bias, Cp, lc.ld, 0, 0, ne, lc.m0, la.m0, 1.0f, false, gate ? &g[0] : nullptr));
+    CHK(gemm_pl(eng, 1, pass, Apl, la.ld, la.m1re, la.m1im, Wm1, lc.m1w, nullptr, Cp, lc.ld, lc.m1re, lc.m1im, ne, lc.m1w, la.m1w, conj, false, gate ? &g[1] : nullptr));
+    return gemm_pl(eng, 1, pass, Apl, la.ld, la.m2re, la.m2im, Wm2, lc.m2w, nullptr, Cp, lc.ld, lc.m2re, lc.m2im, ne, lc.m2w, la.m2w, conj, false, gate ? &g[2] : nullptr);
   }
   const float* Af = static_cast<const float*>(A);
   GemmP p = gp_zero();

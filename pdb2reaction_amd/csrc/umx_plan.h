@@ -452,12 +452,31 @@ void plan_edge_bwd(Plan& P, WS& w, const ChunkCtx& c, int i) {
   if (c.ne <= 0) return;
   const LayerW* L = &c.eng->lw[i];
   if (c.eng->prec.planes) {
-    P.matrix([=, &w]() -> int { return so2_conv(c.eng, REV, w.gmsgpl, SO2_MSG, w.hid, SO2_MSG, L->c2m0T, L->c2m1T, L->c2m2T, nullptr, c.ne, -1.0f); });
-    P.stream([=, &w]() -> int {
-      UMX_STAGE(c);
-      DBG("g_hid." + std::to_string(i), w.hid, ne * ROW);
-      return link_gate_bwd(eng, w, i, ne);
-    });
+    // bf16x3: conv 2^T applies gate^T in its epilogues and writes g_hg itself (umx_gemm_q.h EP = 1; the gate sums pass through the first
+    // E x 256 floats of w.hid, which then holds no g_hid).  With debug captures on the two links run apart, so that g_hid exists and
+    // "gemm:launches" names the table's rows.  Small chunks keep the two links as well: where conv 2^T's m = 1 grid does not put a
+    // workgroup on every CU (choose_pl's `fills`: fewer than 16 257 edges) a launch lasts as long as ONE tile, the epilogue's round trip
+    // to hg lengthens exactly that, and there is no second tile on the CU to run beside it.  A precaution, not a measured gain: c1 (13 k
+    // edges) measured the same step time with and without the epilogue (profiles/gate_epilogue_ab.txt sections 1, 1b); c2 and c3 gain.
+    // UMX_GATE_EPI (dev): 0 never, 1 as described, 2 always
+    const int ge = c.eng->gate_epi;
+    const bool fills = (c.ne + 127) / 128 * (SO2_MSG.m1w / 128) >= 256;
+    if (c.eng->prec.rev_quad() && (ge == 2 || (ge == 1 && !c.eng->dbg_on && fills))) {
+      P.matrix([=, &w]() -> int {
+        UMX_STAGE(c);
+        // (so2_conv's C argument is not written in this form -- the epilogues store to gate.ghg --; w.hid is passed as the gate sums' buffer)
+        const GateEpi gate{w.hg[i], reinterpret_cast<float*>(w.ghgpl), w.hid, 0};
+        CHK(so2_conv(eng, REV, w.gmsgpl, SO2_MSG, w.hid, SO2_MSG, L->c2m0T, L->c2m1T, L->c2m2T, nullptr, ne, -1.0f, nullptr, &gate));
+        return dbg_operand(eng, "ghg", i, OP_QUAD, w.ghgpl, ne, HG);
+      });
+    } else {
+      P.matrix([=, &w]() -> int { return so2_conv(c.eng, REV, w.gmsgpl, SO2_MSG, w.hid, SO2_MSG, L->c2m0T, L->c2m1T, L->c2m2T, nullptr, c.ne, -1.0f); });
+      P.stream([=, &w]() -> int {
+        UMX_STAGE(c);
+        DBG("g_hid." + std::to_string(i), w.hid, ne * ROW);
+        return link_gate_bwd(eng, w, i, ne);
+      });
+    }
     P.matrix([=, &w]() -> int { return so2_conv(c.eng, REV, w.ghgpl, SO2_HG, w.gy1, SO2_Y1, L->c1m0T, L->c1m1T, L->c1m2T, nullptr, c.ne, -1.0f); });
     // (a matrix-token segment although it is HBM-bound: at 240 VGPRs its waves cannot share a SIMD with a GEMM wave, so beside
     //  the other lane's GEMM it would only take CUs away from it; the other lane's throttled stream kernels do fit beside it)
