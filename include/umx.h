@@ -354,6 +354,56 @@ int umx_pin_graphs_f64(umx_engine* eng, int n_refs, const double* pos_ang);
 int umx_pin_assign(umx_engine* eng, int n_images, const int32_t* ref_of_image);
 int umx_pinned_graphs(const umx_engine* eng, int capacity, int64_t* n_edges, int32_t* max_degree);
 
+/* HESSIAN-VECTOR PRODUCTS (additive to ABI v10).  H.v along a few collective directions -- what a Lanczos, dimer, LOBPCG or Davidson loop
+ * asks for -- as ONE call: the displaced images are formed on the device in float64, evaluated on the pinned graphs of their bases in one
+ * batched evaluation, and the difference of their forces comes back in float64.
+ *   base_ang: [n_bases][n_atoms][3] float64 Angstrom; dir: [n_dirs][n_atoms][3] float64 (NOT normalised by the engine); base_of: [n_dirs],
+ *   the base direction m is taken at -- a HOST pointer in both entries (the host range-checks it; nothing a caller passes is used as an
+ *   index on the device unchecked), NULL allowed when n_bases == 1; step_ang > 0, the displacement per unit of dir.
+ *   hv: [n_dirs][n_atoms][3] float64, eV/A^2 per unit of dir; curv: [n_dirs] float64 or NULL, dir.hv / dir.dir (0 for a zero direction:
+ *   no 0/0); e0: [n_bases] float64 and f0: [n_bases][n_atoms][3] float32, or NULL: energies and forces of the bases themselves, which
+ *   only the forward scheme evaluates.
+ *   flags: bit 0 = forward scheme (default: central); bit 1 = do not pin: every image builds its own graph (the reference's semantics,
+ *   kept for A/B); bit 2 (with bit 0 only) = f0 is an INPUT, the bases' forces as an earlier forward call returned them, and the bases are
+ *   not evaluated again: the images are the n_dirs displaced ones alone (e0 must be NULL).  Every image being its evaluation alone on
+ *   the pinned graph, bit for bit, such an f0 is what this call would have computed: a recursion pays for its base once.  The
+ *   engine cannot tell where f0 came from: it must be the bases' forces on the SAME pinned graphs in the SAME precision mode -- after
+ *   umx_set_precision / a re-load (the Python binding's widening after UMX_ERR_RANGE) an older f0 would mix two arithmetics in one
+ *   difference; evaluate the bases again then (Engine.hvp does so by itself when it widens, the GSM driver drops its copy).
+ * Images: central -- image 2m is base[base_of[m]] + step * dir[m], image 2m + 1 is base[base_of[m]] - step * dir[m]; forward -- the
+ * n_bases bases first, then base[base_of[m]] + step * dir[m].  Product and sum are rounded separately, in float64: the images are bit for
+ * bit the NumPy expressions.  They are float64 positions and take the float64 graph path (umx_energy_forces_f64): there is no float32
+ * variant of this entry -- a collective unit displacement moves a coordinate by step / sqrt(3 n_atoms), which float32 positions swallow.
+ * Difference, in float64 on the device: central hv = -(double(F+) - double(F-)) / (2.0 * step) -- the operation order of the
+ * finite-difference Hessian, so that a unit vector e_k gives its unsymmetrised column bit for bit; forward hv = -(double(F+) -
+ * double(F0)) / step, with F0 from the SAME batched evaluation as F+ (one arithmetic).  curv: one workgroup per direction, a fixed-order
+ * tree in float64, no atomics: its bits do not depend on batch, chunking or lanes.
+ * Graphs: with nothing pinned the entry pins the n_bases bases (umx_pin_graphs_f64) for the call and leaves the engine unpinned on every
+ * way out, failures included.  With a pin of n_bases references in force, direction m replays reference base_of[m]; with a pin of ONE
+ * reference every image replays it -- so a caller may pin at x_ref and probe at bases near it.  The caller's umx_pin_assign state is saved
+ * and restored.  Any other number of pinned references is UMX_ERR_ARG, and so is bit 1 while a pin is in force.
+ * Row parity: the GEMM producers negate odd operand rows (see umx_pin_assign), so every evaluation this entry makes -- one base, one
+ * pinned reference and unpinned images included -- ends a chunk behind an odd number of edges: each displaced image is, bit for bit, its
+ * evaluation alone under umx_pin_graph_f64(base), and +v / -v of an odd-edge base never differ by that rounding (about 1e-7 eV/A, which
+ * a central difference would divide by 2 * step).  Chunks, two lanes, target-node partitions and recompute plans run as they are.
+ * UMX_ERR_ARG, before anything runs (umx_last_error names the direction or base): no system bound; a graph-parallel evaluation in
+ * progress; step not finite or <= 0; base_of[m] outside [0, n_bases); base_of == NULL with n_bases > 1; a non-finite base or direction
+ * (host entry; the device entry reports it as umx_energy_forces_f64_dev does); per-image cells bound (umx_set_cells), with any number of bases -- the images of a base
+ * share one cell: bind it with umx_set_cell;
+ * e0 or f0 with the central scheme.  A non-finite energy: UMX_ERR_RANGE from the host entry, the sticky flag from the device entry, as for
+ * umx_energy_forces_f64[_dev].
+ * umx_hvp_dev: base, dir, hv, curv, e0, f0 are DEVICE pointers, the work is enqueued on hip_stream as umx_energy_forces_f64_dev does;
+ * while a caller's pin is in force nothing is read back (without one the bases are read back once, to be pinned).  The float32 forces of the
+ * images stay in an engine-owned buffer; only hv, curv, e0 and f0 reach the caller.  With this entry unused no kernel, launch or result
+ * of any other entry changes.
+ * Not provided: analytic (autograd-style) products; products through the graph-parallel entries; a skin criterion or re-pinning.
+ * Replaces: the forward difference of two single-image gradients in the reference's Lanczos recursion, which rebuilds the graph at every
+ * probe and rounds the probe to float32 positions.                                                                                     */
+int umx_hvp(umx_engine* eng, int n_bases, const double* base_ang, int n_dirs, const double* dir, const int32_t* base_of, double step_ang,
+            int flags, double* hv, double* curv, double* e0, float* f0);
+int umx_hvp_dev(umx_engine* eng, int n_bases, const double* d_base_ang, int n_dirs, const double* d_dir, const int32_t* base_of,
+                double step_ang, int flags, double* d_hv, double* d_curv, double* d_e0, float* d_f0, void* hip_stream);
+
 /* Graph-parallel evaluation of ONE image across several engines / ranks (ABI v5) -- the reference's `workers > 1` semantics
  * (ParallelMLIPPredictUnit: the atoms' graph partitioned over workers, uma_pysis.py:220-242), for single large systems when there are
  * fewer images than GPUs.  Every rank passes the FULL positions; rank r builds the incoming edges of the

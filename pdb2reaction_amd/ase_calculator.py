@@ -234,6 +234,17 @@ class UMXCalculator(_AseBase):
         refs = np.stack([np.asarray(im.get_positions(), dtype=np.float64) for im in images])
         return _Pinned(eng, refs, self._dp_kw(), "pin_graphs")
 
+    def hvp(self, atoms, vectors, step: float = 1e-3, scheme: str = "central", pin: bool = True, return_curvature: bool = False):
+        """Hessian-vector products at ``atoms`` in eV/A^2: ``vectors`` (N,3) or (M,N,3), not normalised -> ``hv`` (M,N,3) float64 per unit
+        of ``vectors`` (and ``curv`` (M,), ``v.Hv / v.v``, with ``return_curvature``).  One engine call (``Engine.hvp``): the displaced
+        images ``positions +- step * vectors`` (``step`` in A) are formed in float64 on the device and evaluated on the pinned graph of
+        ``atoms`` -- its positions, cell and pbc flags -- whatever ``double_positions`` this calculator was built with.  Inside
+        ``with calc.pinned(ref)`` the pinned graph of ``ref`` is used instead.  ``scheme``: "central" or "forward"; ``pin=False``: every
+        image builds its own graph (for comparison; refused inside ``pinned``)."""
+        eng = self._ensure(atoms)
+        return eng.hvp(np.array(atoms.get_positions(), dtype=np.float64), np.asarray(vectors, dtype=np.float64), step=float(step), scheme=scheme,
+                       pin=pin, return_curvature=return_curvature)
+
     def _stress_kw(self) -> dict:
         """What ``energy_forces_stress`` is called with: the graph-parallel opt-in when this calculator runs a pool of engines."""
         return {"graph_parallel": True} if self.gp_stress and len(self.local_devices or []) > 1 else {}

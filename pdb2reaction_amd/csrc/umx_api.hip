@@ -14,6 +14,7 @@
 #include "umx_periodic.h"    // host side of the graph stage: the bound cells, the wrapped copy, the dispatcher and the graph-kernel launchers
 #include "umx_virial.h"      // the strain derivative of every image: the two reduction kernels behind k_force_edge and their launcher
 #include "umx_plan.h"        // the launch plan of one chunk, its executors, and one evaluation as its phases
+#include "umx_hvp.h"         // Hessian-vector products: displace, difference and curvature kernels around one batched evaluation
 #include "umx_weights.h"     // the weight loader
 #include "umx_experts.h"     // expert-form weights: the Mixture-of-Linear-Experts merge and its plane copies on the device
 
@@ -196,6 +197,79 @@ int pin_graphs_impl(umx_engine* eng, const char* who, int R, const P* pos) {
   keep.pin = true;
   return UMX_OK;
 }
+
+// ---- Hessian-vector products (umx_hvp[_dev]; kernels and launchers in umx_hvp.h) -------------------------------------------------------
+// what both entries refuse before anything runs; base_of is a HOST pointer in both
+int hvp_check(umx_engine* eng, int R, const void* base, int M, const void* dir, const int32_t* base_of, double step, int flags, const void* hv,
+              const void* e0, const void* f0) {
+  if (!eng) return UMX_ERR_ARG;
+  if (eng->need_merge()) return fail(eng, UMX_ERR_ARG, "umx_hvp: " NOT_MERGED);
+  if (!eng->have_system) return fail(eng, UMX_ERR_ARG, "umx_hvp: bind a system first (umx_set_system)");
+  if (R < 1 || M < 1 || !base || !dir || !hv || (flags & ~(HVP_FORWARD | HVP_NO_PIN | HVP_GIVEN_F0))) return fail(eng, UMX_ERR_ARG, "umx_hvp: bad arguments");
+  if ((flags & HVP_GIVEN_F0) && (!(flags & HVP_FORWARD) || !f0 || e0))
+    return fail(eng, UMX_ERR_ARG, "umx_hvp: flags bit 2 hands the bases' forces IN through f0: the forward scheme (bit 0), f0 given, e0 NULL");
+  if (eng->gp_plan) return fail(eng, UMX_ERR_ARG, "umx_hvp: a graph-parallel evaluation is in progress (finish it with umx_gp_step)");
+  if (!std::isfinite(step) || step <= 0.0) return fail(eng, UMX_ERR_ARG, "umx_hvp: the step must be finite and positive");
+  if (R > 1 && !base_of) return fail(eng, UMX_ERR_ARG, "umx_hvp: base_of may be NULL only with one base, " + std::to_string(R) + " were given");
+  for (int m = 0; base_of && m < M; ++m)
+    if (base_of[m] < 0 || base_of[m] >= R)
+      return fail(eng, UMX_ERR_ARG, "umx_hvp: direction " + std::to_string(m) + " names base " + std::to_string(base_of[m]) + ", but " + std::to_string(R) + " were given");
+  // (the rule of umx_pin_graphs for several bases; with one base the images +v and -v would each take another cell of the list)
+  if (eng->pbc_on && !eng->cells_shared)
+    return fail(eng, UMX_ERR_ARG, "umx_hvp: per-image cells are bound (umx_set_cells): the displaced images of a base share ONE cell -- the bases are "
+                "evaluated open or in the one cell of umx_set_cell");
+  if (!(flags & HVP_FORWARD) && (e0 || f0))
+    return fail(eng, UMX_ERR_ARG, "umx_hvp: e0 and f0 are the bases' own energies and forces, which only the forward scheme evaluates (flags bit 0)");
+  if ((flags & HVP_NO_PIN) && eng->pin_on)
+    return fail(eng, UMX_ERR_ARG, "umx_hvp: flags bit 1 asks every image to build its own graph, but a graph is pinned: call umx_unpin_graph first");
+  if (eng->pin_on && eng->pin_refs != 1 && eng->pin_refs != R)
+    return fail(eng, UMX_ERR_ARG, "umx_hvp: " + std::to_string(eng->pin_refs) + " graphs are pinned and " + std::to_string(R) + " bases were given: "
+                "the entry replays one pinned reference for all bases, or one per base");
+  return periodic_check_images(eng, hvp_images(R, M, flags), "umx_hvp");
+}
+
+// The call on stream s with device pointers (h_base: the bases on the host as well, or nullptr -- then they are read back when the entry
+// has to pin them itself).  Whatever the way out, the caller's assignment is back in force and a pin of the entry's own is gone.
+int hvp_run(umx_engine* eng, hipStream_t s, int R, const double* d_base, const double* h_base, int M, const double* d_dir, const int32_t* base_of,
+            double step, int flags, double* d_hv, double* d_curv, double* d_e0, float* d_f0) {
+  const int N = eng->natoms;
+  const long K = hvp_images(R, M, flags);
+  const bool fwd = (flags & HVP_FORWARD) != 0;
+  struct Restore {
+    umx_engine* e; std::vector<int> assign; bool own_pin = false;
+    ~Restore() { e->hvp_rows = false; if (own_pin) pin_clear(e); e->pin_assign = std::move(assign); }
+  } restore{eng, eng->pin_assign};
+  if (!(flags & HVP_NO_PIN) && !eng->pin_on) {
+    std::vector<double> back;
+    if (!h_base) {
+      back.resize((size_t)R * N * 3);
+      HIPCHK(eng, hipMemcpyAsync(back.data(), d_base, back.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+      HIPCHK(eng, hipStreamSynchronize(s));
+      h_base = back.data();
+    }
+    CHK(pin_graphs_impl<double>(eng, "umx_hvp", R, h_base));
+    restore.assign.clear();
+    restore.own_pin = true;
+  }
+  if (eng->pin_on) {                    // image k replays the reference of its base (one reference: all of them that one)
+    eng->pin_assign.clear();
+    if (eng->pin_refs > 1) {
+      eng->pin_assign.resize((size_t)K);
+      const long nb = hvp_bases(R, flags);
+      for (long k = 0; k < K; ++k) eng->pin_assign[k] = fwd ? (k < nb ? (int)k : base_of[k - nb]) : base_of[k >> 1];
+    }
+  }
+  eng->hvp_rows = true;
+  const int* d_bof = nullptr;
+  CHK(hvp_prepare(eng, s, K, M, R > 1 ? base_of : nullptr, &d_bof));
+  CHK(hvp_displace(eng, s, R, d_base, M, d_dir, d_bof, step, flags));
+  CHK(energy_forces_on(eng, s, (int)K, PosPtr(static_cast<const double*>(eng->d_hvp_x)), eng->d_hvp_e, eng->d_hvp_f));
+  CHK(hvp_combine(eng, s, R, M, d_dir, d_bof, step, flags, d_f0, d_hv, d_curv));
+  if (d_e0) HIPCHK(eng, hipMemcpyAsync(d_e0, eng->d_hvp_e, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
+  if (d_f0 && !(flags & HVP_GIVEN_F0)) HIPCHK(eng, hipMemcpyAsync(d_f0, eng->d_hvp_f, (size_t)R * N * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  HIPCHK(eng, hipEventRecord(eng->ev_done, s));
+  return UMX_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -261,7 +335,7 @@ int umx_destroy(umx_engine* eng) {
   (void)hipSetDevice(eng->dev);
   (void)hipStreamSynchronize(eng->stream);
   for (auto& r : eng->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-  void* ptrs[] = {eng->d_w, eng->d_dw, eng->d_bw, eng->d_gmu, eng->d_z, eng->d_sysemb, eng->arena, eng->d_deg_all, eng->d_cand_all, eng->d_img_edges, eng->d_io_pos, eng->d_io_e, eng->d_io_f, eng->d_flags, eng->d_dtab, eng->d_part_deg, eng->d_part_f, eng->d_ex, eng->d_mjobs, eng->d_pjobs, eng->d_mx, eng->d_cells, eng->d_shifts_pk, eng->d_wrap, eng->d_wrap64, eng->d_lats, eng->d_io_pos64, eng->d_vir_part, eng->d_vir_wp, eng->d_io_w, eng->d_pin_src, eng->d_pin_dst, eng->d_pin_tix, eng->d_pin_wrap, eng->d_pin_deg, eng->d_pin_img, eng->d_pin_shifts};
+  void* ptrs[] = {eng->d_w, eng->d_dw, eng->d_bw, eng->d_gmu, eng->d_z, eng->d_sysemb, eng->arena, eng->d_deg_all, eng->d_cand_all, eng->d_img_edges, eng->d_io_pos, eng->d_io_e, eng->d_io_f, eng->d_flags, eng->d_dtab, eng->d_part_deg, eng->d_part_f, eng->d_ex, eng->d_mjobs, eng->d_pjobs, eng->d_mx, eng->d_cells, eng->d_shifts_pk, eng->d_wrap, eng->d_wrap64, eng->d_lats, eng->d_io_pos64, eng->d_vir_part, eng->d_vir_wp, eng->d_io_w, eng->d_pin_src, eng->d_pin_dst, eng->d_pin_tix, eng->d_pin_wrap, eng->d_pin_deg, eng->d_pin_img, eng->d_pin_shifts, eng->d_hvp_x, eng->d_hvp_f, eng->d_hvp_e, eng->d_hvp_bof, eng->d_hvp_in, eng->d_hvp_out};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   (void)hipStreamSynchronize(eng->stream2);
   (void)hipEventDestroy(eng->ev_fork); (void)hipEventDestroy(eng->ev_join);
@@ -617,6 +691,56 @@ int umx_pinned_graph(const umx_engine* eng, int64_t* n_edges, int32_t* max_degre
   if (!eng) return UMX_ERR_ARG;
   if (n_edges) *n_edges = eng->pin_on ? (int64_t)eng->pin_edges : 0;
   if (max_degree) *max_degree = eng->pin_on ? (int32_t)eng->pin_maxdeg : 0;
+  return UMX_OK;
+}
+
+int umx_hvp_dev(umx_engine* eng, int n_bases, const double* d_base_ang, int n_dirs, const double* d_dir, const int32_t* base_of, double step_ang,
+                int flags, double* d_hv, double* d_curv, double* d_e0, float* d_f0, void* hip_stream) {
+  CHK(hvp_check(eng, n_bases, d_base_ang, n_dirs, d_dir, base_of, step_ang, flags, d_hv, d_e0, d_f0));
+  HIPCHK(eng, hipSetDevice(eng->dev));
+  return hvp_run(eng, static_cast<hipStream_t>(hip_stream), n_bases, d_base_ang, nullptr, n_dirs, d_dir, base_of, step_ang, flags, d_hv, d_curv, d_e0, d_f0);
+}
+
+int umx_hvp(umx_engine* eng, int n_bases, const double* base_ang, int n_dirs, const double* dir, const int32_t* base_of, double step_ang, int flags,
+            double* hv, double* curv, double* e0, float* f0) {
+  CHK(hvp_check(eng, n_bases, base_ang, n_dirs, dir, base_of, step_ang, flags, hv, e0, f0));
+  const int R = n_bases, M = n_dirs;
+  const size_t n3 = (size_t)eng->natoms * 3;
+  for (size_t i = 0; i < (size_t)R * n3; ++i)
+    if (!std::isfinite(base_ang[i])) return fail(eng, UMX_ERR_ARG, "umx_hvp: non-finite position (base " + std::to_string(i / n3) + ")");
+  for (size_t i = 0; i < (size_t)M * n3; ++i)
+    if (!std::isfinite(dir[i])) return fail(eng, UMX_ERR_ARG, "umx_hvp: non-finite component (direction " + std::to_string(i / n3) + ")");
+  HIPCHK(eng, hipSetDevice(eng->dev));
+  hipStream_t s = eng->stream;
+  const bool given = (flags & HVP_GIVEN_F0) != 0;
+  const long in = (long)(2 * R + M) * eng->natoms, out = (long)M * eng->natoms;      // (bases, directions, and room for the bases' forces handed in)
+  if (eng->hvp_in_cap < in) CHK(grow(eng, eng->hvp_in_cap, in, {s}, {DevBuf(eng->d_hvp_in, (size_t)in * 3)}));
+  if (eng->hvp_out_cap < out) CHK(grow(eng, eng->hvp_out_cap, out, {s}, {DevBuf(eng->d_hvp_out, (size_t)out * 3 + M)}));
+  double *d_base = eng->d_hvp_in, *d_dir = eng->d_hvp_in + (size_t)R * n3, *d_hv = eng->d_hvp_out, *d_curv = eng->d_hvp_out + (size_t)M * n3;
+  HIPCHK(eng, hipMemcpyAsync(d_base, base_ang, (size_t)R * n3 * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(eng, hipMemcpyAsync(d_dir, dir, (size_t)M * n3 * sizeof(double), hipMemcpyHostToDevice, s));
+  float* d_f0 = given ? reinterpret_cast<float*>(eng->d_hvp_in + (size_t)(R + M) * n3) : nullptr;
+  if (given) {
+    for (size_t i = 0; i < (size_t)R * n3; ++i)
+      if (!std::isfinite(f0[i])) return fail(eng, UMX_ERR_ARG, "umx_hvp: non-finite force handed in (base " + std::to_string(i / n3) + ")");
+    HIPCHK(eng, hipMemcpyAsync(d_f0, f0, (size_t)R * n3 * sizeof(float), hipMemcpyHostToDevice, s));
+  }
+  CHK(hvp_run(eng, s, R, d_base, base_ang, M, d_dir, base_of, step_ang, flags, d_hv, curv ? d_curv : nullptr, nullptr, d_f0));
+  const long K = hvp_images(R, M, flags);
+  std::vector<double> en((size_t)K);
+  HIPCHK(eng, hipMemcpyAsync(en.data(), eng->d_hvp_e, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(eng, hipMemcpyAsync(hv, d_hv, (size_t)M * n3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (curv) HIPCHK(eng, hipMemcpyAsync(curv, d_curv, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (e0) HIPCHK(eng, hipMemcpyAsync(e0, eng->d_hvp_e, (size_t)R * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (f0 && !given) HIPCHK(eng, hipMemcpyAsync(f0, eng->d_hvp_f, (size_t)R * n3 * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIPCHK(eng, hipStreamSynchronize(s));
+  for (long k = 0; k < K; ++k)
+    if (!std::isfinite(en[k])) {
+      (void)hipMemset(eng->d_flags, 0, sizeof(int));         // reported right here: do not fail the NEXT call for it as well
+      return fail(eng, UMX_ERR_RANGE, "umx_hvp: image " + std::to_string(k) + ": non-finite energy" +
+                  (eng->prec.fwd_f16() ? " (an activation beyond the fp16 operand range of UMX_PRECISION=split: try split-bf16, bf16x3 or fp32)"
+                                      : " (an overflow in float32)"));
+    }
   return UMX_OK;
 }
 

@@ -355,6 +355,14 @@ struct umx_engine {
   float4* d_pin_shifts = nullptr; long pin_shifts_cap = 0;   // [cells in force][pin_codes] translation vectors (pin_upload_shifts)
   long pin_ref_edges(int r) const { return pin_ref_e0[(size_t)r + 1] - pin_ref_e0[(size_t)r]; }
   const long* pin_row_of(int r) const { return pin_row.data() + (size_t)r * ((size_t)natoms + 1); }
+  // Hessian-vector products (umx_hvp, umx_hvp.h): the displaced images, their float32 forces and energies, and the base of every direction
+  // on the device; engine-owned, grown like d_io_f.  The host entry's staging: bases and directions in, hv and curv out.
+  bool hvp_rows = false;                           // set for the evaluation inside umx_hvp: every image starts at an even row of its chunk (plan_chunks)
+  double* d_hvp_x = nullptr; float* d_hvp_f = nullptr; long hvp_cap = 0;       // [images][natoms][3]
+  double* d_hvp_e = nullptr; long hvp_img_cap = 0;                            // [images]
+  int* d_hvp_bof = nullptr; long hvp_bof_cap = 0; std::vector<int> hvp_bof_dev;   // [directions] base_of, and what the device copy holds
+  double* d_hvp_in = nullptr; long hvp_in_cap = 0;                            // [bases + directions][natoms][3]
+  double* d_hvp_out = nullptr; long hvp_out_cap = 0;                          // [directions][natoms][3] hv, then [directions] curv
   bool may_truncate = true;      // the largest degree of the evaluation being planned reaches max_neigh: k_graph_fill takes its truncating (LDS) form
   bool prof_on = false;
   std::vector<ProfRec> prof;

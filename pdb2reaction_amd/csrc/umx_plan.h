@@ -940,7 +940,9 @@ int plan_chunks(umx_engine* eng, long K, const ImageEdges& ie, long cap, size_t 
   // Several pinned references: image k is promised to be, bit for bit, its evaluation alone.  The GEMM producers negate the operand rows
   // of odd index (umx_edge.h, sign-alternating rows), so the rounding of an edge depends on the parity of its row in the chunk:
   // an image never starts at an odd row -- behind an odd number of edges the chunk ends.  (Alone, an image starts at row 0.)
-  const bool even_rows = eng->pin_on && eng->pin_refs > 1;
+  // umx_hvp asks for the same of every evaluation it makes, one pinned reference and unpinned images included: +v and -v of a base with
+  // an odd edge count would otherwise sit on different parities, and a central difference divides that rounding by 2 * step.
+  const bool even_rows = (eng->pin_on && eng->pin_refs > 1) || eng->hvp_rows;
   for (long k0 = 0; k0 < K;) {
     long k1 = k0, e = 0;
     while (k1 < K && (k1 - k0) < cap) {

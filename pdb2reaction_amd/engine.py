@@ -99,6 +99,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "umx_pin_graphs_f64": ([vp, i32, dp], i32),
         "umx_pin_assign": ([vp, i32, C.POINTER(C.c_int32)], i32),
         "umx_pinned_graphs": ([vp, i32, i64p, C.POINTER(C.c_int32)], i32),
+        "umx_hvp": ([vp, i32, dp, i32, dp, C.POINTER(C.c_int32), C.c_double, i32, dp, dp, dp, fp], i32),
+        "umx_hvp_dev": ([vp, i32, vp, i32, vp, C.POINTER(C.c_int32), C.c_double, i32, vp, vp, vp, vp, vp], i32),
         "umx_last_partitions": ([vp], i32),
         "umx_last_lanes": ([vp], i32),
         "umx_set_recompute": ([vp, i32], i32),
@@ -148,7 +150,7 @@ EXPORTED_SYMBOLS = (
     "umx_set_expert_coefficients", "umx_expert_count", "umx_set_recompute", "umx_last_recompute", "umx_workspace_bytes",
     "umx_set_cell", "umx_set_cells", "umx_last_graph_shifts", "umx_energy_forces_virial", "umx_energy_forces_virial_dev",
     "umx_gp_begin_virial", "umx_pin_graph", "umx_unpin_graph", "umx_pinned_graph",
-    "umx_pin_graphs", "umx_pin_assign", "umx_pinned_graphs", "umx_bond_changes_cell",
+    "umx_pin_graphs", "umx_pin_assign", "umx_pinned_graphs", "umx_bond_changes_cell", "umx_hvp", "umx_hvp_dev",
 )
 # The float64-position entries, listed apart: tests/test_boundary_cpu.py holds EXPORTED_SYMBOLS to the names it reads out of the header
 # with a pattern of letters and underscores, which a name with a digit in it does not match.  load_library declares (and so demands)
@@ -591,6 +593,92 @@ class Engine:
                                                         C.c_void_p(d_forces) if d_forces else None, C.c_void_p(d_virial) if d_virial else None,
                                                         C.c_void_p(stream) if stream else None),
                   "umx_energy_forces_f64_dev" if double_positions else "umx_energy_forces_virial_dev")
+
+    # ---- Hessian-vector products ------------------------------------------------------------------
+    def _hvp_args(self, base, dirs, base_of):
+        """(base (R,N,3), dirs (M,N,3), base_of (M,) int32 | None) as ``umx_hvp`` takes them, shapes checked."""
+        b = self._positions(base, True)
+        d = self._positions(dirs, True)
+        if base_of is None:
+            if b.shape[0] != 1:
+                raise ValueError(f"hvp: {b.shape[0]} bases need base_of, the base of every direction")
+            return b, d, None
+        a = np.ascontiguousarray(base_of, dtype=np.int32).reshape(-1)
+        if len(a) != d.shape[0]:
+            raise ValueError(f"hvp: {d.shape[0]} directions, but base_of has {len(a)} entries")
+        return b, d, a
+
+    @staticmethod
+    def _hvp_flags(scheme: str, pin: bool, given: bool = False) -> int:
+        if scheme not in ("central", "forward"):
+            raise ValueError(f"hvp: scheme must be 'central' or 'forward', got {scheme!r}")
+        if given and scheme != "forward":
+            raise ValueError("hvp: the bases' forces are an input of the forward scheme only")
+        return (1 if scheme == "forward" else 0) | (0 if pin else 2) | (4 if given else 0)
+
+    def hvp(self, base, dirs, base_of=None, step: float = 1e-3, scheme: str = "central", pin: bool = True, return_curvature: bool = False,
+            return_base: bool = False, base_forces=None):
+        """Hessian-vector products by finite differences of the forces, one engine call (``umx_hvp``): ``base`` (N,3) or (R,N,3)
+        Angstrom, ``dirs`` (N,3) or (M,N,3) -- not normalised --, ``base_of`` (M,) the base of every direction (optional with one
+        base), ``step`` in Angstrom per unit of ``dirs`` -> ``hv`` (M,N,3) float64 in eV/A^2 per unit of ``dirs``.
+
+        The displaced images ``base +- step * dirs`` are formed on the device in float64 and evaluated, as float64 positions, in one
+        batch on the pinned graphs of their bases: with nothing pinned the call pins the bases for its own duration; with one reference
+        pinned (``pin_graph``) every image replays it, with R pinned (``pin_graphs``) direction m replays reference ``base_of[m]``; the
+        caller's pin and ``pin_assign`` are untouched.  ``scheme="central"``: ``-(F+ - F-) / (2 step)``, two images per direction --
+        ``hessian.fd_hessian``'s expression, so a unit vector gives its unsymmetrised column bit for bit; ``"forward"``:
+        ``-(F+ - F0) / step`` with the bases in the same batch, one image per direction plus the bases.  ``pin=False``: every image builds
+        its own graph (the reference's semantics, for comparison; refused while a graph is pinned).
+        return_curvature: also ``curv`` (M,) = ``dirs.hv / dirs.dirs`` (0 for a zero direction), a fixed-order float64 sum on the device.
+        return_base (forward scheme): also ``(e0 (R,), f0 (R,N,3) float32)`` of the bases themselves.
+        base_forces (forward scheme): ``f0`` as an earlier call returned it -- the bases are then not evaluated again, the call costs M
+        images; every image is its evaluation alone on the pinned graph, so the result is the same bits.  They must come from the same
+        pinned graph and the same precision mode (the engine cannot tell): do not reuse them across a widening (``widened``).
+        An fp16 range violation widens the engine and repeats the call, like every evaluation; with ``base_forces`` the repeat
+        evaluates the bases again instead of using forces of the narrower arithmetic."""
+        b, d, a = self._hvp_args(base, dirs, base_of)
+        flags = self._hvp_flags(scheme, pin, base_forces is not None)
+        if return_base and (scheme != "forward" or base_forces is not None):
+            raise ValueError("hvp: the bases themselves are evaluated by the forward scheme only, and not when their forces are handed in")
+        dp, fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
+        hv = np.empty(d.shape, dtype=np.float64)
+        curv = np.empty(d.shape[0], dtype=np.float64) if return_curvature else None
+        e0 = np.empty(b.shape[0], dtype=np.float64) if return_base else None
+        f0 = np.empty(b.shape, dtype=np.float32) if return_base else None
+        if base_forces is not None:
+            f0 = np.ascontiguousarray(base_forces, dtype=np.float32).reshape(-1, self.natoms, 3).copy()
+            if f0.shape != b.shape:
+                raise ValueError(f"hvp: base_forces must be {b.shape}, got {f0.shape}")
+
+        def call(fl):
+            self._chk(self.lib.umx_hvp(self._h, b.shape[0], b.ctypes.data_as(dp), d.shape[0], d.ctypes.data_as(dp),
+                                       a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None, float(step), fl,
+                                       hv.ctypes.data_as(dp), curv.ctypes.data_as(dp) if return_curvature else None,
+                                       e0.ctypes.data_as(dp) if return_base else None, f0.ctypes.data_as(fp) if f0 is not None else None), "umx_hvp")
+        try:
+            call(flags)
+        except UmxError as err:
+            if getattr(err, "status", 0) != UMX_ERR_RANGE or not self._widen(str(err)):
+                raise
+            # the forces handed in are of the narrower arithmetic: the repeat evaluates the bases itself (f0, a copy, is overwritten),
+            # so that no difference mixes two arithmetics
+            call(flags & ~4)
+        out = (hv,) + ((curv,) if return_curvature else ()) + ((e0, f0) if return_base else ())
+        return out[0] if len(out) == 1 else out
+
+    def hvp_dev(self, n_bases: int, d_base: int, n_dirs: int, d_dirs: int, d_hv: int, base_of=None, step: float = 1e-3, scheme: str = "central",
+                pin: bool = True, d_curv: int = 0, d_e0: int = 0, d_f0: int = 0, stream: int = 0, given_f0: bool = False):
+        """Device-pointer form of ``hvp`` (``umx_hvp_dev``): ``d_base`` [n_bases][N][3], ``d_dirs`` [n_dirs][N][3] and ``d_hv`` float64 on
+        the device, ``d_curv`` / ``d_e0`` (float64) and ``d_f0`` (float32) or 0; ``base_of`` stays a host sequence; ``given_f0``: ``d_f0`` is read (``base_forces`` of ``hvp``).  Enqueues on ``stream``
+        as ``energy_forces_dev`` does; reads nothing back while a caller's pin is in force.  A range violation is reported late
+        (``take_range_error``)."""
+        a = None if base_of is None else np.ascontiguousarray(base_of, dtype=np.int32).reshape(-1)
+        if a is not None and len(a) != int(n_dirs):
+            raise ValueError(f"hvp_dev: {n_dirs} directions, but base_of has {len(a)} entries")
+        p = lambda x: C.c_void_p(x) if x else None
+        self._chk(self.lib.umx_hvp_dev(self._h, int(n_bases), C.c_void_p(d_base), int(n_dirs), C.c_void_p(d_dirs),
+                                       a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None, float(step), self._hvp_flags(scheme, pin, given_f0),
+                                       C.c_void_p(d_hv), p(d_curv), p(d_e0), p(d_f0), p(stream)), "umx_hvp_dev")
 
     # ---- graph-parallel single-image mode (reference workers > 1; see parallel.GraphParallelEvaluator) -----------------
     def gp_begin(self, d_pos: int, node_lo: int, node_hi: int, d_energy: int, d_forces: int, stream: int = 0, d_virial: int = 0):

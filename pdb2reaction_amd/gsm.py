@@ -245,11 +245,15 @@ def _place(x: np.ndarray, targets: np.ndarray) -> np.ndarray:
 
 
 def lanczos_lowest_mode_t(grad_fn: Callable[[torch.Tensor], torch.Tensor], x: torch.Tensor, g0: torch.Tensor, guess: torch.Tensor, *,
-                          dx: float = 5e-3, dl: float = 1e-2, max_cycles: int = 25, orient: Optional[torch.Tensor] = None) -> Tuple[float, torch.Tensor, int]:
+                          dx: float = 5e-3, dl: float = 1e-2, max_cycles: int = 25, orient: Optional[torch.Tensor] = None,
+                          hvp_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None) -> Tuple[float, torch.Tensor, int]:
     """Lowest Hessian eigenpair at x from a Lanczos recursion on forward-difference Hessian-vector products
     H q ~ (g(x + dx q) - g(x)) / dx; one gradient per step, started from `guess` (the string tangent).  Vectors stay on x's device;
     the recursion coefficients (two scalars per step) come to the host, where the small tridiagonal eigenproblem is solved --
     every step is a force evaluation anyway.
+
+    hvp_fn: None (default) -- exactly the recursion above.  Given -- ``u = hvp_fn(q)`` (q the unit Lanczos vector, a tensor like x)
+    replaces the forward difference; `grad_fn`, `g0` and `dx` are then unused (the product's own step is hvp_fn's business).
 
     Returns (eigenvalue, unit eigenvector, gradient evaluations).  Stops when the lowest Ritz value changes by less than
     `dl` (relative) between two steps, when the Krylov space is exhausted, or after `max_cycles` steps.  The vector is
@@ -275,7 +279,10 @@ def lanczos_lowest_mode_t(grad_fn: Callable[[torch.Tensor], torch.Tensor], x: to
             for _ in range(1):
                 q = q - qm.T @ (qm @ q)
         q = q / q.norm().clamp_min(1e-30)
-        u = (grad_fn(x + dx * q).reshape(-1) - g0.reshape(-1)) / dx
+        if hvp_fn is not None:
+            u = hvp_fn(q).reshape(-1).to(x.dtype)
+        else:
+            u = (grad_fn(x + dx * q).reshape(-1) - g0.reshape(-1)) / dx
         if qs:
             u = u - beta * q_prev
         alpha = float(q @ u)
@@ -351,6 +358,17 @@ class GrowingStringDriver:
         self.device = torch.device(device) if device is not None else torch.device("cpu")
         if evaluate_device is None and self.device.type != "cpu":
             raise ValueError("a non-CPU `device` needs `evaluate_device` (a numpy evaluator would pull the string to the host every cycle)")
+        # climb_lanczos_hvp (own extension, default None = today's recursion): "central" | "forward" -- the Lanczos products come from the
+        # evaluator's ``hvp`` (pinned graph, float64 positions; parallel.EngineStringEvaluator.hvp) instead of single-image gradients
+        self._hvp_src = None
+        mode = self.gs.get("climb_lanczos_hvp")
+        if mode is not None:
+            if mode not in ("central", "forward"):
+                raise ValueError(f"GrowingStringDriver: climb_lanczos_hvp={mode!r}: None, 'central' or 'forward'")
+            self._hvp_src = next((o for o in (evaluate_device, evaluate, calc) if o is not None and callable(getattr(o, "hvp", None))), None)
+            if self._hvp_src is None:
+                raise ValueError(f"GrowingStringDriver: climb_lanczos_hvp={mode!r} needs an evaluator with an `hvp(x0, q, dx, scheme)` method "
+                                 "(parallel.EngineStringEvaluator has one); this one has none")
         self.max_images = int(self.gs["max_nodes"]) + 2
         if hasattr(calc, "reserve_images"):                  # the string grows to max_images: one workspace allocation instead of one per growth
             calc.reserve_images(self.max_images)
@@ -481,6 +499,50 @@ class GrowingStringDriver:
     def _single_forces(self, xq: torch.Tensor) -> torch.Tensor:
         """Forces of ONE geometry through the same (batched) evaluator -- the serial steps of the Lanczos recursion."""
         return self._raw_eval(xq.reshape(1, -1))[1].reshape(-1)
+
+    def _lanczos(self, x: torch.Tensor, g0: torch.Tensor, guess: torch.Tensor, orient: Optional[torch.Tensor] = None, dx: float = 5e-3):
+        """One Lanczos recursion at x: (lowest Ritz value, unit vector, IMAGES evaluated).  climb_lanczos_hvp None: the forward
+        difference of single-image gradients, one image per step.  "central": ``hvp(x, q, dx, "central")``, two images per step in one
+        call.  "forward": the first product also evaluates the base and returns its forces, which every further product of the
+        recursion hands back -- one image per step plus the base once, all from one arithmetic."""
+        mode = self.gs.get("climb_lanczos_hvp")
+        if mode is None:
+            kw = {} if orient is None else {"orient": orient}
+            return lanczos_lowest_mode_t(lambda xq: -self._single_forces(xq), x, g0, guess, **kw)
+        import time
+
+        src, on_dev = self._hvp_src, self._hvp_src is self._evaluate_device
+        x0 = x if on_dev else x.detach().cpu().numpy()
+        wide = lambda: bool(getattr(getattr(src, "engine", None), "widened", False))      # noqa: E731
+        state = {"f0": None, "images": 0, "wide": wide()}
+
+        def hvp_fn(q: torch.Tensor) -> torch.Tensor:
+            t0 = time.perf_counter()
+            qq = q if on_dev else q.detach().cpu().numpy()
+            if state["wide"] != wide():                  # the engine changed its arithmetic: the base's forces kept so far are of the old one
+                state["f0"], state["wide"] = None, wide()
+            if mode == "central":
+                hv, n = src.hvp(x0, qq, dx, "central"), 2
+            elif state["f0"] is None:
+                (hv, state["f0"]), n = src.hvp(x0, qq, dx, "forward", return_base=True), 2
+            else:
+                hv, n = src.hvp(x0, qq, dx, "forward", base=state["f0"]), 1
+            state["images"] += n
+            self.n_eval += n
+            self.t_eval += time.perf_counter() - t0
+            return hv if on_dev else torch.as_tensor(np.asarray(hv, dtype=np.float64), device=self.device)
+
+        # an evaluator that can pin (EngineStringEvaluator.hvp_pin) pins the graph of x ONCE for the recursion: its products then neither
+        # read the base back nor build a graph per step
+        pinned = callable(getattr(src, "hvp_pin", None)) and callable(getattr(src, "hvp_unpin", None))
+        if pinned:
+            src.hvp_pin(x0)
+        try:
+            w, v, _ = lanczos_lowest_mode_t(None, x, g0, guess, orient=orient, dx=dx, hvp_fn=hvp_fn)
+        finally:
+            if pinned:
+                src.hvp_unpin()
+        return w, v, state["images"]
 
     def _targets(self, k: int, nl: int) -> torch.Tensor:
         if k >= self.max_images:
@@ -653,7 +715,6 @@ class GrowingStringDriver:
                         # `climb_lanczos_refresh`-th recursion (10) is a cold one, which sees every direction again.
                         t_hei = t_dev[hei] / t_dev[hei].norm().clamp_min(1e-30)
                         lp = self._lanczos_prev
-                        grad_fn = lambda xq: -self._single_forces(xq)                      # noqa: E731
                         warm = bool(gs.get("climb_lanczos_warm_start", True)) and lp is not None and lp[0] == hei and lp[1] == k
                         guard = bool(gs.get("climb_lanczos_warm_guard", True))          # False: measurement only (bench.py) -- any warm result is kept
                         min_ov = float(gs.get("climb_lanczos_warm_overlap", -1.0))
@@ -662,13 +723,13 @@ class GrowingStringDriver:
                         trusted = lambda w_, v_: (not guard) or (w_ < 0.0 and float(v_ @ t_hei) >= min_ov)     # noqa: E731
                         done = False
                         if warm:
-                            w_l, lanczos_t, n_l = lanczos_lowest_mode_t(grad_fn, self._x[hei], -self._f[hei], lp[2], orient=t_hei)
+                            w_l, lanczos_t, n_l = self._lanczos(self._x[hei], -self._f[hei], lp[2], orient=t_hei)
                             self.lanczos_evals += n_l
                             done = trusted(w_l, lanczos_t)
                             self.lanczos_warm_calls += int(done)
                             self.lanczos_warm_rejected += int(not done)
                         if not done:
-                            w_l, lanczos_t, n_l = lanczos_lowest_mode_t(grad_fn, self._x[hei], -self._f[hei], t_hei)
+                            w_l, lanczos_t, n_l = self._lanczos(self._x[hei], -self._f[hei], t_hei)
                             self.lanczos_evals += n_l
                         # only a mode that can be trusted next cycle is remembered
                         self._lanczos_prev = (hei, k, lanczos_t) if trusted(w_l, lanczos_t) else None

@@ -351,6 +351,43 @@ class EngineStringEvaluator(ShardedStringEvaluator):
             return e.to(torch.float64) * self._e2h, f.reshape(1, -1)
         return super().__call__(x)
 
+    def hvp(self, x0: torch.Tensor, q: torch.Tensor, dx: float, scheme: str = "central", base=None, return_base: bool = False):
+        """``H(x0) . q`` in Hartree/Bohr^2, (3N,) float64 on the device, through ``umx_hvp_dev`` on torch's current stream: ``x0`` (3N,)
+        Bohr and ``q`` (3N,) stay on the device, the displaced images ``x0 +- dx q`` are formed there in float64 and evaluated on the
+        pinned graph of ``x0`` (the engine pins it for the call unless the caller holds a pin).  Rows of frozen atoms are zeroed in ``q``
+        before the displacement and in the result: the product of the active block.  ``scheme="central"``: two images; ``"forward"``:
+        the base and one image -- ``return_base=True`` also returns the base's forces (a float32 device tensor, eV/A), and handing them
+        back as ``base`` makes every further product at the same ``x0`` cost ONE image.  ``images_last`` says what the call cost.
+        Single rank only: a product through the sharded evaluators is not provided (``ValueError``)."""
+        from .hessian import EV_PER_ANG2_TO_AU
+
+        if self._world > 1:
+            raise ValueError("EngineStringEvaluator.hvp: Hessian-vector products through the sharded evaluators are not provided (one rank only)")
+        n = self.n_atoms
+        b = (x0.reshape(n, 3).to(torch.float64) * self._b2a).contiguous()
+        d = q.reshape(n, 3).to(torch.float64).clone()
+        if self._frozen.numel():
+            d[self._frozen, :] = 0.0
+        hv = torch.empty(n, 3, dtype=torch.float64, device=self.device)
+        f0 = base if base is not None else (torch.empty(n, 3, dtype=torch.float32, device=self.device) if return_base else None)
+        self.engine.hvp_dev(1, b.data_ptr(), 1, d.data_ptr(), hv.data_ptr(), step=float(dx) * self._b2a, scheme=scheme,
+                            d_f0=f0.data_ptr() if f0 is not None else 0, given_f0=base is not None,
+                            stream=torch.cuda.current_stream(self.device).cuda_stream)
+        self.images_last = 2 if (scheme == "central" or base is None) else 1
+        hv = hv * float(EV_PER_ANG2_TO_AU)
+        if self._frozen.numel():
+            hv[self._frozen, :] = 0.0
+        return (hv.reshape(-1), f0) if return_base else hv.reshape(-1)
+
+    def hvp_pin(self, x0: torch.Tensor) -> None:
+        """Pin the graph of ``x0`` (3N,) Bohr -- the float64 Angstrom geometry ``hvp`` takes as its base, read to the host ONCE -- so
+        that the products of a whole recursion at ``x0`` replay it: no read-back, no graph build, no allocation per product
+        (``gsm.GrowingStringDriver`` pins around each Lanczos recursion).  The graph is the one ``hvp`` would pin for itself: same bits."""
+        self.engine.pin_graph((x0.reshape(self.n_atoms, 3).to(torch.float64) * self._b2a).cpu().numpy(), double_positions=True)
+
+    def hvp_unpin(self) -> None:
+        self.engine.unpin_graph()
+
     def _local(self, c_bohr: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         kl = c_bohr.shape[0]
         self._reserve(kl)
@@ -776,6 +813,40 @@ class LocalEnginePool:
         e = np.concatenate([r[0] for r in res])
         f = np.concatenate([r[1] for r in res]) if forces else None
         return e, f
+
+    def hvp(self, base, dirs, base_of=None, step: float = 1e-3, scheme: str = "central", pin: bool = True, return_curvature: bool = False):
+        """``Engine.hvp`` over the pool: the M directions are dealt over the engines in the contiguous blocks ``shard_bounds(M, G, r)``;
+        every engine gets ALL bases and its slice of ``base_of``, pins (or replays) the graphs as ``Engine.hvp`` does and returns its
+        rows of ``hv`` (and ``curv``).  A single direction runs on engine 0 (``last_route == "single"``).  Every displaced image is its
+        evaluation alone on the pinned graph of its base, so the result is the single engine's, bit for bit.  Per-image cells
+        (``set_cells``) are taken only when exactly one is bound, as ``Engine.hvp`` takes them."""
+        b, d = self._images(base, True), self._images(dirs, True)
+        m, g = d.shape[0], len(self.engines)
+        a = None if base_of is None else np.ascontiguousarray(base_of, dtype=np.int32).reshape(-1)
+        if a is not None and len(a) != m:
+            raise ValueError(f"hvp: {m} directions, but base_of has {len(a)} entries")
+        if self._cells is not None:
+            if len(self._cells[0]) != 1:
+                raise ValueError(f"hvp: set_cells bound cells for {len(self._cells[0])} images; the displaced images of a base share its one cell (set_cell)")
+            self._bind_cells(1, None)
+        blocks = [shard_bounds(m, g, r) for r in range(g)] if m > 1 else [(0, 1)] + [(0, 0)] * (g - 1)
+        busy = [r for r in range(g) if blocks[r][1] > blocks[r][0]]
+        self.last_route, self.last_blocks = ("batch" if m > 1 else "single"), blocks
+
+        def call(r):
+            lo, hi = blocks[r]
+            return self.engines[r].hvp(b, d[lo:hi], None if a is None else a[lo:hi], step=step, scheme=scheme, pin=pin, return_curvature=True)
+
+        for attempt in range(2):
+            was_wide = [bool(getattr(eng, "widened", False)) for eng in self.engines]
+            res = self._run_all(call, busy)
+            now_wide = [bool(getattr(eng, "widened", False)) for eng in self.engines]
+            if attempt == 0 and now_wide != was_wide:          # (as _deal: one result never mixes two arithmetics)
+                self._widen_all("fp16 range violation on another engine of the local pool")
+                continue
+            break
+        hv = np.concatenate([r[0] for r in res])
+        return (hv, np.concatenate([r[1] for r in res])) if return_curvature else hv
 
     def energy_forces_virial(self, pos_ang, graph_parallel: bool = False, double_positions: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """``Engine.energy_forces_virial`` over the pool: (E [K], F [K,N,3], W [K,3,3] float64).  A batch is dealt over the engines in

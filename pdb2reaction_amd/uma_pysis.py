@@ -70,6 +70,8 @@ CALC_KW: Dict[str, Any] = {
 
 PIN_NOT_GP = ("hessian_pin_graph=True cannot be combined with the graph-parallel mode (workers == world size / enable_graph_parallel): its "
               "entries (umx_gp_begin) build their own graph and refuse a pinned engine")
+HVP_NOT_GP = ("get_hvp cannot be combined with the graph-parallel mode (workers == world size / enable_graph_parallel): Hessian-vector "
+              "products need the pinned graph, and the graph-parallel entries (umx_gp_begin) build their own")
 
 # number of displaced geometries evaluated per engine call while building an FD Hessian
 FD_BATCH = int(os.environ.get("UMX_FD_BATCH", "64"))
@@ -352,6 +354,17 @@ class UMAcore:
                                "coordinates, or an overflow that wider forward planes cannot cure")
         return f
 
+    def hvp(self, coord_ang: np.ndarray, vectors: np.ndarray, *, step: float = 1e-3, scheme: str = "central", base_of=None) -> np.ndarray:
+        """Hessian-vector products of the FULL Hessian: ``coord_ang`` (N,3) or (R,N,3) A, ``vectors`` (M,N,3) -> (M,N,3) float64 eV/A^2
+        per unit of ``vectors``, through ``Engine.hvp`` (or the pool's): displaced images formed in float64 on the device, evaluated on
+        the pinned graph of their base in one batched call.  The graph-parallel mode has no such entry: ``ValueError``."""
+        if getattr(self, "_gp", None) is not None:
+            raise ValueError(HVP_NOT_GP)
+        n = len(self.z)
+        return (getattr(self, "_pool", None) or self.engine).hvp(np.asarray(coord_ang, dtype=np.float64).reshape(-1, n, 3),
+                                                                 np.asarray(vectors, dtype=np.float64).reshape(-1, n, 3), base_of,
+                                                                 step=float(step), scheme=scheme)
+
     def compute(self, coord_ang: np.ndarray, *, forces: bool = False, hessian: bool = False) -> Dict[str, Any]:
         """Energy (eV) and optionally forces (eV/A) of one geometry; same contract as reference ``:330-419``."""
         if hessian:
@@ -572,6 +585,38 @@ class uma_pysis(Calculator):
         c = np.asarray(coords_batch, dtype=np.float64)
         res = core.compute_batch(c.reshape(c.shape[0], -1, 3) * BOHR2ANG, forces=False)
         return {"energy": np.asarray(res["energy"], dtype=np.float64) * EV2AU}
+
+    def get_hvp(self, elem, coords_bohr, vectors, step_bohr: Optional[float] = None, scheme: str = "central"):
+        """Hessian-vector products without a Hessian: ``coords_bohr`` (3N,) or (N,3) Bohr, ``vectors`` (3N,), (M,3N) or (M,N,3) --
+        directions in the coordinates' space, not normalised -- -> ``{"hvp": (M,3N) float64 Hartree/Bohr^2}`` per unit of ``vectors``.
+        ``step_bohr``: the displacement per unit of ``vectors`` (None: 1e-3 A, the FD Hessian's step); ``scheme``: "central" (two images
+        per vector) or "forward" (one, plus the base once per call).  One engine call (``Engine.hvp``): displaced images in float64,
+        on the pinned graph of the geometry at hand; the cell of ``uma_pysis(cell=...)`` applies.
+
+        ``freeze_atoms``: the rows of frozen atoms are zeroed in the vectors BEFORE the displacement and in the result -- this is the
+        product of the ACTIVE BLOCK of the Hessian (what ``return_partial_hessian`` cuts out, embedded in 3N with zeros), not rows of
+        the full Hessian times an arbitrary vector.  A graph-parallel core (``workers`` == world size / ``enable_graph_parallel``)
+        raises ``ValueError``, as ``hessian_pin_graph`` does; so do a bad shape, a bad scheme and a step that is not positive."""
+        core = self._ensure_core(elem)
+        if getattr(core, "_gp", None) is not None:
+            raise ValueError(HVP_NOT_GP)
+        if scheme not in ("central", "forward"):
+            raise ValueError(f"get_hvp: scheme must be 'central' or 'forward', got {scheme!r}")
+        x = _bohr_to_ang(coords_bohr)
+        n = x.shape[0]
+        v = np.array(vectors, dtype=np.float64)
+        if v.size == 0 or v.size % (3 * n) != 0 or (v.ndim > 1 and v.shape[0] != v.size // (3 * n)):
+            raise ValueError(f"get_hvp: vectors must be (3N,), (M,3N) or (M,N,3) with N = {n}, got {v.shape}")
+        v = v.reshape(-1, n, 3)
+        step_ang = H.FD_STEP_ANG if step_bohr is None else float(step_bohr) * BOHR2ANG
+        if not (np.isfinite(step_ang) and step_ang > 0.0):
+            raise ValueError(f"get_hvp: the step must be finite and positive, got {step_bohr!r}")
+        if self.freeze_atoms:
+            v[:, np.asarray(self.freeze_atoms, dtype=int), :] = 0.0
+        hv = np.array(core.hvp(x, v, step=step_ang, scheme=scheme), dtype=np.float64).reshape(-1, n, 3)
+        if self.freeze_atoms:
+            hv[:, np.asarray(self.freeze_atoms, dtype=int), :] = 0.0
+        return {"hvp": (hv * H.EV_PER_ANG2_TO_AU).reshape(-1, 3 * n)}
 
     def get_hessian(self, elem, coords):
         """Hessian per ``hessian_calc_mode`` with the reference's dispatch (``:708-780``): "Analytical" only when the core
