@@ -555,10 +555,37 @@ int umx_bond_changes(umx_engine* eng, int n, const double* r1, const double* r2,
  *   - UMX_ERR_ARG, outputs untouched: a non-finite cell entry; a degenerate periodic sub-lattice (the messages of umx_set_cell);
  *     M_k > 4 on some axis (at most 9^3 = 729 candidates are searched).
  *   - cost per pair: up to prod (2 M_k + 1) distance evaluations (125 in a cubic cell, M_k = 2), fewer with the skipping.
- * Not provided: many pairs of geometries in one call.  No reference counterpart (compare_structures measures open-space distances). */
+ * Many pairs of geometries in one call: umx_bond_events.  No reference counterpart (compare_structures measures open-space distances). */
 int umx_bond_changes_cell(umx_engine* eng, int n, const double* r1, const double* r2, const double* cov, const double cell[9],
                           const int pbc[3], double bond_factor, double margin_fraction, double delta_fraction, double* d1,
                           double* d2, uint8_t* code);
+
+/* BOND-CHANGE EVENTS OF MANY PAIRS OF GEOMETRIES (additive to ABI v10).  The formed / broken pairs of umx_bond_changes[_cell] as a
+ * compact list, for a stack of geometries of the same atoms and a list of pairs of them, without any n x n matrix.
+ * r: [n_geoms][n_atoms][3] float64 (host); pair p compares geometry geom_a[p] (lengths d1) with geometry geom_b[p] (lengths d2);
+ * geom_a == geom_b == NULL: the consecutive pairs (0,1), (1,2), ... (n_pairs is then ignored and taken as n_geoms - 1).  cov, the
+ * three fractions, cell and pbc: as umx_bond_changes_cell (cell in the unit of the coordinates; NULL or no flag set: open space).
+ *   - An event is a pair i < j with code 1 (formed) or 2 (broken) and its two lengths: bit for bit the entries code[i][j], d1[i][j],
+ *     d2[i][j] of umx_bond_changes (open space) / umx_bond_changes_cell (cell) for the two geometries of its pair.
+ *   - Order: ascending in (pair, i, j), the same in every call (three passes -- count, prefix sum, fill -- and no atomics).
+ *   - Capacity: the first min(total, capacity) events are written; *n_events is always the total, as with snprintf: repeat the call
+ *     with a larger buffer.  capacity == 0 (events may be NULL) only counts.  per_pair (NULL or [n_pairs]): the total of every pair.
+ *   - Memory: geometries, radii, 12 bytes per (pair, atom) and 32 bytes per written event -- nothing of order n^2, and no limit of the
+ *     n^2 <= 2^31 kind; row counters and totals are 64-bit.
+ *   - UMX_ERR_ARG before anything is launched, outputs untouched, the message names the offender: a size <= 0 (fewer than two
+ *     geometries for consecutive pairs); only one of geom_a / geom_b; a pair index outside [0, n_geoms) -- every index is checked on
+ *     the host before it reaches the device; a non-finite coordinate (names the geometry) or radius; a negative capacity, or a
+ *     positive one without a buffer; a cell umx_bond_changes_cell refuses (the same messages).
+ *   - cost per pair of geometries: n (n - 1) / 2 pairs of atoms in the count pass, two distances each (in a cell: the candidate search
+ *     of umx_bond_changes_cell per distance); the fill pass repeats only rows that hold an event, up to their last one.
+ * Needs no weights and no bound system; the engine's bound cell is not read.
+ * Not provided: a device-pointer variant; spatial binning (the search is brute force over the upper triangle on purpose: the bits are
+ * those of the matrix kernels); a list of bonded pairs (connectivity).
+ * Replaces: the loops over _has_bond_change, path_search.py:1015,1200,1310,1361-1366.                                                  */
+typedef struct umx_bond_event { int32_t pair, i, j, code; double d1, d2; } umx_bond_event;   /* 32 bytes; i < j; code 1 formed, 2 broken */
+int umx_bond_events(umx_engine* eng, int n_atoms, int n_geoms, const double* r, int n_pairs, const int32_t* geom_a, const int32_t* geom_b,
+                    const double* cov, const double cell[9], const int pbc[3], double bond_factor, double margin_fraction,
+                    double delta_fraction, int64_t capacity, umx_bond_event* events, int64_t* n_events, int64_t* per_pair);
 
 /* Test hook: copy a named intermediate buffer of the most recent evaluation's last chunk to the
  * host.  Returns the buffer size in bytes through *nbytes_out when host_buf == NULL.           */

@@ -4,6 +4,8 @@ Reference: ``pdb2reaction/bond_changes.py`` -- ``compare_structures`` (:142-187,
 boolean masks), ``summarize_changes`` (:196-232), ``BondChangeResult`` (:93-100).  Here the two distance matrices and the
 formed/broken classification come from ONE HIP kernel (``umx_bond_changes`` in ``include/umx.h``); there is no CPU path.
 With ``cell=`` / ``pbc=`` the distances are minimum-image distances in that cell (``umx_bond_changes_cell``).
+``compare_structures(matrices=False)`` and :func:`compare_path` take the event route instead (``umx_bond_events``): only the formed /
+broken pairs and their two lengths come back, for any number of pairs of geometries from one engine call, with memory of order N.
 
 Covalent radii: the reference takes ``pysisyphus.elem_data.COVALENT_RADII`` (third-party, absent here).  The table below
 restates the published Cordero et al. 2008 single-bond radii (Dalton Trans. 2008, 2832) in Angstrom and converts them to
@@ -13,7 +15,7 @@ the unit of the coordinates (Bohr for pysisyphus geometries) -- [3P-UNVERIFIED a
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Dict, Iterable, List, Optional, Sequence, Set, Tuple
+from typing import Dict, Iterable, List, Optional, Sequence, Set, Tuple, Union
 
 import numpy as np
 
@@ -41,12 +43,14 @@ COVALENT_RADII_ANG: Dict[str, float] = {
 @dataclass
 class BondChangeResult:
     """Zero-based (i < j) index pairs of formed / broken covalent bonds and the two N x N distance matrices
-    (same unit as the input coordinates)."""
+    (same unit as the input coordinates).  The event route leaves the matrices ``None`` and fills ``lengths``: for every formed or
+    broken pair its length in the first and in the second geometry -- the entries the matrices would hold, bit for bit."""
 
     formed_covalent: Set[Pair]
     broken_covalent: Set[Pair]
     distances_1: Optional[np.ndarray] = None
     distances_2: Optional[np.ndarray] = None
+    lengths: Optional[Dict[Pair, Tuple[float, float]]] = None
 
 
 def element_radii(atoms: Iterable[str], unit_scale: float = ANG2BOHR, radii: Optional[Dict[str, float]] = None) -> Tuple[List[str], np.ndarray]:
@@ -76,7 +80,7 @@ def _engine(device: str = "cuda"):
 
 def compare_structures(geom1, geom2, device: str = "cuda", bond_factor: float = 1.20, margin_fraction: float = 0.05,
                        delta_fraction: float = 0.05, *, engine=None, radii: Optional[Dict[str, float]] = None,
-                       unit_scale: float = ANG2BOHR, cell=None, pbc=None) -> BondChangeResult:
+                       unit_scale: float = ANG2BOHR, cell=None, pbc=None, matrices: bool = True) -> BondChangeResult:
     """Formed / broken covalent bonds between two geometries with identical atoms (``.atoms``, ``.coords3d`` [N,3]).
 
     bonded(i,j) <=> D_ij <= T - margin_fraction*T with T = bond_factor*(r_i + r_j); a pair changes only when
@@ -86,7 +90,13 @@ def compare_structures(geom1, geom2, device: str = "cuda", bond_factor: float = 
     ``cell`` (3,3, rows as lattice vectors, IN THE UNIT OF THE COORDINATES -- Bohr for pysisyphus geometries) and ``pbc`` (a bool or
     three flags): D is the minimum-image distance over all lattice translations (``umx_bond_changes_cell``), so a bond across the
     boundary is a bond.  Without them the open-space call as it was.  No reference counterpart.
+
+    ``matrices=False``: the event route (:func:`compare_path` on the one pair) -- the same sets, ``distances_1/2`` are ``None`` and
+    ``lengths`` holds the two lengths of every changed pair; nothing of size N x N is formed on the device or the host.
     """
+    if not matrices:
+        return compare_path([geom1, geom2], [(0, 1)], device, bond_factor, margin_fraction, delta_fraction, engine=engine, radii=radii,
+                            unit_scale=unit_scale, cell=cell, pbc=pbc)[0]
     if list(geom1.atoms) != list(geom2.atoms):
         raise AssertionError("Atom types and ordering must be identical.")
     _, cov = element_radii(geom1.atoms, unit_scale, radii)
@@ -98,6 +108,52 @@ def compare_structures(geom1, geom2, device: str = "cuda", bond_factor: float = 
     return BondChangeResult(formed_covalent=formed, broken_covalent=broken, distances_1=d1, distances_2=d2)
 
 
+def path_pairs(pairs: Union[str, Sequence[Pair]], n_geoms: int) -> List[Pair]:
+    """The pairs of images :func:`compare_path` compares: ``"consecutive"`` (k, k + 1), ``"endpoints"`` (0, K - 1), ``"all"`` every
+    a < b, or the given list as it is."""
+    if isinstance(pairs, str):
+        if pairs == "consecutive":
+            return [(k, k + 1) for k in range(n_geoms - 1)]
+        if pairs == "endpoints":
+            return [(0, n_geoms - 1)]
+        if pairs == "all":
+            return [(a, b) for a in range(n_geoms) for b in range(a + 1, n_geoms)]
+        raise ValueError(f"compare_path: pairs={pairs!r} is none of 'consecutive', 'endpoints', 'all'")
+    return [(int(a), int(b)) for a, b in pairs]
+
+
+def compare_path(geoms, pairs: Union[str, Sequence[Pair]] = "consecutive", device: str = "cuda", bond_factor: float = 1.20,
+                 margin_fraction: float = 0.05, delta_fraction: float = 0.05, *, engine=None, radii: Optional[Dict[str, float]] = None,
+                 unit_scale: float = ANG2BOHR, cell=None, pbc=None) -> List[BondChangeResult]:
+    """Formed / broken covalent bonds between pairs of the geometries of a path, from ONE engine call (``umx_bond_events``).
+
+    ``geoms``: geometries with identical atoms (``.atoms``, ``.coords3d``); ``pairs``: see :func:`path_pairs` -- pair (a, b) reports
+    what forms or breaks going from ``geoms[a]`` to ``geoms[b]``.  One :class:`BondChangeResult` per pair, in the given order, with
+    ``lengths`` filled and no matrices; the sets are those of :func:`compare_structures` on the same two geometries.  The other
+    arguments as there: ``cell`` in the unit of the coordinates, and -- as there -- the cell is used only when BOTH ``cell`` and ``pbc``
+    are given; one without the other is the open-space call.  Replaces the loops over ``_has_bond_change`` of the reference's ``path_search.py`` (:1015, :1200, :1310,
+    :1361-1366)."""
+    geoms = list(geoms)
+    if not geoms:
+        raise ValueError("compare_path: no geometries")
+    atoms = list(geoms[0].atoms)
+    if any(list(g.atoms) != atoms for g in geoms[1:]):
+        raise AssertionError("Atom types and ordering must be identical.")
+    todo = path_pairs(pairs, len(geoms))
+    if not todo:
+        return []
+    _, cov = element_radii(atoms, unit_scale, radii)
+    eng = engine if engine is not None else _engine(device)
+    stack = np.stack([np.asarray(g.coords3d, dtype=np.float64).reshape(len(atoms), 3) for g in geoms])
+    in_cell = {} if cell is None or pbc is None else {"cell": cell, "pbc": pbc}
+    ev = eng.bond_events(stack, cov, todo, bond_factor, margin_fraction, delta_fraction, **in_cell)
+    out = [BondChangeResult(formed_covalent=set(), broken_covalent=set(), lengths={}) for _ in todo]
+    for p, i, j, code, d1, d2 in ev.tolist():
+        (out[p].formed_covalent if code == 1 else out[p].broken_covalent).add((i, j))
+        out[p].lengths[(i, j)] = (d1, d2)
+    return out
+
+
 def _bond_str(i: int, j: int, elems: Sequence[str], one_based: bool = True) -> str:
     o = 1 if one_based else 0
     return f"{elems[i]}{i + o}-{elems[j]}{j + o}"
@@ -105,10 +161,12 @@ def _bond_str(i: int, j: int, elems: Sequence[str], one_based: bool = True) -> s
 
 def summarize_changes(geom, result: BondChangeResult, one_based: bool = True) -> str:
     """Text report in the reference's format ("Bond formed (n):" / "  - C1-O2 : 1.500 Å --> 1.360 Å" / "...: None");
-    lengths are converted from Bohr to Angstrom (reference bond_changes.py:196-232)."""
+    lengths are converted from Bohr to Angstrom (reference bond_changes.py:196-232).  They are read from the two matrices, or, when the
+    result has none (the event route), from ``result.lengths``."""
     elems = [str(a).capitalize() for a in geom.atoms]
     d1, d2 = result.distances_1, result.distances_2
     have = isinstance(d1, np.ndarray) and isinstance(d2, np.ndarray) and d1.shape == d2.shape
+    lengths = result.lengths if not have and result.lengths is not None else {}
     out: List[str] = []
     for title, pairs in (("Bond formed", result.formed_covalent), ("Bond broken", result.broken_covalent)):
         if not pairs:
@@ -116,6 +174,7 @@ def summarize_changes(geom, result: BondChangeResult, one_based: bool = True) ->
             continue
         out.append(f"{title} ({len(pairs)}):")
         for i, j in sorted(pairs):
-            tail = f" : {float(d1[i, j]) * BOHR2ANG:.3f} Å --> {float(d2[i, j]) * BOHR2ANG:.3f} Å" if have else ""
+            ab = (d1[i, j], d2[i, j]) if have else lengths.get((i, j))
+            tail = f" : {float(ab[0]) * BOHR2ANG:.3f} Å --> {float(ab[1]) * BOHR2ANG:.3f} Å" if ab is not None else ""
             out.append(f"  - {_bond_str(i, j, elems, one_based)}{tail}")
     return "\n".join(out)

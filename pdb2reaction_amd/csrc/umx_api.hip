@@ -17,6 +17,7 @@
 #include "umx_hvp.h"         // Hessian-vector products: displace, difference and curvature kernels around one batched evaluation
 #include "umx_weights.h"     // the weight loader
 #include "umx_experts.h"     // expert-form weights: the Mixture-of-Linear-Experts merge and its plane copies on the device
+#include "umx_bonds.h"       // bond-change events of many pairs of geometries: count, scan and fill kernels and their launcher
 
 // ================================================================================================
 //                                           C ABI
@@ -342,6 +343,7 @@ int umx_destroy(umx_engine* eng) {
   (void)hipEventDestroy(eng->ev_tok[0]); (void)hipEventDestroy(eng->ev_tok[1]);
   if (eng->ev_done) (void)hipEventDestroy(eng->ev_done);
   if (eng->ev_m0) { (void)hipEventDestroy(eng->ev_m0); (void)hipEventDestroy(eng->ev_m1); }
+  for (hipEvent_t e : eng->ev_bond) if (e) (void)hipEventDestroy(e);
   (void)hipStreamDestroy(eng->stream2);
   (void)hipStreamDestroy(eng->stream);
   delete eng;
@@ -832,6 +834,18 @@ int umx_debug_fetch(umx_engine* eng, const char* name, void* host_buf, size_t ca
     }
     return UMX_OK;
   }
+  if (nm == "bond_events:kernel_ms") {
+    // three floats: the milliseconds of the count, scan and fill kernels of the last umx_bond_events, between its four events
+    if (!eng->bond_timed) return fail(eng, UMX_ERR_ARG, "umx_debug_fetch: no umx_bond_events call has run");
+    float ms[3];
+    for (int k = 0; k < 3; ++k) HIPCHK(eng, hipEventElapsedTime(&ms[k], eng->ev_bond[k], eng->ev_bond[k + 1]));
+    if (nbytes_out) *nbytes_out = sizeof(ms);
+    if (host_buf) {
+      if (capacity < sizeof(ms)) return fail(eng, UMX_ERR_ARG, "umx_debug_fetch: buffer too small");
+      std::memcpy(host_buf, ms, sizeof(ms));
+    }
+    return UMX_OK;
+  }
   if (nm.rfind("weights:", 0) == 0 || nm.rfind("experts:", 0) == 0) {
     // fetched on demand: the three weight arenas as they are on the device, the tensor table of d_w ("<name> <first float> <floats>" per
     // line), and the kernel time of the last umx_set_expert_coefficients (one float, milliseconds between its two events)
@@ -929,6 +943,47 @@ int umx_bond_changes_cell(umx_engine* eng, int n, const double* r1, const double
   std::string why;
   if (!bond_cell_candidates(cell, pbc, &bc, &cand, &why)) return fail(eng, UMX_ERR_ARG, "umx_bond_changes_cell: " + why);
   return bond_changes_run(eng, "umx_bond_changes_cell", n, r1, r2, cov, &bc, cand, bond_factor, margin_fraction, delta_fraction, d1, d2, code);
+}
+
+// every refusal comes before the first allocation and leaves the outputs as they were; the passes are umx_bonds.h
+int umx_bond_events(umx_engine* eng, int n_atoms, int n_geoms, const double* r, int n_pairs, const int32_t* geom_a, const int32_t* geom_b,
+                    const double* cov, const double cell[9], const int pbc[3], double bond_factor, double margin_fraction, double delta_fraction,
+                    int64_t capacity, umx_bond_event* events, int64_t* n_events, int64_t* per_pair) {
+  if (!eng) return UMX_ERR_ARG;
+  const std::string w = "umx_bond_events: ";
+  if (n_atoms <= 0 || n_geoms <= 0) return fail(eng, UMX_ERR_ARG, w + "n_atoms = " + std::to_string(n_atoms) + " and n_geoms = " + std::to_string(n_geoms) + " must be positive");
+  if (!r || !cov || !n_events) return fail(eng, UMX_ERR_ARG, w + "r, cov and n_events must be given");
+  if (!geom_a != !geom_b) return fail(eng, UMX_ERR_ARG, w + "only one of geom_a / geom_b is given (both, or neither for consecutive pairs)");
+  std::vector<int32_t> consecutive;
+  if (!geom_a) {
+    if (n_geoms < 2) return fail(eng, UMX_ERR_ARG, w + "consecutive pairs need at least two geometries, n_geoms = " + std::to_string(n_geoms));
+    n_pairs = n_geoms - 1;
+    consecutive.resize(2 * (size_t)n_pairs);
+    for (int p = 0; p < n_pairs; ++p) { consecutive[p] = p; consecutive[(size_t)n_pairs + p] = p + 1; }
+    geom_a = consecutive.data(); geom_b = geom_a + n_pairs;
+  }
+  if (n_pairs <= 0) return fail(eng, UMX_ERR_ARG, w + "n_pairs = " + std::to_string(n_pairs) + " must be positive");
+  if (capacity < 0 || (capacity > 0 && !events)) return fail(eng, UMX_ERR_ARG, w + "capacity = " + std::to_string(capacity) + (capacity < 0 ? " is negative" : " without an event buffer"));
+  for (int p = 0; p < n_pairs; ++p)
+    for (const int32_t g : {geom_a[p], geom_b[p]})
+      if (g < 0 || g >= n_geoms)
+        return fail(eng, UMX_ERR_ARG, w + "pair " + std::to_string(p) + " names geometry " + std::to_string(g) + ", outside [0, " + std::to_string(n_geoms) + ")");
+  const size_t per_geom = (size_t)n_atoms * 3;
+  for (int g = 0; g < n_geoms; ++g)
+    for (size_t k = 0; k < per_geom; ++k)
+      if (!std::isfinite(r[(size_t)g * per_geom + k]))
+        return fail(eng, UMX_ERR_ARG, w + "non-finite coordinate in geometry " + std::to_string(g) + " (atom " + std::to_string(k / 3) + ")");
+  for (int i = 0; i < n_atoms; ++i)
+    if (!std::isfinite(cov[i])) return fail(eng, UMX_ERR_ARG, w + "non-finite radius of atom " + std::to_string(i));
+  if (!cell || !pbc || !(pbc[0] || pbc[1] || pbc[2]))
+    return bond_events_run(eng, n_atoms, n_geoms, r, n_pairs, geom_a, geom_b, cov, nullptr, {}, bond_factor, margin_fraction, delta_fraction, capacity, events,
+                           n_events, per_pair);
+  umx::BondCell bc;
+  std::vector<double> cand;
+  std::string why;
+  if (!bond_cell_candidates(cell, pbc, &bc, &cand, &why)) return fail(eng, UMX_ERR_ARG, w + why);
+  return bond_events_run(eng, n_atoms, n_geoms, r, n_pairs, geom_a, geom_b, cov, &bc, cand, bond_factor, margin_fraction, delta_fraction, capacity, events,
+                         n_events, per_pair);
 }
 
 }  // extern "C"

@@ -363,6 +363,8 @@ struct umx_engine {
   int* d_hvp_bof = nullptr; long hvp_bof_cap = 0; std::vector<int> hvp_bof_dev;   // [directions] base_of, and what the device copy holds
   double* d_hvp_in = nullptr; long hvp_in_cap = 0;                            // [bases + directions][natoms][3]
   double* d_hvp_out = nullptr; long hvp_out_cap = 0;                          // [directions][natoms][3] hv, then [directions] curv
+  hipEvent_t ev_bond[4] = {nullptr, nullptr, nullptr, nullptr};   // umx_bond_events: before count | scan | fill | after fill, of the last call
+  bool bond_timed = false;                                        // ev_bond hold a finished call (umx_debug_fetch "bond_events:kernel_ms")
   bool may_truncate = true;      // the largest degree of the evaluation being planned reaches max_neigh: k_graph_fill takes its truncating (LDS) form
   bool prof_on = false;
   std::vector<ProfRec> prof;

@@ -27,6 +27,16 @@ class ProfileStats(C.Structure):
     _fields_ = [("ms", C.c_double * 3), ("launches", C.c_int64 * 3), ("alg_flops", C.c_double * 3), ("mfma_flops", C.c_double * 3)]
 
 
+class BondEvent(C.Structure):
+    """Mirror of ``umx_bond_event`` (include/umx.h), 32 bytes: pair ``i < j`` of pair-of-geometries ``pair``, code 1 formed / 2 broken,
+    its length in the first and in the second geometry."""
+
+    _fields_ = [("pair", C.c_int32), ("i", C.c_int32), ("j", C.c_int32), ("code", C.c_int32), ("d1", C.c_double), ("d2", C.c_double)]
+
+
+# the same record as a NumPy structured dtype (Engine.bond_events returns arrays of it)
+BOND_EVENT_DTYPE = np.dtype([("pair", np.int32), ("i", np.int32), ("j", np.int32), ("code", np.int32), ("d1", np.float64), ("d2", np.float64)])
+
 UMX_ERR_RANGE = -6      # include/umx.h
 
 
@@ -112,6 +122,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "umx_profile_read": ([vp, C.POINTER(ProfileStats), i32], i32),
         "umx_bond_changes": ([vp, i32, dp, dp, dp, C.c_double, C.c_double, C.c_double, dp, dp, C.POINTER(C.c_uint8)], i32),
         "umx_bond_changes_cell": ([vp, i32, dp, dp, dp, dp, C.POINTER(C.c_int), C.c_double, C.c_double, C.c_double, dp, dp, C.POINTER(C.c_uint8)], i32),
+        "umx_bond_events": ([vp, i32, i32, dp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, dp, C.POINTER(C.c_int), C.c_double, C.c_double, C.c_double,
+                             C.c_int64, C.POINTER(BondEvent), i64p, i64p], i32),
         "umx_debug_fetch": ([vp, C.c_char_p, vp, C.c_size_t, C.POINTER(C.c_size_t)], i32),
         "umx_debug_keep": ([vp, i32], i32),
     }
@@ -151,6 +163,7 @@ EXPORTED_SYMBOLS = (
     "umx_set_cell", "umx_set_cells", "umx_last_graph_shifts", "umx_energy_forces_virial", "umx_energy_forces_virial_dev",
     "umx_gp_begin_virial", "umx_pin_graph", "umx_unpin_graph", "umx_pinned_graph",
     "umx_pin_graphs", "umx_pin_assign", "umx_pinned_graphs", "umx_bond_changes_cell", "umx_hvp", "umx_hvp_dev",
+    "umx_bond_events",
 )
 # The float64-position entries, listed apart: tests/test_boundary_cpu.py holds EXPORTED_SYMBOLS to the names it reads out of the header
 # with a pattern of letters and underscores, which a name with a digit in it does not match.  load_library declares (and so demands)
@@ -730,6 +743,52 @@ class Engine:
                                                  f.ctypes.data_as(C.POINTER(C.c_int)), float(bond_factor), float(margin_fraction), float(delta_fraction),
                                                  *out), "umx_bond_changes_cell")
         return d1, d2, code
+
+    def bond_events(self, geoms: np.ndarray, cov: np.ndarray, pairs=None, bond_factor: float = 1.20, margin_fraction: float = 0.05,
+                    delta_fraction: float = 0.05, cell=None, pbc=None, capacity: int = 4096, per_pair: bool = False):
+        """Formed / broken pairs of many pairs of geometries in ONE call (``umx_bond_events``), without the N x N matrices.
+
+        ``geoms`` (K, N, 3) float64; ``pairs``: a sequence of (a, b) indices into it -- pair p compares geometry a (``d1``) with geometry
+        b (``d2``) -- or ``None`` for the consecutive pairs (0, 1), (1, 2), ...  ``cov``, the fractions, ``cell`` and ``pbc`` as
+        :meth:`bond_changes`.  Returns a structured array (``BOND_EVENT_DTYPE``: pair, i, j, code, d1, d2; i < j, code 1 formed / 2
+        broken) ascending in (pair, i, j); every record carries the bits :meth:`bond_changes` writes at ``[i, j]`` for its pair.  The
+        buffer holds ``capacity`` events; when the call finds more it is repeated ONCE with a buffer of the size it reported.
+        ``per_pair=True``: (events, int64 counts per pair)."""
+        g = np.ascontiguousarray(geoms, dtype=np.float64)
+        c = np.ascontiguousarray(cov, dtype=np.float64).reshape(-1)
+        n = c.shape[0]
+        if g.ndim < 2 or n == 0 or g.size == 0 or g.size % (3 * n):
+            raise ValueError(f"bond_events: inconsistent sizes {g.shape}, {c.shape}")
+        g = g.reshape(-1, n, 3)
+        i32p, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        if pairs is None:
+            n_pairs, ga, gb = g.shape[0] - 1, None, None
+        else:
+            pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+            if pr.size and (np.abs(pr) > 2**31 - 1).any():
+                raise ValueError("bond_events: pair index beyond int32")
+            ga_, gb_ = np.ascontiguousarray(pr[:, 0], dtype=np.int32), np.ascontiguousarray(pr[:, 1], dtype=np.int32)
+            n_pairs, ga, gb = len(pr), ga_.ctypes.data_as(i32p), gb_.ctypes.data_as(i32p)
+        flags = None if pbc is None else np.broadcast_to(np.asarray(pbc, dtype=bool), (3,))
+        lat = f = None
+        if cell is not None and flags is not None and flags.any():
+            lat = np.ascontiguousarray(np.asarray(cell, dtype=np.float64).reshape(3, 3))
+            f = np.ascontiguousarray(flags, dtype=np.intc)
+        counts = np.zeros(max(n_pairs, 0), dtype=np.int64)
+        total = C.c_int64(0)
+        cap = max(int(capacity), 0)
+        for _ in range(2):
+            ev = np.zeros(cap, dtype=BOND_EVENT_DTYPE)
+            self._chk(self.lib.umx_bond_events(self._h, n, g.shape[0], g.ctypes.data_as(dp), n_pairs, ga, gb, c.ctypes.data_as(dp),
+                                               None if lat is None else lat.ctypes.data_as(dp), None if f is None else f.ctypes.data_as(C.POINTER(C.c_int)),
+                                               float(bond_factor), float(margin_fraction), float(delta_fraction), cap,
+                                               ev.ctypes.data_as(C.POINTER(BondEvent)) if cap else None, C.byref(total),
+                                               counts.ctypes.data_as(C.POINTER(C.c_int64)) if n_pairs > 0 else None), "umx_bond_events")
+            if total.value <= cap:
+                break
+            cap = int(total.value)
+        ev = ev[:total.value]
+        return (ev, counts) if per_pair else ev
 
     # ---- diagnostics -----------------------------------------------------------------------------
     def graph_stats(self) -> Tuple[int, int]:

@@ -31,7 +31,7 @@ def optimize_path_gsm(elem: Sequence[str], reactant_ang: np.ndarray, product_ang
                       fix_ends: bool = False, thresh: Optional[str] = None, preopt: bool = False, preopt_max_cycles: int = 10000,
                       sopt_kind: str = "lbfgs", sopt_cfg: Optional[Dict[str, Any]] = None, align: bool = True, align_kw: Optional[Dict[str, Any]] = None,
                       gs_kw: Optional[Dict[str, Any]] = None, stopt_kw: Optional[Dict[str, Any]] = None, out_dir: Optional[str] = None,
-                      group=None, log=None, cell=None, pbc=None) -> Dict[str, Any]:
+                      group=None, log=None, cell=None, pbc=None, bond_changes: bool = False, bond_engine=None) -> Dict[str, Any]:
     """Minimum-energy path between two endpoint geometries (Angstrom) by the growing-string method on the HIP engine.
 
     calc: a ``uma_pysis`` instance shared by every step (created from ``calc_kw`` + ``freeze_atoms`` when None, as ``path_opt.py:823``).
@@ -43,7 +43,11 @@ def optimize_path_gsm(elem: Sequence[str], reactant_ang: np.ndarray, product_ang
     created with the cell, or a given one must carry the same cell (``ValueError`` otherwise; a calculator that carries a cell hands it
     over when none is passed).  The pre-optimisation runs as it is; the rigid alignment is NOT run -- a rotation is no symmetry of a
     lattice -- and reported as ``"align": [{"skipped": "periodic cell"}]``: the driver's minimum-image unwrapping of the product onto the
-    reactant takes its place.  The images come back unwrapped, as the driver holds them; the file formats do not change."""
+    reactant takes its place.  The images come back unwrapped, as the driver holds them; the file formats do not change.
+
+    bond_changes=True: the result gains ``"bond_changes"`` (:func:`path_bond_changes`): the report text first image -> last image and,
+    per neighbouring pair of final images, the formed / broken pairs -- one ``umx_bond_events`` call on ``bond_engine`` (default: the
+    process's light engine), in a periodic run with the run's cell and flags.  False (default): exactly the keys above."""
     log = log or (lambda s: None)
     elem = [str(e).capitalize() for e in elem]
     n = len(elem)
@@ -108,7 +112,29 @@ def optimize_path_gsm(elem: Sequence[str], reactant_ang: np.ndarray, product_ang
         formats.write_trj_with_energy(elem, images_ang, res.energies, files["final_geometries"])
         files["hei"] = os.path.join(out_dir, "hei.xyz")
         formats.write_xyz(elem, images_ang[hei], files["hei"], energy_hartree=float(res.energies[hei]))
-    return {"images_ang": images_ang, "energies": res.energies, "hei_index": int(hei), "converged": bool(res.converged), "cycles": int(res.cycles),
-            "force_evaluations": int(res.force_evaluations), "fully_grown": bool(res.fully_grown), "history": res.history, "timing": res.timing,
-            "device": str(drv.device), "preopt": pre, "align": align_info, "files": files, "defaults": {"GS_KW": dict(GS_KW), "STOPT_KW": dict(STOPT_KW)},
-            "cell": None if not periodic else np.array(cell, dtype=np.float64).reshape(3, 3), "pbc": PBC.pbc_flags(pbc) if periodic else None}
+    out = {"images_ang": images_ang, "energies": res.energies, "hei_index": int(hei), "converged": bool(res.converged), "cycles": int(res.cycles),
+           "force_evaluations": int(res.force_evaluations), "fully_grown": bool(res.fully_grown), "history": res.history, "timing": res.timing,
+           "device": str(drv.device), "preopt": pre, "align": align_info, "files": files, "defaults": {"GS_KW": dict(GS_KW), "STOPT_KW": dict(STOPT_KW)},
+           "cell": None if not periodic else np.array(cell, dtype=np.float64).reshape(3, 3), "pbc": PBC.pbc_flags(pbc) if periodic else None}
+    if bond_changes:
+        out["bond_changes"] = path_bond_changes(elem, np.asarray(res.coords, dtype=np.float64).reshape(len(res.coords), n, 3), engine=bond_engine,
+                                                **({"cell": np.asarray(cell, dtype=np.float64).reshape(3, 3) * ANG2BOHR, "pbc": pbc} if periodic else {}))
+    return out
+
+
+def path_bond_changes(elem: Sequence[str], images_bohr: np.ndarray, *, engine=None, cell=None, pbc=None) -> Dict[str, Any]:
+    """Which bonds change along a string, from ONE engine call (``bond_changes.compare_path``: the consecutive pairs of images plus
+    first against last).  images_bohr (K, N, 3) and ``cell`` in Bohr.  ``{"endpoints": the reference's report text for image 0 ->
+    image K - 1 (``summarize_changes``), "segments": [{"images": [k, k + 1], "formed": [[i, j], ...], "broken": [...]}, ...]}`` -- what
+    the reference's path code reports after every string (``path_search.py:1200``, ``:1361-1366``)."""
+    import types
+
+    from . import bond_changes as BC
+
+    geoms = [types.SimpleNamespace(atoms=list(elem), coords3d=x) for x in np.asarray(images_bohr, dtype=np.float64)]
+    k = len(geoms)
+    pairs = [(a, a + 1) for a in range(k - 1)] + [(0, k - 1)]
+    res = BC.compare_path(geoms, pairs, engine=engine, **({} if cell is None or pbc is None else {"cell": cell, "pbc": pbc}))
+    segs = [{"images": [a, b], "formed": [list(p) for p in sorted(r.formed_covalent)], "broken": [list(p) for p in sorted(r.broken_covalent)]}
+            for (a, b), r in zip(pairs[:-1], res[:-1])]
+    return {"endpoints": BC.summarize_changes(geoms[-1], res[-1]), "segments": segs}
