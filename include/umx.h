@@ -404,6 +404,29 @@ int umx_hvp(umx_engine* eng, int n_bases, const double* base_ang, int n_dirs, co
 int umx_hvp_dev(umx_engine* eng, int n_bases, const double* d_base_ang, int n_dirs, const double* d_dir, const int32_t* base_of,
                 double step_ang, int flags, double* d_hv, double* d_curv, double* d_e0, float* d_f0, void* hip_stream);
 
+/* FLOAT64 BLOCK KERNELS (additive to ABI v10).  What a matrix-free eigensolver on umx_hvp_dev -- a block Davidson, LOBPCG or Lanczos loop
+ * -- does between two products, on blocks of ROW vectors [p][n] float64 (n = 3 n_atoms) that stay on the device: projections
+ * v - Q^T (Q v), mass weighting and freeze masks, Gram-Schmidt against a basis, Ritz vectors V.C, residuals AX - X diag(theta).
+ *   umx_blk_gram_dev     g[a][b] = sum_c x[a][c] * y[b][c]; x: [p][n], y: [q][n], g: [p][q] row-major.  One 256-thread workgroup per
+ *                        entry in umx_hvp's curv order: lane t adds c = t, t + 256, ... ascending, the 256 partials are added in the LDS
+ *                        tree s = 128 ... 1.  d_x == d_y is allowed; g is then symmetric bit for bit.
+ *   umx_blk_combine_dev  y[j][c] = z[j][c] - sum_i C[i][j] * x[i][c] (subtract != 0) or z[j][c] + sum_i ... (subtract == 0); x: [p][n],
+ *                        C: [p][q] row-major ON THE DEVICE, z, y: [q][n].  One thread per (j, c): acc = z[j][c], or 0.0 when d_z is NULL,
+ *                        then i = 0 ... p - 1 ascending, acc = fl(acc -+ fl(C * x)).  d_y may be d_z; it must not overlap d_x.
+ *   umx_blk_scale_dev    y[a][c] = fl(w[c] * x[a][c]); x, y: [p][n], w: [n].  d_y may be d_x.
+ * Float64 throughout, products and sums rounded separately (no fused multiply-add), no atomics, 64-bit indexing: the bits depend on the
+ * inputs only and are those of the NumPy functions blk_gram / blk_combine / blk_scale of pdb2reaction_amd/modes.py.
+ * All pointers are DEVICE pointers; the kernel is enqueued on hip_stream (NULL = the legacy default stream) and nothing is waited for:
+ * stream order with umx_hvp_dev is the only synchronisation.  They need no weights and no bound system.
+ * UMX_ERR_ARG before any launch, the outputs untouched: p, q or n <= 0; p or q > 64; a NULL operand (d_z alone may be NULL); d_y
+ * overlapping d_x in combine.  With these entries unused no kernel, launch or result of any other entry changes.
+ * Not provided: host-pointer forms; a preconditioner; the small dense eigenproblem (<= 64 x 64: the caller's, on the host).
+ * Replaces: the dense mass-weighted Hessian the reference builds to ask for its lowest eigenpairs (tsopt.py, freq.py).                  */
+int umx_blk_gram_dev(umx_engine* eng, int p, const double* d_x, int q, const double* d_y, int64_t n, double* d_g, void* hip_stream);
+int umx_blk_combine_dev(umx_engine* eng, int p, const double* d_x, int q, const double* d_c, int64_t n, const double* d_z, int subtract,
+                        double* d_y, void* hip_stream);
+int umx_blk_scale_dev(umx_engine* eng, int p, const double* d_x, const double* d_w, int64_t n, double* d_y, void* hip_stream);
+
 /* Graph-parallel evaluation of ONE image across several engines / ranks (ABI v5) -- the reference's `workers > 1` semantics
  * (ParallelMLIPPredictUnit: the atoms' graph partitioned over workers, uma_pysis.py:220-242), for single large systems when there are
  * fewer images than GPUs.  Every rank passes the FULL positions; rank r builds the incoming edges of the

@@ -245,6 +245,15 @@ class UMXCalculator(_AseBase):
         return eng.hvp(np.array(atoms.get_positions(), dtype=np.float64), np.asarray(vectors, dtype=np.float64), step=float(step), scheme=scheme,
                        pin=pin, return_curvature=return_curvature)
 
+    def lowest_modes(self, atoms, k: int = 1, frozen=(), **kw):
+        """The ``k`` lowest vibrational modes at ``atoms`` without a Hessian (``Engine.lowest_modes`` / ``LocalEnginePool.lowest_modes``;
+        ``modes.lowest_modes`` documents the keywords and the :class:`modes.ModesResult` returned, eV/A^2/amu and cm^-1): masses from
+        ``atoms.get_masses()``, the graph, cell and pbc flags of ``atoms``; ``frozen``: atom indices held fixed.  Inside
+        ``with calc.pinned(ref)`` the pinned graph of ``ref`` is used and left in place."""
+        eng = self._ensure(atoms)
+        return eng.lowest_modes(np.array(atoms.get_positions(), dtype=np.float64), np.asarray(atoms.get_masses(), dtype=np.float64), int(k),
+                                frozen=frozen, **kw)
+
     def _stress_kw(self) -> dict:
         """What ``energy_forces_stress`` is called with: the graph-parallel opt-in when this calculator runs a pool of engines."""
         return {"graph_parallel": True} if self.gp_stress and len(self.local_devices or []) > 1 else {}

@@ -18,6 +18,7 @@
 #include "umx_weights.h"     // the weight loader
 #include "umx_experts.h"     // expert-form weights: the Mixture-of-Linear-Experts merge and its plane copies on the device
 #include "umx_bonds.h"       // bond-change events of many pairs of geometries: count, scan and fill kernels and their launcher
+#include "umx_modes.h"       // float64 block kernels of a matrix-free eigensolver on umx_hvp: gram, combine, scale
 
 // ================================================================================================
 //                                           C ABI
@@ -984,6 +985,41 @@ int umx_bond_events(umx_engine* eng, int n_atoms, int n_geoms, const double* r, 
   if (!bond_cell_candidates(cell, pbc, &bc, &cand, &why)) return fail(eng, UMX_ERR_ARG, w + why);
   return bond_events_run(eng, n_atoms, n_geoms, r, n_pairs, geom_a, geom_b, cov, &bc, cand, bond_factor, margin_fraction, delta_fraction, capacity, events,
                          n_events, per_pair);
+}
+
+// ---- float64 block kernels (kernels and the shared refusals in umx_modes.h): every refusal comes before the launch -----------------------
+int umx_blk_gram_dev(umx_engine* eng, int p, const double* d_x, int q, const double* d_y, int64_t n, double* d_g, void* hip_stream) {
+  if (!eng) return UMX_ERR_ARG;
+  CHK(blk_check(eng, "umx_blk_gram_dev", p, q, (long)n));
+  if (!d_x || !d_y || !d_g) return fail(eng, UMX_ERR_ARG, "umx_blk_gram_dev: d_x, d_y and d_g must be given");
+  HIPCHK(eng, hipSetDevice(eng->dev));
+  hipLaunchKernelGGL(umx::k_blk_gram, dim3((unsigned)(p * q)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), d_x, d_y, (long)q, (long)n, d_g);
+  HIPCHK(eng, hipGetLastError());
+  return UMX_OK;
+}
+
+int umx_blk_combine_dev(umx_engine* eng, int p, const double* d_x, int q, const double* d_c, int64_t n, const double* d_z, int subtract, double* d_y,
+                        void* hip_stream) {
+  if (!eng) return UMX_ERR_ARG;
+  CHK(blk_check(eng, "umx_blk_combine_dev", p, q, (long)n));
+  if (!d_x || !d_c || !d_y) return fail(eng, UMX_ERR_ARG, "umx_blk_combine_dev: d_x, d_c and d_y must be given (d_z may be NULL)");
+  if (blk_overlap(d_x, (size_t)p * (size_t)n, d_y, (size_t)q * (size_t)n))
+    return fail(eng, UMX_ERR_ARG, "umx_blk_combine_dev: d_y overlaps d_x -- every output element reads a whole column of X (d_y may be d_z)");
+  HIPCHK(eng, hipSetDevice(eng->dev));
+  hipLaunchKernelGGL(umx::k_blk_combine, dim3(nblk((long)q * (long)n, 256)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), d_x, d_c, d_z, (long)p, (long)q,
+                     (long)n, subtract ? 1 : 0, d_y);
+  HIPCHK(eng, hipGetLastError());
+  return UMX_OK;
+}
+
+int umx_blk_scale_dev(umx_engine* eng, int p, const double* d_x, const double* d_w, int64_t n, double* d_y, void* hip_stream) {
+  if (!eng) return UMX_ERR_ARG;
+  CHK(blk_check(eng, "umx_blk_scale_dev", p, 1, (long)n));
+  if (!d_x || !d_w || !d_y) return fail(eng, UMX_ERR_ARG, "umx_blk_scale_dev: d_x, d_w and d_y must be given");
+  HIPCHK(eng, hipSetDevice(eng->dev));
+  hipLaunchKernelGGL(umx::k_blk_scale, dim3(nblk((long)p * (long)n, 256)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), d_x, d_w, (long)p, (long)n, d_y);
+  HIPCHK(eng, hipGetLastError());
+  return UMX_OK;
 }
 
 }  // extern "C"

@@ -111,6 +111,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "umx_pinned_graphs": ([vp, i32, i64p, C.POINTER(C.c_int32)], i32),
         "umx_hvp": ([vp, i32, dp, i32, dp, C.POINTER(C.c_int32), C.c_double, i32, dp, dp, dp, fp], i32),
         "umx_hvp_dev": ([vp, i32, vp, i32, vp, C.POINTER(C.c_int32), C.c_double, i32, vp, vp, vp, vp, vp], i32),
+        "umx_blk_gram_dev": ([vp, i32, vp, i32, vp, C.c_int64, vp, vp], i32),
+        "umx_blk_combine_dev": ([vp, i32, vp, i32, vp, C.c_int64, vp, i32, vp, vp], i32),
+        "umx_blk_scale_dev": ([vp, i32, vp, vp, C.c_int64, vp, vp], i32),
         "umx_last_partitions": ([vp], i32),
         "umx_last_lanes": ([vp], i32),
         "umx_set_recompute": ([vp, i32], i32),
@@ -163,7 +166,7 @@ EXPORTED_SYMBOLS = (
     "umx_set_cell", "umx_set_cells", "umx_last_graph_shifts", "umx_energy_forces_virial", "umx_energy_forces_virial_dev",
     "umx_gp_begin_virial", "umx_pin_graph", "umx_unpin_graph", "umx_pinned_graph",
     "umx_pin_graphs", "umx_pin_assign", "umx_pinned_graphs", "umx_bond_changes_cell", "umx_hvp", "umx_hvp_dev",
-    "umx_bond_events",
+    "umx_bond_events", "umx_blk_gram_dev", "umx_blk_combine_dev", "umx_blk_scale_dev",
 )
 # The float64-position entries, listed apart: tests/test_boundary_cpu.py holds EXPORTED_SYMBOLS to the names it reads out of the header
 # with a pattern of letters and underscores, which a name with a digit in it does not match.  load_library declares (and so demands)
@@ -692,6 +695,35 @@ class Engine:
         self._chk(self.lib.umx_hvp_dev(self._h, int(n_bases), C.c_void_p(d_base), int(n_dirs), C.c_void_p(d_dirs),
                                        a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None, float(step), self._hvp_flags(scheme, pin, given_f0),
                                        C.c_void_p(d_hv), p(d_curv), p(d_e0), p(d_f0), p(stream)), "umx_hvp_dev")
+
+    # ---- float64 block kernels and the lowest modes ------------------------------------------------------
+    def blk_gram_dev(self, p: int, d_x: int, q: int, d_y: int, n: int, d_g: int, stream: int = 0):
+        """``umx_blk_gram_dev``: ``g[a][b] = sum_c x[a][c] y[b][c]`` of the float64 row blocks ``d_x`` [p][n] and ``d_y`` [q][n] into
+        ``d_g`` [p][q], all device pointers, enqueued on ``stream``; fixed summation order (``modes.blk_gram`` states it)."""
+        self._chk(self.lib.umx_blk_gram_dev(self._h, int(p), C.c_void_p(d_x), int(q), C.c_void_p(d_y), int(n), C.c_void_p(d_g),
+                                            C.c_void_p(stream) if stream else None), "umx_blk_gram_dev")
+
+    def blk_combine_dev(self, p: int, d_x: int, q: int, d_c: int, n: int, d_z: int, subtract: bool, d_y: int, stream: int = 0):
+        """``umx_blk_combine_dev``: ``y[j] = z[j] -+ sum_i C[i][j] x[i]`` -- ``d_x`` [p][n], ``d_c`` [p][q] on the device, ``d_z`` [q][n] or 0
+        (zeros), ``d_y`` [q][n]; ``d_y`` may be ``d_z``, not ``d_x`` (``modes.blk_combine``)."""
+        self._chk(self.lib.umx_blk_combine_dev(self._h, int(p), C.c_void_p(d_x), int(q), C.c_void_p(d_c), int(n), C.c_void_p(d_z) if d_z else None,
+                                               1 if subtract else 0, C.c_void_p(d_y), C.c_void_p(stream) if stream else None), "umx_blk_combine_dev")
+
+    def blk_scale_dev(self, p: int, d_x: int, d_w: int, n: int, d_y: int, stream: int = 0):
+        """``umx_blk_scale_dev``: ``y[a][c] = w[c] x[a][c]`` -- ``d_x``, ``d_y`` [p][n], ``d_w`` [n]; in place allowed (``modes.blk_scale``)."""
+        self._chk(self.lib.umx_blk_scale_dev(self._h, int(p), C.c_void_p(d_x), C.c_void_p(d_w), int(n), C.c_void_p(d_y),
+                                             C.c_void_p(stream) if stream else None), "umx_blk_scale_dev")
+
+    def lowest_modes(self, base, masses, k: int = 1, *, frozen=(), project: str = "auto", step: float = 1e-3, scheme: str = "central",
+                     block=None, max_subspace=None, tol=None, max_iter: int = 200, v0=None, seed: int = 0):
+        """The ``k`` lowest eigenpairs of the mass-weighted, projected Hessian at ``base`` (N,3) Angstrom without a Hessian: block
+        Davidson on ``hvp_dev`` with every vector on the device (``modes.lowest_modes``, which documents the arguments and the
+        :class:`modes.ModesResult` returned).  ``masses`` (N,) in amu."""
+        from . import modes
+
+        return modes.lowest_modes(modes.DeviceBackend(self), base, masses, k, frozen=frozen, project=project, step=step, scheme=scheme,
+                                  block=block, max_subspace=max_subspace, tol=tol, max_iter=max_iter, v0=v0, seed=seed,
+                                  periodic=self._pbc_flags() is not None)
 
     # ---- graph-parallel single-image mode (reference workers > 1; see parallel.GraphParallelEvaluator) -----------------
     def gp_begin(self, d_pos: int, node_lo: int, node_hi: int, d_energy: int, d_forces: int, stream: int = 0, d_virial: int = 0):

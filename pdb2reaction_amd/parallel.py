@@ -848,6 +848,20 @@ class LocalEnginePool:
         hv = np.concatenate([r[0] for r in res])
         return (hv, np.concatenate([r[1] for r in res])) if return_curvature else hv
 
+    def lowest_modes(self, base, masses, k: int = 1, *, frozen=(), project: str = "auto", step: float = 1e-3, scheme: str = "central",
+                     block=None, max_subspace=None, tol=None, max_iter: int = 200, v0=None, seed: int = 0):
+        """``Engine.lowest_modes`` over the pool: the host backend of ``modes.lowest_modes`` on ``pool.hvp`` -- every iteration's block
+        of directions is dealt over the engines, the small block algebra runs in NumPy in the kernels' operation order.  The graph of
+        ``base`` is pinned on every engine for the call.  Products being the single engine's bit for bit, so is the result (that of
+        the host backend over ``Engine.hvp``).  The forward scheme evaluates the base with every block (``pool.hvp`` hands no base
+        forces back)."""
+        from . import modes
+
+        pbc = getattr(self.engines[0], "_pbc_flags", lambda: None)
+        return modes.lowest_modes(modes.HostBackend(self.hvp, pinner=self), base, masses, k, frozen=frozen, project=project, step=step,
+                                  scheme=scheme, block=block, max_subspace=max_subspace, tol=tol, max_iter=max_iter, v0=v0, seed=seed,
+                                  periodic=self._cells is not None or pbc() is not None)
+
     def energy_forces_virial(self, pos_ang, graph_parallel: bool = False, double_positions: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """``Engine.energy_forces_virial`` over the pool: (E [K], F [K,N,3], W [K,3,3] float64).  A batch is dealt over the engines in
         the same contiguous blocks as ``energy_forces`` and is the single-engine result bit for bit (W does not depend on the batch an

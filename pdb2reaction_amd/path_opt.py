@@ -31,7 +31,8 @@ def optimize_path_gsm(elem: Sequence[str], reactant_ang: np.ndarray, product_ang
                       fix_ends: bool = False, thresh: Optional[str] = None, preopt: bool = False, preopt_max_cycles: int = 10000,
                       sopt_kind: str = "lbfgs", sopt_cfg: Optional[Dict[str, Any]] = None, align: bool = True, align_kw: Optional[Dict[str, Any]] = None,
                       gs_kw: Optional[Dict[str, Any]] = None, stopt_kw: Optional[Dict[str, Any]] = None, out_dir: Optional[str] = None,
-                      group=None, log=None, cell=None, pbc=None, bond_changes: bool = False, bond_engine=None) -> Dict[str, Any]:
+                      group=None, log=None, cell=None, pbc=None, bond_changes: bool = False, bond_engine=None, hei_modes: int = 0, masses_amu=None,
+                      hei_modes_kw: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
     """Minimum-energy path between two endpoint geometries (Angstrom) by the growing-string method on the HIP engine.
 
     calc: a ``uma_pysis`` instance shared by every step (created from ``calc_kw`` + ``freeze_atoms`` when None, as ``path_opt.py:823``).
@@ -47,7 +48,13 @@ def optimize_path_gsm(elem: Sequence[str], reactant_ang: np.ndarray, product_ang
 
     bond_changes=True: the result gains ``"bond_changes"`` (:func:`path_bond_changes`): the report text first image -> last image and,
     per neighbouring pair of final images, the formed / broken pairs -- one ``umx_bond_events`` call on ``bond_engine`` (default: the
-    process's light engine), in a periodic run with the run's cell and flags.  False (default): exactly the keys above."""
+    process's light engine), in a periodic run with the run's cell and flags.  False (default): exactly the keys above.
+
+    hei_modes=k > 0: the result gains ``"hei_modes"``: ``{"freqs_cm" (k,) signed cm^-1, "converged" (k,) bool, "images": evaluations
+    spent, "n_imaginary"}`` of the k lowest vibrational modes of the FINAL highest-energy image -- one ``calc.get_lowest_modes`` call
+    after the run (block Davidson on Hessian-vector products, no Hessian), with the run's frozen atoms and in the run's cell;
+    ``masses_amu`` (N,) as that method takes them, ``hei_modes_kw`` its further keywords.  A first-order saddle has exactly one negative
+    entry.  0 (default): exactly the keys above; the run loop itself never asks for modes."""
     log = log or (lambda s: None)
     elem = [str(e).capitalize() for e in elem]
     n = len(elem)
@@ -119,6 +126,10 @@ def optimize_path_gsm(elem: Sequence[str], reactant_ang: np.ndarray, product_ang
     if bond_changes:
         out["bond_changes"] = path_bond_changes(elem, np.asarray(res.coords, dtype=np.float64).reshape(len(res.coords), n, 3), engine=bond_engine,
                                                 **({"cell": np.asarray(cell, dtype=np.float64).reshape(3, 3) * ANG2BOHR, "pbc": pbc} if periodic else {}))
+    if int(hei_modes) > 0:
+        m = calc.get_lowest_modes(elem, np.asarray(res.coords[hei], dtype=np.float64).reshape(-1), int(hei_modes), masses_amu, **(hei_modes_kw or {}))
+        out["hei_modes"] = {"freqs_cm": np.asarray(m["freqs_cm"]), "converged": np.asarray(m["converged"]), "images": int(m["images"]),
+                            "n_imaginary": int((np.asarray(m["freqs_cm"]) < 0.0).sum())}
     return out
 
 

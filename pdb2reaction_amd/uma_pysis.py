@@ -72,6 +72,8 @@ PIN_NOT_GP = ("hessian_pin_graph=True cannot be combined with the graph-parallel
               "entries (umx_gp_begin) build their own graph and refuse a pinned engine")
 HVP_NOT_GP = ("get_hvp cannot be combined with the graph-parallel mode (workers == world size / enable_graph_parallel): Hessian-vector "
               "products need the pinned graph, and the graph-parallel entries (umx_gp_begin) build their own")
+MODES_NOT_GP = ("get_lowest_modes cannot be combined with the graph-parallel mode (workers == world size / enable_graph_parallel): its "
+                "Hessian-vector products need the pinned graph, and the graph-parallel entries (umx_gp_begin) build their own")
 
 # number of displaced geometries evaluated per engine call while building an FD Hessian
 FD_BATCH = int(os.environ.get("UMX_FD_BATCH", "64"))
@@ -365,6 +367,15 @@ class UMAcore:
                                                                  np.asarray(vectors, dtype=np.float64).reshape(-1, n, 3), base_of,
                                                                  step=float(step), scheme=scheme)
 
+    def lowest_modes(self, coord_ang: np.ndarray, masses_amu, k: int = 1, **kw):
+        """The ``k`` lowest eigenpairs of the mass-weighted, projected Hessian at ``coord_ang`` (N,3) A without a Hessian
+        (``modes.lowest_modes``: keywords and the ``ModesResult`` returned, in eV/A^2/amu): on the engine with every vector on the
+        device, or over the in-process pool.  The graph-parallel mode has no such entry: ``ValueError``."""
+        if getattr(self, "_gp", None) is not None:
+            raise ValueError(MODES_NOT_GP)
+        return (getattr(self, "_pool", None) or self.engine).lowest_modes(np.asarray(coord_ang, dtype=np.float64).reshape(len(self.z), 3),
+                                                                          masses_amu, int(k), **kw)
+
     def compute(self, coord_ang: np.ndarray, *, forces: bool = False, hessian: bool = False) -> Dict[str, Any]:
         """Energy (eV) and optionally forces (eV/A) of one geometry; same contract as reference ``:330-419``."""
         if hessian:
@@ -617,6 +628,41 @@ class uma_pysis(Calculator):
         if self.freeze_atoms:
             hv[:, np.asarray(self.freeze_atoms, dtype=int), :] = 0.0
         return {"hvp": (hv * H.EV_PER_ANG2_TO_AU).reshape(-1, 3 * n)}
+
+    def get_lowest_modes(self, elem, coords_bohr, k: int = 1, masses_amu=None, *, project: str = "auto", step_bohr: Optional[float] = None,
+                         scheme: str = "central", block=None, max_subspace=None, tol=None, max_iter: int = 200, v0=None, seed: int = 0):
+        """The ``k`` lowest vibrational modes without a Hessian (block Davidson on Hessian-vector products, ``modes.lowest_modes``):
+        ``coords_bohr`` (3N,) or (N,3) Bohr -> ``{"freqs_cm": (k,) signed wavenumbers (negative = imaginary), "eigenvalues": (k,)
+        Hartree/Bohr^2/amu, "modes": (k,3N) Cartesian displacements, each normalised (the reference's convention), "converged": (k,)
+        bool, "residuals": (k,) Hartree/Bohr^2/amu, "images": evaluations spent}``.
+
+        masses_amu: (N,) amu; None takes pysisyphus' table for ``elem`` when pysisyphus can be imported and raises ``ValueError``
+        otherwise (the package has no table of its own).  ``freeze_atoms`` are held fixed (their rows of ``modes`` are zero) and the
+        cell of ``uma_pysis(cell=...)`` applies; ``project="auto"``: translations and rotations for open boundaries, translations in a
+        cell without frozen atoms, nothing in a cell with frozen atoms.  ``step_bohr``: per unit of the Cartesian direction (None:
+        1e-3 A); ``tol``: on the residual norms, in Hartree/Bohr^2/amu (None: ``modes.DEFAULT_TOL``, 1.8e-3 eV/A^2/amu).  ``v0``: start
+        vectors in the mass-weighted space, (j,3N).  A graph-parallel core raises ``ValueError``, as ``get_hvp`` does."""
+        core = self._ensure_core(elem)
+        if getattr(core, "_gp", None) is not None:
+            raise ValueError(MODES_NOT_GP)
+        x = _bohr_to_ang(coords_bohr)
+        if masses_amu is None:
+            try:
+                from pysisyphus.elem_data import MASS_DICT
+            except ImportError as exc:
+                raise ValueError("get_lowest_modes: masses_amu is needed (N values in amu): pysisyphus, whose table would be used, "
+                                 "cannot be imported and this package has no table of its own") from exc
+            masses_amu = [MASS_DICT[str(e).lower()] for e in elem]
+        m = np.asarray(masses_amu, dtype=np.float64).reshape(-1)
+        if m.shape[0] != x.shape[0]:
+            raise ValueError(f"get_lowest_modes: {x.shape[0]} atoms, but masses_amu has {m.shape[0]} entries")
+        step_ang = H.FD_STEP_ANG if step_bohr is None else float(step_bohr) * BOHR2ANG
+        res = core.lowest_modes(x, m, int(k), frozen=tuple(self.freeze_atoms or ()), project=project, step=step_ang, scheme=scheme, block=block,
+                                max_subspace=max_subspace, tol=None if tol is None else float(tol) / H.EV_PER_ANG2_TO_AU, max_iter=max_iter,
+                                v0=v0, seed=seed)
+        return {"freqs_cm": np.array(res.freqs_cm), "eigenvalues": np.asarray(res.eigenvalues) * H.EV_PER_ANG2_TO_AU,
+                "modes": np.asarray(res.modes, dtype=np.float64).reshape(len(res.eigenvalues), -1), "converged": np.array(res.converged),
+                "residuals": np.asarray(res.residuals) * H.EV_PER_ANG2_TO_AU, "images": int(res.images)}
 
     def get_hessian(self, elem, coords):
         """Hessian per ``hessian_calc_mode`` with the reference's dispatch (``:708-780``): "Analytical" only when the core
