@@ -427,6 +427,34 @@ int umx_blk_combine_dev(umx_engine* eng, int p, const double* d_x, int q, const 
                         double* d_y, void* hip_stream);
 int umx_blk_scale_dev(umx_engine* eng, int p, const double* d_x, const double* d_w, int64_t n, double* d_y, void* hip_stream);
 
+/* FLOAT64 ROW KERNELS (additive to ABI v10).  What a BATCH of K independent searches on umx_hvp_dev -- K dimers refining K saddle guesses,
+ * one base each, one batched product per round -- does between two products: K vectors [k][n] float64 (n = 3 n_atoms) that stay on the
+ * device, each with scalars of its own.  The block kernels above mix rows through a p x q matrix; this is the diagonal case, which
+ * through them would cost K^2 dots and a read-back of K^2 numbers.
+ *   umx_row_dot_dev     out[r] = sum_c x[r][c] * y[r][c]; x, y: [k][n], out: [k].  One 256-thread workgroup per row in umx_blk_gram_dev's
+ *                       order (lane t adds c = t, t + 256, ... ascending from 0.0, then the LDS tree s = 128 ... 1): out[r] is
+ *                       umx_blk_gram_dev's g[r][r] bit for bit.  d_x == d_y is allowed.
+ *   umx_row_axpby_dev   out[r][c] = fl(fl(a[r] * x[r][c]) + fl(b[r] * y[r][c])); a, b: [k] ON THE DEVICE, x, y, out: [k][n].  d_b == NULL
+ *                       and d_y == NULL together: out = fl(a * x).  One thread per element, read before write: d_out may be d_x or d_y.
+ *   umx_row_absmax_dev  out[r] = max_c |x[r][c]|, NaN when the row holds a NaN (numpy.max(numpy.abs(x), axis=1)); x: [k][n], out: [k].
+ * Float64 throughout, products and sums rounded separately (no fused multiply-add), no atomics, 64-bit indexing: the bits depend on the
+ * inputs only, a row's result does not depend on the rows beside it, and they are those of the NumPy functions row_dot / row_axpby /
+ * row_absmax of pdb2reaction_amd/dimer.py.  All pointers are DEVICE pointers; the kernel is enqueued on hip_stream (NULL = the legacy
+ * default stream) and nothing is waited for.  They need no weights and no bound system.
+ * UMX_ERR_ARG before any launch, the outputs untouched (umx_last_error names the offender): k or n <= 0; k > 64; a NULL operand other
+ * than the pair (d_b, d_y); exactly one of d_b and d_y NULL; d_out of dot / absmax overlapping an input; d_out of axpby overlapping d_a
+ * or d_b, or overlapping d_x or d_y without being that pointer.  With these entries unused no kernel, launch or result of any other
+ * entry changes.
+ * Not provided: host-pointer forms; the dimer itself (pdb2reaction_amd/dimer.py drives these entries and umx_hvp_dev: rotation in the
+ * plane of two products, L-BFGS translation on the reflected force); the reference's flatten loop for further imaginary modes, Bofill
+ * updates, internal coordinates; a transition-state search from a minimum.
+ * Replaces: tsopt.HessianDimer's Hessians -- the full finite-difference Hessian it builds for the first dimer orientation, every
+ * update_interval_hessian steps and at the end (6 n_atoms displaced images each).                                                      */
+int umx_row_dot_dev(umx_engine* eng, int k, const double* d_x, const double* d_y, int64_t n, double* d_out, void* hip_stream);
+int umx_row_axpby_dev(umx_engine* eng, int k, const double* d_a, const double* d_x, const double* d_b, const double* d_y, int64_t n,
+                      double* d_out, void* hip_stream);
+int umx_row_absmax_dev(umx_engine* eng, int k, const double* d_x, int64_t n, double* d_out, void* hip_stream);
+
 /* Graph-parallel evaluation of ONE image across several engines / ranks (ABI v5) -- the reference's `workers > 1` semantics
  * (ParallelMLIPPredictUnit: the atoms' graph partitioned over workers, uma_pysis.py:220-242), for single large systems when there are
  * fewer images than GPUs.  Every rank passes the FULL positions; rank r builds the incoming edges of the

@@ -254,6 +254,19 @@ class UMXCalculator(_AseBase):
         return eng.lowest_modes(np.array(atoms.get_positions(), dtype=np.float64), np.asarray(atoms.get_masses(), dtype=np.float64), int(k),
                                 frozen=frozen, **kw)
 
+    def refine_saddle(self, atoms, mode=None, frozen=(), **kw):
+        """Refine the transition-state guess ``atoms`` to a first-order saddle without a Hessian (``Engine.refine_saddles`` /
+        ``LocalEnginePool.refine_saddles``; ``dimer.refine_saddles`` documents the keywords): ``mode`` (N,3) the start direction (None: the
+        lowest mode), ``frozen`` atom indices held fixed, the cell and pbc flags of ``atoms``; ``verify=True`` takes its masses from
+        ``atoms.get_masses()``.  Returns ``(new atoms, dimer.SaddleResult)``: a copy of ``atoms`` at the refined positions (eV, A)."""
+        eng = self._ensure(atoms)
+        if kw.get("verify") and kw.get("masses") is None:
+            kw["masses"] = np.asarray(atoms.get_masses(), dtype=np.float64)
+        res = eng.refine_saddles(np.array(atoms.get_positions(), dtype=np.float64), mode, frozen=frozen, **kw)[0]
+        new = atoms.copy()
+        new.set_positions(res.x)
+        return new, res
+
     def _stress_kw(self) -> dict:
         """What ``energy_forces_stress`` is called with: the graph-parallel opt-in when this calculator runs a pool of engines."""
         return {"graph_parallel": True} if self.gp_stress and len(self.local_devices or []) > 1 else {}

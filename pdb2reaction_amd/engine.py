@@ -114,6 +114,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "umx_blk_gram_dev": ([vp, i32, vp, i32, vp, C.c_int64, vp, vp], i32),
         "umx_blk_combine_dev": ([vp, i32, vp, i32, vp, C.c_int64, vp, i32, vp, vp], i32),
         "umx_blk_scale_dev": ([vp, i32, vp, vp, C.c_int64, vp, vp], i32),
+        "umx_row_dot_dev": ([vp, i32, vp, vp, C.c_int64, vp, vp], i32),
+        "umx_row_axpby_dev": ([vp, i32, vp, vp, vp, vp, C.c_int64, vp, vp], i32),
+        "umx_row_absmax_dev": ([vp, i32, vp, C.c_int64, vp, vp], i32),
         "umx_last_partitions": ([vp], i32),
         "umx_last_lanes": ([vp], i32),
         "umx_set_recompute": ([vp, i32], i32),
@@ -167,6 +170,7 @@ EXPORTED_SYMBOLS = (
     "umx_gp_begin_virial", "umx_pin_graph", "umx_unpin_graph", "umx_pinned_graph",
     "umx_pin_graphs", "umx_pin_assign", "umx_pinned_graphs", "umx_bond_changes_cell", "umx_hvp", "umx_hvp_dev",
     "umx_bond_events", "umx_blk_gram_dev", "umx_blk_combine_dev", "umx_blk_scale_dev",
+    "umx_row_dot_dev", "umx_row_axpby_dev", "umx_row_absmax_dev",
 )
 # The float64-position entries, listed apart: tests/test_boundary_cpu.py holds EXPORTED_SYMBOLS to the names it reads out of the header
 # with a pattern of letters and underscores, which a name with a digit in it does not match.  load_library declares (and so demands)
@@ -724,6 +728,36 @@ class Engine:
         return modes.lowest_modes(modes.DeviceBackend(self), base, masses, k, frozen=frozen, project=project, step=step, scheme=scheme,
                                   block=block, max_subspace=max_subspace, tol=tol, max_iter=max_iter, v0=v0, seed=seed,
                                   periodic=self._pbc_flags() is not None)
+
+    # ---- float64 row kernels and the batched dimer ---------------------------------------------------------
+    def row_dot_dev(self, k: int, d_x: int, d_y: int, n: int, d_out: int, stream: int = 0):
+        """``umx_row_dot_dev``: ``out[r] = sum_c x[r][c] y[r][c]`` of the float64 rows ``d_x``, ``d_y`` [k][n] into ``d_out`` [k], all
+        device pointers, enqueued on ``stream``; ``blk_gram_dev``'s summation order, so ``out[r]`` is its ``g[r][r]`` (``dimer.row_dot``)."""
+        self._chk(self.lib.umx_row_dot_dev(self._h, int(k), C.c_void_p(d_x), C.c_void_p(d_y), int(n), C.c_void_p(d_out),
+                                           C.c_void_p(stream) if stream else None), "umx_row_dot_dev")
+
+    def row_axpby_dev(self, k: int, d_a: int, d_x: int, d_b: int, d_y: int, n: int, d_out: int, stream: int = 0):
+        """``umx_row_axpby_dev``: ``out[r] = fl(fl(a[r] x[r]) + fl(b[r] y[r]))`` -- ``d_a``, ``d_b`` [k] on the device, ``d_x``, ``d_y``,
+        ``d_out`` [k][n]; ``d_b`` and ``d_y`` both 0: ``out = fl(a x)``; ``d_out`` may be ``d_x`` or ``d_y`` (``dimer.row_axpby``)."""
+        p = lambda x: C.c_void_p(x) if x else None
+        self._chk(self.lib.umx_row_axpby_dev(self._h, int(k), p(d_a), p(d_x), p(d_b), p(d_y), int(n), p(d_out), p(stream)), "umx_row_axpby_dev")
+
+    def row_absmax_dev(self, k: int, d_x: int, n: int, d_out: int, stream: int = 0):
+        """``umx_row_absmax_dev``: ``out[r] = max_c |x[r][c]|`` (NaN when the row holds one) -- ``d_x`` [k][n], ``d_out`` [k]
+        (``dimer.row_absmax``)."""
+        self._chk(self.lib.umx_row_absmax_dev(self._h, int(k), C.c_void_p(d_x), int(n), C.c_void_p(d_out),
+                                              C.c_void_p(stream) if stream else None), "umx_row_absmax_dev")
+
+    def refine_saddles(self, x0, modes0=None, *, frozen=(), project: str = "auto", thresh="gau", step: float = 1e-3, max_cycles: int = 200,
+                       max_rot: int = 2, rot_tol: float = 0.1, max_step: float = 0.1, masses=None, verify: bool = False):
+        """Refine transition-state guesses ``x0`` (N,3) or (K,N,3) Angstrom, K <= 64, to first-order saddles without a Hessian: K dimers
+        advancing together, one batched ``hvp_dev`` call per product round, every vector on the device (``dimer.refine_saddles``, which
+        documents the arguments; a list of :class:`dimer.SaddleResult`, one per candidate)."""
+        from . import dimer
+
+        return dimer.refine_saddles(dimer.DeviceBackend(self), x0, modes0, frozen=frozen, project=project, thresh=thresh, step=step,
+                                    max_cycles=max_cycles, max_rot=max_rot, rot_tol=rot_tol, max_step=max_step, masses=masses, verify=verify,
+                                    periodic=self._pbc_flags() is not None)
 
     # ---- graph-parallel single-image mode (reference workers > 1; see parallel.GraphParallelEvaluator) -----------------
     def gp_begin(self, d_pos: int, node_lo: int, node_hi: int, d_energy: int, d_forces: int, stream: int = 0, d_virial: int = 0):

@@ -22,8 +22,8 @@ Two backends behind one small interface (``put / get / take / cat / gram / combi
 Those three functions are the SPECIFICATION of the three kernels (csrc/umx_modes.h): the same products and sums in the same order, so
 the whole solver gives the same bits through either backend on the same engine.
 
-Not provided: a preconditioner; a transition-state optimiser or dimer; thermochemistry; products through the graph-parallel entries;
-use inside the GSM run loop (``optimize_path_gsm(hei_modes=k)`` is one call after the run)."""
+Not provided: a preconditioner; thermochemistry; products through the graph-parallel entries; use inside the GSM run loop
+(``optimize_path_gsm(hei_modes=k)`` is one call after the run).  The transition-state optimiser on the same products is dimer.py."""
 from __future__ import annotations
 
 import inspect

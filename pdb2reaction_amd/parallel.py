@@ -862,6 +862,55 @@ class LocalEnginePool:
                                   scheme=scheme, block=block, max_subspace=max_subspace, tol=tol, max_iter=max_iter, v0=v0, seed=seed,
                                   periodic=self._cells is not None or pbc() is not None)
 
+    def hvp_candidates(self, bases, dirs, base_of=None, step: float = 1e-3, scheme: str = "forward", return_base: bool = False, base_forces=None):
+        """``Engine.hvp`` for K candidates with ONE direction each (``base_of = arange(K)``, what a batched dimer asks for), dealt over
+        the engines in the contiguous blocks ``shard_bounds(K, G, r)`` as ``hvp`` deals directions -- but every engine gets only the
+        bases of ITS candidates, so the bases' own evaluations (``return_base``: ``(hv, e0, f0)``) are dealt too, and ``base_forces`` are
+        handed back block by block.  A single candidate is block (0, 1) of engine 0 (``last_route == "single"``), as ``hvp`` runs a single
+        direction.  Every image is its evaluation alone on the pinned graph of its base: the single engine's bits.  This is what
+        ``refine_saddles`` deals through; it is not meant as an entry of its own."""
+        b, d = self._images(bases, True), self._images(dirs, True)
+        k, g = d.shape[0], len(self.engines)
+        if b.shape[0] != k or (base_of is not None and not np.array_equal(np.asarray(base_of).reshape(-1), np.arange(k))):
+            raise ValueError(f"hvp_candidates: one direction per base in order is needed, got {b.shape[0]} bases, {k} directions, base_of {base_of!r}")
+        f_in = None if base_forces is None else np.ascontiguousarray(base_forces, dtype=np.float32).reshape(b.shape)
+        if self._cells is not None:
+            if len(self._cells[0]) != 1:
+                raise ValueError(f"hvp_candidates: set_cells bound cells for {len(self._cells[0])} images; the candidates share one cell (set_cell)")
+            self._bind_cells(1, None)
+        blocks = [shard_bounds(k, g, r) for r in range(g)]
+        busy = [r for r in range(g) if blocks[r][1] > blocks[r][0]]
+        self.last_route, self.last_blocks = ("batch" if k > 1 else "single"), blocks
+
+        def call(r):
+            lo, hi = blocks[r]
+            out = self.engines[r].hvp(b[lo:hi], d[lo:hi], np.arange(hi - lo, dtype=np.int32), step=step, scheme=scheme, return_base=return_base,
+                                      base_forces=None if f_in is None else f_in[lo:hi])
+            return out if return_base else (out,)
+
+        for attempt in range(2):
+            was_wide = [bool(getattr(eng, "widened", False)) for eng in self.engines]
+            res = self._run_all(call, busy)
+            now_wide = [bool(getattr(eng, "widened", False)) for eng in self.engines]
+            if attempt == 0 and now_wide != was_wide:          # (as _deal: one result never mixes two arithmetics)
+                self._widen_all("fp16 range violation on another engine of the local pool")
+                continue                                       # (forces handed in are then stale: the dimer repeats its cycle after a widening)
+            break
+        hv = np.concatenate([r[0] for r in res])
+        return (hv, np.concatenate([r[1] for r in res]), np.concatenate([r[2] for r in res])) if return_base else hv
+
+    def refine_saddles(self, x0, modes0=None, *, frozen=(), project: str = "auto", thresh="gau", step: float = 1e-3, max_cycles: int = 200,
+                       max_rot: int = 2, rot_tol: float = 0.1, max_step: float = 0.1, masses=None, verify: bool = False):
+        """``Engine.refine_saddles`` over the pool: the host backend of ``dimer.refine_saddles`` on ``hvp_candidates`` -- the candidates
+        of every product round are dealt over the engines, the row algebra runs in NumPy in the kernels' operation order.  Products
+        being the single engine's bit for bit, so is the result (that of the host backend over ``Engine.hvp``)."""
+        from . import dimer
+
+        pbc = getattr(self.engines[0], "_pbc_flags", lambda: None)
+        return dimer.refine_saddles(dimer.HostBackend(self.hvp_candidates, pinner=self, lowest_modes=self.lowest_modes), x0, modes0, frozen=frozen,
+                                    project=project, thresh=thresh, step=step, max_cycles=max_cycles, max_rot=max_rot, rot_tol=rot_tol,
+                                    max_step=max_step, masses=masses, verify=verify, periodic=self._cells is not None or pbc() is not None)
+
     def energy_forces_virial(self, pos_ang, graph_parallel: bool = False, double_positions: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """``Engine.energy_forces_virial`` over the pool: (E [K], F [K,N,3], W [K,3,3] float64).  A batch is dealt over the engines in
         the same contiguous blocks as ``energy_forces`` and is the single-engine result bit for bit (W does not depend on the batch an

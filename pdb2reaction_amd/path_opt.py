@@ -32,7 +32,7 @@ def optimize_path_gsm(elem: Sequence[str], reactant_ang: np.ndarray, product_ang
                       sopt_kind: str = "lbfgs", sopt_cfg: Optional[Dict[str, Any]] = None, align: bool = True, align_kw: Optional[Dict[str, Any]] = None,
                       gs_kw: Optional[Dict[str, Any]] = None, stopt_kw: Optional[Dict[str, Any]] = None, out_dir: Optional[str] = None,
                       group=None, log=None, cell=None, pbc=None, bond_changes: bool = False, bond_engine=None, hei_modes: int = 0, masses_amu=None,
-                      hei_modes_kw: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+                      hei_modes_kw: Optional[Dict[str, Any]] = None, hei_tsopt: bool = False, hei_tsopt_kw: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
     """Minimum-energy path between two endpoint geometries (Angstrom) by the growing-string method on the HIP engine.
 
     calc: a ``uma_pysis`` instance shared by every step (created from ``calc_kw`` + ``freeze_atoms`` when None, as ``path_opt.py:823``).
@@ -54,7 +54,14 @@ def optimize_path_gsm(elem: Sequence[str], reactant_ang: np.ndarray, product_ang
     spent, "n_imaginary"}`` of the k lowest vibrational modes of the FINAL highest-energy image -- one ``calc.get_lowest_modes`` call
     after the run (block Davidson on Hessian-vector products, no Hessian), with the run's frozen atoms and in the run's cell;
     ``masses_amu`` (N,) as that method takes them, ``hei_modes_kw`` its further keywords.  A first-order saddle has exactly one negative
-    entry.  0 (default): exactly the keys above; the run loop itself never asks for modes."""
+    entry.  0 (default): exactly the keys above; the run loop itself never asks for modes.
+
+    hei_tsopt=True: after the run the final highest-energy image -- which is no stationary point -- is refined to a first-order saddle by
+    one ``calc.get_ts`` call (a dimer on Hessian-vector products, ``dimer.refine_saddles``) with the string tangent there as the start
+    direction (one-sided when the HEI is an end image; ``mode=None``, the lowest mode, when the string has no tangent), the run's frozen
+    atoms and the run's cell; ``hei_tsopt_kw`` its further keywords.  The result gains ``"ts"``:
+    ``{"coords_ang" (N,3), "energy" Hartree, "curvature" Hartree/Bohr^2, "converged", "cycles", "images"}``, and with ``hei_modes=k`` the
+    frequencies are those of the refined geometry.  False (default): exactly the keys above."""
     log = log or (lambda s: None)
     elem = [str(e).capitalize() for e in elem]
     n = len(elem)
@@ -126,8 +133,18 @@ def optimize_path_gsm(elem: Sequence[str], reactant_ang: np.ndarray, product_ang
     if bond_changes:
         out["bond_changes"] = path_bond_changes(elem, np.asarray(res.coords, dtype=np.float64).reshape(len(res.coords), n, 3), engine=bond_engine,
                                                 **({"cell": np.asarray(cell, dtype=np.float64).reshape(3, 3) * ANG2BOHR, "pbc": pbc} if periodic else {}))
+    at_bohr = np.asarray(res.coords[hei], dtype=np.float64).reshape(-1)      # where the modes are asked for: the HEI, or the saddle refined from it
+    if hei_tsopt:
+        pts = np.asarray(res.coords, dtype=np.float64).reshape(len(res.coords), -1)
+        tangent = pts[min(hei + 1, len(pts) - 1)] - pts[max(hei - 1, 0)]      # central difference of the neighbours (one-sided at an end)
+        if not tangent.any():                                                # a string of one point has no tangent: the lowest mode instead
+            tangent = None
+        ts = calc.get_ts(elem, at_bohr, tangent, **(hei_tsopt_kw or {}))
+        at_bohr = np.asarray(ts["coords"], dtype=np.float64).reshape(-1)
+        out["ts"] = {"coords_ang": at_bohr.reshape(n, 3) * BOHR2ANG, "energy": float(ts["energy"]), "curvature": float(ts["curvature"]),
+                     "converged": bool(ts["converged"]), "cycles": int(ts["cycles"]), "images": int(ts["images"])}
     if int(hei_modes) > 0:
-        m = calc.get_lowest_modes(elem, np.asarray(res.coords[hei], dtype=np.float64).reshape(-1), int(hei_modes), masses_amu, **(hei_modes_kw or {}))
+        m = calc.get_lowest_modes(elem, at_bohr, int(hei_modes), masses_amu, **(hei_modes_kw or {}))
         out["hei_modes"] = {"freqs_cm": np.asarray(m["freqs_cm"]), "converged": np.asarray(m["converged"]), "images": int(m["images"]),
                             "n_imaginary": int((np.asarray(m["freqs_cm"]) < 0.0).sum())}
     return out

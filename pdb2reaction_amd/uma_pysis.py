@@ -74,6 +74,8 @@ HVP_NOT_GP = ("get_hvp cannot be combined with the graph-parallel mode (workers 
               "products need the pinned graph, and the graph-parallel entries (umx_gp_begin) build their own")
 MODES_NOT_GP = ("get_lowest_modes cannot be combined with the graph-parallel mode (workers == world size / enable_graph_parallel): its "
                 "Hessian-vector products need the pinned graph, and the graph-parallel entries (umx_gp_begin) build their own")
+TS_NOT_GP = ("get_ts cannot be combined with the graph-parallel mode (workers == world size / enable_graph_parallel): its "
+             "Hessian-vector products need the pinned graph, and the graph-parallel entries (umx_gp_begin) build their own")
 
 # number of displaced geometries evaluated per engine call while building an FD Hessian
 FD_BATCH = int(os.environ.get("UMX_FD_BATCH", "64"))
@@ -376,6 +378,15 @@ class UMAcore:
         return (getattr(self, "_pool", None) or self.engine).lowest_modes(np.asarray(coord_ang, dtype=np.float64).reshape(len(self.z), 3),
                                                                           masses_amu, int(k), **kw)
 
+    def refine_saddles(self, coord_ang: np.ndarray, modes0=None, **kw):
+        """Refine transition-state guesses ``coord_ang`` (N,3) or (K,N,3) A to first-order saddles without a Hessian
+        (``dimer.refine_saddles``: keywords and the ``SaddleResult`` list returned, in eV and A): on the engine with every vector on the
+        device, or over the in-process pool.  The graph-parallel mode has no such entry: ``ValueError``."""
+        if getattr(self, "_gp", None) is not None:
+            raise ValueError(TS_NOT_GP)
+        return (getattr(self, "_pool", None) or self.engine).refine_saddles(np.asarray(coord_ang, dtype=np.float64).reshape(-1, len(self.z), 3),
+                                                                            modes0, **kw)
+
     def compute(self, coord_ang: np.ndarray, *, forces: bool = False, hessian: bool = False) -> Dict[str, Any]:
         """Energy (eV) and optionally forces (eV/A) of one geometry; same contract as reference ``:330-419``."""
         if hessian:
@@ -663,6 +674,38 @@ class uma_pysis(Calculator):
         return {"freqs_cm": np.array(res.freqs_cm), "eigenvalues": np.asarray(res.eigenvalues) * H.EV_PER_ANG2_TO_AU,
                 "modes": np.asarray(res.modes, dtype=np.float64).reshape(len(res.eigenvalues), -1), "converged": np.array(res.converged),
                 "residuals": np.asarray(res.residuals) * H.EV_PER_ANG2_TO_AU, "images": int(res.images)}
+
+    def get_ts(self, elem, coords_bohr, mode=None, **kw):
+        """Refine a transition-state guess to a first-order saddle without a Hessian (a dimer on Hessian-vector products,
+        ``dimer.refine_saddles``): ``coords_bohr`` (3N,) or (N,3) Bohr, ``mode`` (3N,) or (N,3) the start direction (None: the lowest
+        mode of ``lowest_modes`` with unit masses) -> ``{"coords": (3N,) Bohr, "energy": Hartree, "forces": (3N,) Hartree/Bohr (frozen
+        rows zeroed), "mode": (3N,) unit vector, "curvature": Hartree/Bohr^2, "converged", "cycles", "images"}``.
+
+        Keywords: ``thresh`` a name of ``gsm.THRESH`` or ``(max_force, rms_force)`` in Hartree/Bohr; ``step_bohr`` and ``max_step_bohr``
+        (None: 1e-3 A and 0.1 A); ``max_cycles``, ``max_rot``, ``rot_tol``, ``project`` as ``dimer.refine_saddles`` takes them.
+        ``freeze_atoms`` are held fixed and the cell of ``uma_pysis(cell=...)`` applies.  A graph-parallel core raises ``ValueError``, as
+        ``get_hvp`` does."""
+        core = self._ensure_core(elem)
+        if getattr(core, "_gp", None) is not None:
+            raise ValueError(TS_NOT_GP)
+        x = _bohr_to_ang(coords_bohr)
+        n = x.shape[0]
+        kw = dict(kw)
+        thresh = kw.pop("thresh", "gau")
+        if not isinstance(thresh, str):
+            thresh = tuple(float(t) / F_EVAA_2_AU for t in thresh)
+        step_bohr, max_step_bohr = kw.pop("step_bohr", None), kw.pop("max_step_bohr", None)
+        if step_bohr is not None:
+            kw["step"] = float(step_bohr) * BOHR2ANG
+        if max_step_bohr is not None:
+            kw["max_step"] = float(max_step_bohr) * BOHR2ANG
+        m0 = None if mode is None else np.asarray(mode, dtype=np.float64).reshape(1, n, 3)
+        res = core.refine_saddles(x, m0, frozen=tuple(self.freeze_atoms or ()), thresh=thresh, **kw)[0]
+        f_ev = H.mask_frozen(np.asarray(res.forces, dtype=np.float64), self.freeze_atoms)
+        return {"coords": (np.asarray(res.x, dtype=np.float64) * ANG2BOHR).reshape(-1), "energy": float(res.energy) * EV2AU,
+                "forces": (f_ev * F_EVAA_2_AU).reshape(-1), "mode": np.asarray(res.mode, dtype=np.float64).reshape(-1),
+                "curvature": float(res.curvature) * H_EVAA_2_AU, "converged": bool(res.converged), "cycles": int(res.cycles),
+                "images": int(res.images)}
 
     def get_hessian(self, elem, coords):
         """Hessian per ``hessian_calc_mode`` with the reference's dispatch (``:708-780``): "Analytical" only when the core
