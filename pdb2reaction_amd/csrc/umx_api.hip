@@ -18,8 +18,7 @@
 #include "umx_weights.h"     // the weight loader
 #include "umx_experts.h"     // expert-form weights: the Mixture-of-Linear-Experts merge and its plane copies on the device
 #include "umx_bonds.h"       // bond-change events of many pairs of geometries: count, scan and fill kernels and their launcher
-#include "umx_modes.h"       // float64 block kernels of a matrix-free eigensolver on umx_hvp: gram, combine, scale
-#include "umx_rows.h"        // float64 row kernels of a batched dimer on umx_hvp: dot, axpby, absmax of K independent vectors
+#include "umx_rowblocks.h"   // float64 row-block kernels of the Hessian-free solvers on umx_hvp: gram, combine, scale; dot, axpby, absmax
 
 // ================================================================================================
 //                                           C ABI
@@ -988,15 +987,12 @@ int umx_bond_events(umx_engine* eng, int n_atoms, int n_geoms, const double* r, 
                          n_events, per_pair);
 }
 
-// ---- float64 block kernels (kernels and the shared refusals in umx_modes.h): every refusal comes before the launch -----------------------
+// ---- float64 block and row kernels (kernels, the shared refusals and the launch in umx_rowblocks.h): every refusal comes before the launch
 int umx_blk_gram_dev(umx_engine* eng, int p, const double* d_x, int q, const double* d_y, int64_t n, double* d_g, void* hip_stream) {
   if (!eng) return UMX_ERR_ARG;
   CHK(blk_check(eng, "umx_blk_gram_dev", p, q, (long)n));
   if (!d_x || !d_y || !d_g) return fail(eng, UMX_ERR_ARG, "umx_blk_gram_dev: d_x, d_y and d_g must be given");
-  HIPCHK(eng, hipSetDevice(eng->dev));
-  hipLaunchKernelGGL(umx::k_blk_gram, dim3((unsigned)(p * q)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), d_x, d_y, (long)q, (long)n, d_g);
-  HIPCHK(eng, hipGetLastError());
-  return UMX_OK;
+  return blk_launch(eng, umx::k_blk_gram, (unsigned)(p * q), hip_stream, d_x, d_y, q, n, d_g);
 }
 
 int umx_blk_combine_dev(umx_engine* eng, int p, const double* d_x, int q, const double* d_c, int64_t n, const double* d_z, int subtract, double* d_y,
@@ -1004,68 +1000,52 @@ int umx_blk_combine_dev(umx_engine* eng, int p, const double* d_x, int q, const 
   if (!eng) return UMX_ERR_ARG;
   CHK(blk_check(eng, "umx_blk_combine_dev", p, q, (long)n));
   if (!d_x || !d_c || !d_y) return fail(eng, UMX_ERR_ARG, "umx_blk_combine_dev: d_x, d_c and d_y must be given (d_z may be NULL)");
-  if (blk_overlap(d_x, (size_t)p * (size_t)n, d_y, (size_t)q * (size_t)n))
+  if (blk_overlapped(d_y, (size_t)q * (size_t)n, {{"d_x", d_x, (size_t)p * (size_t)n}}))
     return fail(eng, UMX_ERR_ARG, "umx_blk_combine_dev: d_y overlaps d_x -- every output element reads a whole column of X (d_y may be d_z)");
-  HIPCHK(eng, hipSetDevice(eng->dev));
-  hipLaunchKernelGGL(umx::k_blk_combine, dim3(nblk((long)q * (long)n, 256)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), d_x, d_c, d_z, (long)p, (long)q,
-                     (long)n, subtract ? 1 : 0, d_y);
-  HIPCHK(eng, hipGetLastError());
-  return UMX_OK;
+  return blk_launch(eng, umx::k_blk_combine, nblk((long)q * (long)n, 256), hip_stream, d_x, d_c, d_z, p, q, n, subtract ? 1 : 0, d_y);
 }
 
 int umx_blk_scale_dev(umx_engine* eng, int p, const double* d_x, const double* d_w, int64_t n, double* d_y, void* hip_stream) {
   if (!eng) return UMX_ERR_ARG;
   CHK(blk_check(eng, "umx_blk_scale_dev", p, 1, (long)n));
   if (!d_x || !d_w || !d_y) return fail(eng, UMX_ERR_ARG, "umx_blk_scale_dev: d_x, d_w and d_y must be given");
-  HIPCHK(eng, hipSetDevice(eng->dev));
-  hipLaunchKernelGGL(umx::k_blk_scale, dim3(nblk((long)p * (long)n, 256)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), d_x, d_w, (long)p, (long)n, d_y);
-  HIPCHK(eng, hipGetLastError());
-  return UMX_OK;
+  return blk_launch(eng, umx::k_blk_scale, nblk((long)p * (long)n, 256), hip_stream, d_x, d_w, p, n, d_y);
 }
 
-// ---- float64 row kernels (kernels and the shared refusal in umx_rows.h): every refusal comes before the launch ----------------------------
 int umx_row_dot_dev(umx_engine* eng, int k, const double* d_x, const double* d_y, int64_t n, double* d_out, void* hip_stream) {
   if (!eng) return UMX_ERR_ARG;
-  CHK(row_check(eng, "umx_row_dot_dev", k, (long)n));
-  if (!d_x || !d_y || !d_out) return fail(eng, UMX_ERR_ARG, std::string("umx_row_dot_dev: ") + (!d_x ? "d_x" : !d_y ? "d_y" : "d_out") + " must be given");
+  const char* who = "umx_row_dot_dev: ";
+  CHK(blk_check(eng, "umx_row_dot_dev", k, 1, (long)n, true));
+  if (!d_x || !d_y || !d_out) return fail(eng, UMX_ERR_ARG, std::string(who) + (!d_x ? "d_x" : !d_y ? "d_y" : "d_out") + " must be given");
   const size_t kn = (size_t)k * (size_t)n;
-  if (blk_overlap(d_out, (size_t)k, d_x, kn) || blk_overlap(d_out, (size_t)k, d_y, kn))
-    return fail(eng, UMX_ERR_ARG, std::string("umx_row_dot_dev: d_out overlaps ") + (blk_overlap(d_out, (size_t)k, d_x, kn) ? "d_x" : "d_y") + " -- a sum is written while rows are still read");
-  HIPCHK(eng, hipSetDevice(eng->dev));
-  hipLaunchKernelGGL(umx::k_row_dot, dim3((unsigned)k), dim3(256), 0, static_cast<hipStream_t>(hip_stream), d_x, d_y, (long)n, d_out);
-  HIPCHK(eng, hipGetLastError());
-  return UMX_OK;
+  if (const char* hit = blk_overlapped(d_out, (size_t)k, {{"d_x", d_x, kn}, {"d_y", d_y, kn}}))
+    return fail(eng, UMX_ERR_ARG, std::string(who) + "d_out overlaps " + hit + " -- a sum is written while rows are still read");
+  return blk_launch(eng, umx::k_row_dot, (unsigned)k, hip_stream, d_x, d_y, n, d_out);
 }
 
 int umx_row_axpby_dev(umx_engine* eng, int k, const double* d_a, const double* d_x, const double* d_b, const double* d_y, int64_t n, double* d_out,
                       void* hip_stream) {
   if (!eng) return UMX_ERR_ARG;
-  CHK(row_check(eng, "umx_row_axpby_dev", k, (long)n));
-  if (!d_a || !d_x || !d_out) return fail(eng, UMX_ERR_ARG, std::string("umx_row_axpby_dev: ") + (!d_a ? "d_a" : !d_x ? "d_x" : "d_out") + " must be given");
-  if (!d_b != !d_y)
-    return fail(eng, UMX_ERR_ARG, std::string("umx_row_axpby_dev: ") + (!d_b ? "d_b" : "d_y") + " is NULL and " + (!d_b ? "d_y" : "d_b") + " is not -- give both, or neither for out = a * x");
+  const char* who = "umx_row_axpby_dev: ";
+  CHK(blk_check(eng, "umx_row_axpby_dev", k, 1, (long)n, true));
+  if (!d_a || !d_x || !d_out) return fail(eng, UMX_ERR_ARG, std::string(who) + (!d_a ? "d_a" : !d_x ? "d_x" : "d_out") + " must be given");
+  if (!d_b != !d_y) return fail(eng, UMX_ERR_ARG, std::string(who) + (!d_b ? "d_b" : "d_y") + " is NULL and " + (!d_b ? "d_y" : "d_b") + " is not -- give both, or neither for out = a * x");
   const size_t kn = (size_t)k * (size_t)n;
-  // d_out may BE d_x or d_y (every thread reads its own element before it writes it); a shifted overlap would race
-  if ((d_out != d_x && blk_overlap(d_out, kn, d_x, kn)) || (d_y && d_out != d_y && blk_overlap(d_out, kn, d_y, kn)))
-    return fail(eng, UMX_ERR_ARG, std::string("umx_row_axpby_dev: d_out overlaps ") + ((d_out != d_x && blk_overlap(d_out, kn, d_x, kn)) ? "d_x" : "d_y") + " without being it");
-  if (blk_overlap(d_out, kn, d_a, (size_t)k) || (d_b && blk_overlap(d_out, kn, d_b, (size_t)k)))
-    return fail(eng, UMX_ERR_ARG, std::string("umx_row_axpby_dev: d_out overlaps ") + (blk_overlap(d_out, kn, d_a, (size_t)k) ? "d_a" : "d_b") + ", which every thread of a row reads");
-  HIPCHK(eng, hipSetDevice(eng->dev));
-  hipLaunchKernelGGL(umx::k_row_axpby, dim3(nblk((long)k * (long)n, 256)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), d_a, d_x, d_b, d_y, (long)k, (long)n, d_out);
-  HIPCHK(eng, hipGetLastError());
-  return UMX_OK;
+  if (const char* hit = blk_overlapped(d_out, kn, {{"d_x", d_x, kn}, {"d_y", d_y, kn}}, true))       // d_out may BE d_x or d_y
+    return fail(eng, UMX_ERR_ARG, std::string(who) + "d_out overlaps " + hit + " without being it");
+  if (const char* hit = blk_overlapped(d_out, kn, {{"d_a", d_a, (size_t)k}, {"d_b", d_b, (size_t)k}}))
+    return fail(eng, UMX_ERR_ARG, std::string(who) + "d_out overlaps " + hit + ", which every thread of a row reads");
+  return blk_launch(eng, umx::k_row_axpby, nblk((long)k * (long)n, 256), hip_stream, d_a, d_x, d_b, d_y, k, n, d_out);
 }
 
 int umx_row_absmax_dev(umx_engine* eng, int k, const double* d_x, int64_t n, double* d_out, void* hip_stream) {
   if (!eng) return UMX_ERR_ARG;
-  CHK(row_check(eng, "umx_row_absmax_dev", k, (long)n));
-  if (!d_x || !d_out) return fail(eng, UMX_ERR_ARG, std::string("umx_row_absmax_dev: ") + (!d_x ? "d_x" : "d_out") + " must be given");
-  if (blk_overlap(d_out, (size_t)k, d_x, (size_t)k * (size_t)n))
-    return fail(eng, UMX_ERR_ARG, "umx_row_absmax_dev: d_out overlaps d_x -- a maximum is written while rows are still read");
-  HIPCHK(eng, hipSetDevice(eng->dev));
-  hipLaunchKernelGGL(umx::k_row_absmax, dim3((unsigned)k), dim3(256), 0, static_cast<hipStream_t>(hip_stream), d_x, (long)n, d_out);
-  HIPCHK(eng, hipGetLastError());
-  return UMX_OK;
+  const char* who = "umx_row_absmax_dev: ";
+  CHK(blk_check(eng, "umx_row_absmax_dev", k, 1, (long)n, true));
+  if (!d_x || !d_out) return fail(eng, UMX_ERR_ARG, std::string(who) + (!d_x ? "d_x" : "d_out") + " must be given");
+  if (blk_overlapped(d_out, (size_t)k, {{"d_x", d_x, (size_t)k * (size_t)n}}))
+    return fail(eng, UMX_ERR_ARG, std::string(who) + "d_out overlaps d_x -- a maximum is written while rows are still read");
+  return blk_launch(eng, umx::k_row_absmax, (unsigned)k, hip_stream, d_x, n, d_out);
 }
 
 }  // extern "C"

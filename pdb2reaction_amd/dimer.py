@@ -31,21 +31,16 @@ cycle from the current geometry, ``how = modes.resolve_project(project, periodic
 
 A cycle costs 1 + (1 ... 1 + max_rot) images per candidate.  The step criteria of the threshold sets are not applied.
 
-Every dot, norm and maximum is ``row_dot`` / ``row_absmax``, every vector update ``row_axpby`` (``blk_scale`` for the mask, ``blk_gram`` +
-``blk_combine`` per candidate for the Q projection); the small scalars -- K numbers per operation -- are combined on the host.  A row's
+Every dot, norm and maximum is ``row_dot`` / ``row_absmax`` of rowblocks.py, every vector update ``row_axpby`` (``blk_scale`` for the mask,
+``blk_gram`` + ``blk_combine`` per candidate for the Q projection); the small scalars -- K numbers per operation -- are combined on the host.  A row's
 result never depends on the rows beside it and every image of ``umx_hvp`` is its evaluation alone, so a candidate of a batch is bit for bit
 its own K = 1 run.
 
-Two backends behind one small interface, the shape of ``modes.HostBackend`` / ``modes.DeviceBackend``:
-  :class:`DeviceBackend`  float64 torch tensors on the engine's GPU; ``hvp_dev`` of the evaluator (the engine by default; any object with
-                          a method of that shape) plus ``umx_row_{dot,axpby,absmax}_dev`` and ``umx_blk_*_dev`` of the engine on torch's
-                          current stream.  Read back per cycle: the K-vectors of scalars and, once, the K geometries and directions (for
-                          Q and the trajectory); the L-BFGS pairs stay on the device.
-  :class:`HostBackend`    any ``hvp(bases, dirs, base_of=, step=, scheme="forward", return_base=/base_forces=)`` callable (``Engine.hvp``,
-                          a pool's dealing wrapper, an analytic surface) and the NumPy functions :func:`row_dot`, :func:`row_axpby`,
-                          :func:`row_absmax` below with ``modes.blk_*``.
-Those functions are the SPECIFICATION of the kernels (csrc/umx_rows.h): the same products and sums in the same order, so the whole solver
-gives the same bits through either backend on the same engine.
+Backends: the two row classes of rowblocks.py -- which states the vector interface and its bit-for-bit contract -- plus this solver's
+products.  :class:`DeviceBackend`: ``hvp_dev`` of the evaluator (the engine by default; any object with a method of that shape) on torch's
+current stream; read back per cycle are the K-vectors of scalars and, once, the K geometries and directions (for Q and the trajectory);
+the L-BFGS pairs stay on the device.  :class:`HostBackend`: any ``hvp(bases, dirs, base_of=, step=, scheme="forward", return_base=/
+base_forces=)`` callable (``Engine.hvp``, a pool's dealing wrapper, an analytic surface).
 
 Graphs: nothing is pinned across cycles -- the geometry moves; each ``hvp`` call pins its own bases and unpins.  Under a caller's pin
 :func:`refine_saddles` raises ``ValueError``.  An fp16 range violation widens the engine as ``Engine.hvp`` does; the cycle is repeated and
@@ -64,94 +59,22 @@ from . import hessian as H
 from . import modes
 from .engine import UMX_ERR_RANGE, UmxError
 from .gsm import THRESH
+from .rowblocks import BLK_MAX, DeviceRows, HostRows, row_absmax, row_axpby, row_dot, takes  # noqa: F401  (the statements: re-exported)
 
-ROW_MAX = modes.BLK_MAX                        # candidates of one call (umx_rows.h takes at most BLK_MAX rows)
+ROW_MAX = BLK_MAX                              # candidates of one call (the row entries take at most BLK_MAX rows)
 KEEP_LAST = 7                                  # L-BFGS pairs kept per candidate (lbfgs.BatchedLBFGS's default)
 C_FLOOR = 1e-2                                 # eV/A^2: the rotation residual is not chased below rot_tol times this
 
 
-# ---- the three kernels' operation order, in NumPy ----------------------------------------------------------------------------------------
-def row_dot(x: np.ndarray, y: np.ndarray) -> np.ndarray:
-    """``out[r] = sum_c x[r][c] * y[r][c]`` as ``k_row_dot`` adds it -- ``modes.blk_gram``'s order, row by row: lane t of 256 adds the
-    products c = t, t + 256, ... ascending from 0.0, then the 256 partials are added in the tree s = 128, 64, ..., 1."""
-    x, y = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(y, dtype=np.float64)
-    k, n = x.shape
-    rows = (n + 255) // 256
-    prod = np.zeros((k, rows * 256))                   # a lane past the end adds nothing: x + 0.0 is x, and a partial is never -0.0
-    prod[:, :n] = x * y
-    prod = prod.reshape(k, rows, 256)
-    part = np.zeros((k, 256))
-    for r in range(rows):
-        part = part + prod[:, r, :]
-    s = 128
-    while s > 0:
-        part = part[:, :s] + part[:, s:2 * s]
-        s >>= 1
-    return part[:, 0].copy()
-
-
-def row_axpby(a: np.ndarray, x: np.ndarray, b: Optional[np.ndarray] = None, y: Optional[np.ndarray] = None) -> np.ndarray:
-    """``out[r][c] = fl(fl(a[r] * x[r][c]) + fl(b[r] * y[r][c]))``, or ``fl(a[r] * x[r][c])`` without ``(b, y)`` (``k_row_axpby``)."""
-    if (b is None) != (y is None):
-        raise ValueError("row_axpby: give both b and y, or neither")
-    ax = np.asarray(a, dtype=np.float64)[:, None] * np.asarray(x, dtype=np.float64)
-    return ax if y is None else ax + np.asarray(b, dtype=np.float64)[:, None] * np.asarray(y, dtype=np.float64)
-
-
-def row_absmax(x: np.ndarray) -> np.ndarray:
-    """``out[r] = max_c |x[r][c]|``, NaN when the row holds one (``k_row_absmax``)."""
-    return np.max(np.abs(np.asarray(x, dtype=np.float64)), axis=1)
-
-
-# ---- backends ----------------------------------------------------------------------------------------------------------------------------
-class HostBackend:
-    """Rows are NumPy arrays (k, n).  ``hvp(bases (k,N,3), dirs (k,N,3), base_of=, step=, scheme="forward", return_base=True) ->
-    (hv, e0, f0)``; with a ``base_forces`` parameter the rotation products hand ``f0`` back in and cost one image each.
+# ---- backends: the rows of rowblocks.py plus the products ---------------------------------------------------------------------------------
+class HostBackend(HostRows):
+    """``hvp(bases (k,N,3), dirs (k,N,3), base_of=, step=, scheme="forward", return_base=True) -> (hv, e0, f0)``; with a ``base_forces``
+    parameter the rotation products hand ``f0`` back in and cost one image each.
     ``pinner``: the object whose ``pinned_graph()`` / ``widened`` the solver consults (an ``Engine``, a ``LocalEnginePool``), or None."""
 
     def __init__(self, hvp: Callable, pinner=None, lowest_modes: Optional[Callable] = None):
         self._hvp, self.pinner, self._modes = hvp, pinner, lowest_modes
-        self._reuse = modes._takes(hvp, "base_forces")
-
-    def put(self, a):
-        return np.array(a, dtype=np.float64, ndmin=2)
-
-    def get(self, b):
-        return np.array(b)
-
-    def take(self, b, idx):
-        return np.ascontiguousarray(b[list(idx)])
-
-    def scatter(self, b, idx, sub):
-        out = np.array(b)
-        out[list(idx)] = sub
-        return out
-
-    def cat(self, blocks):
-        return np.concatenate(blocks, axis=0)
-
-    def vector(self, w):
-        return np.array(w, dtype=np.float64)
-
-    def dot(self, x, y) -> np.ndarray:
-        return row_dot(x, y)
-
-    def axpby(self, a, x, b=None, y=None):
-        return row_axpby(a, x, b, y)
-
-    def absmax(self, x) -> np.ndarray:
-        return row_absmax(x)
-
-    def mask(self, x, w):
-        return modes.blk_scale(x, w)
-
-    def project(self, qs, u):
-        """Row i of ``u`` minus its components along the rows of ``qs[i]`` (None: untouched): ``blk_gram`` + ``blk_combine`` per row."""
-        out = np.array(u)
-        for i, q in enumerate(qs):
-            if q is not None:
-                out[i:i + 1] = modes.blk_combine(q, modes.blk_gram(q, u[i:i + 1]), u[i:i + 1], True)
-        return out
+        self._reuse = takes(hvp, "base_forces")
 
     def _wide(self) -> bool:
         engines = getattr(self.pinner, "engines", None) or [self.pinner]     # a pool: any of its engines
@@ -192,89 +115,22 @@ class HostBackend:
         return modes.lowest_modes(modes.HostBackend(self._hvp, pinner=self.pinner), x, masses, k, **kw)
 
 
-class DeviceBackend:
-    """Rows are float64 torch tensors (k, n) on the engine's GPU; every operation is one engine entry on torch's current stream (stream
-    order is the only synchronisation); the scalar results are read back as K-vectors.  ``evaluator``: the object whose ``hvp_dev``
-    gives the products (default: the engine); the row and block entries always come from the engine."""
+class DeviceBackend(DeviceRows):
+    """``evaluator``: the object whose ``hvp_dev`` gives the products (default: the engine); the row and block entries always come from
+    the engine."""
 
     def __init__(self, engine, evaluator=None):
-        import torch
-
-        self.torch, self.engine = torch, engine
+        super().__init__(engine)
         self.evaluator = engine if evaluator is None else evaluator
         self.pinner = self.evaluator if hasattr(self.evaluator, "pinned_graph") else None
-        self.dev = torch.device("cuda", int(engine.device))
-
-    def _stream(self) -> int:
-        return self.torch.cuda.current_stream(self.dev).cuda_stream
-
-    def put(self, a):
-        return self.torch.as_tensor(np.array(a, dtype=np.float64, ndmin=2), device=self.dev).contiguous()
-
-    def get(self, b):
-        return b.cpu().numpy()
-
-    def take(self, b, idx):
-        return b[list(idx)].contiguous()
-
-    def scatter(self, b, idx, sub):
-        out = b.clone()
-        out[list(idx)] = sub
-        return out
-
-    def cat(self, blocks):
-        return self.torch.cat(blocks, dim=0).contiguous()
-
-    def vector(self, w):
-        return self.torch.as_tensor(np.array(w, dtype=np.float64), device=self.dev).contiguous()
-
-    def dot(self, x, y) -> np.ndarray:
-        out = self.torch.empty(x.shape[0], dtype=self.torch.float64, device=self.dev)
-        self.engine.row_dot_dev(x.shape[0], x.data_ptr(), y.data_ptr(), x.shape[1], out.data_ptr(), stream=self._stream())
-        return out.cpu().numpy()
-
-    def axpby(self, a, x, b=None, y=None):
-        if (b is None) != (y is None):
-            raise ValueError("row_axpby: give both b and y, or neither")
-        ad = self.vector(a)
-        bd = None if b is None else self.vector(b)
-        out = self.torch.empty_like(x)
-        self.engine.row_axpby_dev(x.shape[0], ad.data_ptr(), x.data_ptr(), 0 if bd is None else bd.data_ptr(), 0 if y is None else y.data_ptr(),
-                                  x.shape[1], out.data_ptr(), stream=self._stream())
-        return out
-
-    def absmax(self, x) -> np.ndarray:
-        out = self.torch.empty(x.shape[0], dtype=self.torch.float64, device=self.dev)
-        self.engine.row_absmax_dev(x.shape[0], x.data_ptr(), x.shape[1], out.data_ptr(), stream=self._stream())
-        return out.cpu().numpy()
-
-    def mask(self, x, w):
-        y = self.torch.empty_like(x)
-        self.engine.blk_scale_dev(x.shape[0], x.data_ptr(), w.data_ptr(), x.shape[1], y.data_ptr(), stream=self._stream())
-        return y
-
-    def project(self, qs, u):
-        n = int(u.shape[1])
-        out = u.clone()
-        s = self._stream()
-        for i, q in enumerate(qs):
-            if q is not None:
-                r = int(q.shape[0])
-                g = self.torch.empty(r, 1, dtype=self.torch.float64, device=self.dev)      # stays on the device: gram's output is combine's C
-                row_in, row_out = u.data_ptr() + 8 * n * i, out.data_ptr() + 8 * n * i
-                self.engine.blk_gram_dev(r, q.data_ptr(), 1, row_in, n, g.data_ptr(), stream=s)
-                self.engine.blk_combine_dev(r, q.data_ptr(), 1, g.data_ptr(), n, row_in, True, row_out, stream=s)
-        return out
 
     def hvp(self, x, d, step, f0=None):
-        t = self.torch
         k, n = d.shape
-        hv = t.empty(k, n, dtype=t.float64, device=self.dev)
+        hv = self.empty(k, n)
         given = f0 is not None
         e0 = None
         if not given:
-            f0 = t.empty(k, n // 3, 3, dtype=t.float32, device=self.dev)
-            e0 = t.empty(k, dtype=t.float64, device=self.dev)
+            f0, e0 = self.empty(k, n // 3, 3, dtype=self.torch.float32), self.empty(k)
         self.evaluator.hvp_dev(k, x.data_ptr(), k, d.data_ptr(), hv.data_ptr(), base_of=np.arange(k, dtype=np.int32), step=step, scheme="forward",
                                d_e0=0 if given else e0.data_ptr(), d_f0=f0.data_ptr(), stream=self._stream(), given_f0=given)
         check = getattr(self.evaluator, "take_range_error", None)
@@ -285,7 +141,7 @@ class DeviceBackend:
             return None, None, None, None, False, True
         if given:
             return hv, None, None, f0, False, False
-        return hv, e0.cpu().numpy(), f0.to(t.float64).reshape(k, n), f0, False, False
+        return hv, e0.cpu().numpy(), f0.to(self.torch.float64).reshape(k, n), f0, False, False
 
     def cost(self, given: bool) -> int:
         return 1 if given else 2
@@ -458,7 +314,7 @@ class _Batch:
 
     def proj(self, u, qs):
         if self.w_dev is not None:
-            u = self.be.mask(u, self.w_dev)
+            u = self.be.scale(u, self.w_dev)
         if any(q is not None for q in qs):
             u = self.be.project(qs, u)
         return u

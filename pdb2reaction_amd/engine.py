@@ -226,6 +226,8 @@ def peer_sum(ptrs: Sequence[int], count: int, devices: Sequence[int], streams: S
 class Engine:
     """One UMA-S engine on one GPU (one per process/rank, or several per process in a ``parallel.LocalEnginePool``)."""
 
+    _ptr = staticmethod(lambda x: C.c_void_p(x) if x else None)     # a device pointer or stream handed over as an integer; 0 is NULL
+
     def __init__(self, device: int = 0, precision: Optional[str] = None, recompute: Optional[int] = None):
         """recompute: None = the UMX_RECOMPUTE environment variable (default 0), else 0 | 1 | 2 (``set_recompute``).
         precision: None = the UMX_PRECISION environment variable (default "auto" = "bf16x3": 3 x 3 bf16 planes / 6 products in both
@@ -695,7 +697,7 @@ class Engine:
         a = None if base_of is None else np.ascontiguousarray(base_of, dtype=np.int32).reshape(-1)
         if a is not None and len(a) != int(n_dirs):
             raise ValueError(f"hvp_dev: {n_dirs} directions, but base_of has {len(a)} entries")
-        p = lambda x: C.c_void_p(x) if x else None
+        p = self._ptr
         self._chk(self.lib.umx_hvp_dev(self._h, int(n_bases), C.c_void_p(d_base), int(n_dirs), C.c_void_p(d_dirs),
                                        a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None, float(step), self._hvp_flags(scheme, pin, given_f0),
                                        C.c_void_p(d_hv), p(d_curv), p(d_e0), p(d_f0), p(stream)), "umx_hvp_dev")
@@ -703,20 +705,18 @@ class Engine:
     # ---- float64 block kernels and the lowest modes ------------------------------------------------------
     def blk_gram_dev(self, p: int, d_x: int, q: int, d_y: int, n: int, d_g: int, stream: int = 0):
         """``umx_blk_gram_dev``: ``g[a][b] = sum_c x[a][c] y[b][c]`` of the float64 row blocks ``d_x`` [p][n] and ``d_y`` [q][n] into
-        ``d_g`` [p][q], all device pointers, enqueued on ``stream``; fixed summation order (``modes.blk_gram`` states it)."""
-        self._chk(self.lib.umx_blk_gram_dev(self._h, int(p), C.c_void_p(d_x), int(q), C.c_void_p(d_y), int(n), C.c_void_p(d_g),
-                                            C.c_void_p(stream) if stream else None), "umx_blk_gram_dev")
+        ``d_g`` [p][q], all device pointers, enqueued on ``stream``; fixed summation order (``rowblocks.blk_gram`` states it)."""
+        self._chk(self.lib.umx_blk_gram_dev(self._h, int(p), self._ptr(d_x), int(q), self._ptr(d_y), int(n), self._ptr(d_g), self._ptr(stream)), "umx_blk_gram_dev")
 
     def blk_combine_dev(self, p: int, d_x: int, q: int, d_c: int, n: int, d_z: int, subtract: bool, d_y: int, stream: int = 0):
         """``umx_blk_combine_dev``: ``y[j] = z[j] -+ sum_i C[i][j] x[i]`` -- ``d_x`` [p][n], ``d_c`` [p][q] on the device, ``d_z`` [q][n] or 0
-        (zeros), ``d_y`` [q][n]; ``d_y`` may be ``d_z``, not ``d_x`` (``modes.blk_combine``)."""
-        self._chk(self.lib.umx_blk_combine_dev(self._h, int(p), C.c_void_p(d_x), int(q), C.c_void_p(d_c), int(n), C.c_void_p(d_z) if d_z else None,
-                                               1 if subtract else 0, C.c_void_p(d_y), C.c_void_p(stream) if stream else None), "umx_blk_combine_dev")
+        (zeros), ``d_y`` [q][n]; ``d_y`` may be ``d_z``, not ``d_x`` (``rowblocks.blk_combine``)."""
+        self._chk(self.lib.umx_blk_combine_dev(self._h, int(p), self._ptr(d_x), int(q), self._ptr(d_c), int(n), self._ptr(d_z), 1 if subtract else 0,
+                                               self._ptr(d_y), self._ptr(stream)), "umx_blk_combine_dev")
 
     def blk_scale_dev(self, p: int, d_x: int, d_w: int, n: int, d_y: int, stream: int = 0):
-        """``umx_blk_scale_dev``: ``y[a][c] = w[c] x[a][c]`` -- ``d_x``, ``d_y`` [p][n], ``d_w`` [n]; in place allowed (``modes.blk_scale``)."""
-        self._chk(self.lib.umx_blk_scale_dev(self._h, int(p), C.c_void_p(d_x), C.c_void_p(d_w), int(n), C.c_void_p(d_y),
-                                             C.c_void_p(stream) if stream else None), "umx_blk_scale_dev")
+        """``umx_blk_scale_dev``: ``y[a][c] = w[c] x[a][c]`` -- ``d_x``, ``d_y`` [p][n], ``d_w`` [n]; in place allowed (``rowblocks.blk_scale``)."""
+        self._chk(self.lib.umx_blk_scale_dev(self._h, int(p), self._ptr(d_x), self._ptr(d_w), int(n), self._ptr(d_y), self._ptr(stream)), "umx_blk_scale_dev")
 
     def lowest_modes(self, base, masses, k: int = 1, *, frozen=(), project: str = "auto", step: float = 1e-3, scheme: str = "central",
                      block=None, max_subspace=None, tol=None, max_iter: int = 200, v0=None, seed: int = 0):
@@ -732,21 +732,19 @@ class Engine:
     # ---- float64 row kernels and the batched dimer ---------------------------------------------------------
     def row_dot_dev(self, k: int, d_x: int, d_y: int, n: int, d_out: int, stream: int = 0):
         """``umx_row_dot_dev``: ``out[r] = sum_c x[r][c] y[r][c]`` of the float64 rows ``d_x``, ``d_y`` [k][n] into ``d_out`` [k], all
-        device pointers, enqueued on ``stream``; ``blk_gram_dev``'s summation order, so ``out[r]`` is its ``g[r][r]`` (``dimer.row_dot``)."""
-        self._chk(self.lib.umx_row_dot_dev(self._h, int(k), C.c_void_p(d_x), C.c_void_p(d_y), int(n), C.c_void_p(d_out),
-                                           C.c_void_p(stream) if stream else None), "umx_row_dot_dev")
+        device pointers, enqueued on ``stream``; ``blk_gram_dev``'s summation order, so ``out[r]`` is its ``g[r][r]`` (``rowblocks.row_dot``)."""
+        self._chk(self.lib.umx_row_dot_dev(self._h, int(k), self._ptr(d_x), self._ptr(d_y), int(n), self._ptr(d_out), self._ptr(stream)), "umx_row_dot_dev")
 
     def row_axpby_dev(self, k: int, d_a: int, d_x: int, d_b: int, d_y: int, n: int, d_out: int, stream: int = 0):
         """``umx_row_axpby_dev``: ``out[r] = fl(fl(a[r] x[r]) + fl(b[r] y[r]))`` -- ``d_a``, ``d_b`` [k] on the device, ``d_x``, ``d_y``,
-        ``d_out`` [k][n]; ``d_b`` and ``d_y`` both 0: ``out = fl(a x)``; ``d_out`` may be ``d_x`` or ``d_y`` (``dimer.row_axpby``)."""
-        p = lambda x: C.c_void_p(x) if x else None
-        self._chk(self.lib.umx_row_axpby_dev(self._h, int(k), p(d_a), p(d_x), p(d_b), p(d_y), int(n), p(d_out), p(stream)), "umx_row_axpby_dev")
+        ``d_out`` [k][n]; ``d_b`` and ``d_y`` both 0: ``out = fl(a x)``; ``d_out`` may be ``d_x`` or ``d_y`` (``rowblocks.row_axpby``)."""
+        self._chk(self.lib.umx_row_axpby_dev(self._h, int(k), self._ptr(d_a), self._ptr(d_x), self._ptr(d_b), self._ptr(d_y), int(n), self._ptr(d_out),
+                                             self._ptr(stream)), "umx_row_axpby_dev")
 
     def row_absmax_dev(self, k: int, d_x: int, n: int, d_out: int, stream: int = 0):
         """``umx_row_absmax_dev``: ``out[r] = max_c |x[r][c]|`` (NaN when the row holds one) -- ``d_x`` [k][n], ``d_out`` [k]
-        (``dimer.row_absmax``)."""
-        self._chk(self.lib.umx_row_absmax_dev(self._h, int(k), C.c_void_p(d_x), int(n), C.c_void_p(d_out),
-                                              C.c_void_p(stream) if stream else None), "umx_row_absmax_dev")
+        (``rowblocks.row_absmax``)."""
+        self._chk(self.lib.umx_row_absmax_dev(self._h, int(k), self._ptr(d_x), int(n), self._ptr(d_out), self._ptr(stream)), "umx_row_absmax_dev")
 
     def refine_saddles(self, x0, modes0=None, *, frozen=(), project: str = "auto", thresh="gau", step: float = 1e-3, max_cycles: int = 200,
                        max_rot: int = 2, rot_tol: float = 0.1, max_step: float = 0.1, masses=None, verify: bool = False):

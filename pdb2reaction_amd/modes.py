@@ -14,24 +14,21 @@ by the projected residuals of the unconverged pairs, thick restart on the lowest
 ``hvp`` call (the new block's directions) and a handful of reads of matrices of at most 64 x 64 doubles; nothing of length n leaves the
 device before the result.
 
-Two backends behind one small interface (``put / get / take / cat / gram / combine / scale / hvp``):
-  :class:`DeviceBackend`  an ``Engine``; torch tensors on its GPU, ``hvp_dev`` and ``umx_blk_{gram,combine,scale}_dev`` on torch's
-                          current stream;
-  :class:`HostBackend`    any ``hvp(base, dirs, step=, scheme=)`` callable (``Engine.hvp``, ``LocalEnginePool.hvp``, a dense matrix)
-                          and the NumPy functions :func:`blk_gram`, :func:`blk_combine`, :func:`blk_scale` below.
-Those three functions are the SPECIFICATION of the three kernels (csrc/umx_modes.h): the same products and sums in the same order, so
-the whole solver gives the same bits through either backend on the same engine.
+Backends: :class:`DeviceBackend` (an ``Engine``: ``hvp_dev`` on torch's current stream) and :class:`HostBackend` (any ``hvp(base, dirs,
+step=, scheme=)`` callable: ``Engine.hvp``, ``LocalEnginePool.hvp``, a dense matrix) are the two row classes of rowblocks.py -- which
+states the vector interface and its bit-for-bit contract -- plus this solver's products.
 
 Not provided: a preconditioner; thermochemistry; products through the graph-parallel entries; use inside the GSM run loop
 (``optimize_path_gsm(hei_modes=k)`` is one call after the run).  The transition-state optimiser on the same products is dimer.py."""
 from __future__ import annotations
 
-import inspect
 import math
 from dataclasses import dataclass
 from typing import Callable, Optional, Sequence
 
 import numpy as np
+
+from .rowblocks import BLK_MAX, DeviceRows, HostRows, blk_combine, blk_gram, blk_scale, takes  # noqa: F401  (the statements: re-exported)
 
 # ---- sqrt(eV/A^2/amu) in cm^-1, from CODATA-2018 values written out ---------------------------------------------------------------------
 ELEMENTARY_CHARGE_C = 1.602176634e-19          # J per eV (exact)
@@ -41,7 +38,6 @@ ANGSTROM_M = 1.0e-10
 # omega = sqrt(lambda [eV/A^2/amu] * e / (A^2 * amu)) rad/s; wavenumber = omega / (2 pi c)
 FREQ_CM = math.sqrt(ELEMENTARY_CHARGE_C / (ANGSTROM_M * ANGSTROM_M * ATOMIC_MASS_KG)) / (2.0 * math.pi * SPEED_OF_LIGHT_CM_S)
 
-BLK_MAX = 64                                   # rows of a block (umx_modes.h): the subspace, and with it every small matrix, stays <= 64
 Q_RANK_TOL = 1e-8                              # singular values of Q below this fraction of the largest are dropped (linear molecule: rank 5)
 # The default convergence threshold on ||A x - theta x|| in eV/A^2/amu: four times the worst residual floor measured in
 # profiles/lowest_modes.txt (4.5e-4, the 50-atom cluster; 2.6e-4 .. 4.4e-4 on the 12-atom cases and at 2000 atoms).  The floor is the
@@ -49,90 +45,17 @@ Q_RANK_TOL = 1e-8                              # singular values of Q below this
 DEFAULT_TOL = 1.8e-3
 
 
-# ---- the three kernels' operation order, in NumPy ----------------------------------------------------------------------------------------
-def blk_gram(x: np.ndarray, y: np.ndarray) -> np.ndarray:
-    """``g[a][b] = sum_c x[a][c] * y[b][c]`` as ``k_blk_gram`` adds it: lane t of 256 adds the products c = t, t + 256, ... in ascending
-    order starting from 0.0, then the 256 partials are added in the tree s = 128, 64, ..., 1 (``part[t] += part[t + s]`` for t < s)."""
-    x, y = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(y, dtype=np.float64)
-    (p, n), q = x.shape, y.shape[0]
-    rows = (n + 255) // 256
-    g = np.empty((p, q))
-    for a in range(p):
-        prod = np.zeros((q, rows * 256))               # a lane past the end adds nothing: x + 0.0 is x, and a partial is never -0.0
-        prod[:, :n] = x[a][None, :] * y
-        prod = prod.reshape(q, rows, 256)
-        part = np.zeros((q, 256))
-        for r in range(rows):
-            part = part + prod[:, r, :]
-        s = 128
-        while s > 0:
-            part = part[:, :s] + part[:, s:2 * s]
-            s >>= 1
-        g[a] = part[:, 0]
-    return g
-
-
-def blk_combine(x: np.ndarray, c: np.ndarray, z: Optional[np.ndarray], subtract: bool) -> np.ndarray:
-    """``y[j] = z[j] -+ sum_i c[i][j] * x[i]`` as ``k_blk_combine`` does it: acc = z[j] (0.0 without z), then i ascending,
-    ``acc = fl(acc -+ fl(c * x))``.  x (p,n), c (p,q), z (q,n) or None -> (q,n)."""
-    x, c = np.asarray(x, dtype=np.float64), np.asarray(c, dtype=np.float64)
-    acc = np.zeros((c.shape[1], x.shape[1])) if z is None else np.array(z, dtype=np.float64)
-    for i in range(x.shape[0]):
-        t = c[i][:, None] * x[i][None, :]
-        acc = acc - t if subtract else acc + t
-    return acc
-
-
-def blk_scale(x: np.ndarray, w: np.ndarray) -> np.ndarray:
-    """``y[a][c] = fl(w[c] * x[a][c])`` (``k_blk_scale``)."""
-    return np.asarray(w, dtype=np.float64)[None, :] * np.asarray(x, dtype=np.float64)
-
-
-# ---- backends ----------------------------------------------------------------------------------------------------------------------------
-def _takes(fn: Callable, name: str) -> bool:
-    try:
-        return name in inspect.signature(fn).parameters
-    except (TypeError, ValueError):
-        return False
-
-
-class HostBackend:
-    """Blocks are NumPy arrays (p, n); the products come from ``hvp(base (N,3), dirs (M,N,3), step=, scheme=) -> (M,N,3)``.
+# ---- backends: the rows of rowblocks.py plus the products ---------------------------------------------------------------------------------
+class HostBackend(HostRows):
+    """The products come from ``hvp(base (N,3), dirs (M,N,3), step=, scheme=) -> (M,N,3)``.
     ``pinner``: an object with ``pin_graph / unpin_graph / pinned_graph`` (an ``Engine``, a ``LocalEnginePool``) whose graph the solver
     pins around its products, or None (a dense matrix has no graph)."""
 
     def __init__(self, hvp: Callable, pinner=None):
         self._hvp, self.pinner = hvp, pinner
-        self._reuse = _takes(hvp, "base_forces") and _takes(hvp, "return_base")
+        self._reuse = takes(hvp, "base_forces") and takes(hvp, "return_base")
         self._f0 = None
         self._wide = None
-
-    def put(self, a):
-        return np.array(a, dtype=np.float64, ndmin=2)
-
-    def get(self, b):
-        return np.array(b, dtype=np.float64)
-
-    def rows(self, b) -> int:
-        return int(b.shape[0])
-
-    def take(self, b, idx):
-        return np.ascontiguousarray(b[list(idx)])
-
-    def cat(self, blocks):
-        return np.concatenate(blocks, axis=0)
-
-    def gram(self, x, y) -> np.ndarray:
-        return blk_gram(x, y)
-
-    def combine(self, x, c, z, subtract):
-        return blk_combine(x, c, z, subtract)
-
-    def scale(self, x, w):
-        return blk_scale(x, w)
-
-    def vector(self, w):
-        return np.array(w, dtype=np.float64)
 
     def hvp(self, base, d, step, scheme):
         """(hv block, images spent)."""
@@ -153,66 +76,24 @@ class HostBackend:
         pass
 
 
-class DeviceBackend:
-    """Blocks are float64 torch tensors (p, n) on the engine's GPU; every operation is one engine entry on torch's current stream
-    (stream order is the only synchronisation, as in ``parallel.EngineStringEvaluator.hvp``).  ``gram`` reads its small matrix back."""
+class DeviceBackend(DeviceRows):
+    """The products are ``hvp_dev`` of the engine on torch's current stream; the base and its forces stay on the device."""
 
     def __init__(self, engine):
-        import torch
-
-        self.torch, self.engine, self.pinner = torch, engine, engine
-        self.dev = torch.device("cuda", int(engine.device))
+        super().__init__(engine)
+        self.pinner = engine
         self._f0 = None
         self._base = None
 
-    def _stream(self) -> int:
-        return self.torch.cuda.current_stream(self.dev).cuda_stream
-
-    def put(self, a):
-        return self.torch.as_tensor(np.array(a, dtype=np.float64, ndmin=2), device=self.dev).contiguous()
-
-    def get(self, b):
-        return b.cpu().numpy()
-
-    def rows(self, b) -> int:
-        return int(b.shape[0])
-
-    def take(self, b, idx):
-        return b[list(idx)].contiguous()
-
-    def cat(self, blocks):
-        return self.torch.cat(blocks, dim=0).contiguous()
-
-    def gram(self, x, y) -> np.ndarray:
-        g = self.torch.empty(x.shape[0], y.shape[0], dtype=self.torch.float64, device=self.dev)
-        self.engine.blk_gram_dev(x.shape[0], x.data_ptr(), y.shape[0], y.data_ptr(), x.shape[1], g.data_ptr(), stream=self._stream())
-        return g.cpu().numpy()
-
-    def combine(self, x, c, z, subtract):
-        c = self.put(c)
-        y = self.torch.empty(c.shape[1], x.shape[1], dtype=self.torch.float64, device=self.dev)
-        self.engine.blk_combine_dev(x.shape[0], x.data_ptr(), c.shape[1], c.data_ptr(), x.shape[1], 0 if z is None else z.data_ptr(), subtract,
-                                    y.data_ptr(), stream=self._stream())
-        return y
-
-    def scale(self, x, w):
-        y = self.torch.empty_like(x)
-        self.engine.blk_scale_dev(x.shape[0], x.data_ptr(), w.data_ptr(), x.shape[1], y.data_ptr(), stream=self._stream())
-        return y
-
-    def vector(self, w):
-        return self.torch.as_tensor(np.array(w, dtype=np.float64), device=self.dev).contiguous()
-
     def hvp(self, base, d, step, scheme):
-        t = self.torch
         m, n = d.shape
         if self._base is None:
-            self._base = t.as_tensor(np.ascontiguousarray(base, dtype=np.float64), device=self.dev).contiguous()
-        hv = t.empty(m, n, dtype=t.float64, device=self.dev)
+            self._base = self.put(base, ndmin=0)                               # (N,3), C-contiguous: the solver's x0
+        hv = self.empty(m, n)
         if scheme == "forward":
             given = self._f0 is not None
             if not given:
-                self._f0 = t.empty(n // 3, 3, dtype=t.float32, device=self.dev)
+                self._f0 = self.empty(n // 3, 3, dtype=self.torch.float32)
             self.engine.hvp_dev(1, self._base.data_ptr(), m, d.data_ptr(), hv.data_ptr(), step=step, scheme=scheme, d_f0=self._f0.data_ptr(),
                                 given_f0=given, stream=self._stream())
             return hv, (m if given else m + 1)

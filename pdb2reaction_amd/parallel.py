@@ -780,17 +780,28 @@ class LocalEnginePool:
         self.last_route, self.last_blocks = "batch", blocks
         self._bind_cells(k, blocks)
         self._bind_assign(k, blocks)
+        return self._run_in_one_arithmetic(lambda r: call(self.engines[r], p[blocks[r][0]: blocks[r][1]]), busy)
+
+    def _run_in_one_arithmetic(self, fn: Callable[[int], object], busy: Sequence[int]) -> list:
+        """``_run_all(fn, busy)`` such that one result never mixes two arithmetics: when an engine left the fp16 operand range during the
+        run and moved itself to bf16 forward planes (``Engine.energy_forces``, ``Engine.hvp``), the blocks of the others are in the
+        narrower arithmetic -- all engines move, and the WHOLE batch is run again, once."""
         for attempt in range(2):
             was_wide = [bool(getattr(eng, "widened", False)) for eng in self.engines]
-            res = self._run_all(lambda r: call(self.engines[r], p[blocks[r][0]: blocks[r][1]]), busy)
-            now_wide = [bool(getattr(eng, "widened", False)) for eng in self.engines]
-            if attempt == 0 and now_wide != was_wide:
-                # an engine left the fp16 operand range and moved itself to bf16 forward planes (Engine.energy_forces): the blocks of
-                # the others are in the narrower arithmetic -- all engines move, and the WHOLE batch is evaluated again
-                self._widen_all("fp16 range violation on another engine of the local pool")
-                continue
-            break
-        return res
+            res = self._run_all(fn, busy)
+            if attempt == 1 or [bool(getattr(eng, "widened", False)) for eng in self.engines] == was_wide:
+                return res
+            self._widen_all("fp16 range violation on another engine of the local pool")
+
+    def _deal_products(self, who: str, shared: str, m: int, blocks: list) -> list:
+        """What ``hvp`` and ``hvp_candidates`` do before they run: per-image cells (``set_cells``) are taken only when exactly one is
+        bound; the ``blocks`` of the ``m`` products become ``last_blocks``.  Returns the engines with a non-empty block."""
+        if self._cells is not None:
+            if len(self._cells[0]) != 1:
+                raise ValueError(f"{who}: set_cells bound cells for {len(self._cells[0])} images; {shared} (set_cell)")
+            self._bind_cells(1, None)
+        self.last_route, self.last_blocks = ("batch" if m > 1 else "single"), blocks
+        return [r for r in range(len(blocks)) if blocks[r][1] > blocks[r][0]]
 
     def energy_forces(self, pos_ang, forces: bool = True, double_positions: bool = False) -> Tuple[np.ndarray, Optional[np.ndarray]]:
         """pos_ang: (K,N,3) or (N,3) Angstrom -> (E [K] eV float64, F [K,N,3] eV/A float32 | None): ``Engine.energy_forces`` over the pool.
@@ -825,26 +836,14 @@ class LocalEnginePool:
         a = None if base_of is None else np.ascontiguousarray(base_of, dtype=np.int32).reshape(-1)
         if a is not None and len(a) != m:
             raise ValueError(f"hvp: {m} directions, but base_of has {len(a)} entries")
-        if self._cells is not None:
-            if len(self._cells[0]) != 1:
-                raise ValueError(f"hvp: set_cells bound cells for {len(self._cells[0])} images; the displaced images of a base share its one cell (set_cell)")
-            self._bind_cells(1, None)
         blocks = [shard_bounds(m, g, r) for r in range(g)] if m > 1 else [(0, 1)] + [(0, 0)] * (g - 1)
-        busy = [r for r in range(g) if blocks[r][1] > blocks[r][0]]
-        self.last_route, self.last_blocks = ("batch" if m > 1 else "single"), blocks
+        busy = self._deal_products("hvp", "the displaced images of a base share its one cell", m, blocks)
 
         def call(r):
             lo, hi = blocks[r]
             return self.engines[r].hvp(b, d[lo:hi], None if a is None else a[lo:hi], step=step, scheme=scheme, pin=pin, return_curvature=True)
 
-        for attempt in range(2):
-            was_wide = [bool(getattr(eng, "widened", False)) for eng in self.engines]
-            res = self._run_all(call, busy)
-            now_wide = [bool(getattr(eng, "widened", False)) for eng in self.engines]
-            if attempt == 0 and now_wide != was_wide:          # (as _deal: one result never mixes two arithmetics)
-                self._widen_all("fp16 range violation on another engine of the local pool")
-                continue
-            break
+        res = self._run_in_one_arithmetic(call, busy)
         hv = np.concatenate([r[0] for r in res])
         return (hv, np.concatenate([r[1] for r in res])) if return_curvature else hv
 
@@ -874,13 +873,8 @@ class LocalEnginePool:
         if b.shape[0] != k or (base_of is not None and not np.array_equal(np.asarray(base_of).reshape(-1), np.arange(k))):
             raise ValueError(f"hvp_candidates: one direction per base in order is needed, got {b.shape[0]} bases, {k} directions, base_of {base_of!r}")
         f_in = None if base_forces is None else np.ascontiguousarray(base_forces, dtype=np.float32).reshape(b.shape)
-        if self._cells is not None:
-            if len(self._cells[0]) != 1:
-                raise ValueError(f"hvp_candidates: set_cells bound cells for {len(self._cells[0])} images; the candidates share one cell (set_cell)")
-            self._bind_cells(1, None)
         blocks = [shard_bounds(k, g, r) for r in range(g)]
-        busy = [r for r in range(g) if blocks[r][1] > blocks[r][0]]
-        self.last_route, self.last_blocks = ("batch" if k > 1 else "single"), blocks
+        busy = self._deal_products("hvp_candidates", "the candidates share one cell", k, blocks)
 
         def call(r):
             lo, hi = blocks[r]
@@ -888,14 +882,7 @@ class LocalEnginePool:
                                       base_forces=None if f_in is None else f_in[lo:hi])
             return out if return_base else (out,)
 
-        for attempt in range(2):
-            was_wide = [bool(getattr(eng, "widened", False)) for eng in self.engines]
-            res = self._run_all(call, busy)
-            now_wide = [bool(getattr(eng, "widened", False)) for eng in self.engines]
-            if attempt == 0 and now_wide != was_wide:          # (as _deal: one result never mixes two arithmetics)
-                self._widen_all("fp16 range violation on another engine of the local pool")
-                continue                                       # (forces handed in are then stale: the dimer repeats its cycle after a widening)
-            break
+        res = self._run_in_one_arithmetic(call, busy)              # (forces handed in are stale after a widening: the dimer repeats its cycle)
         hv = np.concatenate([r[0] for r in res])
         return (hv, np.concatenate([r[1] for r in res]), np.concatenate([r[2] for r in res])) if return_base else hv
 

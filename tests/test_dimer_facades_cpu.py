@@ -39,7 +39,7 @@ def test_the_three_exports_and_their_owners():
     assert callable(U.uma_pysis.get_ts) and callable(UMXCalculator.refine_saddle)
     for name in ("row_dot_dev", "row_axpby_dev", "row_absmax_dev"):
         assert callable(getattr(E.Engine, name))
-    assert any(os.path.basename(d) == "umx_rows.h" for d in build.dependencies())
+    assert any(os.path.basename(d) == "umx_rowblocks.h" for d in build.dependencies())
     sig = inspect.signature(E.Engine.refine_saddles).parameters
     assert [p for p in sig][1:3] == ["x0", "modes0"] and sig["thresh"].default == "gau" and sig["step"].default == 1e-3 and sig["max_cycles"].default == 200
     assert (sig["max_rot"].default, sig["rot_tol"].default, sig["max_step"].default, sig["verify"].default) == (2, 0.1, 0.1, False)

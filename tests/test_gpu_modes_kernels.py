@@ -1,5 +1,5 @@
-"""The three float64 block kernels (``umx_blk_gram_dev`` / ``umx_blk_combine_dev`` / ``umx_blk_scale_dev``, csrc/umx_modes.h) on the
-GPU, bit for bit against their NumPy statements in pdb2reaction_amd/modes.py.  No weights are needed but for the curvature case.
+"""The three float64 block kernels (``umx_blk_gram_dev`` / ``umx_blk_combine_dev`` / ``umx_blk_scale_dev``, csrc/umx_rowblocks.h) on the
+GPU, bit for bit against their NumPy statements in pdb2reaction_amd/rowblocks.py.  No weights are needed but for the curvature case.
 
 Sizes: n in {3, 36, 255, 256, 257, 771} -- below one lane stride, at it, one past it, several strides with a ragged end, more than one
 256-thread block of the element-wise kernels -- and p, q in {1, 3, 17, 64}, the last being the largest block taken."""

@@ -1,5 +1,5 @@
-"""The three float64 row kernels (``umx_row_dot_dev`` / ``umx_row_axpby_dev`` / ``umx_row_absmax_dev``, csrc/umx_rows.h) on the GPU, bit
-for bit against their NumPy statements in pdb2reaction_amd/dimer.py.  No weights are needed.
+"""The three float64 row kernels (``umx_row_dot_dev`` / ``umx_row_axpby_dev`` / ``umx_row_absmax_dev``, csrc/umx_rowblocks.h) on the GPU, bit
+for bit against their NumPy statements in pdb2reaction_amd/rowblocks.py.  No weights are needed.
 
 Sizes: n in {3, 36, 255, 256, 257, 771} -- below one lane stride, at it, one past it, several strides with a ragged end, more than one
 256-thread block of the element-wise kernel -- and k in {1, 3, 17, 64}, the last being the largest batch taken."""

@@ -51,7 +51,7 @@ def test_the_three_exports_and_their_owners():
     assert callable(U.uma_pysis.get_lowest_modes)
     for name in ("blk_gram_dev", "blk_combine_dev", "blk_scale_dev"):
         assert callable(getattr(E.Engine, name))
-    assert any(os.path.basename(d) == "umx_modes.h" for d in build.dependencies())
+    assert any(os.path.basename(d) == "umx_rowblocks.h" for d in build.dependencies())
 
 
 # ---- the NumPy statements of the kernels --------------------------------------------------------------------------------------------------
